@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the DD-PPO training hot path on synthetic PointNav RGB-D 256x256.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the headline line (`metric`, `value`, `unit`, `ms_per_step`, ...); every
+other figure below (per-site roofline, phases, CPU baseline, parity, sub-records, N > 1 extras) is measured only with --full.
+--dump-outputs DIR writes what the timed path computed in its LAST timed step as DIR/<name>.npy (float32 / float64): the update's
+losses, the rollout it collected (actions, log-probs, values, returns, rewards, last hidden state) and the policy's state after the
+update (tensors larger than 32768 elements as a fixed seeded sample).  All inputs are seeded (habitat.seed), so two builds run with
+the same arguments can be compared output for output.
 
 N = 1 runs in this process.  N > 1 needs one rank per GPU: when WORLD_SIZE is not in the environment the script re-launches itself
 as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...` (the form
@@ -13,7 +20,7 @@ minibatch when N > 1].  Workload at N=1 is BASELINE.json configs[1]: PointNav Si
 hyper-parameters of config/pointnav/ppo_pointnav_habitat_iccv19.yaml (E=4, M=4).  `value` = env-steps collected by all ranks /
 max-over-ranks wall time, observations generated on the device (inputs never cross PCIe).
 
-Extra objects on the JSON line (rank 0; the sub-records only at N = 1, all measured in THIS run, after the timed region):
+Extra objects on the JSON line with --full (rank 0; the sub-records only at N = 1, all measured in THIS run, after the timed region):
   roofline      the call site with the largest share of the step ON THE CRITICAL STREAM -- chosen in this run from one untimed
                 cycle with every probe on (`kernels`: ms, share, roofline position of every contraction call site), then HIP-event timed on
                 its launch stream inside the timed region.  The recurrent layers run on the engine's second stream underneath the
@@ -508,6 +515,68 @@ def hbm_traffic(workload, probe):
     return None, None
 
 
+def seed_everything(seed):
+    """run.py's seeding: policy initialisation, the rollout's action noise and the minibatch permutations come from these generators
+    (the synthetic environments are seeded from habitat.seed themselves); distributed ranks re-seed with seed + rank * envs."""
+    import random
+    import numpy as np
+    import torch
+    random.seed(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+
+
+ROLLOUT_OUTPUTS = ("actions", "action_log_probs", "value_preds", "returns", "rewards")
+PARAM_SAMPLE = 32768  # elements kept of a state_dict tensor larger than this (fixed seeded sample)
+
+
+def capture_rollout(trainer, snap):
+    """Copies the rollout of the NEXT update cycle into `snap` when the updater receives it (GAE returns written, before
+    after_update() recycles row 0).  Device-side clones of a few (T + 1) x N arrays; returns the function that removes the hook."""
+    upd = trainer._agent.updater
+    inner = upd.update
+
+    def update(st):
+        B = st.buffers
+        for k in ROLLOUT_OUTPUTS:
+            snap[k] = B[k].detach().clone()
+        snap["last_hidden"] = B["recurrent_hidden_states"][st.current_rollout_step_idx].detach().clone()
+        return inner(st)
+
+    upd.update = update
+
+    def remove():
+        upd.update = inner
+
+    return remove
+
+
+def dump_outputs(out_dir, losses, rollout, policy):
+    """Writes the last timed step's outputs as out_dir/<name>.npy: loss_<key> (float64 scalars of the update's statistics),
+    rollout_<buffer> (float32, the (T + 1) x N arena rows) and policy_state (float32, every floating state_dict tensor flattened in
+    order, sampled above PARAM_SAMPLE elements; policy_state_nonfloat: the integer buffers, float64)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in losses.items():
+        np.save(os.path.join(out_dir, f"loss_{k}.npy"), np.array(float(v), dtype=np.float64))
+    for k, v in rollout.items():
+        np.save(os.path.join(out_dir, f"rollout_{k}.npy"), v.cpu().numpy().astype(np.float32))
+    rng = np.random.default_rng(0)
+    parts, nonfloat = [], []  # state_dict order; a tensor above PARAM_SAMPLE elements as the sorted indices of default_rng(0)
+    for v in policy.state_dict().values():
+        x = v.detach().reshape(-1).cpu()
+        if x.numel() > PARAM_SAMPLE:
+            x = x[torch.from_numpy(np.sort(rng.choice(x.numel(), PARAM_SAMPLE, replace=False)))]
+        if x.is_floating_point():
+            parts.append(x.float().numpy())
+        else:
+            nonfloat.append(x.double().numpy())
+    np.save(os.path.join(out_dir, "policy_state.npy"), np.concatenate(parts).astype(np.float32))
+    if nonfloat:
+        np.save(os.path.join(out_dir, "policy_state_nonfloat.npy"), np.concatenate(nonfloat).astype(np.float64))
+
+
 def relaunch_ranks(a):
     """--gpus N > 1 without a torchrun environment: start the N ranks ourselves (same command line the driver uses)."""
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -524,12 +593,18 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="c2", choices=list(WORKLOADS))
-    ap.add_argument("--probe", default=None, choices=list(PROBES))
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU leg, the parity leg and the sub-records (profiling runs)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the c3 / encoder sub-records only")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-site roofline, phases, CPU baseline, parity and the sub-records (N = 1); c4 and "
+                         "exchange_ab (N > 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--probe", default=None, choices=list(PROBES), help="(--full) the call site the timed roofline probe brackets")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU leg, the parity leg and the sub-records (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the c3 / encoder sub-records only")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU leg (default min(16, host cores); -1 = every host core)")
     ap.add_argument("--encoder-only", type=int, default=0, help="print the ResNet18 encoder record of ONE call of this many frames and exit")
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if a.encoder_only:
         print(json.dumps(encoder_record(a.encoder_only, 1)), flush=True)
         return
@@ -550,6 +625,7 @@ def main():
         raise SystemExit("bench.py needs an MI355X: the hot path has no CPU execution path")
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     trainer, cfg = make_trainer(a.workload, a.warmup + a.steps + 2)
+    seed_everything(cfg.habitat.seed)
     trainer._init_train()
     eng = trainer._agent.actor_critic.engine
     dist = torch.distributed.is_initialized()
@@ -569,7 +645,7 @@ def main():
         return f + (local_steps + n_envs * cycles if probe.endswith("_fwd") and not probe.startswith("rnn") else 0)
 
     table, overlapped = None, None
-    if a.workload == "c2" and world == 1:
+    if a.full and a.workload == "c2" and world == 1:
         # per-call-site table from ONE untimed cycle with every probe on (~1400 event records), BEFORE the timed region: it decides which
         # site the timed probe brackets.  Single-rank runs only (an extra cycle per rank is fine, but the table is rank 0's business).
         tags = {k: PROBES[k] for k in C2_TABLE}
@@ -618,22 +694,31 @@ def main():
         if auto_probe and crit:
             a.probe = crit[0]["site"]
     tag, flops_per_frame = PROBES[a.probe]
-    eng.probe_enable(tag)
-    rollout_ms = time_rollouts(trainer)
+    if a.full:
+        eng.probe_enable(tag)
+        rollout_ms = time_rollouts(trainer)
+    snap, unhook = {}, None
     barrier()
     steps_before, local_before = trainer.num_steps_done, getattr(trainer, "local_steps_done", 0)
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        trainer.run_update_cycle()
+    for i in range(a.steps):
+        if a.dump_outputs and i == a.steps - 1:
+            unhook = capture_rollout(trainer, snap)
+        losses = trainer.run_update_cycle()
     barrier()
     dt = time.perf_counter() - t0
-    probe_ms, probe_cnt = eng.probe_read()
-    eng.probe_enable(-1)
-    phases = phase_record(rollout_ms(a.steps), dt / a.steps * 1e3, ppo)  # (this rank's; before the max over ranks)
+    if unhook is not None:
+        unhook()
+    if a.full:
+        probe_ms, probe_cnt = eng.probe_read()
+        eng.probe_enable(-1)
+        phases = phase_record(rollout_ms(a.steps), dt / a.steps * 1e3, ppo)  # (this rank's; before the max over ranks)
     if dist:
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, losses, snap, trainer._agent.actor_critic)
     if os.environ.get("HAB_BENCH_CHECKSUM"):  # development: parameters must not depend on how the gradient exchange is scheduled
         pf = eng.params_flat.double()
         print(f"[rank {rank}] params checksum {pf.sum().item():.12e} {pf.abs().sum().item():.12e}", flush=True)
@@ -652,7 +737,7 @@ def main():
     assert 0 < steps_total <= world * n_envs * n_steps * a.steps
     local_steps = trainer.local_steps_done - local_before
     c4 = None
-    if world > 1 and a.workload == "c2" and not a.no_extras and not a.no_cpu_baseline:
+    if a.full and world > 1 and a.workload == "c2" and not a.no_extras and not a.no_cpu_baseline:
         # BASELINE.json configs[3] (the workload north_star's >= 6x scaling target is written on): DD-PPO ResNet18 + 2-layer LSTM, 64 envs per
         # rank, run by EVERY rank after the headline cycles (same barrier + max-over-ranks timing)
         trainer.envs.close()
@@ -664,7 +749,7 @@ def main():
         except Exception as exc:  # noqa: BLE001 -- a failure every rank shares (e.g. memory) must not take the headline figure with it
             c4 = {"error": repr(exc)[:300]}
     exchange_ab = None
-    if world > 1 and a.workload == "c2" and not a.no_extras and not a.no_cpu_baseline:
+    if a.full and world > 1 and a.workload == "c2" and not a.no_extras and not a.no_cpu_baseline:
         # Both gradient exchanges in ONE run: the torch.distributed callbacks (default) and the library-owned RCCL
         # communicator (HAB_NATIVE_COMM=1; falls back by a vote of all ranks when it cannot be opened), each on a fresh trainer from the
         # same seeds -- same rollouts, same minibatches -- so the parameter arenas after the cycles must be EQUAL bit for bit on every
@@ -710,21 +795,12 @@ def main():
     if rank != 0:
         torch.distributed.destroy_process_group()
         return
-    frames = frames_seen(a.probe, local_steps, a.steps)
-    if a.probe.startswith("enc_"):
-        kname = f"resnet encoder {a.probe[4:]} (all kernels)"
-    elif a.probe in PROBE_KERNELS:
-        kname = f"{a.probe}: {PROBE_KERNELS[a.probe]}...>"
-    else:
-        kname = f"contraction at call site {a.probe}"
-    rl = site_roofline(a.probe, flops_per_frame, frames, probe_ms) if probe_ms > 0 else {"bound": "mfma", "achieved": None, "peak": None, "frac": None}
-    traffic, traffic_src = hbm_traffic(a.workload, a.probe)
     out = {
         "metric": "env-steps/sec (SPS) PointNav RGB-D 256x256, 64 envs x 128 rollout" if a.workload != "c5" else
                   "env-steps/sec (SPS) ObjectNav RGB-D+semantic 256x256, 32 envs x 64 rollout",
         "value": round(steps_total / dt, 1), "unit": "env-steps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
         "ms_per_step": round(dt / a.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic", "phases": phases,
+        "dtype": "f32", "data": "synthetic",
         # ranks that took part, read from the process group after init (1 without one): a launcher that silently started fewer
         # ranks than --gpus would show here
         "ranks_seen": torch.distributed.get_world_size() if dist else 1,
@@ -733,38 +809,49 @@ def main():
                    "ppo_epoch": ppo.ppo_epoch, "num_mini_batch": ppo.num_mini_batch, "parallelism": f"dp{world}",
                    "matrix_path": "fp32 in / fp32 out; exact 3-term bf16 operand split, 6 (uint8 operand: 3) partial products on "
                                   "v_mfma_f32_32x32x16_bf16, fp32 accumulate (csrc/igemm_bf3.h); HAB_BF3=0 selects v_mfma_f32_32x32x2_f32"},
-        "roofline": dict(rl, kernel=kname, traffic=traffic, traffic_source=traffic_src, launches=probe_cnt,
-                         avg_launch_ms=round(probe_ms / max(probe_cnt, 1), 4), share_of_step=round(probe_ms / (dt * 1e3), 4),
-                         frames_per_launch=round(frames / max(probe_cnt, 1), 1)),
     }
-    if traffic is not None and a.probe in SITE_MODEL and probe_cnt:
-        upd_frames = (frames / probe_cnt if a.probe in PERSISTENT_GRID_SITES else
-                      n_envs * n_steps // ppo.num_mini_batch // site_chunks(a.probe))
-        out["roofline"]["traffic_ratio"] = round(traffic / (SITE_MODEL[a.probe][0] * upd_frames + SITE_LAUNCH_BYTES.get(a.probe, 0)), 3)
-        out["roofline"]["traffic_basis"] = (f"{'mean' if a.probe in PERSISTENT_GRID_SITES else 'update-sized'} launch of {upd_frames:.1f} frames; "
-                                            f"algorithmic bytes {SITE_MODEL[a.probe][0]} per frame"
-                                            + (f" + {SITE_LAUNCH_BYTES[a.probe]} per launch (weights)" if a.probe in SITE_LAUNCH_BYTES else ""))
-    if a.workload in ("c2", "c3"):
-        # FLOPs per env-step of the contractions that are EXECUTED: F = 2 MAC_fwd (1 + 1/T) + E (2 (3 MAC_fwd - MAC_first_dgrad)) -- the data
-        # gradient of the first convolution (wrt the observation) is never computed.  SURVEY.md 8(d)'s formula counts it (C2 2.365,
-        # C3 2.442 GFLOP); both are reported, priced against the fp32 MFMA peak (the round-1 yardstick) for comparability.
-        mac_fwd, mac_first, f_survey = (89.3e6, 32.5e6, 2.365e9) if a.workload == "c2" else (168.82e6, 25.69e6, 2.442e9)
-        f_exec = 2.0 * (mac_fwd * (1.0 + 1.0 / n_steps) + ppo.ppo_epoch * (3.0 * mac_fwd - mac_first))
-        rate = steps_total / world / dt
-        out["roofline"]["whole_cycle_frac"] = round(rate * f_exec / (PEAK_FP32_MFMA_TFLOPS * 1e12), 4)
-        out["roofline"]["whole_cycle"] = {"executed_gflop_per_env_step": round(f_exec / 1e9, 4), "tflops": round(rate * f_exec / 1e12, 2),
-                                          "frac_of_fp32_mfma_peak": out["roofline"]["whole_cycle_frac"],
-                                          "frac_with_survey_formula": round(rate * f_survey / (PEAK_FP32_MFMA_TFLOPS * 1e12), 4),
-                                          # against the pipe in use: bf16 MFMA peak / 6 partial products (conv1: 3.75, priced at 6 here)
-                                          "frac_of_split_ceiling": round(rate * f_exec / (PEAK_BF16_MFMA_TFLOPS / 6.0 * 1e12), 4),
-                                          "split_ceiling_tflops": round(PEAK_BF16_MFMA_TFLOPS / 6.0, 1)}
-    if table is not None:
-        out["roofline"]["kernels"] = table
-        out["roofline"]["site_choice"] = ("largest share of the step among the call sites of the critical stream in this run's all-probes cycle"
-                                          if auto_probe else "--probe")
-    if overlapped is not None:
-        out["roofline"]["overlapped"] = overlapped
-    if world == 1 and not a.no_cpu_baseline and a.workload == "c2":
+    if a.full:
+        frames = frames_seen(a.probe, local_steps, a.steps)
+        if a.probe.startswith("enc_"):
+            kname = f"resnet encoder {a.probe[4:]} (all kernels)"
+        elif a.probe in PROBE_KERNELS:
+            kname = f"{a.probe}: {PROBE_KERNELS[a.probe]}...>"
+        else:
+            kname = f"contraction at call site {a.probe}"
+        rl = site_roofline(a.probe, flops_per_frame, frames, probe_ms) if probe_ms > 0 else {"bound": "mfma", "achieved": None, "peak": None, "frac": None}
+        traffic, traffic_src = hbm_traffic(a.workload, a.probe)
+        out["phases"] = phases
+        out["roofline"] = dict(rl, kernel=kname, traffic=traffic, traffic_source=traffic_src, launches=probe_cnt,
+                             avg_launch_ms=round(probe_ms / max(probe_cnt, 1), 4), share_of_step=round(probe_ms / (dt * 1e3), 4),
+                             frames_per_launch=round(frames / max(probe_cnt, 1), 1))
+        if traffic is not None and a.probe in SITE_MODEL and probe_cnt:
+            upd_frames = (frames / probe_cnt if a.probe in PERSISTENT_GRID_SITES else
+                          n_envs * n_steps // ppo.num_mini_batch // site_chunks(a.probe))
+            out["roofline"]["traffic_ratio"] = round(traffic / (SITE_MODEL[a.probe][0] * upd_frames + SITE_LAUNCH_BYTES.get(a.probe, 0)), 3)
+            out["roofline"]["traffic_basis"] = (f"{'mean' if a.probe in PERSISTENT_GRID_SITES else 'update-sized'} launch of {upd_frames:.1f} frames; "
+                                                f"algorithmic bytes {SITE_MODEL[a.probe][0]} per frame"
+                                                + (f" + {SITE_LAUNCH_BYTES[a.probe]} per launch (weights)" if a.probe in SITE_LAUNCH_BYTES else ""))
+        if a.workload in ("c2", "c3"):
+            # FLOPs per env-step of the contractions that are EXECUTED: F = 2 MAC_fwd (1 + 1/T) + E (2 (3 MAC_fwd - MAC_first_dgrad)) -- the data
+            # gradient of the first convolution (wrt the observation) is never computed.  SURVEY.md 8(d)'s formula counts it (C2 2.365,
+            # C3 2.442 GFLOP); both are reported, priced against the fp32 MFMA peak (the round-1 yardstick) for comparability.
+            mac_fwd, mac_first, f_survey = (89.3e6, 32.5e6, 2.365e9) if a.workload == "c2" else (168.82e6, 25.69e6, 2.442e9)
+            f_exec = 2.0 * (mac_fwd * (1.0 + 1.0 / n_steps) + ppo.ppo_epoch * (3.0 * mac_fwd - mac_first))
+            rate = steps_total / world / dt
+            out["roofline"]["whole_cycle_frac"] = round(rate * f_exec / (PEAK_FP32_MFMA_TFLOPS * 1e12), 4)
+            out["roofline"]["whole_cycle"] = {"executed_gflop_per_env_step": round(f_exec / 1e9, 4), "tflops": round(rate * f_exec / 1e12, 2),
+                                              "frac_of_fp32_mfma_peak": out["roofline"]["whole_cycle_frac"],
+                                              "frac_with_survey_formula": round(rate * f_survey / (PEAK_FP32_MFMA_TFLOPS * 1e12), 4),
+                                              # against the pipe in use: bf16 MFMA peak / 6 partial products (conv1: 3.75, priced at 6 here)
+                                              "frac_of_split_ceiling": round(rate * f_exec / (PEAK_BF16_MFMA_TFLOPS / 6.0 * 1e12), 4),
+                                              "split_ceiling_tflops": round(PEAK_BF16_MFMA_TFLOPS / 6.0, 1)}
+        if table is not None:
+            out["roofline"]["kernels"] = table
+            out["roofline"]["site_choice"] = ("largest share of the step among the call sites of the critical stream in this run's all-probes cycle"
+                                              if auto_probe else "--probe")
+        if overlapped is not None:
+            out["roofline"]["overlapped"] = overlapped
+    if a.full and world == 1 and not a.no_cpu_baseline and a.workload == "c2":
         base, par = cpu_baseline_and_parity(trainer, cfg, cpu_threads=(os.cpu_count() or 1) if a.cpu_threads < 0 else a.cpu_threads)
         other = next((p_ for p_ in (os.path.join(ROOT, "profiles", f"{t_}_cpu_leg_threads.json") for t_ in ("r06", "r05", "r04", "r03")) if os.path.exists(p_)), "")
         if other:  # the same leg timed once at every thread setting on the GPU box's host (committed measurement)
@@ -787,7 +874,7 @@ def main():
                 out["c5"]["parity"], out["c5"]["cpu_baseline"] = c3_parity_record(c5_state, envs=2, steps=64, workload="c5")
             del c5_state
             out["encoder_r18_b8192"] = encoder_record_one_call()
-    if world > 1:
+    if a.full and world > 1:
         if c4 is not None:
             out["c4"] = c4
         if exchange_ab is not None:

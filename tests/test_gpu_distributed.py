@@ -224,7 +224,7 @@ def test_ddppo_running_mean_var_with_uneven_frame_counts():
 
 def test_bench_py_launches_two_ranks_and_reports_whole_job_rate():
     """The driver's multi-GPU scaling run is the first time RCCL sees more than one rank; everything around the transport must not be
-    able to fail there.  `bench.py --gpus 2` (the self-launching form: torchrun with --master-addr 127.0.0.1) on ONE GPU with the gloo
+    able to fail there.  `bench.py --full --gpus 2` (the self-launching form: torchrun with --master-addr 127.0.0.1) on ONE GPU with the gloo
     transport (HAB_BENCH_DISTRIB_BACKEND=GLOO; both ranks wrap onto device 0): exactly one JSON line, n_gpus = ranks_seen = 2,
     parallelism dp2, all 2 x 64 x 128 x K env-steps counted, value = env-steps / max-over-ranks time; the `exchange` record and the
     `c4` sub-record (ResNet18 + LSTM on both ranks) are there."""
@@ -233,7 +233,7 @@ def test_bench_py_launches_two_ranks_and_reports_whole_job_rate():
     env = dict(os.environ, HAB_BENCH_DISTRIB_BACKEND="GLOO", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -15,13 +15,13 @@ R=$PWD
 O=$R/gpurun_out
 mkdir -p $O
 export TMPDIR=/tmp
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_c2_bench.json 2> $O/${TAG}_c2_bench.err   # the driver's command
-python bench.py --workload c3 --steps 10 --warmup 2 > $O/${TAG}_c3_bench.json 2> $O/${TAG}_c3_bench.err
-python bench.py --workload c5 --steps 5 --warmup 2 > $O/${TAG}_c5_bench.json 2> $O/${TAG}_c5_bench.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_c2_bench.json 2> $O/${TAG}_c2_bench.err   # the headline command with every extra record
+python bench.py --full --workload c3 --steps 10 --warmup 2 > $O/${TAG}_c3_bench.json 2> $O/${TAG}_c3_bench.err
+python bench.py --full --workload c5 --steps 5 --warmup 2 > $O/${TAG}_c5_bench.json 2> $O/${TAG}_c5_bench.err
 cd /tmp
 for W in c2 c3 c5; do
   rm -rf /tmp/prof_${TAG}_$W
-  timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_${TAG}_$W -o $W -- python $R/bench.py --workload $W --steps 3 --warmup 1 --no-cpu-baseline > $O/prof_${TAG}_$W.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_${TAG}_$W -o $W -- python $R/bench.py --full --workload $W --steps 3 --warmup 1 --no-cpu-baseline > $O/prof_${TAG}_$W.log 2>&1
   DB=$(ls /tmp/prof_${TAG}_$W/*results.db /tmp/prof_${TAG}_$W/*/*results.db 2>/dev/null | head -1)
   python $R/tools/rocprof_summary.py $DB $O/${TAG}_${W}_kernel_stats.txt > /dev/null
   python $R/tools/trace_phases.py $DB $O/${TAG}_${W}_phases.txt > /dev/null
@@ -33,23 +33,23 @@ done
 for W in c2 c3 ${PMC_C5:+c5}; do
   rm -rf /tmp/pmc_${TAG}_$W
   for PM in FETCH_SIZE WRITE_SIZE; do
-    timeout 300 rocprofv3 --pmc $PM --kernel-trace -d /tmp/pmc_${TAG}_$W -o $PM --output-format csv -- python $R/bench.py --workload $W --steps 1 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
+    timeout 300 rocprofv3 --pmc $PM --kernel-trace -d /tmp/pmc_${TAG}_$W -o $PM --output-format csv -- python $R/bench.py --full --workload $W --steps 1 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
   done
   python $R/tools/pmc_traffic.py /tmp/pmc_${TAG}_$W $O/${TAG}_${W}_hbm_traffic.json $O/${TAG}_${W}_hbm_traffic.txt
   rm -rf /tmp/pmc_${TAG}_$W
 done
 cd $R
-tools/pmc_run.sh /tmp/pmcsq_${TAG} python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline
+tools/pmc_run.sh /tmp/pmcsq_${TAG} python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline
 python tools/pmc_sq.py /tmp/pmcsq_${TAG} $O/${TAG}_c2_sq_counters.txt > /dev/null
 rm -rf /tmp/pmcsq_${TAG}
 for W in c3 ${PMC_C5:+c5}; do
-  PMC_GROUPS=1 tools/pmc_run.sh /tmp/pmcsq_${TAG}_$W python $R/bench.py --workload $W --steps 1 --warmup 1 --no-cpu-baseline
+  PMC_GROUPS=1 tools/pmc_run.sh /tmp/pmcsq_${TAG}_$W python $R/bench.py --full --workload $W --steps 1 --warmup 1 --no-cpu-baseline
   python tools/pmc_sq.py /tmp/pmcsq_${TAG}_$W $O/${TAG}_${W}_sq_counters.txt > /dev/null
   rm -rf /tmp/pmcsq_${TAG}_$W
 done
 # the CPU leg at further thread settings (the default line uses 16; every core of the 256-thread host did not finish in 400 s in round 3)
 for TH in 32 64; do
-  timeout 300 python bench.py --steps 1 --warmup 1 --no-extras --cpu-threads $TH > $O/${TAG}_c2_cpu_${TH}.json 2> $O/${TAG}_c2_cpu_${TH}.err
+  timeout 300 python bench.py --full --steps 1 --warmup 1 --no-extras --cpu-threads $TH > $O/${TAG}_c2_cpu_${TH}.json 2> $O/${TAG}_c2_cpu_${TH}.err
 done
 python - <<PY
 import json

@@ -7,7 +7,7 @@ R=$PWD; O=$R/gpurun_out; mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
 rm -rf /tmp/prof_${TAG}_$W
-timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_${TAG}_$W -o $W -- python $R/bench.py --workload $W --steps $STEPS --warmup 1 --no-cpu-baseline > $O/prof_${TAG}_$W.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_${TAG}_$W -o $W -- python $R/bench.py --full --workload $W --steps $STEPS --warmup 1 --no-cpu-baseline > $O/prof_${TAG}_$W.log 2>&1
 DB=$(ls /tmp/prof_${TAG}_$W/*results.db /tmp/prof_${TAG}_$W/*/*results.db 2>/dev/null | head -1)
 python $R/tools/rocprof_summary.py $DB $O/${TAG}_${W}_kernel_stats.txt > /dev/null
 python $R/tools/trace_phases.py $DB $O/${TAG}_${W}_phases.txt > /dev/null
