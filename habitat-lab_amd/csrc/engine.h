@@ -30,6 +30,12 @@ struct Arena {
     }
 };
 
+// How an evaluate runs the recurrent encoder (rnn.hip); all forms are bit-identical
+struct RnnForm {
+    int chunks = 0;     // > 0: time-major, the minibatch cut into this many time chunks (second stream); 0: packed
+    bool wave = false;  // packed: all layers as one wavefront (one launch per packed step) instead of layer by layer
+};
+
 struct hab_policy {
     hab_policy_desc d;
     std::vector<ParamSpec> params;
@@ -50,7 +56,6 @@ struct hab_policy {
     int64_t pk_c1img = -1;  // conv1's bf16 weight image for the patch-resident kernel, rebuilt by every repack (-1: no image for this filter)
     std::vector<int64_t> pk_whht;
     std::vector<int64_t> pk_wiht;  // layers >= 1: W_ih transposed [H][G*H] (layer wavefront BPTT, rnn.hip); entry 0 unused (-1)
-    bool last_wave = false;        // the last evaluate ran the recurrent layers as a wavefront (the backward must mirror it)
     int64_t pk_wih0 = -1;  // layer 0 W_ih, rows padded with zeros to rnn_ld floats (fused input projection of the rollout step, rnn.hip)
     // workspace offsets (floats)
     int64_t w_a1, w_a2, w_a3, w_rnnin, w_da1, w_da2, w_da3, w_drnnin, w_hinit, w_cinit, w_feat_d, w_probs, w_logitsn, w_dzv,
@@ -63,7 +68,7 @@ struct hab_policy {
     hipStream_t s2 = nullptr;
     std::vector<hipEvent_t> evs;
     int64_t w_ws2 = -1, ws2_floats = 0, w_fmask = -1, w_iota = -1;
-    int last_tm = 0;  // the last evaluate ran the time-major form with this many chunks (0: packed form)
+    RnnForm form;  // form of the recurrent encoder in the last evaluate (engine.hip: rnn_form); the backward mirrors it
     // ResNet policy (engine_resnet.hip)
     struct ResNetPlan* rn = nullptr;
     int save_acts = 1;                                  // 0 inside act / encode: no backward follows, the fused kernels skip the saved copies
@@ -108,8 +113,7 @@ inline int add_param(hab_policy* e, const std::string& name, std::initializer_li
 }
 
 
-int tm_chunks_cfg();         // time chunks of the time-major recurrence (HAB_RNN_CHUNKS; 0 / 1: packed form / one chunk)
-int tm_chunks_resnet_cfg(int frames);  // ... for the ResNet policies (HAB_RNN_CHUNKS_RESNET; default: 2 chunks from 4096 frames on, else packed)
+void plan_tm_workspace(hab_policy* e, Arena& wk);  // the time-major form's scratch, if this engine can ever select that form (engine.hip)
 int build_resnet(hab_policy* e);
 void destroy_resnet(hab_policy* e);
 int resnet_repack(hab_policy* e, hipStream_t s);

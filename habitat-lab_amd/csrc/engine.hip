@@ -101,11 +101,7 @@ static int build_baseline(hab_policy* e) {
     // split-K / column-sum scratch: big enough for 64 slabs of the largest weight-gradient (fc) or 1024 colsum rows
     e->ws_floats = std::max<int64_t>((int64_t)16 << 20, (int64_t)8 * H * e->fc_in / 4);
     e->w_ws = wk.take(e->ws_floats);
-    // second stream of the time-major chunked recurrence: its own split-K scratch, the dense per-frame episode-start mask, an iota
-    e->ws2_floats = e->ws_floats;  // same cap as the first stream's: the split-K plans (hence the bits) must not depend on the stream
-    e->w_ws2 = wk.take(e->ws2_floats);
-    e->w_fmask = wk.take((B + 3) / 4 + 64);
-    e->w_iota = wk.take(B + 64);
+    plan_tm_workspace(e, wk);
     e->work_floats = wk.used;
     return HAB_OK;
 }
@@ -310,8 +306,10 @@ static int encoder_forward(hab_policy* e, const hab_obs* obs, const uint8_t* mas
     return HAB_OK;
 }
 
-// ---- time-major chunked recurrence: second stream + events ----
-int tm_chunks_cfg() { static const int v = hab_env_int("HAB_RNN_CHUNKS", 4); return v; }
+// ---- form of the recurrent encoder (RnnForm): chosen here for every evaluate and for the workspace plan ----
+// Time-major form (rnn.hip): a regular T x n minibatch is cut into time chunks; the encoder of chunk c + 1 runs on the caller's stream while
+// the recurrence walks chunk c on the engine's second stream.  HAB_RNN_CHUNKS (default 4) chunks; 0 / 1 selects the packed form / one
+// chunk for both policies.
 // ResNet policies: bit-identical to the packed form at one chunk (tests/test_gpu_determinism.py).  With one launch per step the time-major
 // form measured SLOWER than the packed form on C3 (round 4: 28.5 k vs 29.1 k env-steps/s: all T = 128 steps of 32 rows against max_len ~ 107
 // packed steps, and every chunk is another pass through ~60 encoder kernels).  With the persistent recurrence (rnn_persist.h, round 6) a
@@ -319,13 +317,40 @@ int tm_chunks_cfg() { static const int v = hab_env_int("HAB_RNN_CHUNKS", 4); ret
 //   C3 (ResNet18, 4096 frames per minibatch): packed 32.27 k / 32.54 k, 1 chunk 32.68 k, 2 chunks 33.15 k / 33.24 k, 3 chunks 32.27 k, 4 chunks 32.87 k
 //   C5 (ResNet50, 1024 frames per minibatch): packed 4.995 k, 1 chunk 5.003 k, 2 chunks 4.92 k, 3 chunks 4.74 k
 // Default (HAB_RNN_CHUNKS_RESNET unset or < 0): 2 chunks from 4096 frames per minibatch on, packed below; k >= 0 forces k chunks
-// (0 = packed).  HAB_RNN_CHUNKS = 0 / 1 still selects the packed form / one chunk for both policies.
-int tm_chunks_resnet_cfg(int frames) {
-    static const int v = hab_env_int("HAB_RNN_CHUNKS_RESNET", -1);
-    const int base = tm_chunks_cfg();
-    if (base <= 1) return base;
-    if (v >= 0) return v;
-    return frames >= 4096 ? 2 : 0;
+// (0 = packed).
+// Packed form: 2 to 4 layers run as a wavefront (one launch per packed step for ALL layers, layer l one step behind layer l - 1) unless
+// HAB_RNN_WAVE=0.  Its other conditions (rnn_seq_wave_forward / _backward) hold for every engine: hidden % 64 == 0, aligned arenas.
+// frames / n: the evaluate's B / n; tm_shape: the call can take the time-major form at all (rnn_form).  Also asked with the largest
+// regular minibatch by the workspace plan (plan_tm_workspace).
+static RnnForm rnn_form_cfg(const hab_policy* e, int frames, int n, bool tm_shape) {
+    static const int chunks = hab_env_int("HAB_RNN_CHUNKS", 4), chunks_resnet = hab_env_int("HAB_RNN_CHUNKS_RESNET", -1);
+    static const int wave = hab_env_int("HAB_RNN_WAVE", 1);
+    RnnForm f;
+    if (tm_shape) {
+        int nc = chunks;
+        if (e->rn && chunks > 1) nc = chunks_resnet >= 0 ? chunks_resnet : frames >= 4096 ? 2 : 0;
+        f.chunks = std::max(0, std::min(nc, frames / n));
+    }
+    if (f.chunks == 0) f.wave = wave && e->L >= 2 && e->L <= 4;
+    return f;
+}
+// The form of an evaluate of B frames of n envs: time-major for a regular T x n minibatch (T >= 2) gathered through `rows`, of a policy with
+// a visual encoder, whose per-layer BPTT carries ([2][n][H], w_scratch) fit, in an engine that planned the second stream's scratch.
+static RnnForm rnn_form(const hab_policy* e, const int* rows, const hab_pack_info* pack, int B, int n) {
+    const bool tm_shape = e->Cin > 0 && rows && !pack->env_first_frame && (B % n) == 0 && B / n >= 2 && e->w_ws2 >= 0 &&
+                          (int64_t)e->L * 2 * n <= 3 * (int64_t)e->d.max_frames;
+    return rnn_form_cfg(e, B, n, tm_shape);
+}
+// Second stream of the time-major form: its own split-K scratch (same cap as the first stream's: the split-K plans, hence the bits, must not
+// depend on the stream), the dense per-frame episode-start mask, an iota -- only in an engine that can ever select that form (every
+// engine, incl. each VER inference worker's private one, would otherwise carry 128 MB + 5 bytes per frame for nothing).
+void plan_tm_workspace(hab_policy* e, Arena& wk) {
+    const int64_t B = e->d.max_frames;
+    if (rnn_form_cfg(e, (int)B, 1, true).chunks == 0) return;
+    e->ws2_floats = e->ws_floats;
+    e->w_ws2 = wk.take(e->ws2_floats);
+    e->w_fmask = wk.take((B + 3) / 4 + 64);
+    e->w_iota = wk.take(B + 64);
 }
 static int tm_setup(hab_policy* e, int nev) {
     if (!e->s2) {
@@ -344,7 +369,8 @@ static int tm_setup(hab_policy* e, int nev) {
     }
     return HAB_OK;
 }
-// everything enqueued on `from` so far happens before whatever is enqueued on `to` from now on
+// everything enqueued on `from` so far happens before whatever is enqueued on `to` from now on.  Events (tm_setup: 2 * NC + 4): forward
+// chunk c -> c, forward join -> NC; backward fork -> NC + 1, backward chunk c -> NC + 2 + c, backward join -> 2 * NC + 3
 static int tm_order(hab_policy* e, int ev, hipStream_t from, hipStream_t to) {
     hipError_t err = hipEventRecord(e->evs[ev], from);
     if (err != hipSuccess) return (int)err;
@@ -370,6 +396,19 @@ static RnnWork layer_work(hab_policy* e, int l) {
     wk.cprev = W + e->w_cprev[l]; wk.c = W + e->w_c[l]; wk.out = W + e->w_out[l]; wk.dgi = W + e->w_dgi[l];
     wk.dgh = W + e->w_dgh[l];
     return wk;
+}
+// layer l's input [B][layer_ld] (rnn_in below layer 0, the output of layer l - 1 above it), the gradient wrt it, and the gradient wrt its
+// output (the heads' gradient wrt the features above the top layer)
+static const float* layer_x(const hab_policy* e, int l) { return e->WK + (l == 0 ? e->w_rnnin : e->w_out[l - 1]); }
+static int layer_ld(const hab_policy* e, int l) { return l == 0 ? e->rnn_ld : e->d.hidden; }
+static float* layer_dx(const hab_policy* e, int l) { return e->WK + (l == 0 ? e->w_drnnin : e->w_dlayer[l]); }
+static const float* layer_dout(const hab_policy* e, int l) { return l == e->L - 1 ? e->WK + e->w_dfeat : layer_dx(e, l + 1); }
+static PackInfo pack_info(const hab_pack_info* pack, int n) {
+    PackInfo pk;
+    pk.select_inds = pack->select_inds; pk.step_offsets = pack->step_offsets_host; pk.num_seqs_at_step = pack->num_seqs_at_step_host;
+    pk.frag_env = pack->frag_env; pk.frag_start = pack->frag_start; pk.P = pack->P; pk.F = pack->F; pk.max_len = pack->max_len;
+    pk.n_envs = n;
+    return pk;
 }
 
 extern "C" int hab_policy_encode(hab_policy* e, const hab_obs* obs, int n, float* out, hipStream_t stream) {
@@ -451,6 +490,75 @@ extern "C" int hab_policy_act(hab_policy* e, const hab_obs* obs, const float* hi
 }
 
 // ------------------------------------------------------------------------------------------
+// The recurrent encoder of hab_policy_evaluate, in the form e->form names (rnn_form)
+// ------------------------------------------------------------------------------------------
+// State entering the recurrence, per layer (h, and c for an LSTM): env j of the minibatch is frame j (t = 0), its arena row is rows[j].
+// Packed form: F fragments (frag_env / frag_start); time-major form: one per env (null, F = n).
+static int rnn_state_init(hab_policy* e, const float* hidden0, int hidden_env_stride, const int* rows, const uint8_t* masks,
+                          const int* frag_env, const int* frag_start, int F, const int* env_first_frame, hipStream_t s) {
+    const int H = e->d.hidden, L = e->L;
+    for (int l = 0; l < L; ++l) {
+        HAB_TRY(rnn_frag_init(hidden0 + (size_t)l * H, rows, hidden_env_stride, masks, rows, frag_env, frag_start, F, H,
+                              e->WK + e->w_hinit + (size_t)l * F * H, s, env_first_frame));
+        if (e->d.rnn_type == HAB_RNN_LSTM)
+            HAB_TRY(rnn_frag_init(hidden0 + (size_t)(L + l) * H, rows, hidden_env_stride, masks, rows, frag_env, frag_start, F, H,
+                                  e->WK + e->w_cinit + (size_t)l * F * H, s, env_first_frame));
+    }
+    return HAB_OK;
+}
+// Time-major: per time chunk, the encoder of its frames on `stream`, then its recurrence on the second stream -- which runs under the
+// encoder of the next chunk.  Bit-identical to the packed form.
+static int rnn_tm_forward(hab_policy* e, const hab_obs* obs, const int* rows, const float* hidden0, int hidden_env_stride,
+                          const uint8_t* masks, int B, int n, hipStream_t stream) {
+    float* W = e->WK;
+    const int H = e->d.hidden, L = e->L, NC = e->form.chunks, T = B / n, Tc = (T + NC - 1) / NC;
+    HAB_TRY(tm_setup(e, 2 * NC + 4));
+    hipStream_t sB = e->s2;
+    uint8_t* fmask = reinterpret_cast<uint8_t*>(W + e->w_fmask);
+    HAB_TRY(rnn_tm_prepare(masks, rows, B, fmask, reinterpret_cast<int*>(W + e->w_iota), stream));
+    HAB_TRY(rnn_state_init(e, hidden0, hidden_env_stride, rows, masks, nullptr, nullptr, n, nullptr, stream));
+    for (int c = 0; c < NC; ++c) {
+        const int t0 = c * Tc, t1 = std::min(T, t0 + Tc);
+        if (t0 >= t1) break;
+        HAB_TRY(encoder_forward(e, obs, masks, rows, B, stream, t0 * n, (t1 - t0) * n));
+        HAB_TRY(tm_order(e, c, stream, sB));  // also orders everything before this evaluate (parameters, pack info) ahead of stream B
+        for (int l = 0; l < L; ++l) {
+            Probe pr(e, HAB_PROBE_RNN_FWD, sB);
+            HAB_TRY(rnn_tm_layer_forward(e->d.rnn_type, H, layer_params(e, l), layer_work(e, l), layer_x(e, l), layer_ld(e, l),
+                                         W + e->w_hinit + (size_t)l * n * H, W + e->w_cinit + (size_t)l * n * H, fmask, n, T, t0, t1,
+                                         W + e->w_ws2, e->ws2_floats, sB));
+        }
+    }
+    return tm_order(e, NC, sB, stream);  // the heads (and everything after this evaluate) wait for the recurrence
+}
+// Packed: the recurrence over the whole minibatch (whose encoder ran before) on `stream`, as a wavefront or layer by layer.
+static int rnn_packed_forward(hab_policy* e, const int* rows, const float* hidden0, int hidden_env_stride, const uint8_t* masks,
+                              const hab_pack_info* pack, int n, hipStream_t stream) {
+    float* W = e->WK;
+    const int H = e->d.hidden, L = e->L;
+    const PackInfo pk = pack_info(pack, n);
+    HAB_TRY(rnn_state_init(e, hidden0, hidden_env_stride, rows, masks, pk.frag_env, pk.frag_start, pk.F, pack->env_first_frame, stream));
+    if (e->form.wave) {
+        RnnLayerParams lps[4]; RnnWork wks[4]; const float* hin[4]; const float* cin[4];
+        for (int l = 0; l < L; ++l) {
+            lps[l] = layer_params(e, l); wks[l] = layer_work(e, l);
+            hin[l] = W + e->w_hinit + (size_t)l * pk.F * H; cin[l] = W + e->w_cinit + (size_t)l * pk.F * H;
+        }
+        Probe pr(e, HAB_PROBE_RNN_FWD, stream);
+        const int rc = rnn_seq_wave_forward(e->d.rnn_type, H, L, lps, wks, layer_x(e, 0), layer_ld(e, 0), hin, cin, pk, W + e->w_ws,
+                                            e->ws_floats, stream);
+        return rc == 1 ? HAB_ERR_UNSUPPORTED : rc;
+    }
+    for (int l = 0; l < L; ++l) {
+        Probe pr(e, HAB_PROBE_RNN_FWD, stream);
+        HAB_TRY(rnn_seq_layer_forward(e->d.rnn_type, H, layer_params(e, l), layer_work(e, l), layer_x(e, l), layer_ld(e, l),
+                                      W + e->w_hinit + (size_t)l * pk.F * H, W + e->w_cinit + (size_t)l * pk.F * H, pk, W + e->w_ws,
+                                      e->ws_floats, stream));
+    }
+    return HAB_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // NetPolicy.evaluate_actions (rl/ppo/policy.py:361-402) on B = T*n frames gathered from the
 // rollout arena through rows[f]; activations are kept for hab_policy_backward.
 // ------------------------------------------------------------------------------------------
@@ -463,98 +571,19 @@ extern "C" int hab_policy_evaluate(hab_policy* e, const hab_obs* obs, const int*
     if (pack->P != B || pack->F <= 0 || pack->F > B || pack->max_len <= 0) return HAB_ERR_ARG;
     float* W = e->WK;
     const int H = e->d.hidden, L = e->L;
-    // Time-major chunked form (rnn.hip): a regular T x n minibatch of the SimpleCNN policy is cut into time chunks; the encoder of
-    // chunk c + 1 runs on `stream` while the recurrence walks chunk c on the engine's second stream.  Bit-identical to the packed form.
-    const int T = B / n;
-    // (ResNet policies too since round 4: their encoder runs per chunk behind a whole-batch ingest, engine_resnet.hip)
-    int NC = (e->Cin > 0 && rows && !pack->env_first_frame && (B % n) == 0 && T >= 2 && e->w_ws2 >= 0 && (int64_t)L * 2 * n <= 3 * (int64_t)e->d.max_frames)
-                 ? (e->rn ? tm_chunks_resnet_cfg(B) : tm_chunks_cfg()) : 0;
-    if (NC > T) NC = T;
-    const float* x = W + e->w_rnnin;
-    int ldx = e->rnn_ld;
-    if (NC > 0) {
-        HAB_TRY(tm_setup(e, 2 * NC + 4));
-        hipStream_t sB = e->s2;
-        uint8_t* fmask = reinterpret_cast<uint8_t*>(W + e->w_fmask);
-        int* iota = reinterpret_cast<int*>(W + e->w_iota);
-        HAB_TRY(rnn_tm_prepare(masks, rows, B, fmask, iota, stream));
-        for (int l = 0; l < L; ++l) {  // state entering t = 0: env j of the minibatch is frame j; its arena row is rows[j]
-            HAB_TRY(rnn_frag_init(hidden0 + (size_t)l * H, rows, hidden_env_stride, masks, rows, nullptr, nullptr, n, H,
-                                  W + e->w_hinit + (size_t)l * n * H, stream, nullptr));
-            if (e->d.rnn_type == HAB_RNN_LSTM)
-                HAB_TRY(rnn_frag_init(hidden0 + (size_t)(L + l) * H, rows, hidden_env_stride, masks, rows, nullptr, nullptr, n, H,
-                                      W + e->w_cinit + (size_t)l * n * H, stream, nullptr));
-        }
-        const int Tc = (T + NC - 1) / NC;
-        for (int c = 0; c < NC; ++c) {
-            const int t0 = c * Tc, t1 = std::min(T, t0 + Tc);
-            if (t0 >= t1) break;
-            HAB_TRY(encoder_forward(e, obs, masks, rows, B, stream, t0 * n, (t1 - t0) * n));
-            HAB_TRY(tm_order(e, c, stream, sB));  // also orders everything before this evaluate (parameters, pack info) ahead of stream B
-            const float* xl = W + e->w_rnnin;
-            int ldl = e->rnn_ld;
-            for (int l = 0; l < L; ++l) {
-                RnnLayerParams lp = layer_params(e, l);
-                RnnWork wk = layer_work(e, l);
-                Probe pr(e, HAB_PROBE_RNN_FWD, sB);
-                HAB_TRY(rnn_tm_layer_forward(e->d.rnn_type, H, lp, wk, xl, ldl, W + e->w_hinit + (size_t)l * n * H,
-                                             W + e->w_cinit + (size_t)l * n * H, fmask, n, T, t0, t1, W + e->w_ws2, e->ws2_floats, sB));
-                xl = wk.out;
-                ldl = H;
-            }
-        }
-        HAB_TRY(tm_order(e, NC, sB, stream));  // the heads (and everything after this evaluate) wait for the recurrence
-        x = W + e->w_out[L - 1];
-        ldx = H;
+    e->form = rnn_form(e, rows, pack, B, n);
+    if (e->form.chunks > 0) {
+        HAB_TRY(rnn_tm_forward(e, obs, rows, hidden0, hidden_env_stride, masks, B, n, stream));
     } else {
-    HAB_TRY(encoder_forward(e, obs, masks, rows, B, stream));
-    PackInfo pk;
-    pk.select_inds = pack->select_inds; pk.step_offsets = pack->step_offsets_host; pk.num_seqs_at_step = pack->num_seqs_at_step_host;
-    pk.frag_env = pack->frag_env; pk.frag_start = pack->frag_start; pk.P = pack->P; pk.F = pack->F; pk.max_len = pack->max_len;
-    pk.n_envs = n;
-    for (int l = 0; l < L; ++l) {
-        float* hinit = W + e->w_hinit + (size_t)l * pk.F * H;
-        float* cinit = W + e->w_cinit + (size_t)l * pk.F * H;
-        // env j of the minibatch is frame j (t = 0); its arena row is rows[j]
-        HAB_TRY(rnn_frag_init(hidden0 + (size_t)l * H, rows, hidden_env_stride, masks, rows, pk.frag_env, pk.frag_start, pk.F, H,
-                              hinit, stream, pack->env_first_frame));
-        if (e->d.rnn_type == HAB_RNN_LSTM)
-            HAB_TRY(rnn_frag_init(hidden0 + (size_t)(L + l) * H, rows, hidden_env_stride, masks, rows, pk.frag_env,
-                                  pk.frag_start, pk.F, H, cinit, stream, pack->env_first_frame));
+        HAB_TRY(encoder_forward(e, obs, masks, rows, B, stream));
+        HAB_TRY(rnn_packed_forward(e, rows, hidden0, hidden_env_stride, masks, pack, n, stream));
     }
-    // several layers: one launch per packed step for ALL layers (layer l one step behind layer l - 1), rnn.hip
-    static const int wave_cfg = hab_env_int("HAB_RNN_WAVE", 1);
-    e->last_wave = false;
-    if (wave_cfg && L >= 2 && L <= 4) {
-        RnnLayerParams lps[4]; RnnWork wks[4]; const float* hin[4]; const float* cin[4];
-        for (int l = 0; l < L; ++l) {
-            lps[l] = layer_params(e, l); wks[l] = layer_work(e, l);
-            hin[l] = W + e->w_hinit + (size_t)l * pk.F * H; cin[l] = W + e->w_cinit + (size_t)l * pk.F * H;
-        }
-        Probe pr(e, HAB_PROBE_RNN_FWD, stream);
-        const int rcw = rnn_seq_wave_forward(e->d.rnn_type, H, L, lps, wks, x, ldx, hin, cin, pk, W + e->w_ws, e->ws_floats, stream);
-        if (rcw != 0 && rcw != 1) return rcw;
-        e->last_wave = rcw == 0;
-        if (e->last_wave) { x = wks[L - 1].out; ldx = H; }
-    }
-    if (!e->last_wave)
-    for (int l = 0; l < L; ++l) {
-        float* hinit = W + e->w_hinit + (size_t)l * pk.F * H;
-        float* cinit = W + e->w_cinit + (size_t)l * pk.F * H;
-        RnnLayerParams lp = layer_params(e, l);
-        RnnWork wk = layer_work(e, l);
-        Probe pr(e, HAB_PROBE_RNN_FWD, stream);
-        HAB_TRY(rnn_seq_layer_forward(e->d.rnn_type, H, lp, wk, x, ldx, hinit, cinit, pk, W + e->w_ws, e->ws_floats, stream));
-        x = wk.out;
-        ldx = H;
-    }
-    }
-    e->last_tm = NC;
+    const float* feats = W + e->w_out[L - 1];  // rnn_output [B][H], whichever form ran
     if (e->d.action_dist == HAB_DIST_GAUSSIAN) {
         GaussHeadsArgs ga;
         ga.B = B; ga.H = H; ga.A = e->d.num_actions; ga.K = e->head_K; ga.flags = e->d.gauss_flags; ga.mode = 0;
         ga.min_std = e->d.gauss_min_std; ga.max_std = e->d.gauss_max_std;
-        ga.feats = x; ga.feats_ld = ldx; ga.w = e->p(e->i_aw); ga.b = e->p(e->i_ab);
+        ga.feats = feats; ga.feats_ld = H; ga.w = e->p(e->i_aw); ga.b = e->p(e->i_ab);
         ga.std_param = e->i_astd >= 0 ? e->p(e->i_astd) : nullptr; ga.w_critic = e->p(e->i_cw); ga.b_critic = e->p(e->i_cb);
         ga.actions_in = reinterpret_cast<const float*>(actions); ga.rows = rows; ga.noise = nullptr; ga.actions_out = nullptr;
         ga.value = value ? value : W + e->w_value; ga.logp = log_prob ? log_prob : W + e->w_logp;
@@ -563,7 +592,7 @@ extern "C" int hab_policy_evaluate(hab_policy* e, const hab_obs* obs, const int*
     } else {
     HeadsArgs ha;
         ha.B = B; ha.H = H; ha.A = e->d.num_actions; ha.mode = 0;
-        ha.feats = x; ha.feats_ld = ldx; ha.w_actor = e->p(e->i_aw); ha.b_actor = e->p(e->i_ab); ha.w_critic = e->p(e->i_cw); ha.b_critic = e->p(e->i_cb);
+        ha.feats = feats; ha.feats_ld = H; ha.w_actor = e->p(e->i_aw); ha.b_actor = e->p(e->i_ab); ha.w_critic = e->p(e->i_cw); ha.b_critic = e->p(e->i_cb);
         ha.actions_in = actions; ha.rows = rows; ha.noise = nullptr; ha.actions_out = nullptr;
         ha.value = value ? value : W + e->w_value; ha.logp = log_prob ? log_prob : W + e->w_logp;
         ha.entropy = entropy ? entropy : W + e->w_ent;
@@ -616,6 +645,82 @@ extern "C" int hab_policy_set_extra_grads(hab_policy* e, const float* d_rnn_outp
     return HAB_OK;
 }
 
+// SimpleCNN data-gradient chain (fc, conv3, conv2: per-frame work) of frames [f0, f0 + nB): d_rnnin[:, :H], which carries the ReLU mask,
+// -> d a3 -> d a2 -> d a1
+static int cnn_dgrad(hab_policy* e, int64_t f0, int nB, hipStream_t s) {
+    float* W = e->WK;
+    float* ws = W + e->w_ws;
+    const int64_t m1 = (int64_t)e->c1.Ho() * e->c1.Wo() * 32, m2 = (int64_t)e->c2.Ho() * e->c2.Wo() * 64, m3 = e->fc_in;
+    ConvDesc c2 = e->c2, c3 = e->c3;
+    c2.B = c3.B = nB;
+    { Probe pr(e, HAB_PROBE_FC_DGRAD, s);
+      HAB_TRY(linear_dgrad(W + e->w_drnnin + f0 * e->rnn_ld, e->rnn_ld, e->PK + e->pk_fc, e->fc_in, nullptr, 0, 0, W + e->w_da3 + f0 * m3,
+                           e->fc_in, nB, e->fc_in, e->d.hidden, 0, ws, e->ws_floats, s)); }
+    { Probe pr(e, HAB_PROBE_CONV3_DGRAD, s);
+      HAB_TRY(conv_dgrad(c3, W + e->w_da3 + f0 * m3, e->PK + e->pk_c3d, W + e->w_a2 + f0 * m2, nullptr, W + e->w_da2 + f0 * m2, ws,
+                         e->ws_floats, s)); }
+    { Probe pr(e, HAB_PROBE_CONV2_DGRAD, s);
+      HAB_TRY(conv_dgrad(c2, W + e->w_da2 + f0 * m2, e->PK + e->pk_c2d, W + e->w_a1 + f0 * m1, nullptr, W + e->w_da1 + f0 * m1, ws,
+                         e->ws_floats, s)); }
+    return HAB_OK;
+}
+// Time-major BPTT on the second stream: the chunks of the last evaluate from the last to the first, layers top down; behind each chunk
+// the SimpleCNN data-gradient chain of its frames runs on `stream`.  Then the recurrent weight gradients over all frames, on the second
+// stream beside the encoder's; the caller joins it (event 2 * NC + 3) where the policy's tail needs them.
+static int rnn_tm_backward(hab_policy* e, int B, hipStream_t stream) {
+    float* W = e->WK;
+    const int H = e->d.hidden, L = e->L, n = e->last_n, T = B / n, NC = e->form.chunks, Tc = (T + NC - 1) / NC;
+    hipStream_t sB = e->s2;
+    const uint8_t* fmask = reinterpret_cast<const uint8_t*>(W + e->w_fmask);
+    const int* iota = reinterpret_cast<const int*>(W + e->w_iota);
+    HAB_TRY(tm_order(e, NC + 1, stream, sB));  // the head gradients are in place
+    for (int c = NC - 1; c >= 0; --c) {
+        const int t0 = c * Tc, t1 = std::min(T, t0 + Tc);
+        if (t0 >= t1) continue;
+        for (int l = L - 1; l >= 0; --l) {  // layer 0 masks the ReLU(visual fc) columns of rnn_in (fused ReLU backward)
+            Probe pr(e, HAB_PROBE_RNN_BWD, sB);
+            HAB_TRY(rnn_tm_layer_backward(e->d.rnn_type, H, layer_params(e, l), layer_work(e, l), layer_dout(e, l), layer_dx(e, l), layer_ld(e, l),
+                                          l == 0 ? layer_x(e, 0) : nullptr, layer_ld(e, l), H, fmask, iota, n, T, t0, t1,
+                                          W + e->w_scratch + (size_t)l * 2 * n * H, W + e->w_ws2, e->ws2_floats, sB));
+        }
+        if (!e->rn) {
+            HAB_TRY(tm_order(e, NC + 2 + c, sB, stream));  // d_rnnin of the chunk's frames is final
+            HAB_TRY(cnn_dgrad(e, (int64_t)t0 * n, (t1 - t0) * n, stream));
+        }
+    }
+    for (int l = L - 1; l >= 0; --l)
+        HAB_TRY(rnn_tm_layer_param_grads(e->d.rnn_type, H, layer_params(e, l), layer_work(e, l), layer_x(e, l), layer_ld(e, l), B, W + e->w_ws2,
+                                         e->ws2_floats, sB));
+    return HAB_OK;
+}
+// Packed BPTT on `stream`, in the form the forward took (a wavefront's upper layers keep no gi of their own: the backward must mirror it).
+// blind0: the baseline net's rnn_in is the goal vector alone -- no gradient is wanted for it; nofc: no ReLU(visual fc) columns at the head
+// of rnn_in, i.e. nothing to mask (both blind forms; the blind ResNet net still wants d rnn_in for its embeddings).  Otherwise layer 0
+// masks those columns (fused ReLU backward).
+static int rnn_packed_backward(hab_policy* e, const hab_pack_info* pack, hipStream_t stream) {
+    float* W = e->WK;
+    const int H = e->d.hidden, L = e->L;
+    const PackInfo pk = pack_info(pack, e->last_n);
+    const bool blind0 = !e->rn && e->Cin == 0, nofc = e->Cin == 0;
+    const float* x0 = layer_x(e, 0);
+    if (e->form.wave) {
+        RnnLayerParams lps[4]; RnnWork wks[4]; const float* wiht[4];
+        for (int l = 0; l < L; ++l) { lps[l] = layer_params(e, l); wks[l] = layer_work(e, l); wiht[l] = l ? e->PK + e->pk_wiht[l] : nullptr; }
+        Probe pr(e, HAB_PROBE_RNN_BWD, stream);
+        const int rc = rnn_seq_wave_backward(e->d.rnn_type, H, L, lps, wiht, wks, x0, e->rnn_ld, layer_dout(e, L - 1), blind0 ? nullptr : layer_dx(e, 0),
+                                             e->rnn_ld, nofc ? nullptr : x0, e->rnn_ld, nofc ? 0 : H, pk, W + e->w_scratch, W + e->w_ws, e->ws_floats,
+                                             stream);
+        return rc == 1 ? HAB_ERR_UNSUPPORTED : rc;
+    }
+    for (int l = L - 1; l >= 0; --l) {
+        Probe pr(e, HAB_PROBE_RNN_BWD, stream);
+        HAB_TRY(rnn_seq_layer_backward(e->d.rnn_type, H, layer_params(e, l), layer_work(e, l), layer_x(e, l), layer_ld(e, l), layer_dout(e, l),
+                                       (blind0 && l == 0) ? nullptr : layer_dx(e, l), layer_ld(e, l), (l == 0 && !nofc) ? x0 : nullptr,
+                                       layer_ld(e, l), nofc ? 0 : H, pk, W + e->w_scratch, W + e->w_ws, e->ws_floats, stream));
+    }
+    return HAB_OK;
+}
+
 static int policy_backward_impl(hab_policy* e, const hab_obs* obs, const int* rows, const int64_t* actions,
                                 const hab_pack_info* pack, const float* d_value, const float* d_log_prob,
                                 const float* d_entropy, hipStream_t stream) {
@@ -627,10 +732,6 @@ static int policy_backward_impl(hab_policy* e, const hab_obs* obs, const int* ro
     const int H = e->d.hidden, L = e->L, B = e->last_B, A = e->d.num_actions;
     e->cur_stream = stream;
     e->comm_first = -1;
-    PackInfo pk;
-    pk.select_inds = pack->select_inds; pk.step_offsets = pack->step_offsets_host; pk.num_seqs_at_step = pack->num_seqs_at_step_host;
-    pk.frag_env = pack->frag_env; pk.frag_start = pack->frag_start; pk.P = pack->P; pk.F = pack->F; pk.max_len = pack->max_len;
-    pk.n_envs = e->last_n;
     const float* feats = W + e->w_out[L - 1];
     if (e->d.action_dist == HAB_DIST_GAUSSIAN) {
         const int K = e->head_K;
@@ -655,160 +756,44 @@ static int policy_backward_impl(hab_policy* e, const hab_obs* obs, const int* ro
         HAB_TRY(colsum(W + e->w_dzv, 8, B, A, e->g(e->i_ab), 0, ws, e->ws_floats, stream));
         HAB_TRY(colsum(W + e->w_dv, 1, B, 1, e->g(e->i_cb), 0, ws, e->ws_floats, stream));
     }
+    const int NC = e->form.chunks;
     if (e->xg_feat || e->xg_perc) {
-        if (e->last_tm > 0) return HAB_ERR_UNSUPPORTED;  // (time-major chunks consume d_rnnin chunk by chunk: the bridge never takes that form)
+        if (NC > 0) return HAB_ERR_UNSUPPORTED;  // (time-major chunks consume d_rnnin chunk by chunk: the bridge never takes that form)
         if (e->xg_feat) {
             add_rows_kernel<<<(int)std::min<long long>(1024, cdivl((long long)B * H, 256)), 256, 0, stream>>>(W + e->w_dfeat, e->xg_feat, (long long)B * H);
             HAB_LAUNCH_CHECK();
         }
     }
-    ConvDesc c1 = e->c1, c2 = e->c2, c3 = e->c3;
-    c1.B = c2.B = c3.B = B;
-    const float* dfc = W + e->w_drnnin;
-    if (e->last_tm > 0 && e->rn) {
-        // ResNet policy, time-major form: BPTT walks the chunks on the second stream, the recurrent weight gradients follow there, and
-        // the encoder's backward (whose weight gradients reduce over ALL frames: one pass over the whole minibatch) starts once
-        // d_rnnin is complete.  The forward is where this form pays for the ResNets: the recurrence of chunk c runs under the encoder
-        // of chunk c + 1.
-        const int n = e->last_n, T = B / n, NC = e->last_tm, Tc = (T + NC - 1) / NC;
-        hipStream_t sB = e->s2;
-        const uint8_t* fmask = reinterpret_cast<const uint8_t*>(W + e->w_fmask);
-        const int* iota = reinterpret_cast<const int*>(W + e->w_iota);
-        float* ws2 = W + e->w_ws2;
-        HAB_TRY(tm_order(e, NC + 1, stream, sB));  // the head gradients are in place
-        for (int c = NC - 1; c >= 0; --c) {
-            const int t0 = c * Tc, t1 = std::min(T, t0 + Tc);
-            if (t0 >= t1) continue;
-            for (int l = L - 1; l >= 0; --l) {
-                RnnLayerParams lp = layer_params(e, l);
-                RnnWork wk = layer_work(e, l);
-                const float* dout = l == L - 1 ? W + e->w_dfeat : W + e->w_dlayer[l + 1];
-                const float* xin = l == 0 ? W + e->w_rnnin : W + e->w_out[l - 1];
-                const int ldx = l == 0 ? e->rnn_ld : H;
-                float* dx = l == 0 ? W + e->w_drnnin : W + e->w_dlayer[l];
-                Probe pr(e, HAB_PROBE_RNN_BWD, sB);
-                HAB_TRY(rnn_tm_layer_backward(e->d.rnn_type, H, lp, wk, dout, dx, ldx, l == 0 ? xin : nullptr, ldx, H, fmask, iota, n, T, t0, t1,
-                                              W + e->w_scratch + (size_t)l * 2 * n * H, ws2, e->ws2_floats, sB));
-            }
+    if (NC > 0) {
+        HAB_TRY(rnn_tm_backward(e, B, stream));
+    } else {
+        HAB_TRY(rnn_packed_backward(e, pack, stream));
+        if (e->xg_perc) {  // d rnn_in[:, :H] += d perception_embed, through the ReLU between them (the mask the layer-0 backward applied to its own part)
+            add_masked_cols_kernel<<<(int)std::min<long long>(1024, cdivl((long long)B * H, 256)), 256, 0, stream>>>(
+                W + e->w_drnnin, e->rnn_ld, e->xg_perc, W + e->w_rnnin, e->rnn_ld, B, H);
+            HAB_LAUNCH_CHECK();
         }
-        for (int l = L - 1; l >= 0; --l) {
-            RnnLayerParams lp = layer_params(e, l);
-            RnnWork wk = layer_work(e, l);
-            HAB_TRY(rnn_tm_layer_param_grads(e->d.rnn_type, H, lp, wk, l == 0 ? W + e->w_rnnin : W + e->w_out[l - 1], l == 0 ? e->rnn_ld : H, B, ws2,
-                                             e->ws2_floats, sB));
+        if (!e->rn && e->Cin == 0) {  // blind baseline policy: the recurrent encoder and the heads are all there is
+            grad_tail_ready(e, e->i_wih[0]);
+            return HAB_OK;
         }
-        HAB_TRY(tm_order(e, 2 * NC + 3, sB, stream));  // d_rnnin and the recurrent gradients are final
+    }
+    if (e->rn) {  // the encoder's weight gradients reduce over ALL frames: one pass over the whole minibatch once d_rnnin is complete
+        if (NC > 0) HAB_TRY(tm_order(e, 2 * NC + 3, e->s2, stream));  // d_rnnin and the recurrent gradients are final
         Probe pr(e, HAB_PROBE_ENC_BWD, stream);
         return resnet_encoder_backward(e, obs, e->last_masks, rows, B, stream);
     }
-    if (e->last_tm > 0 && !e->rn) {
-        // Time-major chunked backward: BPTT walks the chunks from the last to the first on the second stream; behind each chunk the
-        // DATA-gradient chain of its frames (fc, conv3, conv2 -- per-frame work) runs on `stream`; the weight gradients, which reduce over
-        // all frames, follow once at the end (the recurrent ones on the second stream, beside the encoder's).
-        const int n = e->last_n, T = B / n, NC = e->last_tm, Tc = (T + NC - 1) / NC;
-        hipStream_t sB = e->s2;
-        const uint8_t* fmask = reinterpret_cast<const uint8_t*>(W + e->w_fmask);
-        const int* iota = reinterpret_cast<const int*>(W + e->w_iota);
-        float* ws2 = W + e->w_ws2;
-        const int64_t m1 = (int64_t)e->c1.Ho() * e->c1.Wo() * 32, m2 = (int64_t)e->c2.Ho() * e->c2.Wo() * 64, m3 = e->fc_in;
-        HAB_TRY(tm_order(e, NC + 1, stream, sB));  // the head gradients are in place
-        for (int c = NC - 1; c >= 0; --c) {
-            const int t0 = c * Tc, t1 = std::min(T, t0 + Tc);
-            if (t0 >= t1) continue;
-            const int64_t f0 = (int64_t)t0 * n;
-            const int nB = (t1 - t0) * n;
-            for (int l = L - 1; l >= 0; --l) {
-                RnnLayerParams lp = layer_params(e, l);
-                RnnWork wk = layer_work(e, l);
-                const float* dout = l == L - 1 ? W + e->w_dfeat : W + e->w_dlayer[l + 1];
-                const float* xin = l == 0 ? W + e->w_rnnin : W + e->w_out[l - 1];
-                const int ldx = l == 0 ? e->rnn_ld : H;
-                float* dx = l == 0 ? W + e->w_drnnin : W + e->w_dlayer[l];
-                Probe pr(e, HAB_PROBE_RNN_BWD, sB);
-                HAB_TRY(rnn_tm_layer_backward(e->d.rnn_type, H, lp, wk, dout, dx, ldx, l == 0 ? xin : nullptr, ldx, H, fmask, iota, n, T, t0, t1,
-                                              W + e->w_scratch + (size_t)l * 2 * n * H, ws2, e->ws2_floats, sB));
-            }
-            HAB_TRY(tm_order(e, NC + 2 + c, sB, stream));  // d_rnnin of the chunk's frames is final
-            ConvDesc k2 = c2, k3 = c3;
-            k2.B = k3.B = nB;
-            { Probe pr(e, HAB_PROBE_FC_DGRAD, stream);
-              HAB_TRY(linear_dgrad(dfc + f0 * e->rnn_ld, e->rnn_ld, e->PK + e->pk_fc, e->fc_in, nullptr, 0, 0, W + e->w_da3 + f0 * m3, e->fc_in, nB,
-                                   e->fc_in, H, 0, ws, e->ws_floats, stream)); }
-            { Probe pr(e, HAB_PROBE_CONV3_DGRAD, stream);
-              HAB_TRY(conv_dgrad(k3, W + e->w_da3 + f0 * m3, e->PK + e->pk_c3d, W + e->w_a2 + f0 * m2, nullptr, W + e->w_da2 + f0 * m2, ws,
-                                 e->ws_floats, stream)); }
-            { Probe pr(e, HAB_PROBE_CONV2_DGRAD, stream);
-              HAB_TRY(conv_dgrad(k2, W + e->w_da2 + f0 * m2, e->PK + e->pk_c2d, W + e->w_a1 + f0 * m1, nullptr, W + e->w_da1 + f0 * m1, ws,
-                                 e->ws_floats, stream)); }
-        }
-        for (int l = L - 1; l >= 0; --l) {  // recurrent weight gradients over all frames: second stream, beside the encoder's below
-            RnnLayerParams lp = layer_params(e, l);
-            RnnWork wk = layer_work(e, l);
-            HAB_TRY(rnn_tm_layer_param_grads(e->d.rnn_type, H, lp, wk, l == 0 ? W + e->w_rnnin : W + e->w_out[l - 1], l == 0 ? e->rnn_ld : H, B, ws2,
-                                             e->ws2_floats, sB));
-        }
-        { Probe pr(e, HAB_PROBE_FC_WGRAD, stream);
-          HAB_TRY(linear_wgrad(dfc, e->rnn_ld, W + e->w_a3, e->fc_in, e->g(e->i_fcw), e->fc_in, B, H, e->fc_in, 32, e->fc_in / 32, 0,
-                               ws, e->ws_floats, stream)); }
-        HAB_TRY(colsum(dfc, e->rnn_ld, B, H, e->g(e->i_fcb), 0, ws, e->ws_floats, stream));
-        HAB_TRY(tm_order(e, 2 * NC + 3, sB, stream));  // recurrent gradients final before the tail of the arena is announced
-        grad_tail_ready(e, e->i_fcw);
-    } else {
-    // recurrent layers, top down
-    const float* dout = W + e->w_dfeat;
-    bool waved = false;
-    if (e->last_wave) {  // the forward ran the layers as a wavefront (upper layers' wk.gi do not exist): mirror it
-        RnnLayerParams lps[4]; RnnWork wks[4]; const float* wiht[4];
-        for (int l = 0; l < L; ++l) { lps[l] = layer_params(e, l); wks[l] = layer_work(e, l); wiht[l] = l ? e->PK + e->pk_wiht[l] : nullptr; }
-        // blind0: the baseline net's rnn_in is the goal vector alone -- no gradient is wanted for it; nofc: no ReLU(visual fc) columns
-        // at the head of rnn_in, i.e. nothing to mask (both blind forms; the blind ResNet net still wants d rnn_in for its embeddings)
-        const bool blind0 = !e->rn && e->Cin == 0, nofc = e->Cin == 0;
-        const float* x0 = W + e->w_rnnin;
-        Probe pr(e, HAB_PROBE_RNN_BWD, stream);
-        const int rcw = rnn_seq_wave_backward(e->d.rnn_type, H, L, lps, wiht, wks, x0, e->rnn_ld, dout, blind0 ? nullptr : W + e->w_drnnin, e->rnn_ld,
-                                              nofc ? nullptr : x0, e->rnn_ld, nofc ? 0 : H, pk, W + e->w_scratch, ws, e->ws_floats, stream);
-        if (rcw != 0) return rcw == 1 ? HAB_ERR_UNSUPPORTED : rcw;
-        waved = true;
-    }
-    for (int l = L - 1; l >= 0 && !waved; --l) {
-        RnnLayerParams lp = layer_params(e, l);
-        RnnWork wk = layer_work(e, l);
-        const float* x = l == 0 ? W + e->w_rnnin : W + e->w_out[l - 1];
-        const int ldx = l == 0 ? e->rnn_ld : H;
-        float* dx = l == 0 ? W + e->w_drnnin : W + e->w_dlayer[l];
-        const int lddx = l == 0 ? e->rnn_ld : H;
-        // layer 0: the first H columns of rnn_in are ReLU(fc) -> mask them here (fused ReLU backward); a blind policy's rnn_in is the
-        // goal vector alone: no mask, and no gradient is wanted for it
-        const bool blind0 = !e->rn && e->Cin == 0 && l == 0, nofc = e->Cin == 0;
-        Probe pr(e, HAB_PROBE_RNN_BWD, stream);
-        HAB_TRY(rnn_seq_layer_backward(e->d.rnn_type, H, lp, wk, x, ldx, dout, blind0 ? nullptr : dx, lddx, (l == 0 && !nofc) ? x : nullptr, ldx,
-                                       nofc ? 0 : H, pk, W + e->w_scratch, ws, e->ws_floats, stream));
-        dout = dx;
-    }
-    if (e->xg_perc) {  // d rnn_in[:, :H] += d perception_embed, through the ReLU between them (the mask the layer-0 backward applied to its own part)
-        add_masked_cols_kernel<<<(int)std::min<long long>(1024, cdivl((long long)B * H, 256)), 256, 0, stream>>>(
-            W + e->w_drnnin, e->rnn_ld, e->xg_perc, W + e->w_rnnin, e->rnn_ld, B, H);
-        HAB_LAUNCH_CHECK();
-    }
-    if (!e->rn && e->Cin == 0) {  // blind baseline policy: the recurrent encoder and the heads are all there is
-        grad_tail_ready(e, e->i_wih[0]);
-        return HAB_OK;
-    }
-    if (e->rn) { Probe pr(e, HAB_PROBE_ENC_BWD, stream); return resnet_encoder_backward(e, obs, e->last_masks, rows, B, stream); }
     // fc (Flatten -> Linear -> ReLU): d_rnnin[:, :H] already carries the ReLU mask
+    const float* dfc = W + e->w_drnnin;
     { Probe pr(e, HAB_PROBE_FC_WGRAD, stream);
       HAB_TRY(linear_wgrad(dfc, e->rnn_ld, W + e->w_a3, e->fc_in, e->g(e->i_fcw), e->fc_in, B, H, e->fc_in, 32, e->fc_in / 32, 0,
                            ws, e->ws_floats, stream)); }
     HAB_TRY(colsum(dfc, e->rnn_ld, B, H, e->g(e->i_fcb), 0, ws, e->ws_floats, stream));
+    if (NC > 0) HAB_TRY(tm_order(e, 2 * NC + 3, e->s2, stream));  // recurrent gradients final before the tail of the arena is announced
     grad_tail_ready(e, e->i_fcw);  // fc, recurrent encoder and heads are final; the conv stack's gradients follow
-    { Probe pr(e, HAB_PROBE_FC_DGRAD, stream);
-      HAB_TRY(linear_dgrad(dfc, e->rnn_ld, e->PK + e->pk_fc, e->fc_in, nullptr, 0, 0, W + e->w_da3, e->fc_in, B, e->fc_in, H, 0,
-                           ws, e->ws_floats, stream)); }
-    { Probe pr(e, HAB_PROBE_CONV3_DGRAD, stream);
-      HAB_TRY(conv_dgrad(c3, W + e->w_da3, e->PK + e->pk_c3d, W + e->w_a2, nullptr, W + e->w_da2, ws, e->ws_floats, stream)); }
-    { Probe pr(e, HAB_PROBE_CONV2_DGRAD, stream);
-      HAB_TRY(conv_dgrad(c2, W + e->w_da2, e->PK + e->pk_c2d, W + e->w_a1, nullptr, W + e->w_da1, ws, e->ws_floats, stream)); }
-    }
+    if (NC == 0) HAB_TRY(cnn_dgrad(e, 0, B, stream));  // (time-major: chunk by chunk, behind the chunk's BPTT)
+    ConvDesc c1 = e->c1, c2 = e->c2, c3 = e->c3;
+    c1.B = c2.B = c3.B = B;
     // conv3 (no ReLU after it; its input a2 is post-ReLU -> mask on the data gradient)
     { Probe pr(e, HAB_PROBE_CONV3_WGRAD, stream);
       HAB_TRY(conv_wgrad(c3, W + e->w_a2, W + e->w_da3, e->g(e->i_c3w), e->g(e->i_c3b), ws, e->ws_floats, stream)); }

@@ -357,16 +357,7 @@ int build_resnet(hab_policy* e) {
     e->w_step_h = wk.take((int64_t)d.max_envs * H * 2);
     e->ws_floats = (int64_t)32 << 20;
     e->w_ws = wk.take(e->ws_floats);
-    // second stream of the time-major chunked recurrence (engine.hip): its own split-K scratch (same cap: the split-K plans, hence the
-    // bits, must not depend on the stream), the dense per-frame episode-start mask, an iota
-    // -- only when that form is selected (default for ResNet policies: packed; measured slower, engine.hip): every ResNet engine, incl. each
-    // VER inference worker's private one, would otherwise carry 128 MB + 5 bytes per frame for nothing (w_ws2 < 0 keeps the packed form)
-    if (tm_chunks_resnet_cfg((int)B) > 0) {  // (B = max_frames: the form this engine can ever select)
-        e->ws2_floats = e->ws_floats;
-        e->w_ws2 = wk.take(e->ws2_floats);
-        e->w_fmask = wk.take((B + 3) / 4 + 64);
-        e->w_iota = wk.take(B + 64);
-    }
+    plan_tm_workspace(e, wk);  // (ResNet policies select the time-major form by default from 4096 frames per minibatch on, engine.hip)
     e->work_floats = wk.used;
     return HAB_OK;
 }

@@ -431,12 +431,15 @@ def test_autograd_bridge_matches_fused_path():
 
 
 # (2 and 3 layers run the packed recurrence as a layer wavefront, csrc/rnn.hip: 64 -> 4 waves per workgroup, 128 / 512 -> 8)
-@pytest.mark.parametrize("rnn_type,layers,hidden", [("LSTM", 2, 64), ("GRU", 2, 64), ("GRU", 1, 512), ("LSTM", 1, 256), ("LSTM", 3, 128),
-                                                    ("GRU", 3, 64)])
-def test_engine_lstm_gru_multilayer_vs_oracle(rnn_type, layers, hidden):
+MULTILAYER_CASES = [("LSTM", 2, 64), ("GRU", 2, 64), ("GRU", 1, 512), ("LSTM", 1, 256), ("LSTM", 3, 128), ("GRU", 3, 64)]
+
+
+@pytest.mark.parametrize("rnn_type,layers,hidden", MULTILAYER_CASES)
+def test_engine_lstm_gru_multilayer_vs_oracle(rnn_type, layers, hidden, time_major=False):
     """The engine also runs LSTM / multi-layer encoders on the baseline net; checked against the oracle's
     masked-scan restatement incl. all gradients (autograd on the oracle).  hidden 512 / 256 = the benchmark width: the
-    8-wave recurrent kernels and the vector-load heads kernel only exist for hidden % 128 / % 256 == 0."""
+    8-wave recurrent kernels and the vector-load heads kernel only exist for hidden % 128 / % 256 == 0.  Dense frames
+    (rows=None): the packed form."""
     from habitat_amd.engine import DevicePackInfo, PolicyEngine
     H = W = 44
     T, n = 7, 3
@@ -460,18 +463,27 @@ def test_engine_lstm_gru_multilayer_vs_oracle(rnn_type, layers, hidden):
     gv, glp, gent = (torch.from_numpy(rng.standard_normal((B, 1)).astype(np.float32)) for _ in range(3))
     ((v * gv).sum() + (lp * glp).sum() + (ent * gent).sum()).backward()
     pack = DevicePackInfo(np.logical_not(masks.view(T, n).numpy()), "cuda")
+    rows = torch.arange(B, dtype=torch.int32, device="cuda") if time_major else None
     dv, dl, de = (torch.zeros(B, device="cuda") for _ in range(3))
-    eng.evaluate(rgb.cuda(), depth.cuda(), goal.cuda(), None, h0.cuda(), masks.cuda(), actions.cuda(), pack, B, n, value=dv, log_prob=dl, entropy=de)
+    eng.evaluate(rgb.cuda(), depth.cuda(), goal.cuda(), rows, h0.cuda(), masks.cuda(), actions.cuda(), pack, B, n, value=dv, log_prob=dl, entropy=de)
     assert rel_ok(dv.cpu().numpy(), v.detach().numpy().reshape(-1))
     assert rel_ok(dl.cpu().numpy(), lp.detach().numpy().reshape(-1))
     assert rel_ok(de.cpu().numpy(), ent.detach().numpy().reshape(-1))
     hf = torch.zeros(n, Lh, hidden, device="cuda")
     eng.final_hidden(hf)
     assert rel_ok(hf.cpu().numpy(), hfin.detach().numpy())
-    eng.backward(rgb.cuda(), depth.cuda(), goal.cuda(), None, actions.cuda(), pack, gv.view(-1).cuda(), glp.view(-1).cuda(), gent.view(-1).cuda())
+    eng.backward(rgb.cuda(), depth.cuda(), goal.cuda(), rows, actions.cuda(), pack, gv.view(-1).cuda(), glp.view(-1).cuda(), gent.view(-1).cuda())
     bad = [(k, float((g.cpu() - p[k].grad).abs().max()), float(p[k].grad.abs().max())) for k, g in eng.grad_views.items()
            if not rel_ok(g.cpu().numpy(), p[k].grad.numpy(), tol=1e-4, floor=1e-4)]
     assert not bad, bad
+
+
+@pytest.mark.parametrize("rnn_type,layers,hidden", MULTILAYER_CASES)
+def test_engine_lstm_gru_multilayer_time_major_vs_oracle(rnn_type, layers, hidden):
+    """The same cases and tolerances through the time-major form (frames gathered through identity rows: T = 7 steps in 4 chunks on the
+    engine's second stream, csrc/engine.hip): the persistent recurrence at hidden 128 / 256 / 512 (1 / 2 / 4 K-chunks per wave,
+    csrc/rnn_persist.h), one launch per step at hidden 64."""
+    test_engine_lstm_gru_multilayer_vs_oracle(rnn_type, layers, hidden, time_major=True)
 
 
 def test_blind_baseline_policy_vs_oracle():

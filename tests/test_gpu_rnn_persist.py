@@ -2,8 +2,8 @@
 workgroups of a row tile through write-through stores + an agent-scope arrival counter) against the step-per-launch form it replaces
 (csrc/rnn.hip, selected by matrix-path bit 12): the two run the same MFMA sequence and the same summation trees, so every output of the
 engine's evaluate -- values, log-probs, entropy, final hidden state -- and every gradient must be EQUAL bit for bit.  The oracle parity of
-either form then is the other's (tests/test_gpu_policy.py::test_engine_lstm_gru_multilayer_vs_oracle runs through the persistent form at
-hidden 512 / 256 / 128; the golden updates at hidden 512).
+either form is pinned directly: tests/test_gpu_policy.py::test_engine_lstm_gru_multilayer_time_major_vs_oracle runs the persistent form at
+hidden 512 / 256 / 128 and the step-per-launch form at hidden 64 (its packed twin, test_engine_lstm_gru_multilayer_vs_oracle, takes neither).
 
 Cases: GRU and LSTM, 1 and 2 layers, hidden 128 / 256 / 512, one row tile with fewer than 16 environments, several row tiles with a ragged
 last one, chunk lengths that do and do not divide T (HAB_RNN_CHUNKS, default 4, is read once per process), episode starts in every step,
