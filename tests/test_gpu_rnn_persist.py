@@ -1,9 +1,11 @@
 """GPU: the persistent time-major recurrence (csrc/rnn_persist.h: ONE launch per layer and time chunk, state exchanged between the
 workgroups of a row tile through write-through stores + an agent-scope arrival counter) against the step-per-launch form it replaces
 (csrc/rnn.hip, selected by matrix-path bit 12): the two run the same MFMA sequence and the same summation trees, so every output of the
-engine's evaluate -- values, log-probs, entropy, final hidden state -- and every gradient must be EQUAL bit for bit.  The oracle parity of
-either form is pinned directly: tests/test_gpu_policy.py::test_engine_lstm_gru_multilayer_time_major_vs_oracle runs the persistent form at
-hidden 512 / 256 / 128 and the step-per-launch form at hidden 64 (its packed twin, test_engine_lstm_gru_multilayer_vs_oracle, takes neither).
+engine's evaluate -- values, log-probs, entropy, final hidden state -- and every gradient must be EQUAL bit for bit.  Bit identity of two
+forms that share rnn_gates.h, the operand layout and the MFMA index maps says nothing about a mistake in those: each form is pinned to a
+float64 reference of the recurrence on its own in tests/test_gpu_rnn_reference.py (the persistent form at hidden 128 / 256 / 512 and 1 .. 15
+row tiles, step launches at every other width, at 16 tiles and -- forced through bit 12 -- at three tiles; the packed form at all of them),
+and to the fp32 oracle of the whole policy at T = 7, n = 3 in tests/test_gpu_policy.py::test_engine_lstm_gru_multilayer_time_major_vs_oracle.
 
 Cases: GRU and LSTM, 1 and 2 layers, hidden 128 / 256 / 512, one row tile with fewer than 16 environments, several row tiles with a ragged
 last one, chunk lengths that do and do not divide T (HAB_RNN_CHUNKS, default 4, is read once per process), episode starts in every step,
