@@ -46,20 +46,22 @@ struct hab_policy {
     hab::ConvDesc c1, c2, c3;  // SimpleCNN geometry (B filled per call)
     int fc_in = 0, rnn_in = 0, rnn_ld = 0, G_ = 3, L = 1;
     // param indices
-    int i_c1w, i_c1b, i_c2w, i_c2b, i_c3w, i_c3b, i_fcw, i_fcb, i_aw, i_ab, i_cw, i_cb;
+    int i_c1w = -1, i_c1b = -1, i_c2w = -1, i_c2b = -1, i_c3w = -1, i_c3b = -1, i_fcw = -1, i_fcb = -1, i_aw = -1, i_ab = -1, i_cw = -1, i_cb = -1;
     int i_astd = -1;   // Gaussian head: state-independent std parameter `action_distribution.std` (or -1)
     int head_K = 0;    // Gaussian head: linear outputs (A or 2A)
     int64_t w_gsaved = -1;  // Gaussian head: [B][16] mu / std / chain factors of the last evaluate
     std::vector<int> i_wih, i_whh, i_bih, i_bhh;
     // packed offsets
-    int64_t pk_c1f, pk_c2f, pk_c2d, pk_c3f, pk_c3d, pk_fc;
+    int64_t pk_c1f = -1, pk_c2f = -1, pk_c2d = -1, pk_c3f = -1, pk_c3d = -1, pk_fc = -1;
     int64_t pk_c1img = -1;  // conv1's bf16 weight image for the patch-resident kernel, rebuilt by every repack (-1: no image for this filter)
     std::vector<int64_t> pk_whht;
     std::vector<int64_t> pk_wiht;  // layers >= 1: W_ih transposed [H][G*H] (layer wavefront BPTT, rnn.hip); entry 0 unused (-1)
     int64_t pk_wih0 = -1;  // layer 0 W_ih, rows padded with zeros to rnn_ld floats (fused input projection of the rollout step, rnn.hip)
     // workspace offsets (floats)
-    int64_t w_a1, w_a2, w_a3, w_rnnin, w_da1, w_da2, w_da3, w_drnnin, w_hinit, w_cinit, w_feat_d, w_probs, w_logitsn, w_dzv,
-        w_dv, w_dfeat, w_scratch, w_ws, w_value, w_logp, w_ent, w_hmask, w_gistep, w_step_h;
+    int64_t w_a1 = -1, w_a2 = -1, w_a3 = -1, w_da1 = -1, w_da2 = -1, w_da3 = -1;
+    // shared tail (plan_tail_workspace)
+    int64_t w_rnnin = -1, w_drnnin = -1, w_hinit = -1, w_cinit = -1, w_probs = -1, w_logitsn = -1, w_dzv = -1, w_dv = -1, w_dfeat = -1,
+            w_scratch = -1, w_value = -1, w_logp = -1, w_ent = -1, w_hmask = -1, w_gistep = -1, w_step_h = -1, w_ws = -1;
     std::vector<int64_t> w_gi, w_gates, w_hn, w_hprev, w_cprev, w_c, w_out, w_dgi, w_dgh, w_dlayer;
     int64_t ws_floats = 0;
     int last_B = 0, last_n = 0;
@@ -111,9 +113,14 @@ inline int add_param(hab_policy* e, const std::string& name, std::initializer_li
     e->params.push_back(s);
     return (int)e->params.size() - 1;
 }
+inline int conv_out(int x, int k, int s, int p) { return (x + 2 * p - k) / s + 1; }
 
-
-void plan_tm_workspace(hab_policy* e, Arena& wk);  // the time-major form's scratch, if this engine can ever select that form (engine.hip)
+// The recurrent encoder, the action head and the critic -- the tail both policy families share (engine.hip).  rnn.hip and heads.hip read
+// these indices and offsets for either family, so each builder calls the same four functions where its tail goes.
+void add_tail_params(hab_policy* e);                               // parameter table, the reference's state_dict() order
+void pack_tail(hab_policy* e, Arena& pk);                          // kernel-layout copies of the recurrent weights
+void plan_tail_workspace(hab_policy* e, Arena& wk, int64_t ws_floats);  // w_rnnin .. w_step_h, then w_ws (ws_floats) and the time-major scratch
+int repack_tail(hab_policy* e, hipStream_t s);                     // fills what pack_tail took
 int build_resnet(hab_policy* e);
 void destroy_resnet(hab_policy* e);
 int resnet_repack(hab_policy* e, hipStream_t s);

@@ -17,7 +17,68 @@
 
 using namespace hab;
 
-static int conv_out(int x, int k, int s, int p) { return (x + 2 * p - k) / s + 1; }
+// ---- the tail both policy families share: recurrent encoder, action head, critic (declared in engine.h) ----
+static void plan_tm_workspace(hab_policy* e, Arena& wk);  // the time-major form's scratch, if this engine can ever select that form
+void add_tail_params(hab_policy* e) {
+    const hab_policy_desc& d = e->d;
+    const int H = d.hidden;
+    const std::string rn = "net.state_encoder.rnn.";
+    for (int l = 0; l < d.rnn_layers; ++l) {
+        const int in = l == 0 ? e->rnn_in : H;
+        const std::string sfx = "_l" + std::to_string(l);
+        e->i_wih.push_back(add_param(e, rn + "weight_ih" + sfx, {e->G_ * H, in}));
+        e->i_whh.push_back(add_param(e, rn + "weight_hh" + sfx, {e->G_ * H, H}));
+        e->i_bih.push_back(add_param(e, rn + "bias_ih" + sfx, {e->G_ * H}));
+        e->i_bhh.push_back(add_param(e, rn + "bias_hh" + sfx, {e->G_ * H}));
+    }
+    if (d.action_dist == HAB_DIST_GAUSSIAN) {  // GaussianNet (utils/common.py:124-149): the std parameter is registered before the linear layer
+        if (d.gauss_flags & HAB_GAUSS_USE_STD_PARAM) e->i_astd = add_param(e, "action_distribution.std", {d.num_actions});
+        e->head_K = (d.gauss_flags & HAB_GAUSS_USE_STD_PARAM) ? d.num_actions : 2 * d.num_actions;
+        e->i_aw = add_param(e, "action_distribution.mu_maybe_std.weight", {e->head_K, H});
+        e->i_ab = add_param(e, "action_distribution.mu_maybe_std.bias", {e->head_K});
+    } else {
+        e->i_aw = add_param(e, "action_distribution.linear.weight", {d.num_actions, H});
+        e->i_ab = add_param(e, "action_distribution.linear.bias", {d.num_actions});
+    }
+    e->i_cw = add_param(e, "critic.fc.weight", {1, H});
+    e->i_cb = add_param(e, "critic.fc.bias", {1});
+}
+void pack_tail(hab_policy* e, Arena& pk) {
+    const int64_t GH = (int64_t)e->G_ * e->d.hidden;
+    for (int l = 0; l < e->L; ++l) e->pk_whht.push_back(pk.take(GH * e->d.hidden));
+    for (int l = 0; l < e->L; ++l) e->pk_wiht.push_back(l == 0 ? -1 : pk.take(GH * e->d.hidden));
+    e->pk_wih0 = pk.take(GH * e->rnn_ld);  // layer 0's W_ih with rows padded to rnn_ld (fused step projection of `act`)
+}
+int repack_tail(hab_policy* e, hipStream_t s) {
+    const int H = e->d.hidden;
+    for (int l = 0; l < e->L; ++l) HAB_TRY(transpose2d(e->p(e->i_whh[l]), e->PK + e->pk_whht[l], e->G_ * H, H, s));
+    for (int l = 1; l < e->L; ++l) HAB_TRY(transpose2d(e->p(e->i_wih[l]), e->PK + e->pk_wiht[l], e->G_ * H, H, s));
+    return pad_rows(e->p(e->i_wih[0]), e->PK + e->pk_wih0, e->G_ * H, e->rnn_in, e->rnn_ld, s);
+}
+void plan_tail_workspace(hab_policy* e, Arena& wk, int64_t ws_floats) {
+    const hab_policy_desc& d = e->d;
+    const int64_t B = d.max_frames, F = d.max_frames;  // F: worst case, every frame its own fragment
+    const int64_t H = d.hidden, GH = e->G_ * H;
+    e->w_rnnin = wk.take(B * e->rnn_ld); e->w_drnnin = wk.take(B * e->rnn_ld);
+    e->w_hinit = wk.take(e->L * F * H); e->w_cinit = wk.take(e->L * F * H);
+    for (int l = 0; l < e->L; ++l) {
+        e->w_gi.push_back(wk.take(B * GH)); e->w_gates.push_back(wk.take(B * GH));
+        e->w_hn.push_back(wk.take(B * H)); e->w_hprev.push_back(wk.take(B * H));
+        e->w_cprev.push_back(wk.take(B * H)); e->w_c.push_back(wk.take(B * H)); e->w_out.push_back(wk.take(B * H));
+        e->w_dgi.push_back(wk.take(B * GH)); e->w_dgh.push_back(wk.take(B * GH));
+        e->w_dlayer.push_back(wk.take(B * H));
+    }
+    e->w_probs = wk.take(B * 8); e->w_logitsn = wk.take(B * 8); e->w_dzv = wk.take(B * 8); e->w_dv = wk.take(B);
+    e->w_dfeat = wk.take(B * H); e->w_scratch = wk.take((int64_t)std::max(3, 2 * e->L) * F * H);
+    e->w_value = wk.take(B); e->w_logp = wk.take(B); e->w_ent = wk.take(B);
+    if (d.action_dist == HAB_DIST_GAUSSIAN) e->w_gsaved = wk.take(B * 16);
+    e->w_hmask = wk.take(2 * H * e->L * d.max_envs);
+    e->w_gistep = wk.take(d.max_envs * GH);
+    e->w_step_h = wk.take(d.max_envs * H * 2);
+    e->ws_floats = ws_floats;  // split-K / column-sum scratch
+    e->w_ws = wk.take(ws_floats);
+    plan_tm_workspace(e, wk);
+}
 
 static int build_baseline(hab_policy* e) {
     const hab_policy_desc& d = e->d;
@@ -47,22 +108,8 @@ static int build_baseline(hab_policy* e) {
         e->i_c3b = add_param(e, ve + "4.bias", {32});
         e->i_fcw = add_param(e, ve + "6.weight", {H, e->fc_in});
         e->i_fcb = add_param(e, ve + "6.bias", {H});
-    } else {
-        e->i_c1w = e->i_c1b = e->i_c2w = e->i_c2b = e->i_c3w = e->i_c3b = e->i_fcw = e->i_fcb = -1;
     }
-    const std::string rn = "net.state_encoder.rnn.";
-    for (int l = 0; l < d.rnn_layers; ++l) {
-        const int in = l == 0 ? e->rnn_in : H;
-        const std::string sfx = "_l" + std::to_string(l);
-        e->i_wih.push_back(add_param(e, rn + "weight_ih" + sfx, {e->G_ * H, in}));
-        e->i_whh.push_back(add_param(e, rn + "weight_hh" + sfx, {e->G_ * H, H}));
-        e->i_bih.push_back(add_param(e, rn + "bias_ih" + sfx, {e->G_ * H}));
-        e->i_bhh.push_back(add_param(e, rn + "bias_hh" + sfx, {e->G_ * H}));
-    }
-    e->i_aw = add_param(e, "action_distribution.linear.weight", {d.num_actions, H});
-    e->i_ab = add_param(e, "action_distribution.linear.bias", {d.num_actions});
-    e->i_cw = add_param(e, "critic.fc.weight", {1, H});
-    e->i_cb = add_param(e, "critic.fc.bias", {1});
+    add_tail_params(e);
 
     Arena pk;
     e->pk_c1f = pk.take(32 * 64 * (blind ? 4 : e->Cin));
@@ -72,36 +119,16 @@ static int build_baseline(hab_policy* e) {
     e->pk_c3f = pk.take(32 * 9 * 64);
     e->pk_c3d = pk.take(32 * 9 * 64);
     e->pk_fc = pk.take((int64_t)H * std::max(e->fc_in, 4));
-    for (int l = 0; l < d.rnn_layers; ++l) e->pk_whht.push_back(pk.take((int64_t)e->G_ * H * H));
-    for (int l = 0; l < d.rnn_layers; ++l) e->pk_wiht.push_back(l == 0 ? -1 : pk.take((int64_t)e->G_ * H * H));
-    e->pk_wih0 = pk.take((int64_t)e->G_ * H * e->rnn_ld);  // layer 0's W_ih with rows padded to rnn_ld (fused step projection of `act`)
+    pack_tail(e, pk);
     e->packed_floats = pk.used;
 
     Arena wk;
     const int64_t B = d.max_frames;
-    const int64_t F = d.max_frames;  // worst case: every frame its own fragment
     const int64_t m1 = blind ? 0 : (int64_t)e->c1.Ho() * e->c1.Wo() * 32, m2 = blind ? 0 : (int64_t)e->c2.Ho() * e->c2.Wo() * 64, m3 = e->fc_in;
     e->w_a1 = wk.take(B * m1); e->w_a2 = wk.take(B * m2); e->w_a3 = wk.take(B * m3);
     e->w_da1 = wk.take(B * m1); e->w_da2 = wk.take(B * m2); e->w_da3 = wk.take(B * m3);
-    e->w_rnnin = wk.take(B * e->rnn_ld); e->w_drnnin = wk.take(B * e->rnn_ld);
-    e->w_hinit = wk.take((int64_t)d.rnn_layers * F * H); e->w_cinit = wk.take((int64_t)d.rnn_layers * F * H);
-    for (int l = 0; l < d.rnn_layers; ++l) {
-        e->w_gi.push_back(wk.take(B * e->G_ * H)); e->w_gates.push_back(wk.take(B * e->G_ * H));
-        e->w_hn.push_back(wk.take(B * H)); e->w_hprev.push_back(wk.take(B * H));
-        e->w_cprev.push_back(wk.take(B * H)); e->w_c.push_back(wk.take(B * H)); e->w_out.push_back(wk.take(B * H));
-        e->w_dgi.push_back(wk.take(B * e->G_ * H)); e->w_dgh.push_back(wk.take(B * e->G_ * H));
-        e->w_dlayer.push_back(wk.take(B * H));
-    }
-    e->w_probs = wk.take(B * 8); e->w_logitsn = wk.take(B * 8); e->w_dzv = wk.take(B * 8); e->w_dv = wk.take(B);
-    e->w_dfeat = wk.take(B * H); e->w_scratch = wk.take((int64_t)std::max(3, 2 * d.rnn_layers) * F * H);
-    e->w_value = wk.take(B); e->w_logp = wk.take(B); e->w_ent = wk.take(B);
-    e->w_hmask = wk.take((int64_t)2 * d.rnn_layers * d.max_envs * H);
-    e->w_gistep = wk.take((int64_t)d.max_envs * e->G_ * H);
-    e->w_step_h = wk.take((int64_t)d.max_envs * H * 2);
-    // split-K / column-sum scratch: big enough for 64 slabs of the largest weight-gradient (fc) or 1024 colsum rows
-    e->ws_floats = std::max<int64_t>((int64_t)16 << 20, (int64_t)8 * H * e->fc_in / 4);
-    e->w_ws = wk.take(e->ws_floats);
-    plan_tm_workspace(e, wk);
+    // w_ws: big enough for 64 slabs of the largest weight-gradient (fc) or 1024 colsum rows
+    plan_tail_workspace(e, wk, std::max<int64_t>((int64_t)16 << 20, (int64_t)8 * H * e->fc_in / 4));
     e->work_floats = wk.used;
     return HAB_OK;
 }
@@ -200,13 +227,7 @@ extern "C" int hab_policy_bind(hab_policy* e, float* params, float* grads, float
 extern "C" int hab_policy_repack(hab_policy* e, hipStream_t stream) {
     if (!e || !e->P) return HAB_ERR_ARG;
     if (e->rn) return resnet_repack(e, stream);
-    const int H = e->d.hidden;
-    if (e->pk_wih0 >= 0) HAB_TRY(pad_rows(e->p(e->i_wih[0]), e->PK + e->pk_wih0, e->G_ * H, e->rnn_in, e->rnn_ld, stream));
-    if (e->Cin == 0) {  // blind baseline policy: only the recurrent weights have a kernel-layout copy
-        for (int l = 0; l < e->L; ++l) HAB_TRY(transpose2d(e->p(e->i_whh[l]), e->PK + e->pk_whht[l], e->G_ * H, H, stream));
-        for (int l = 1; l < e->L; ++l) HAB_TRY(transpose2d(e->p(e->i_wih[l]), e->PK + e->pk_wiht[l], e->G_ * H, H, stream));
-        return HAB_OK;
-    }
+    if (e->Cin == 0) return repack_tail(e, stream);  // blind baseline policy: only the recurrent weights have a kernel-layout copy
     HAB_TRY(repack_conv(e->p(e->i_c1w), e->PK + e->pk_c1f, nullptr, 32, e->Cin, 8, 8, e->Cin, stream));
     if (e->pk_c1img >= 0) {  // (was one launch in front of EVERY conv1 call: 12 -> 11 launches per rollout step)
         const int rc = obs_conv_weight_image(e->PK + e->pk_c1f, 32, 8, 8, e->Cin, e->PK + e->pk_c1img, stream);
@@ -214,10 +235,8 @@ extern "C" int hab_policy_repack(hab_policy* e, hipStream_t stream) {
     }
     HAB_TRY(repack_conv(e->p(e->i_c2w), e->PK + e->pk_c2f, e->PK + e->pk_c2d, 64, 32, 4, 4, 32, stream));
     HAB_TRY(repack_conv(e->p(e->i_c3w), e->PK + e->pk_c3f, e->PK + e->pk_c3d, 32, 64, 3, 3, 64, stream));
-    HAB_TRY(repack_flatten(e->p(e->i_fcw), e->PK + e->pk_fc, H, 32, e->fc_in / 32, stream));
-    for (int l = 0; l < e->L; ++l) HAB_TRY(transpose2d(e->p(e->i_whh[l]), e->PK + e->pk_whht[l], e->G_ * H, H, stream));
-    for (int l = 1; l < e->L; ++l) HAB_TRY(transpose2d(e->p(e->i_wih[l]), e->PK + e->pk_wiht[l], e->G_ * H, H, stream));
-    return HAB_OK;
+    HAB_TRY(repack_flatten(e->p(e->i_fcw), e->PK + e->pk_fc, e->d.hidden, 32, e->fc_in / 32, stream));
+    return repack_tail(e, stream);
 }
 
 // ---- probes: HIP-event timing of one tagged kernel call site (bench.py's roofline leg) ----
@@ -344,7 +363,7 @@ static RnnForm rnn_form(const hab_policy* e, const int* rows, const hab_pack_inf
 // Second stream of the time-major form: its own split-K scratch (same cap as the first stream's: the split-K plans, hence the bits, must not
 // depend on the stream), the dense per-frame episode-start mask, an iota -- only in an engine that can ever select that form (every
 // engine, incl. each VER inference worker's private one, would otherwise carry 128 MB + 5 bytes per frame for nothing).
-void plan_tm_workspace(hab_policy* e, Arena& wk) {
+static void plan_tm_workspace(hab_policy* e, Arena& wk) {
     const int64_t B = e->d.max_frames;
     if (rnn_form_cfg(e, (int)B, 1, true).chunks == 0) return;
     e->ws2_floats = e->ws_floats;

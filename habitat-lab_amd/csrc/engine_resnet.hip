@@ -76,17 +76,16 @@ struct ResNetPlan {
     int64_t gdense_floats = 0;
     int cmax = 0;
     int nlayers[4] = {2, 2, 2, 2};
-    // stem of the last forward: GroupNorm + ReLU + max-pool ran fused (the normalised stem output was not stored); stem_act_valid: it
-    // has been materialised since (a debug tap asked for it) -- the backward then takes the unfused form, which reads it as the ReLU
-    // mask (so that activations patched through the tap are honoured, oracle/parity.py::MaskInjector)
-    bool stem_fused = false, stem_act_valid = true;
+    // the normalised stem output (stem.w_out) of the last evaluate is in memory: false after a fused training forward (GroupNorm + ReLU +
+    // max-pool in one pass, never stored), true after an unfused one, and true once HAB_TAP_STEM has materialised it -- the backward then
+    // takes the unfused form, which reads it as the ReLU mask (so that activations patched through the tap are honoured,
+    // oracle/parity.py::MaskInjector)
+    bool stem_act_stored = true;
     // training-mode RunningMeanAndVar with both stem kernels of the strip family: the ingest leaves x0 UN-normalised (it accumulates the batch
     // moments in the same pass) and the stem forward / weight gradient apply the per-channel affine while staging (w_stats + 32: 16 floats).
     // x0_raw: x0 of the last forward is in that state (a debug tap of the encoder input normalises it in place and clears the flag).
     bool stem_takes_raw = false, x0_raw = false;
 };
-
-static int conv_out(int x, int k, int s, int p) { return (x + 2 * p - k) / s + 1; }
 
 static int add_conv_gn(hab_policy* e, RnConv& c, const std::string& wname, const std::string& gnname, int cin_real) {
     c.i_w = add_param(e, wname + ".weight", {c.cd.Cout, cin_real, c.cd.KH, c.cd.KW});
@@ -251,26 +250,7 @@ int build_resnet(hab_policy* e) {
     e->rnn_in = (blind ? 0 : H) + 32 * r->nslots;
     e->rnn_ld = (e->rnn_in + 15) & ~15;
     if (e->rnn_ld != e->rnn_in) return HAB_ERR_UNSUPPORTED;  // (32-wide embedding slots behind a hidden size % 64 == 0: never padded)
-    const std::string rn = "net.state_encoder.rnn.";
-    for (int l = 0; l < d.rnn_layers; ++l) {
-        const int in = l == 0 ? e->rnn_in : H;
-        const std::string sfx = "_l" + std::to_string(l);
-        e->i_wih.push_back(add_param(e, rn + "weight_ih" + sfx, {e->G_ * H, in}));
-        e->i_whh.push_back(add_param(e, rn + "weight_hh" + sfx, {e->G_ * H, H}));
-        e->i_bih.push_back(add_param(e, rn + "bias_ih" + sfx, {e->G_ * H}));
-        e->i_bhh.push_back(add_param(e, rn + "bias_hh" + sfx, {e->G_ * H}));
-    }
-    if (gauss) {  // GaussianNet (utils/common.py:124-149): the std parameter is registered before the linear layer
-        if (d.gauss_flags & HAB_GAUSS_USE_STD_PARAM) e->i_astd = add_param(e, "action_distribution.std", {d.num_actions});
-        e->head_K = (d.gauss_flags & HAB_GAUSS_USE_STD_PARAM) ? d.num_actions : 2 * d.num_actions;
-        e->i_aw = add_param(e, "action_distribution.mu_maybe_std.weight", {e->head_K, H});
-        e->i_ab = add_param(e, "action_distribution.mu_maybe_std.bias", {e->head_K});
-    } else {
-        e->i_aw = add_param(e, "action_distribution.linear.weight", {d.num_actions, H});
-        e->i_ab = add_param(e, "action_distribution.linear.bias", {d.num_actions});
-    }
-    e->i_cw = add_param(e, "critic.fc.weight", {1, H});
-    e->i_cb = add_param(e, "critic.fc.bias", {1});
+    add_tail_params(e);
 
     // ---- packed weights ----
     Arena pk;
@@ -290,14 +270,12 @@ int build_resnet(hab_policy* e) {
     pack_conv(r->comp, true);
     r->pk_fc = pk.take((int64_t)H * r->fc_in);
     }
-    for (int l = 0; l < d.rnn_layers; ++l) e->pk_whht.push_back(pk.take((int64_t)e->G_ * H * H));
-    for (int l = 0; l < d.rnn_layers; ++l) e->pk_wiht.push_back(l == 0 ? -1 : pk.take((int64_t)e->G_ * H * H));
-    e->pk_wih0 = pk.take((int64_t)e->G_ * H * e->rnn_ld);
+    pack_tail(e, pk);
     e->packed_floats = pk.used;
 
     // ---- workspace ----
     Arena wk;
-    const int64_t B = d.max_frames, F = d.max_frames;
+    const int64_t B = d.max_frames;
     if (!blind) r->w_x0 = wk.take(B * r->H2 * r->W2 * r->cpad);
     auto place = [&](RnConv& c, bool own_out) {
         c.w_raw = wk.take(B * c.out_floats());
@@ -338,26 +316,7 @@ int build_resnet(hab_policy* e) {
     if (r->gdense_floats) r->w_gdense = wk.take(r->gdense_floats);
     }  // !blind
     r->w_embsave = wk.take(B * 4 * EMB_MAX_SLOTS);
-    // shared tail (RNN, heads) -- same layout as the SimpleCNN engine
-    e->w_rnnin = wk.take(B * e->rnn_ld); e->w_drnnin = wk.take(B * e->rnn_ld);
-    e->w_hinit = wk.take((int64_t)d.rnn_layers * F * H); e->w_cinit = wk.take((int64_t)d.rnn_layers * F * H);
-    for (int l = 0; l < d.rnn_layers; ++l) {
-        e->w_gi.push_back(wk.take(B * e->G_ * H)); e->w_gates.push_back(wk.take(B * e->G_ * H));
-        e->w_hn.push_back(wk.take(B * H)); e->w_hprev.push_back(wk.take(B * H));
-        e->w_cprev.push_back(wk.take(B * H)); e->w_c.push_back(wk.take(B * H)); e->w_out.push_back(wk.take(B * H));
-        e->w_dgi.push_back(wk.take(B * e->G_ * H)); e->w_dgh.push_back(wk.take(B * e->G_ * H));
-        e->w_dlayer.push_back(wk.take(B * H));
-    }
-    e->w_probs = wk.take(B * 8); e->w_logitsn = wk.take(B * 8); e->w_dzv = wk.take(B * 8); e->w_dv = wk.take(B);
-    e->w_dfeat = wk.take(B * H); e->w_scratch = wk.take((int64_t)std::max(3, 2 * d.rnn_layers) * F * H);
-    e->w_value = wk.take(B); e->w_logp = wk.take(B); e->w_ent = wk.take(B);
-    if (gauss) e->w_gsaved = wk.take(B * 16);
-    e->w_hmask = wk.take((int64_t)2 * d.rnn_layers * d.max_envs * H);
-    e->w_gistep = wk.take((int64_t)d.max_envs * e->G_ * H);
-    e->w_step_h = wk.take((int64_t)d.max_envs * H * 2);
-    e->ws_floats = (int64_t)32 << 20;
-    e->w_ws = wk.take(e->ws_floats);
-    plan_tm_workspace(e, wk);  // (ResNet policies select the time-major form by default from 4096 frames per minibatch on, engine.hip)
+    plan_tail_workspace(e, wk, (int64_t)32 << 20);  // (ResNet policies select the time-major form by default from 4096 frames per minibatch on)
     e->work_floats = wk.used;
     return HAB_OK;
 }
@@ -369,7 +328,6 @@ void destroy_resnet(hab_policy* e) {
 
 int resnet_repack(hab_policy* e, hipStream_t s) {
     ResNetPlan* r = e->rn;
-    const int H = e->d.hidden;
     auto rp = [&](const RnConv& c, int cin_real) {
         if (c.cgroups > 1)
             return repack_conv_grouped(e->p(c.i_w), e->PK + c.pk_f, c.pk_d >= 0 ? e->PK + c.pk_d : nullptr, c.cd.Cout, c.cd.C, c.cgroups,
@@ -387,12 +345,9 @@ int resnet_repack(hab_policy* e, hipStream_t s) {
         for (const auto& c : r->convs) { HAB_TRY(rp(c, c.cd.C)); HAB_TRY(planes(c)); }
         HAB_TRY(rp(r->comp, r->comp.cd.C));
         HAB_TRY(planes(r->comp));
-        HAB_TRY(repack_flatten(e->p(r->i_fcw), e->PK + r->pk_fc, H, r->comp_c, r->comp_hw, s));
+        HAB_TRY(repack_flatten(e->p(r->i_fcw), e->PK + r->pk_fc, e->d.hidden, r->comp_c, r->comp_hw, s));
     }
-    for (int l = 0; l < e->L; ++l) HAB_TRY(transpose2d(e->p(e->i_whh[l]), e->PK + e->pk_whht[l], e->G_ * H, H, s));
-    for (int l = 1; l < e->L; ++l) HAB_TRY(transpose2d(e->p(e->i_wih[l]), e->PK + e->pk_wiht[l], e->G_ * H, H, s));
-    HAB_TRY(pad_rows(e->p(e->i_wih[0]), e->PK + e->pk_wih0, e->G_ * H, e->rnn_in, e->rnn_ld, s));
-    return HAB_OK;
+    return repack_tail(e, s);
 }
 
 // Embedding slots in the order PointNavResNetNet.forward concatenates them (resnet_policy.py:662-755):
@@ -419,28 +374,26 @@ static int fill_embed_slots(hab_policy* e, const hab_obs* obs, EmbedSlot* sl, bo
     return (ok && n == r->nslots) ? HAB_OK : HAB_ERR_ARG;
 }
 
-// conv -> raw, GroupNorm (+residual, +ReLU) -> out.  f0: first frame of the workspace buffers this call works on (time-major chunks of
-// a minibatch, engine.hip); `in` / `residual` are already offset by the caller.
+// GroupNorm of conv c's output on frames [f0, f0 + B) of its workspace buffers: raw -> out (+residual, +ReLU), statistics kept
+static GnArgs gn_args(hab_policy* e, const RnConv& c, int B, int f0, int relu, const float* residual) {
+    float* W = e->WK;
+    GnArgs g;
+    g.x = W + c.w_raw + (int64_t)f0 * c.out_floats(); g.y = W + c.w_out + (int64_t)f0 * c.out_floats();
+    g.gamma = e->p(c.i_gamma); g.beta = e->p(c.i_beta); g.residual = residual;
+    g.mean = W + c.w_mean + (int64_t)f0 * c.groups; g.rstd = W + c.w_rstd + (int64_t)f0 * c.groups;
+    g.B = B; g.HW = c.cd.Ho() * c.cd.Wo(); g.C = c.cd.Cout; g.groups = c.groups; g.relu = relu; g.eps = 1e-5f;
+    g.scratch = W + e->w_ws; g.scratch_floats = e->ws_floats;  // chunk-parallel statistics for frames > 128 KB
+    return g;
+}
+
+// A block or compression convolution: conv -> raw, GroupNorm (+residual, +ReLU) -> out.  f0: first frame of the workspace buffers this
+// call works on (time-major chunks of a minibatch, engine.hip); `in` / `residual` are already offset by the caller.
 static int conv_gn_forward(hab_policy* e, const RnConv& c, const float* in, const float* residual, int relu, int B, hipStream_t s, int f0 = 0) {
     float* W = e->WK;
     ConvDesc cd = c.cd;
     cd.B = B;
     float* raw = W + c.w_raw + (int64_t)f0 * c.out_floats();
-    float* out = W + c.w_out + (int64_t)f0 * c.out_floats();
-    float* mean = W + c.w_mean + (int64_t)f0 * c.groups;
-    float* rstd = W + c.w_rstd + (int64_t)f0 * c.groups;
-    if (&c == &e->rn->stem && c.pk_p >= 0) {  // stem: input strip resident in LDS (stem_conv_strip.h)
-        const int rc = stem_conv_forward(in, reinterpret_cast<const unsigned short*>(e->PK + c.pk_p), raw, B, cd.H, cd.W, s,
-                                         e->rn->x0_raw ? W + e->rn->w_stats + 32 : nullptr);
-        if (rc == 1 && e->rn->x0_raw) return HAB_ERR_UNSUPPORTED;
-        if (rc != 0 && rc != 1) return rc;
-        if (rc == 1) HAB_TRY(conv_fwd(cd, in, e->PK + c.pk_f, nullptr, raw, 0, W + e->w_ws, e->ws_floats, s));
-        GnArgs g;
-        g.x = raw; g.y = out; g.gamma = e->p(c.i_gamma); g.beta = e->p(c.i_beta); g.residual = residual;
-        g.mean = mean; g.rstd = rstd; g.B = B; g.HW = cd.Ho() * cd.Wo(); g.C = cd.Cout; g.groups = c.groups;
-        g.relu = relu; g.eps = 1e-5f; g.scratch = W + e->w_ws; g.scratch_floats = e->ws_floats;
-        return groupnorm_forward(g, s);
-    }
+    const GnArgs g = gn_args(e, c, B, f0, relu, residual);
     // the rollout's act / encode (small batches, nothing kept for a backward): convolution + GroupNorm in one launch (conv_gn_slab.h).
     // Small evaluate minibatches keep the unfused pair -- the kernels every update-sized minibatch runs, so that the golden update tests
     // exercise the production learner path (the fused kernels can also write the pre-normalisation output and the statistics a backward
@@ -449,18 +402,13 @@ static int conv_gn_forward(hab_policy* e, const RnConv& c, const float* in, cons
     if (c.pk_p >= 0 && B <= cgs_max_b && !e->save_acts) {
         ConvGnArgs q;
         q.x = in; q.w_planes = reinterpret_cast<const unsigned short*>(e->PK + c.pk_p); q.gamma = e->p(c.i_gamma); q.beta = e->p(c.i_beta);
-        q.residual = residual; q.y = out;
+        q.residual = residual; q.y = g.y;
         q.B = B; q.H = cd.H; q.W = cd.W; q.C = cd.C; q.Cout = cd.Cout; q.KH = cd.KH; q.KW = cd.KW; q.stride = cd.stride; q.pad = cd.pad;
         q.groups = c.groups; q.relu = relu; q.eps = 1e-5f;
         const int rc = conv_gn_fused(q, s);
         if (rc != 1) return rc;
     }
     HAB_TRY(conv_fwd(cd, in, e->PK + c.pk_f, nullptr, raw, 0, W + e->w_ws, e->ws_floats, s));
-    GnArgs g;
-    g.x = raw; g.y = out; g.gamma = e->p(c.i_gamma); g.beta = e->p(c.i_beta); g.residual = residual;
-    g.mean = mean; g.rstd = rstd; g.B = B; g.HW = cd.Ho() * cd.Wo(); g.C = cd.Cout; g.groups = c.groups;
-    g.relu = relu; g.eps = 1e-5f;
-    g.scratch = W + e->w_ws; g.scratch_floats = e->ws_floats;  // chunk-parallel statistics for frames > 128 KB
     return groupnorm_forward(g, s);
 }
 
@@ -598,6 +546,28 @@ static int resnet_ingest(hab_policy* e, const hab_obs* obs, const int* rows, int
     return HAB_OK;
 }
 
+// Stem convolution of frames [f0, f0 + B): x0 -> stem.w_raw, by the strip kernel where it covers the geometry (stem_conv_strip.h).
+// want_part: the strip kernel leaves the GroupNorm partial statistics of its strips (STEM_STAT_ROWS output rows) in w_ws, which spares
+// the fused GroupNorm its statistics pass; *have_part: it did.
+static int stem_conv(hab_policy* e, int B, int f0, hipStream_t s, bool want_part = false, bool* have_part = nullptr) {
+    ResNetPlan* r = e->rn;
+    float* W = e->WK;
+    const RnConv& st = r->stem;
+    const float* x0 = W + r->w_x0 + (int64_t)f0 * st.in_floats();
+    float* raw = W + st.w_raw + (int64_t)f0 * st.out_floats();
+    ConvDesc cd = st.cd;
+    cd.B = B;
+    const int stat_chunks = (cd.Ho() + STEM_STAT_ROWS - 1) / STEM_STAT_ROWS;
+    want_part = want_part && (st.groups == 8 || st.groups == 16 || st.groups == 32) && (size_t)B * stat_chunks * st.groups * 2 <= e->ws_floats;
+    const int rc = st.pk_p >= 0 ? stem_conv_forward(x0, reinterpret_cast<const unsigned short*>(e->PK + st.pk_p), raw, B, cd.H, cd.W, s,
+                                                    r->x0_raw ? W + r->w_stats + 32 : nullptr, want_part ? W + e->w_ws : nullptr, st.groups) : 1;
+    if (have_part) *have_part = want_part && rc == 0;
+    if (rc != 0 && rc != 1) return rc;
+    if (rc == 1 && r->x0_raw) return HAB_ERR_UNSUPPORTED;  // (stem_takes_raw was decided on the same coverage predicates)
+    if (rc == 1) HAB_TRY(conv_fwd(cd, x0, e->PK + st.pk_f, nullptr, raw, 0, W + e->w_ws, e->ws_floats, s));
+    return HAB_OK;
+}
+
 // stem, blocks, compression on frames [f0, f0 + B) of a Btot-frame batch: x0 -> comp.w_out [frame][Hf*Wf][C].  Every workspace buffer
 // is [frame][...], so a chunk works at frame offset f0 of each; decisions that the backward (which sees the whole batch) must share --
 // the fused stem -- are taken for Btot.
@@ -606,60 +576,36 @@ static int resnet_layers_forward(hab_policy* e, int Btot, int f0, int B, hipStre
     float* W = e->WK;
     const int64_t F0 = f0;
     const RnConv& st = r->stem;
-    const int64_t stem_out = st.out_floats(), pool_floats = (int64_t)r->poolH * r->poolW * st.cd.Cout;
-    float* x0 = W + r->w_x0 + F0 * r->H2 * r->W2 * r->cpad;
-    float* stem_raw = W + st.w_raw + F0 * stem_out;
-    float* stem_act = W + st.w_out + F0 * stem_out;
+    const int sH = st.cd.Ho(), sW = st.cd.Wo();
+    const int64_t pool_floats = (int64_t)r->poolH * r->poolW * st.cd.Cout;
     float* pool = W + r->w_pool + F0 * pool_floats;
     uint8_t* pool_idx = reinterpret_cast<uint8_t*>(W + r->w_pool_idx) + F0 * pool_floats;  // one byte per pooled element
-    ConvDesc scd = st.cd;
-    scd.B = B;
-    // the strip kernel leaves the GroupNorm partial statistics of its strips (8 output rows) with the output: no statistics pass
-    const int stat_chunks = (scd.Ho() + STEM_STAT_ROWS - 1) / STEM_STAT_ROWS;
-    float* gn_part = W + e->w_ws;
+    const GnArgs g = gn_args(e, st, B, f0, 1, nullptr);
+    GnArgs gf = g;  // fused with ReLU + max-pool: the normalised frame is never written
+    gf.y = nullptr;
+    const float* gn_part = W + e->w_ws;
     bool have_part = false;
-    auto stem_conv = [&](bool want_part) -> int {
-        want_part = want_part && (st.groups == 8 || st.groups == 16 || st.groups == 32) &&
-                    (size_t)B * stat_chunks * st.groups * 2 <= e->ws_floats;
-        const int rcs = st.pk_p >= 0 ? stem_conv_forward(x0, reinterpret_cast<const unsigned short*>(e->PK + st.pk_p), stem_raw, B,
-                                                                         scd.H, scd.W, s, r->x0_raw ? W + r->w_stats + 32 : nullptr,
-                                                                         want_part ? gn_part : nullptr, st.groups) : 1;
-        have_part = want_part && rcs == 0;
-        if (rcs != 0 && rcs != 1) return rcs;
-        if (rcs == 1 && r->x0_raw) return HAB_ERR_UNSUPPORTED;  // (stem_takes_raw was decided on the same coverage predicates)
-        if (rcs == 1) HAB_TRY(conv_fwd(scd, x0, e->PK + st.pk_f, nullptr, stem_raw, 0, W + e->w_ws, e->ws_floats, s));
-        return HAB_OK;
-    };
-    GnArgs g;
-    g.x = stem_raw; g.y = nullptr; g.gamma = e->p(st.i_gamma); g.beta = e->p(st.i_beta); g.residual = nullptr;
-    g.mean = nullptr; g.rstd = nullptr; g.B = B; g.HW = scd.Ho() * scd.Wo(); g.C = scd.Cout; g.groups = st.groups; g.relu = 1;
-    g.eps = 1e-5f; g.scratch = W + e->w_ws; g.scratch_floats = e->ws_floats;
-    bool stem_done = false;
-    if (!e->save_acts) {  // act / encode: GroupNorm + ReLU + max-pool in one pass, the normalised frame is never written
-        HAB_TRY(stem_conv(groupnorm_pool_fusable(B, g.HW, g.C, g.groups, e->ws_floats)));
-        const int rc = groupnorm_relu_maxpool_forward(g, scd.Ho(), scd.Wo(), pool, nullptr, s, have_part ? gn_part : nullptr, STEM_STAT_ROWS);
+    const bool fusable = groupnorm_pool_fusable(B, g.HW, g.C, g.groups, e->ws_floats);
+    if (!e->save_acts) {  // act / encode: nothing is kept, neither the statistics nor the arg-max bytes
+        gf.mean = gf.rstd = nullptr;
+        HAB_TRY(stem_conv(e, B, f0, s, fusable, &have_part));
+        const int rc = groupnorm_relu_maxpool_forward(gf, sH, sW, pool, nullptr, s, have_part ? gn_part : nullptr, STEM_STAT_ROWS);
         if (rc != 0 && rc != 1) return rc;
         if (rc == 1) {  // small frames: the register-resident GroupNorm, then the pool
-            g.y = stem_act; g.mean = W + st.w_mean + F0 * st.groups; g.rstd = W + st.w_rstd + F0 * st.groups;
             HAB_TRY(groupnorm_forward(g, s));
-            HAB_TRY(maxpool_forward(stem_act, pool, pool_idx, B, scd.Ho(), scd.Wo(), scd.Cout, s));
+            HAB_TRY(maxpool_forward(g.y, pool, pool_idx, B, sH, sW, g.C, s));
         }
-        stem_done = true;
-    }
-    // (the fused form needs its chunk-parallel kernels for the chunk AND for the whole batch the backward runs on)
-    if (!stem_done && groupnorm_pool_fusable(B, g.HW, g.C, g.groups, e->ws_floats) &&
-        groupnorm_pool_fusable(Btot, g.HW, g.C, g.groups, e->ws_floats)) {
-        // training forward: the same fused pass, keeping the statistics and the arg-max bytes; the ReLU mask is recomputed in the backward
-        HAB_TRY(stem_conv(true));
-        g.mean = W + st.w_mean + F0 * st.groups; g.rstd = W + st.w_rstd + F0 * st.groups;
-        HAB_TRY(groupnorm_relu_maxpool_forward(g, scd.Ho(), scd.Wo(), pool, pool_idx, s, have_part ? gn_part : nullptr, STEM_STAT_ROWS));
-        r->stem_fused = true; r->stem_act_valid = false;
-        stem_done = true;
-    }
-    if (!stem_done) {
-        HAB_TRY(conv_gn_forward(e, st, x0, nullptr, 1, B, s, f0));
-        HAB_TRY(maxpool_forward(stem_act, pool, pool_idx, B, scd.Ho(), scd.Wo(), scd.Cout, s));
-        r->stem_fused = false; r->stem_act_valid = true;
+    } else if (fusable && groupnorm_pool_fusable(Btot, g.HW, g.C, g.groups, e->ws_floats)) {
+        // training forward (the fused form needs its chunk-parallel kernels for the chunk AND for the whole batch the backward runs on):
+        // the same fused pass, keeping the statistics and the arg-max bytes; the ReLU mask is recomputed in the backward
+        HAB_TRY(stem_conv(e, B, f0, s, true, &have_part));
+        HAB_TRY(groupnorm_relu_maxpool_forward(gf, sH, sW, pool, pool_idx, s, have_part ? gn_part : nullptr, STEM_STAT_ROWS));
+        r->stem_act_stored = false;
+    } else {
+        HAB_TRY(stem_conv(e, B, f0, s));
+        HAB_TRY(groupnorm_forward(g, s));
+        HAB_TRY(maxpool_forward(g.y, pool, pool_idx, B, sH, sW, g.C, s));
+        r->stem_act_stored = true;
     }
     int64_t in_floats = pool_floats;  // per-frame size of the current block's input
     for (const auto& blk : r->blocks) {
@@ -699,10 +645,11 @@ namespace {
 struct GPool {  // tiny allocator over the gradient scratch buffers
     float* buf[6];
     bool used[6] = {false, false, false, false, false, false};
-    float* get() {
+    // p = a free buffer.  The backward's peak use is fixed by the block structure and fits; running dry is an error of that plan
+    int take(float*& p) {
         for (int i = 0; i < 6; ++i)
-            if (!used[i]) { used[i] = true; return buf[i]; }
-        return nullptr;
+            if (!used[i]) { used[i] = true; p = buf[i]; return HAB_OK; }
+        return HAB_ERR_ARG;
     }
     void put(const float* p) {
         for (int i = 0; i < 6; ++i)
@@ -711,21 +658,28 @@ struct GPool {  // tiny allocator over the gradient scratch buffers
 };
 }  // namespace
 
-// GroupNorm backward of conv c: dy (optionally masked by relu_out) -> d_raw; gamma / beta gradients.
-static int gn_backward(hab_policy* e, const RnConv& c, const float* dy, const float* relu_out, float* d_raw, float* dy_masked, int B,
-                       hipStream_t s) {
+// GroupNorm backward of conv c on the whole batch: dy (optionally masked by relu_out) -> dx, the per-frame channel sums -> w_chansums
+static GnBwdArgs gn_bwd_args(hab_policy* e, const RnConv& c, int B, const float* dy, const float* relu_out, float* dx, float* dy_masked) {
     float* W = e->WK;
-    ResNetPlan* r = e->rn;
     GnBwdArgs g;
-    g.x = W + c.w_raw; g.dy = dy; g.relu_out = relu_out; g.dx = d_raw; g.dy_masked = dy_masked; g.gamma = e->p(c.i_gamma);
-    g.mean = W + c.w_mean; g.rstd = W + c.w_rstd; g.chan_sums = W + r->w_chansums; g.B = B; g.HW = c.cd.Ho() * c.cd.Wo();
+    g.x = W + c.w_raw; g.dy = dy; g.relu_out = relu_out; g.dx = dx; g.dy_masked = dy_masked; g.gamma = e->p(c.i_gamma);
+    g.mean = W + c.w_mean; g.rstd = W + c.w_rstd; g.chan_sums = W + e->rn->w_chansums; g.B = B; g.HW = c.cd.Ho() * c.cd.Wo();
     g.C = c.cd.Cout; g.groups = c.groups;
     g.scratch = W + e->w_ws; g.scratch_floats = e->ws_floats;
-    HAB_TRY(groupnorm_backward(g, s));
+    return g;
+}
+// gamma / beta gradients of conv c's GroupNorm from the channel sums its backward left
+static int gn_param_grads(hab_policy* e, const RnConv& c, int B, hipStream_t s) {
+    float* W = e->WK;
+    const float* cs = W + e->rn->w_chansums;
     const int C = c.cd.Cout;
-    HAB_TRY(colsum(W + r->w_chansums, 2 * C, B, C, e->g(c.i_beta), 0, W + e->w_ws, e->ws_floats, s));
-    HAB_TRY(colsum(W + r->w_chansums + C, 2 * C, B, C, e->g(c.i_gamma), 0, W + e->w_ws, e->ws_floats, s));
-    return HAB_OK;
+    HAB_TRY(colsum(cs, 2 * C, B, C, e->g(c.i_beta), 0, W + e->w_ws, e->ws_floats, s));
+    return colsum(cs + C, 2 * C, B, C, e->g(c.i_gamma), 0, W + e->w_ws, e->ws_floats, s);
+}
+static int gn_backward(hab_policy* e, const RnConv& c, const float* dy, const float* relu_out, float* d_raw, float* dy_masked, int B,
+                       hipStream_t s) {
+    HAB_TRY(groupnorm_backward(gn_bwd_args(e, c, B, dy, relu_out, d_raw, dy_masked), s));
+    return gn_param_grads(e, c, B, s);
 }
 
 // Weight gradient of one convolution of the backbone; the call sites that land on the generic implicit-GEMM kernel (no strip-resident
@@ -738,6 +692,19 @@ static int rn_conv_wgrad(hab_policy* e, const ConvDesc& c, const float* x, const
     Probe pr(e, HAB_PROBE_RN_WGRAD_IM2COL, s, 2.0 * pix * c.Cout * c.KH * c.KW * c.C,
              4.0 * ((double)c.B * c.H * c.W * c.C + pix * c.Cout + (double)c.Cout * c.KH * c.KW * c.C));
     return conv_wgrad(c, x, dy, dw, nullptr, ws, e->ws_floats, s);
+}
+// Backward of convolution c on B frames: the weight gradient from its input x and dy (a grouped convolution's dense into scratch, its block
+// diagonal gathered into the (Cout, C / groups, KH, KW) gradient), then the data gradient dx = dgrad(dy) * (relu_mask > 0) + add (either
+// may be null).
+static int rn_conv_backward(hab_policy* e, const RnConv& c, int B, const float* x, const float* dy, const float* relu_mask, const float* add,
+                            float* dx, hipStream_t s) {
+    float* W = e->WK;
+    float* ws = W + e->w_ws;
+    ConvDesc cd = c.cd;
+    cd.B = B;
+    HAB_TRY(rn_conv_wgrad(e, cd, x, dy, c.cgroups > 1 ? W + e->rn->w_gdense : e->g(c.i_w), ws, s));
+    if (c.cgroups > 1) HAB_TRY(gather_grouped_wgrad(W + e->rn->w_gdense, e->g(c.i_w), cd.Cout, cd.C, c.cgroups, cd.KH, cd.KW, s));
+    return conv_dgrad(cd, dy, e->PK + c.pk_d, relu_mask, add, dx, ws, e->ws_floats, s);
 }
 
 int resnet_encoder_backward(hab_policy* e, const hab_obs* obs, const uint8_t* masks, const int* rows, int B, hipStream_t s) {
@@ -762,19 +729,16 @@ int resnet_encoder_backward(hab_policy* e, const hab_obs* obs, const uint8_t* ma
     HAB_TRY(colsum(dfc, e->rnn_ld, B, H, e->g(r->i_fcb), 0, ws, e->ws_floats, s));
     grad_tail_ready(e, r->i_fcw);  // visual_fc, recurrent encoder, heads are final (the embeddings in front of the encoder are too)
     if (obs->visual_features) return HAB_OK;  // frozen encoder: its parameters get no gradient (the arena slots stay zero)
-    float* d_comp = gp.get();  // gradient wrt compression output, masked by its ReLU
+    float *d_comp, *d_raw, *d_out;  // gradients wrt the compression output (masked by its ReLU), its GroupNorm input, the last block's output
+    HAB_TRY(gp.take(d_comp));
     HAB_TRY(linear_dgrad(dfc, e->rnn_ld, e->PK + r->pk_fc, r->fc_in, W + r->comp.w_out, r->fc_in, r->fc_in, d_comp, r->fc_in, B,
                          r->fc_in, H, 0, ws, e->ws_floats, s));
     // compression conv + GN(1)
-    float* d_raw = gp.get();
+    HAB_TRY(gp.take(d_raw));
     HAB_TRY(gn_backward(e, r->comp, d_comp, nullptr, d_raw, nullptr, B, s));
     gp.put(d_comp);
-    ConvDesc cd = r->comp.cd;
-    cd.B = B;
-    const float* comp_in = W + r->blocks.back().w_out;
-    HAB_TRY(rn_conv_wgrad(e, cd, comp_in, d_raw, e->g(r->comp.i_w), ws, s));
-    float* d_out = gp.get();  // gradient wrt the last block's output (pre ReLU mask)
-    HAB_TRY(conv_dgrad(cd, d_raw, e->PK + r->comp.pk_d, nullptr, nullptr, d_out, ws, e->ws_floats, s));
+    HAB_TRY(gp.take(d_out));
+    HAB_TRY(rn_conv_backward(e, r->comp, B, W + r->blocks.back().w_out, d_raw, nullptr, nullptr, d_out, s));
     gp.put(d_raw);
     // blocks, last to first
     for (int bi = (int)r->blocks.size() - 1; bi >= 0; --bi) {
@@ -782,9 +746,9 @@ int resnet_encoder_backward(hab_policy* e, const hab_obs* obs, const uint8_t* ma
         const int n = (int)blk.convs.size();
         const float* in = W + blk.w_in;
         const float* out = W + blk.w_out;
-        float* d_pre = gp.get();
-        float* cur = gp.get();
-        if (!d_pre || !cur) return HAB_ERR_ARG;
+        float *d_pre, *cur;
+        HAB_TRY(gp.take(d_pre));
+        HAB_TRY(gp.take(cur));
         if (blk.se_c) {
             // through the gate: dm = d_out * (out > 0) (= the identity branch's gradient), dgate = sum_hw dm * y, then the two tiny
             // linears backwards, and dy = dm * gate + dpool / HW is what the last GroupNorm receives
@@ -801,8 +765,8 @@ int resnet_encoder_backward(hab_policy* e, const hab_obs* obs, const uint8_t* ma
             HAB_TRY(linear_wgrad(dh, R, W + blk.w_se_pool, C, e->g(blk.i_se1w), C, B, R, C, 0, 0, 0, ws, e->ws_floats, s));
             HAB_TRY(colsum(dh, R, B, R, e->g(blk.i_se1b), 0, ws, e->ws_floats, s));
             HAB_TRY(linear_dgrad(dh, R, e->p(blk.i_se1w), C, nullptr, 0, 0, dpool, C, B, C, R, 0, ws, e->ws_floats, s));
-            float* dy_gn = gp.get();
-            if (!dy_gn) return HAB_ERR_ARG;
+            float* dy_gn;
+            HAB_TRY(gp.take(dy_gn));
             HAB_TRY(se_backward_apply(d_pre, W + blk.w_se_gate, dpool, dy_gn, B, HW, C, s));
             HAB_TRY(gn_backward(e, c, dy_gn, nullptr, cur, nullptr, B, s));
             gp.put(dy_gn);
@@ -813,20 +777,11 @@ int resnet_encoder_backward(hab_policy* e, const hab_obs* obs, const uint8_t* ma
         for (int q = n - 1; q >= 1; --q) {
             const RnConv& c = r->convs[blk.convs[q]];
             const RnConv& pc = r->convs[blk.convs[q - 1]];
-            ConvDesc c2 = c.cd;
-            c2.B = B;
-            if (c.cgroups > 1) {  // dense weight gradient into scratch, block diagonal gathered into the (Cout, C / groups, 3, 3) gradient
-                HAB_TRY(rn_conv_wgrad(e, c2, W + pc.w_out, cur, W + r->w_gdense, ws, s));
-                HAB_TRY(gather_grouped_wgrad(W + r->w_gdense, e->g(c.i_w), c.cd.Cout, c.cd.C, c.cgroups, c.cd.KH, c.cd.KW, s));
-            } else {
-                HAB_TRY(rn_conv_wgrad(e, c2, W + pc.w_out, cur, e->g(c.i_w), ws, s));
-            }
-            float* tmp = gp.get();
-            if (!tmp) return HAB_ERR_ARG;
-            HAB_TRY(conv_dgrad(c2, cur, e->PK + c.pk_d, W + pc.w_out /* ReLU mask */, nullptr, tmp, ws, e->ws_floats, s));
+            float *tmp, *nxt;
+            HAB_TRY(gp.take(tmp));
+            HAB_TRY(rn_conv_backward(e, c, B, W + pc.w_out, cur, W + pc.w_out /* ReLU mask */, nullptr, tmp, s));
             gp.put(cur);
-            float* nxt = gp.get();
-            if (!nxt) return HAB_ERR_ARG;
+            HAB_TRY(gp.take(nxt));
             HAB_TRY(gn_backward(e, pc, tmp, nullptr, nxt, nullptr, B, s));
             gp.put(tmp);
             cur = nxt;
@@ -834,26 +789,18 @@ int resnet_encoder_backward(hab_policy* e, const hab_obs* obs, const uint8_t* ma
         const float* add_ptr = d_pre;
         if (blk.ds >= 0) {
             const RnConv& dc = r->convs[blk.ds];
-            float* t1 = gp.get();
-            if (!t1) return HAB_ERR_ARG;
+            float *t1, *t2;
+            HAB_TRY(gp.take(t1));
             HAB_TRY(gn_backward(e, dc, d_pre, nullptr, t1, nullptr, B, s));
-            ConvDesc c2 = dc.cd;
-            c2.B = B;
-            HAB_TRY(rn_conv_wgrad(e, c2, in, t1, e->g(dc.i_w), ws, s));
-            float* t2 = gp.get();
-            if (!t2) return HAB_ERR_ARG;
-            HAB_TRY(conv_dgrad(c2, t1, e->PK + dc.pk_d, nullptr, nullptr, t2, ws, e->ws_floats, s));
+            HAB_TRY(gp.take(t2));
+            HAB_TRY(rn_conv_backward(e, dc, B, in, t1, nullptr, nullptr, t2, s));
             gp.put(t1);
             gp.put(d_pre);
             add_ptr = t2;
         }
-        const RnConv& c0 = r->convs[blk.convs[0]];
-        ConvDesc c2 = c0.cd;
-        c2.B = B;
-        HAB_TRY(rn_conv_wgrad(e, c2, in, cur, e->g(c0.i_w), ws, s));
-        float* d_in = gp.get();
-        if (!d_in) return HAB_ERR_ARG;
-        HAB_TRY(conv_dgrad(c2, cur, e->PK + c0.pk_d, nullptr, add_ptr, d_in, ws, e->ws_floats, s));
+        float* d_in;
+        HAB_TRY(gp.take(d_in));
+        HAB_TRY(rn_conv_backward(e, r->convs[blk.convs[0]], B, in, cur, nullptr, add_ptr, d_in, s));
         gp.put(cur);
         gp.put(add_ptr);
         d_out = d_in;
@@ -866,20 +813,15 @@ int resnet_encoder_backward(hab_policy* e, const hab_obs* obs, const uint8_t* ma
     // maxpool + stem
     float* d_n0 = W + r->w_gstem[0];
     float* d_raw0 = W + r->w_gstem[1];
-    if (r->stem_fused && !r->stem_act_valid) {
+    if (!r->stem_act_stored) {
         // fused stem: the max-pool gradient is gathered and the ReLU mask recomputed inside the GroupNorm backward kernels -- the
         // gradient of the (never stored) normalised stem output is not materialised either
         const RnConv& c = r->stem;
-        GnBwdArgs g;
-        g.x = W + c.w_raw; g.dy = nullptr; g.relu_out = nullptr; g.dx = d_raw0; g.dy_masked = nullptr; g.gamma = e->p(c.i_gamma);
-        g.mean = W + c.w_mean; g.rstd = W + c.w_rstd; g.chan_sums = W + r->w_chansums; g.B = B; g.HW = c.cd.Ho() * c.cd.Wo();
-        g.C = c.cd.Cout; g.groups = c.groups; g.scratch = W + e->w_ws; g.scratch_floats = e->ws_floats;
+        GnBwdArgs g = gn_bwd_args(e, c, B, nullptr, nullptr, d_raw0, nullptr);
         g.pool_dy = d_out; g.pool_idx = reinterpret_cast<const uint8_t*>(W + r->w_pool_idx); g.beta = e->p(c.i_beta);
         g.pH = c.cd.Ho(); g.pW = c.cd.Wo();
         HAB_TRY(groupnorm_backward(g, s));
-        const int C = c.cd.Cout;
-        HAB_TRY(colsum(W + r->w_chansums, 2 * C, B, C, e->g(c.i_beta), 0, W + e->w_ws, e->ws_floats, s));
-        HAB_TRY(colsum(W + r->w_chansums + C, 2 * C, B, C, e->g(c.i_gamma), 0, W + e->w_ws, e->ws_floats, s));
+        HAB_TRY(gn_param_grads(e, c, B, s));
     } else {
         HAB_TRY(maxpool_backward(d_out, reinterpret_cast<const uint8_t*>(W + r->w_pool_idx), d_n0, B, r->stem.cd.Ho(), r->stem.cd.Wo(),
                                  r->stem.cd.Cout, s));
@@ -912,16 +854,11 @@ int resnet_tap(hab_policy* e, int which, const float** ptr, int64_t* floats) {
             }
             *ptr = W + r->w_x0; *floats = B * r->H2 * r->W2 * r->cpad; return HAB_OK;
         case HAB_TAP_STEM:
-            if (r->stem_fused && !r->stem_act_valid) {  // the fused forward skipped it: build it from the kept GroupNorm input + statistics
-                const RnConv& c = r->stem;
-                GnArgs g;
-                g.x = W + c.w_raw; g.y = W + c.w_out; g.gamma = e->p(c.i_gamma); g.beta = e->p(c.i_beta); g.residual = nullptr;
-                g.mean = W + c.w_mean; g.rstd = W + c.w_rstd; g.B = (int)B; g.HW = c.cd.Ho() * c.cd.Wo(); g.C = c.cd.Cout; g.groups = c.groups;
-                g.relu = 1; g.eps = 1e-5f;
+            if (!r->stem_act_stored) {  // the fused forward skipped it: build it from the kept GroupNorm input + statistics
                 if (hipDeviceSynchronize() != hipSuccess) return HAB_ERR_ARG;
-                HAB_TRY(groupnorm_relu_materialize(g, nullptr));
+                HAB_TRY(groupnorm_relu_materialize(gn_args(e, r->stem, (int)B, 0, 1, nullptr), nullptr));  // (reads no scratch)
                 if (hipDeviceSynchronize() != hipSuccess) return HAB_ERR_ARG;
-                r->stem_act_valid = true;  // the backward now reads it as its ReLU mask (unfused form)
+                r->stem_act_stored = true;  // the backward now reads it as its ReLU mask (unfused form)
             }
             *ptr = W + r->stem.w_out; *floats = B * r->stem.out_floats(); return HAB_OK;
         case HAB_TAP_POOL: *ptr = W + r->w_pool; *floats = B * r->poolH * r->poolW * r->stem.cd.Cout; return HAB_OK;
