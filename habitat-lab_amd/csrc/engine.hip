@@ -138,8 +138,10 @@ extern "C" int hab_policy_create(const hab_policy_desc* desc, hab_policy** out) 
     if (!desc || !out) return HAB_ERR_ARG;
     if (desc->hidden <= 0 || desc->hidden % 64 || desc->num_actions <= 0 || desc->num_actions > 8 || desc->max_frames <= 0 ||
         desc->max_envs <= 0 || desc->rnn_layers <= 0 || desc->goal_dim < 0 ||
-        ((desc->has_rgb || desc->has_depth || desc->has_semantic) && (desc->H <= 0 || desc->W <= 0)))
+        ((desc->has_rgb || desc->has_depth || desc->has_semantic || desc->num_visual > 0) && (desc->H <= 0 || desc->W <= 0)))
         return HAB_ERR_ARG;
+    // named visual sensors and fused 1-D sensors are PointNavResNetPolicy's (the reference's SimpleCNN reads rgb / depth by name)
+    if (desc->arch != HAB_ARCH_RESNET && (desc->num_visual != 0 || desc->num_fused != 0)) return HAB_ERR_UNSUPPORTED;
     if (desc->action_dist != HAB_DIST_CATEGORICAL && (desc->action_dist != HAB_DIST_GAUSSIAN || desc->arch != HAB_ARCH_RESNET))
         return HAB_ERR_UNSUPPORTED;  // PointNavBaselinePolicy never builds a Gaussian head (rl/ppo/policy.py:439-460)
     // the Gaussian head kernels (heads.hip: saved[f][16], dz stride 8, std column sums at dz + A) hold 2A <= 8 values per frame

@@ -59,7 +59,15 @@ struct ResNetPlan {
     int i_embb = -1;
     int i_fcw = -1, i_fcb = -1, i_emb = -1, i_tgw = -1, i_tgb = -1, i_mean = -1, i_var = -1, i_count = -1;
     int i_objw = -1, i_gpsw = -1, i_gpsb = -1, i_cmpw = -1, i_cmpb = -1, i_pgw = -1, i_pgb = -1, i_pxw = -1, i_pxb = -1;
-    int c_rgb = -1, c_depth = -1, c_sem = -1;  // first channel of each visual key in the concatenated encoder input
+    // the visual sensors in concatenation order -- the ONE form the engine keeps them in, whether the descriptor named them in its table or
+    // through the legacy has_rgb / has_depth / has_semantic / visual_order flags.  vis_legacy[i]: 0 = hab_obs::visual[i], else the typed
+    // pointer of hab_obs the sensor arrives through (1 rgb, 2 depth, 3 semantic).
+    int nvis = 0;
+    int vis_dtype[HAB_MAX_VISUAL] = {0, 0, 0, 0}, vis_ch[HAB_MAX_VISUAL] = {0, 0, 0, 0}, vis_legacy[HAB_MAX_VISUAL] = {0, 0, 0, 0};
+    float vis_scale[HAB_MAX_VISUAL] = {1.f, 1.f, 1.f, 1.f};
+    // raw 1-D sensors fused into the recurrent encoder's input at columns [fuse_col0, fuse_col0 + D) (resnet_policy.py:648-660)
+    int nfused = 0, fused_w[HAB_MAX_FUSED] = {0, 0, 0, 0, 0, 0, 0, 0}, D = 0, fuse_col0 = 0;
+    int emb_col0 = 0;  // first column of the embedding slots
     int nslots = 0;
     int64_t pk_fc = -1;
     int fc_in = 0, comp_c = 0, comp_hw = 0, comp_fh = 0, comp_fw = 0;
@@ -100,7 +108,9 @@ int build_resnet(hab_policy* e) {
         d.backbone != HAB_BACKBONE_SE_RESNET50 && d.backbone != HAB_BACKBONE_SE_RESNEXT50 && d.backbone != HAB_BACKBONE_SE_RESNEXT101)
         return HAB_ERR_UNSUPPORTED;
     if (d.baseplanes <= 0 || d.baseplanes % 8) return HAB_ERR_UNSUPPORTED;
-    const bool blind = !d.has_rgb && !d.has_depth && !d.has_semantic;
+    if (d.num_visual < 0 || d.num_visual > HAB_MAX_VISUAL || d.num_fused < 0 || d.num_fused > HAB_MAX_FUSED) return HAB_ERR_UNSUPPORTED;
+    if (d.num_visual > 0 && (d.has_rgb || d.has_depth || d.has_semantic || d.visual_order)) return HAB_ERR_ARG;  // one way of naming them
+    const bool blind = !d.has_rgb && !d.has_depth && !d.has_semantic && d.num_visual == 0;
     if (!blind && (d.H < 2 || d.W < 2)) return HAB_ERR_UNSUPPORTED;  // odd sizes: avg_pool2d(2) floors, the last row / column is dropped (F.avg_pool2d)
     if (d.rnn_type != HAB_RNN_GRU && d.rnn_type != HAB_RNN_LSTM) return HAB_ERR_ARG;
     if (d.goal_dim != 0 && d.goal_dim != 2) return HAB_ERR_UNSUPPORTED;  // 2-D polar pointgoal (resnet_policy.py:662-672)
@@ -109,21 +119,41 @@ int build_resnet(hab_policy* e) {
     const int H = d.hidden;
     e->G_ = d.rnn_type == HAB_RNN_GRU ? 3 : 4;
     e->L = d.rnn_layers;
-    r->creal = (d.has_rgb ? 3 : 0) + (d.has_depth ? 1 : 0) + (d.has_semantic ? 1 : 0);
     r->blind = blind;
-    e->Cin = r->creal;
-    r->cpad = r->creal <= 4 ? 4 : 8;
-    if (!blind) {   // channel offsets from the observation-space key order
-        int off = 0, seen = 0;
-        int order = d.visual_order ? d.visual_order : (1 | (2 << 2) | (3 << 4));
+    if (d.num_visual > 0) {
+        for (int i = 0; i < d.num_visual; ++i) {
+            const int dt = d.visual_dtype[i], ch = d.visual_channels[i];
+            if ((dt != HAB_DTYPE_U8 && dt != HAB_DTYPE_F32 && dt != HAB_DTYPE_I32) || ch <= 0 || ch > 8) return HAB_ERR_UNSUPPORTED;
+            if (dt == HAB_DTYPE_U8 && !(d.visual_scale[i] > 0.f)) return HAB_ERR_ARG;
+            r->vis_dtype[i] = dt; r->vis_ch[i] = ch; r->vis_scale[i] = dt == HAB_DTYPE_U8 ? d.visual_scale[i] : 1.f;
+        }
+        r->nvis = d.num_visual;
+    } else if (!blind) {   // the legacy flags, converted here and nowhere else: keys in observation-space order
+        int seen = 0;
+        bool used[4] = {false, false, false, false};
+        const int order = d.visual_order ? d.visual_order : (1 | (2 << 2) | (3 << 4));
+        auto put = [&](int key, int dt, int ch, float scale) {
+            used[key] = true; ++seen;
+            r->vis_dtype[r->nvis] = dt; r->vis_ch[r->nvis] = ch; r->vis_scale[r->nvis] = scale; r->vis_legacy[r->nvis] = key; ++r->nvis;
+        };
         for (int q = 0; q < 3; ++q) {
             const int key = (order >> (2 * q)) & 3;
-            if (key == 1 && d.has_rgb && r->c_rgb < 0) { r->c_rgb = off; off += 3; ++seen; }
-            else if (key == 2 && d.has_depth && r->c_depth < 0) { r->c_depth = off; off += 1; ++seen; }
-            else if (key == 3 && d.has_semantic && r->c_sem < 0) { r->c_sem = off; off += 1; ++seen; }
+            if (key == 1 && d.has_rgb && !used[1]) put(1, HAB_DTYPE_U8, 3, (float)(1.0 / 255.0));
+            else if (key == 2 && d.has_depth && !used[2]) put(2, HAB_DTYPE_F32, 1, 1.f);
+            else if (key == 3 && d.has_semantic && !used[3]) put(3, HAB_DTYPE_I32, 1, 1.f);
         }
-        if (off != r->creal || seen != (d.has_rgb ? 1 : 0) + (d.has_depth ? 1 : 0) + (d.has_semantic ? 1 : 0)) return HAB_ERR_ARG;
+        if (seen != (d.has_rgb ? 1 : 0) + (d.has_depth ? 1 : 0) + (d.has_semantic ? 1 : 0)) return HAB_ERR_ARG;
     }
+    r->creal = 0;
+    for (int i = 0; i < r->nvis; ++i) r->creal += r->vis_ch[i];
+    if (r->creal > 8) return HAB_ERR_UNSUPPORTED;  // the encoder input is padded to 4 or 8 channels
+    e->Cin = r->creal;
+    r->cpad = r->creal <= 4 ? 4 : 8;
+    for (int i = 0; i < d.num_fused; ++i) {
+        if (d.fused_width[i] <= 0) return HAB_ERR_ARG;
+        r->fused_w[i] = d.fused_width[i]; r->D += d.fused_width[i];
+    }
+    r->nfused = d.num_fused;
     r->H2 = d.H / 2; r->W2 = d.W / 2;
     const int bp = d.baseplanes, ng = bp / 2;
     // resnet.py:296-345: block type, stage depths, ResNeXt (expansion 2, base width x2, grouped 3x3 with cardinality
@@ -247,9 +277,12 @@ int build_resnet(hab_policy* e) {
     r->i_fcb = add_param(e, "net.visual_fc.1.bias", {H});
     }  // !blind
     e->fc_in = r->fc_in;
-    e->rnn_in = (blind ? 0 : H) + 32 * r->nslots;
-    e->rnn_ld = (e->rnn_in + 15) & ~15;
-    if (e->rnn_ld != e->rnn_in) return HAB_ERR_UNSUPPORTED;  // (32-wide embedding slots behind a hidden size % 64 == 0: never padded)
+    // recurrent input = [visual_fc output | fused 1-D sensors | embeddings] (resnet_policy.py:647-757)
+    r->fuse_col0 = blind ? 0 : H;
+    r->emb_col0 = r->fuse_col0 + r->D;
+    e->rnn_in = r->emb_col0 + 32 * r->nslots;
+    e->rnn_ld = (e->rnn_in + 15) & ~15;  // rows padded to the K-chunk of the fused step projection; the fused gather zeroes the padding
+    if (e->rnn_ld != e->rnn_in && r->nfused == 0) return HAB_ERR_UNSUPPORTED;  // (32-wide slots behind a hidden size % 64 == 0: never padded)
     add_tail_params(e);
 
     // ---- packed weights ----
@@ -454,6 +487,19 @@ int resnet_encode(hab_policy* e, const hab_obs* obs, int n, float* out, hipStrea
 }
 
 static int resnet_ingest(hab_policy* e, const hab_obs* obs, const int* rows, int B, hipStream_t s);
+// The fused 1-D sensors of nB frames into rin[:, fuse_col0 : fuse_col0 + D] and zeros into the rows' padding columns: one launch, none
+// for a policy without fused sensors.
+static int fused_forward(hab_policy* e, const hab_obs* obs, const int* rows, float* rin, int nB, hipStream_t s) {
+    const ResNetPlan* r = e->rn;
+    if (r->nfused == 0) return HAB_OK;
+    FusedTable t{};
+    t.n = r->nfused; t.D = r->D;
+    for (int i = 0; i < r->nfused; ++i) {
+        if (!obs->fused[i]) return HAB_ERR_ARG;
+        t.src[i] = obs->fused[i]; t.width[i] = r->fused_w[i];
+    }
+    return fused_gather(t, rows, rin, e->rnn_ld, r->fuse_col0, e->rnn_in, e->rnn_ld - e->rnn_in, nB, s);
+}
 static int resnet_layers_forward(hab_policy* e, int Btot, int f0, int nB, hipStream_t s);
 
 // Encoder forward of frames [f0, f0 + nB) of a B-frame batch (time-major chunks of a minibatch, engine.hip; f0 = 0, nB = B: the whole
@@ -469,9 +515,10 @@ int resnet_encoder_forward(hab_policy* e, const hab_obs* obs, const uint8_t* mas
         EmbedArgs ea;
         HAB_TRY(fill_embed_slots(e, obs, ea.slot, false));
         ea.nslots = r->nslots; ea.masks = masks; ea.rows = rows ? rows + f0 : nullptr;
-        ea.out = W + e->w_rnnin + (int64_t)f0 * e->rnn_ld; ea.ld = e->rnn_ld; ea.col0 = 0; ea.B = nB;
+        ea.out = W + e->w_rnnin + (int64_t)f0 * e->rnn_ld; ea.ld = e->rnn_ld; ea.col0 = r->emb_col0; ea.B = nB;
         ea.saved = W + r->w_embsave + (int64_t)f0 * r->nslots * 4;
         if (!masks) return HAB_ERR_ARG;
+        HAB_TRY(fused_forward(e, obs, ea.rows, ea.out, nB, s));
         return embed_forward(ea, s);
     }
     if (obs->visual_features) {  // frozen encoder: the rollout already holds its output (resnet_policy.py:636-646)
@@ -493,8 +540,9 @@ int resnet_encoder_forward(hab_policy* e, const hab_obs* obs, const uint8_t* mas
     EmbedArgs ea;
     HAB_TRY(fill_embed_slots(e, obs, ea.slot, false));
     ea.nslots = r->nslots; ea.masks = masks; ea.rows = rows ? rows + f0 : nullptr;
-    ea.out = rin; ea.ld = e->rnn_ld; ea.col0 = H; ea.B = nB; ea.saved = W + r->w_embsave + (int64_t)f0 * r->nslots * 4;
+    ea.out = rin; ea.ld = e->rnn_ld; ea.col0 = r->emb_col0; ea.B = nB; ea.saved = W + r->w_embsave + (int64_t)f0 * r->nslots * 4;
     if (!masks) return HAB_ERR_ARG;
+    HAB_TRY(fused_forward(e, obs, ea.rows, rin, nB, s));
     return embed_forward(ea, s);
 }
 
@@ -509,15 +557,22 @@ static int resnet_ingest(hab_policy* e, const hab_obs* obs, const int* rows, int
     float* W = e->WK;
     const hab_policy_desc& d = e->d;
     float* x0 = W + r->w_x0;
-    if ((d.has_rgb && !obs->rgb) || (d.has_depth && !obs->depth) || (d.has_semantic && !obs->semantic)) return HAB_ERR_ARG;
+    IngestTable tb{};
+    tb.n = r->nvis;
+    for (int i = 0; i < r->nvis; ++i) {
+        const int k = r->vis_legacy[i];
+        tb.src[i] = k == 1 ? (const void*)obs->rgb : k == 2 ? (const void*)obs->depth : k == 3 ? (const void*)obs->semantic : obs->visual[i];
+        if (!tb.src[i]) return HAB_ERR_ARG;
+        tb.dtype[i] = (signed char)r->vis_dtype[i]; tb.ch[i] = (signed char)r->vis_ch[i]; tb.scale[i] = r->vis_scale[i];
+    }
     // evaluation mode: RunningMeanAndVar is a fixed affine per channel -> applied by the ingest itself (one launch, one pass less)
     const bool fused_norm = d.normalize_visual_inputs && !e->training;
     const bool moments = d.normalize_visual_inputs && e->training;
     double* ds = reinterpret_cast<double*>(W + r->w_dscratch);  // [0..15] totals, then the per-workgroup partials
     int mom_blocks = 0;
-    HAB_TRY(ingest_pool(d.has_rgb ? obs->rgb : nullptr, d.has_depth ? obs->depth : nullptr, d.has_semantic ? obs->semantic : nullptr, rows,
-                        x0, B, d.H, d.W, r->cpad, r->c_rgb, r->c_depth, r->c_sem, s, fused_norm ? e->p(r->i_mean) : nullptr,
-                        fused_norm ? e->p(r->i_var) : nullptr, moments ? e->p(r->i_mean) : nullptr, moments ? ds + 16 : nullptr, &mom_blocks));
+    HAB_TRY(ingest_pool_sensors(tb, rows, x0, B, d.H, d.W, r->cpad, s, fused_norm ? e->p(r->i_mean) : nullptr,
+                                fused_norm ? e->p(r->i_var) : nullptr, moments ? e->p(r->i_mean) : nullptr, moments ? ds + 16 : nullptr,
+                                &mom_blocks));
     const long long npix = (long long)B * r->H2 * r->W2;
     r->x0_raw = false;
     if (moments) {
@@ -715,7 +770,7 @@ int resnet_encoder_backward(hab_policy* e, const hab_obs* obs, const uint8_t* ma
     const float* dfc = W + e->w_drnnin;  // [B][rnn_ld]; first H columns already carry visual_fc's ReLU mask
     EmbedBwdArgs eb;
     HAB_TRY(fill_embed_slots(e, obs, eb.slot, true));
-    eb.nslots = r->nslots; eb.saved = W + r->w_embsave; eb.dout = dfc; eb.ld = e->rnn_ld; eb.col0 = r->blind ? 0 : H; eb.B = B;
+    eb.nslots = r->nslots; eb.saved = W + r->w_embsave; eb.dout = dfc; eb.ld = e->rnn_ld; eb.col0 = r->emb_col0; eb.B = B;
     HAB_TRY(embed_backward(eb, ws, e->ws_floats, s));
     if (r->blind) {  // embeddings, recurrent encoder and heads are all there is: the whole arena is final
         grad_tail_ready(e, 0);

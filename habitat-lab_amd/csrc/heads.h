@@ -56,6 +56,15 @@ int gauss_heads_forward(const GaussHeadsArgs& a, hipStream_t stream);
 int gauss_heads_backward(const GaussHeadsBwdArgs& a, hipStream_t stream);
 int heads_forward(const HeadsArgs& a, hipStream_t stream);
 int heads_backward(const HeadsBwdArgs& a, hipStream_t stream);
+// Raw 1-D `fuse_keys` sensors of PointNavResNetNet (resnet_policy.py:648-660) into the recurrent encoder's input, by value to the kernel
+constexpr int FUSED_MAX_SENSORS = 8;
+struct FusedTable {
+    const float* src[FUSED_MAX_SENSORS];
+    int width[FUSED_MAX_SENSORS];
+    int n, D;  // D = sum of the widths
+};
+// dst[f][col0 + off_i + c] = src_i[rows ? rows[f] : f][c]; dst[f][pad0 .. pad0 + npad) = 0 -- one launch
+int fused_gather(const FusedTable& t, const int* rows, float* dst, int ld, int col0, int pad0, int npad, int B, hipStream_t stream);
 int gather_cols(const float* src, int src_ld, const int* rows, float* dst, int dst_ld, int col0, int ncols, int npad, int B,
                 hipStream_t stream);
 int masked_rows(const float* src, int src_stride, const uint8_t* masks, float* dst, int n, int H, hipStream_t stream);

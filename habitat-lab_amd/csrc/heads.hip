@@ -236,6 +236,42 @@ int gather_cols(const float* src, int src_ld, const int* rows, float* dst, int d
     return HAB_OK;
 }
 
+// Fused 1-D sensors: element e of a row's D + npad work items is either value c of the sensor that covers fused column c (found by
+// walking the <= 8 widths; the table sits in kernel-argument registers, hence the select chain instead of an indexed read) or one of the
+// row's padding columns.
+__global__ void fused_gather_kernel(FusedTable t, const int* __restrict__ rows, float* __restrict__ dst, int ld, int col0, int pad0,
+                                    int npad, int B) {
+    const int per = t.D + npad;
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long long)B * per) return;
+    const int f = (int)(e / per), c = (int)(e % per);
+    if (c >= t.D) { dst[(size_t)f * ld + pad0 + (c - t.D)] = 0.f; return; }
+    const float* src = nullptr;
+    int w = 0, o = c;
+    bool found = false;
+#pragma unroll
+    for (int k = 0; k < FUSED_MAX_SENSORS; ++k) {
+        if (k < t.n && !found) {
+            if (o < t.width[k]) { src = t.src[k]; w = t.width[k]; found = true; }
+            else o -= t.width[k];
+        }
+    }
+    if (!found) return;  // (c < D = sum of the widths: cannot happen)
+    dst[(size_t)f * ld + col0 + c] = src[(size_t)(rows ? rows[f] : f) * w + o];
+}
+int fused_gather(const FusedTable& t, const int* rows, float* dst, int ld, int col0, int pad0, int npad, int B, hipStream_t stream) {
+    if (!dst || B <= 0 || t.n <= 0 || t.n > FUSED_MAX_SENSORS || npad < 0 || col0 < 0 || pad0 < 0) return HAB_ERR_ARG;
+    int D = 0;
+    for (int i = 0; i < t.n; ++i) {
+        if (!t.src[i] || t.width[i] <= 0) return HAB_ERR_ARG;
+        D += t.width[i];
+    }
+    if (D != t.D || col0 + D > ld || (npad > 0 && (pad0 < col0 + D || pad0 + npad > ld))) return HAB_ERR_ARG;
+    const long long total = (long long)B * (D + npad);
+    fused_gather_kernel<<<(int)((total + 255) / 256), 256, 0, stream>>>(t, rows, dst, ld, col0, pad0, npad, B);
+    HAB_LAUNCH_CHECK();
+    return HAB_OK;
+}
 // hidden (n, L, H) slice copy helpers for the rollout step: dst[q][u] = mask[q] ? src[q*stride + u] : 0
 __global__ void masked_rows_kernel(const float* __restrict__ src, int src_stride, const uint8_t* __restrict__ masks,
                                    float* __restrict__ dst, int n, int H) {
@@ -265,3 +301,11 @@ int copy_rows(const float* src, const int* idx, int src_ld, float* dst, int dst_
 }
 
 }  // namespace hab
+extern "C" int hab_fused_gather(const float* const* sensors, const int32_t* widths, int n, const int* rows, float* dst, int ld, int col0,
+                                int pad0, int npad, int B, hipStream_t stream) {
+    if (!sensors || !widths || n <= 0 || n > hab::FUSED_MAX_SENSORS) return HAB_ERR_ARG;
+    hab::FusedTable t{};
+    t.n = n;
+    for (int i = 0; i < n; ++i) { t.src[i] = sensors[i]; t.width[i] = widths[i]; t.D += widths[i] > 0 ? widths[i] : 0; }
+    return hab::fused_gather(t, rows, dst, ld, col0, pad0, npad, B, stream);
+}

@@ -67,6 +67,108 @@ struct EmbedBwdArgs {
 int ingest_pool(const uint8_t* rgb, const float* depth, const int32_t* semantic, const int* rows, float* y, int B, int H, int W, int cpad,
                 int c_rgb, int c_depth, int c_sem, hipStream_t s, const float* norm_mean = nullptr, const float* norm_var = nullptr,
                 const float* pivot = nullptr, double* mom_partial = nullptr, int* mom_blocks = nullptr);
+// The visual sensors of a ResNetEncoder as a table (resnet_policy.py:178-199: every rank-3 observation, under any name, in concatenation
+// order); travels to the ingest kernel by value.  vec[i]: the sensor's two horizontal taps may be fetched as one aligned unit (even W and
+// an aligned base: uint8 x 3 as three 16-bit loads, float32 x 1 as one 8-byte load).
+constexpr int INGEST_MAX_SENSORS = 4;
+struct IngestTable {
+    const void* src[INGEST_MAX_SENSORS];
+    float scale[INGEST_MAX_SENSORS];                         // uint8: fp32(1 / high.max())
+    signed char dtype[INGEST_MAX_SENSORS], ch[INGEST_MAX_SENSORS], off[INGEST_MAX_SENSORS], vec[INGEST_MAX_SENSORS];  // HAB_DTYPE_*, channels, first output channel
+    int n;
+};
+constexpr int INGEST_U8 = 0, INGEST_F32 = 1, INGEST_I32 = 2;  // = HAB_DTYPE_* (checked in resnet_ops.hip)
+// Fills off[] / vec[] and checks the table; *creal = total channels.
+inline int ingest_table_finish(IngestTable& t, int W, int cpad, int* creal) {
+    if (t.n <= 0 || t.n > INGEST_MAX_SENSORS || (cpad != 4 && cpad != 8)) return HAB_ERR_ARG;
+    int off = 0;
+    for (int i = 0; i < t.n; ++i) {
+        const int dt = t.dtype[i], C = t.ch[i];
+        if (!t.src[i] || C <= 0 || C > 8 || (dt != INGEST_U8 && dt != INGEST_F32 && dt != INGEST_I32)) return HAB_ERR_ARG;
+        t.off[i] = (signed char)off;
+        off += C;
+        if (off > cpad) return HAB_ERR_ARG;
+        const uintptr_t a = reinterpret_cast<uintptr_t>(t.src[i]);
+        t.vec[i] = 0;
+        if (!(W & 1)) {
+            if (dt == INGEST_U8 && C == 3 && !(a & 1)) t.vec[i] = 1;
+            if (dt == INGEST_F32 && C == 1 && !(a & 7)) t.vec[i] = 1;
+        }
+        if (dt != INGEST_U8) t.scale[i] = 1.f;
+    }
+    if (creal) *creal = off;
+    return HAB_OK;
+}
+__host__ __device__ __forceinline__ void ingest_put(float (&out)[8], int k, float v) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+        if (c == k) out[c] = v;   // select chain: out[] stays in registers
+}
+// One output pixel of the table-driven ingest: out[0 .. 8) = the concatenated channels (zeros behind the last sensor).  px: pixel index of
+// tap (0,0) in a sensor's (rows, H, W) plane; (0,1) = px + 1, (1,0) = px + W, (1,1) = px + W + 1.  Host-callable so that the CPU suite pins
+// the arithmetic and the byte unpacking without a GPU (tests/hostcheck/hostcheck_ingest.hip).
+__host__ __device__ __forceinline__ void ingest_table_pixel(const IngestTable& t, size_t px, int W, float (&out)[8]) {
+#pragma clang fp contract(off)  // the reference rounds the uint8 scaling and every addition of the 2x2 average separately
+#pragma unroll
+    for (int c = 0; c < 8; ++c) out[c] = 0.f;
+#pragma unroll
+    for (int i = 0; i < INGEST_MAX_SENSORS; ++i) {
+        if (i >= t.n) break;
+        const int C = t.ch[i], c0 = t.off[i], dt = t.dtype[i];
+        if (dt == INGEST_U8) {
+            const uint8_t* p = static_cast<const uint8_t*>(t.src[i]);
+            const float sc = t.scale[i];
+            if (C == 3 && t.vec[i]) {
+                const uint16_t* r0 = reinterpret_cast<const uint16_t*>(p + px * 3);
+                const uint16_t* r1 = reinterpret_cast<const uint16_t*>(p + (px + W) * 3);
+                const unsigned a0 = r0[0], a1 = r0[1], a2 = r0[2], b0 = r1[0], b1 = r1[1], b2 = r1[2];
+                // bytes of a row: tap 0 = (a0 & 255, a0 >> 8, a1 & 255), tap 1 = (a1 >> 8, a2 & 255, a2 >> 8)
+                const unsigned t00[3] = {a0 & 255u, a0 >> 8, a1 & 255u}, t01[3] = {a1 >> 8, a2 & 255u, a2 >> 8};
+                const unsigned t10[3] = {b0 & 255u, b0 >> 8, b1 & 255u}, t11[3] = {b1 >> 8, b2 & 255u, b2 >> 8};
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    float s = 0.f;
+                    s = s + (float)t00[c] * sc; s = s + (float)t01[c] * sc; s = s + (float)t10[c] * sc; s = s + (float)t11[c] * sc;
+                    ingest_put(out, c0 + c, s * 0.25f);
+                }
+            } else {
+                for (int c = 0; c < C; ++c) {
+                    float s = 0.f;
+                    s = s + (float)p[px * C + c] * sc; s = s + (float)p[(px + 1) * C + c] * sc;
+                    s = s + (float)p[(px + W) * C + c] * sc; s = s + (float)p[(px + W + 1) * C + c] * sc;
+                    ingest_put(out, c0 + c, s * 0.25f);
+                }
+            }
+        } else if (dt == INGEST_F32) {
+            const float* p = static_cast<const float*>(t.src[i]);
+            if (C == 1 && t.vec[i]) {
+                const float2 u = *reinterpret_cast<const float2*>(p + px), v = *reinterpret_cast<const float2*>(p + px + W);
+                float s = 0.f;
+                s = s + u.x; s = s + u.y; s = s + v.x; s = s + v.y;
+                ingest_put(out, c0, s * 0.25f);
+            } else {
+                for (int c = 0; c < C; ++c) {
+                    float s = 0.f;
+                    s = s + p[px * C + c]; s = s + p[(px + 1) * C + c]; s = s + p[(px + W) * C + c]; s = s + p[(px + W + 1) * C + c];
+                    ingest_put(out, c0 + c, s * 0.25f);
+                }
+            }
+        } else {  // int32 ids are concatenated by type promotion (torch.cat) and averaged like any channel
+            const int32_t* p = static_cast<const int32_t*>(t.src[i]);
+            for (int c = 0; c < C; ++c) {
+                float s = 0.f;
+                s = s + (float)p[px * C + c]; s = s + (float)p[(px + 1) * C + c];
+                s = s + (float)p[(px + W) * C + c]; s = s + (float)p[(px + W + 1) * C + c];
+                ingest_put(out, c0 + c, s * 0.25f);
+            }
+        }
+    }
+}
+// The ingest of a sensor table: the legacy triple (at most one uint8 x 3 sensor scaled by 1/255, one float32 x 1, one int32 x 1) keeps its
+// three-pointer kernel, every other table runs the table-driven one; same arithmetic, same moments / normalisation contract.
+int ingest_pool_sensors(const IngestTable& t, const int* rows, float* y, int B, int H, int W, int cpad, hipStream_t s,
+                        const float* norm_mean = nullptr, const float* norm_var = nullptr, const float* pivot = nullptr,
+                        double* mom_partial = nullptr, int* mom_blocks = nullptr, bool force_table_kernel = false);
 // fused moments of the ingest (training-mode RunningMeanAndVar): mom_partial holds [<= INGEST_MOM_MAX_BLOCKS][16] doubles
 constexpr int INGEST_MOM_MAX_BLOCKS = 2048;
 int moment_finish_mean(const double* partial, int nblocks, int cpad, const float* pivot, int creal, long long npix, double* sums,

@@ -9,6 +9,9 @@
 
 namespace hab {
 
+static_assert(INGEST_U8 == HAB_DTYPE_U8 && INGEST_F32 == HAB_DTYPE_F32 && INGEST_I32 == HAB_DTYPE_I32 && INGEST_MAX_SENSORS == HAB_MAX_VISUAL,
+              "resnet_ops.h restates the element-type codes of habitat_amd.h");
+
 // ------------------------------------------------------------------------------------------------------
 // Ingest (resnet_policy.py:259-271): per visual key permute -> uint8 * fp32(1/255) -> cat -> avg_pool2d(2).
 // Output y[f][h/2][w/2][cpad]: channels rgb(3), depth(1), zero padding up to cpad.
@@ -147,6 +150,124 @@ int ingest_pool(const uint8_t* rgb, const float* depth, const int32_t* semantic,
         ingest_pool_kernel<false><<<(int)fmin(8192.0, (double)cdivl(total, 256)), 256, 0, s>>>(rgb, depth, semantic, rows, y, B, H, W, cpad,
                                                                                                 c_rgb, c_depth, c_sem, norm_mean, norm_var, n,
                                                                                                 nullptr, nullptr);
+    }
+    HAB_LAUNCH_CHECK();
+    return HAB_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Table-driven ingest: the same pass for n <= 4 visual sensors under any name (ResNetEncoder, resnet_policy.py:178-199,259-271).  Per output
+// pixel and sensor: load the 2x2 window, scale (uint8) / cast (int32), add the taps in the order (0,0), (0,1), (1,0), (1,1), * 0.25, write
+// at the sensor's channel offset -- operation for operation what ingest_pool_kernel does for its three keys; normalisation and moments
+// are the same code on the concatenated channels.  The table is a kernel argument.  Loads: the two horizontal taps of a window are
+// adjacent in memory, so a uint8 x 3 sensor is fetched as three 16-bit units per row and a float32 x 1 sensor as one 8-byte unit per row
+// (t.vec[i]: even W and an aligned base make every such unit naturally aligned) instead of byte by byte / tap by tap.
+// ------------------------------------------------------------------------------------------------------
+template <bool MOM>
+__global__ void __launch_bounds__(256) ingest_table_kernel(IngestTable t, const int* __restrict__ rows, float* __restrict__ y, int B, int H,
+                                                           int W, int cpad, const float* __restrict__ nmean, const float* __restrict__ nvar,
+                                                           int creal, const float* __restrict__ pivot, double* __restrict__ mom_partial) {
+#pragma clang fp contract(off)  // the reference rounds the uint8 scaling and every addition of the 2x2 average separately
+    __shared__ float na[8], nb[8];
+    if (nmean) {
+        if (threadIdx.x < 8) {
+            const int c = threadIdx.x;
+            float a_ = 0.f, b_ = 0.f;
+            if (c < creal) { b_ = rsqrtf(fmaxf(nvar[c], 1e-2f)); a_ = -nmean[c] * b_; }
+            na[c] = a_; nb[c] = b_;
+        }
+        __syncthreads();
+    }
+    const int Ho = H / 2, Wo = W / 2;
+    const long long total = (long long)B * Ho * Wo;
+    double s1[MOM ? 8 : 1], s2[MOM ? 8 : 1];
+    float f1[MOM ? 8 : 1], f2[MOM ? 8 : 1], pv[MOM ? 8 : 1];
+    int run = 0;
+    if constexpr (MOM) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) { s1[c] = 0.0; s2[c] = 0.0; f1[c] = 0.f; f2[c] = 0.f; pv[c] = c < creal ? pivot[c] : 0.f; }
+    }
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const int wo = (int)(e % Wo);
+        const long long tt = e / Wo;
+        const int ho = (int)(tt % Ho);
+        const int f = (int)(tt / Ho);
+        const size_t srow = rows ? rows[f] : f;
+        const size_t px = (srow * H + 2 * ho) * W + 2 * wo;  // pixel index of tap (0,0); (0,1) = px + 1, (1,0) = px + W, (1,1) = px + W + 1
+        float out[8];
+        ingest_table_pixel(t, px, W, out);
+        if (nmean) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) out[c] = __builtin_fmaf(out[c], nb[c], na[c]);
+        }
+        if constexpr (MOM) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c)
+                if (c < cpad) { const float d = out[c] - pv[c]; f1[c] = f1[c] + d; f2[c] = __builtin_fmaf(d, d, f2[c]); }
+            if (++run == 32) {
+                run = 0;
+#pragma unroll
+                for (int c = 0; c < 8; ++c)
+                    if (c < cpad) { s1[c] += (double)f1[c]; s2[c] += (double)f2[c]; f1[c] = 0.f; f2[c] = 0.f; }
+            }
+        }
+        float* o = y + (size_t)e * cpad;
+        for (int c = 0; c < cpad; c += 4) *reinterpret_cast<f32x4*>(o + c) = *reinterpret_cast<const f32x4*>(out + c);
+    }
+    if constexpr (MOM) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+            if (c < cpad) { s1[c] += (double)f1[c]; s2[c] += (double)f2[c]; }
+        __shared__ double red[4][16];
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+            if (c < cpad) {
+#pragma unroll
+                for (int off = 32; off; off >>= 1) { s1[c] += __shfl_xor(s1[c], off); s2[c] += __shfl_xor(s2[c], off); }
+                if (lane == 0) { red[wave][c] = s1[c]; red[wave][8 + c] = s2[c]; }
+            }
+        __syncthreads();
+        if (threadIdx.x < 16) {
+            const int c = threadIdx.x & 7;
+            double tsum = 0.0;
+            if (c < cpad) tsum = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+            mom_partial[(size_t)blockIdx.x * 16 + threadIdx.x] = tsum;
+        }
+    }
+}
+
+int ingest_pool_sensors(const IngestTable& tin, const int* rows, float* y, int B, int H, int W, int cpad, hipStream_t s, const float* norm_mean,
+                        const float* norm_var, const float* pivot, double* mom_partial, int* mom_blocks, bool force_table_kernel) {
+    if (!y || B <= 0 || H < 2 || W < 2) return HAB_ERR_ARG;
+    if ((norm_mean == nullptr) != (norm_var == nullptr)) return HAB_ERR_ARG;
+    if (mom_partial && (!pivot || !mom_blocks || norm_mean)) return HAB_ERR_ARG;  // moments are those of the un-normalised tensor
+    IngestTable t = tin;
+    int creal = 0;
+    HAB_TRY(ingest_table_finish(t, W, cpad, &creal));
+    if (!force_table_kernel) {
+        // the legacy triple -- at most one rgb-like (uint8 x 3, 1/255), one depth-like (float32 x 1), one semantic-like (int32 x 1) sensor --
+        // stays on the three-pointer kernel it has always run on
+        const uint8_t* rgb = nullptr; const float* depth = nullptr; const int32_t* sem = nullptr;
+        int c_rgb = -1, c_depth = -1, c_sem = -1;
+        bool legacy = true;
+        for (int i = 0; i < t.n && legacy; ++i) {
+            if (t.dtype[i] == HAB_DTYPE_U8 && t.ch[i] == 3 && t.scale[i] == (float)(1.0 / 255.0) && !rgb) { rgb = static_cast<const uint8_t*>(t.src[i]); c_rgb = t.off[i]; }
+            else if (t.dtype[i] == HAB_DTYPE_F32 && t.ch[i] == 1 && !depth) { depth = static_cast<const float*>(t.src[i]); c_depth = t.off[i]; }
+            else if (t.dtype[i] == HAB_DTYPE_I32 && t.ch[i] == 1 && !sem) { sem = static_cast<const int32_t*>(t.src[i]); c_sem = t.off[i]; }
+            else legacy = false;
+        }
+        if (legacy)
+            return ingest_pool(rgb, depth, sem, rows, y, B, H, W, cpad, c_rgb, c_depth, c_sem, s, norm_mean, norm_var, pivot, mom_partial, mom_blocks);
+    }
+    const long long total = (long long)B * (H / 2) * (W / 2);
+    if (mom_partial) {
+        const int blocks = (int)fmin((double)INGEST_MOM_MAX_BLOCKS, (double)cdivl(total, 256));
+        *mom_blocks = blocks;
+        ingest_table_kernel<true><<<blocks, 256, 0, s>>>(t, rows, y, B, H, W, cpad, nullptr, nullptr, creal, pivot, mom_partial);
+    } else {
+        ingest_table_kernel<false><<<(int)fmin(8192.0, (double)cdivl(total, 256)), 256, 0, s>>>(t, rows, y, B, H, W, cpad, norm_mean, norm_var,
+                                                                                                 creal, nullptr, nullptr);
     }
     HAB_LAUNCH_CHECK();
     return HAB_OK;
@@ -1647,7 +1768,33 @@ using namespace hab;
 
 extern "C" int hab_obs_ingest_pool(const uint8_t* rgb, const float* depth, const int32_t* semantic, const int* rows, float* y, int B, int H,
                                    int W, int cpad, int c_rgb, int c_depth, int c_sem, hipStream_t stream) {
-    return ingest_pool(rgb, depth, semantic, rows, y, B, H, W, cpad, c_rgb, c_depth, c_sem, stream);
+    // adapter onto the table form: the keys that are present, in the order of their output channels
+    IngestTable t{};
+    for (int c = 0; c < 8 && t.n < 3; ++c) {
+        const int i = t.n;
+        if (rgb && c == c_rgb) { t.src[i] = rgb; t.dtype[i] = HAB_DTYPE_U8; t.ch[i] = 3; t.scale[i] = (float)(1.0 / 255.0); ++t.n; }
+        else if (depth && c == c_depth) { t.src[i] = depth; t.dtype[i] = HAB_DTYPE_F32; t.ch[i] = 1; ++t.n; }
+        else if (semantic && c == c_sem) { t.src[i] = semantic; t.dtype[i] = HAB_DTYPE_I32; t.ch[i] = 1; ++t.n; }
+    }
+    if (t.n != (rgb ? 1 : 0) + (depth ? 1 : 0) + (semantic ? 1 : 0)) return HAB_ERR_ARG;
+    int creal = 0;
+    HAB_TRY(ingest_table_finish(t, W, cpad, &creal));
+    for (int i = 0; i < t.n; ++i)  // the offsets the caller named are the ones concatenation gives
+        if (t.off[i] != (t.dtype[i] == HAB_DTYPE_U8 ? c_rgb : t.dtype[i] == HAB_DTYPE_F32 ? c_depth : c_sem)) return HAB_ERR_ARG;
+    return ingest_pool_sensors(t, rows, y, B, H, W, cpad, stream);
+}
+extern "C" int hab_obs_ingest_pool_sensors(const void* const* sensors, const int32_t* dtypes, const int32_t* channels, const float* scales, int n,
+                                           const int* rows, float* y, int B, int H, int W, int cpad, const float* norm_mean,
+                                           const float* norm_var, const float* pivot, double* mom_partial, int* mom_blocks,
+                                           hipStream_t stream) {
+    if (!sensors || !dtypes || !channels || !scales || n <= 0 || n > INGEST_MAX_SENSORS) return HAB_ERR_ARG;
+    IngestTable t{};
+    t.n = n;
+    for (int i = 0; i < n; ++i) {
+        if (channels[i] <= 0 || channels[i] > 8 || dtypes[i] < 0 || dtypes[i] > 2) return HAB_ERR_ARG;
+        t.src[i] = sensors[i]; t.dtype[i] = (signed char)dtypes[i]; t.ch[i] = (signed char)channels[i]; t.scale[i] = scales[i];
+    }
+    return ingest_pool_sensors(t, rows, y, B, H, W, cpad, stream, norm_mean, norm_var, pivot, mom_partial, mom_blocks);
 }
 extern "C" int hab_channel_moments(const float* x, int64_t npix, int cpad, int mode, const float* mean, float* out, double* scratch,
                                    int scratch_len, hipStream_t stream) {

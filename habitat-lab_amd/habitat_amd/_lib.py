@@ -28,7 +28,17 @@ class PolicyDesc(C.Structure):
         "num_object_categories", "has_compass", "has_gps", "action_dist", "gauss_flags")] + [("gauss_min_std", c_float),
                                                                                                 ("gauss_max_std", c_float),
                                                                                                 ("pointgoal_dim", c_int32),
-                                                                                                ("proximity_dim", c_int32)]
+                                                                                                ("proximity_dim", c_int32),
+                                                                                                ("num_visual", c_int32),
+                                                                                                ("visual_dtype", c_int32 * 4),
+                                                                                                ("visual_channels", c_int32 * 4),
+                                                                                                ("visual_scale", c_float * 4),
+                                                                                                ("num_fused", c_int32),
+                                                                                                ("fused_width", c_int32 * 8)]
+
+
+MAX_VISUAL, MAX_FUSED = 4, 8                  # HAB_MAX_VISUAL, HAB_MAX_FUSED
+DTYPE_U8, DTYPE_F32, DTYPE_I32 = 0, 1, 2      # HAB_DTYPE_*
 
 
 GAUSS_TANH_MU, GAUSS_USE_LOG_STD, GAUSS_USE_SOFTPLUS, GAUSS_USE_STD_PARAM, GAUSS_CLAMP_STD = 1, 2, 4, 8, 16  # HAB_GAUSS_*
@@ -36,7 +46,7 @@ GAUSS_TANH_MU, GAUSS_USE_LOG_STD, GAUSS_USE_SOFTPLUS, GAUSS_USE_STD_PARAM, GAUSS
 
 class Obs(C.Structure):
     _fields_ = [("rgb", vp), ("depth", vp), ("goal", vp), ("prev_actions", vp), ("semantic", vp), ("objectgoal", vp), ("compass", vp),
-                ("gps", vp), ("visual_features", vp), ("pointgoal", vp), ("proximity", vp)]
+                ("gps", vp), ("visual_features", vp), ("pointgoal", vp), ("proximity", vp), ("visual", vp * 4), ("fused", vp * 8)]
 
 
 class EmbedSlot(C.Structure):
@@ -82,6 +92,8 @@ SIGNATURES = {
     "hab_repack_flatten_weight": (c_int, [vp, vp, c_int, c_int, c_int, vp]),
     "hab_transpose2d": (c_int, [vp, vp, c_int, c_int, vp]),
     "hab_obs_ingest_pool": (c_int, [vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp]),
+    "hab_obs_ingest_pool_sensors": (c_int, [vp, vp, vp, vp, c_int, vp, vp, c_int, c_int, c_int, c_int, vp, vp, vp, vp, vp, vp]),
+    "hab_fused_gather": (c_int, [vp, vp, c_int, vp, vp, c_int, c_int, c_int, c_int, c_int, vp]),
     "hab_channel_moments": (c_int, [vp, c_int64, c_int, c_int, vp, vp, vp, c_int, vp]),
     "hab_running_mean_var_update": (c_int, [vp, vp, vp, vp, vp, c_float, c_int, vp]),
     "hab_running_mean_var_normalize": (c_int, [vp, c_int64, c_int, c_int, vp, vp, vp]),

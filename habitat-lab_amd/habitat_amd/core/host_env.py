@@ -1,7 +1,8 @@
 """A CPU stand-in for one simulator-backed environment (the `RLEnv` a VectorEnv worker owns: habitat/core/env.py:337-430):
 numpy-generated RGB-D + pointgoal observations of the benchmark's sizes, Bernoulli episode ends, a step budget.  It exists so
 that the process-per-env transport (core/vector_env.py) and the trainer's host path can be exercised and timed end to end
-without habitat-sim; it makes no attempt to be a navigation task."""
+without habitat-sim; it makes no attempt to be a navigation task.  `task="rearrange"` emits the observation set of a rearrangement
+skill instead (two named depth cameras and raw 1-D robot-state sensors, no goal sensor with an embedding; discrete actions)."""
 from __future__ import annotations
 
 import numpy as np
@@ -27,17 +28,27 @@ class Episode:
 class HostSyntheticNavEnv:
     def __init__(self, seed: int = 0, height: int = 256, width: int = 256, use_rgb: bool = True, use_depth: bool = True,
                  num_actions: int = 4, max_episode_steps: int = 500, p_done: float = 1.0 / 25.0, work_us: int = 0,
-                 num_episodes: int = 0):
+                 num_episodes: int = 0, task: str = "pointnav"):
+        assert task in ("pointnav", "rearrange"), task
+        self._task = task
         self._rng = np.random.default_rng(seed)
         self._seed = seed
         self._h, self._w, self._use_rgb, self._use_depth = height, width, use_rgb, use_depth
         self._max_steps, self._p_done, self._work_us = max_episode_steps, p_done, work_us
         sp = {}
-        if use_rgb:
-            sp["rgb"] = spaces.Box(0, 255, (height, width, 3), np.uint8)
-        if use_depth:
-            sp["depth"] = spaces.Box(0.0, 1.0, (height, width, 1), np.float32)
-        sp[GOAL_UUID] = spaces.Box(np.finfo(np.float32).min, np.finfo(np.float32).max, (2,), np.float32)
+        fmin, fmax = np.finfo(np.float32).min, np.finfo(np.float32).max
+        if task == "rearrange":  # the sensors of the reference's rearrangement skills (head / arm cameras, joint state, holding flag, goal)
+            sp["head_depth"] = spaces.Box(0.0, 1.0, (height, width, 1), np.float32)
+            sp["arm_depth"] = spaces.Box(0.0, 1.0, (height, width, 1), np.float32)
+            sp["joint"] = spaces.Box(fmin, fmax, (7,), np.float32)
+            sp["is_holding"] = spaces.Box(0.0, 1.0, (1,), np.float32)
+            sp["goal_to_agent_gps_compass"] = spaces.Box(fmin, fmax, (2,), np.float32)
+        else:
+            if use_rgb:
+                sp["rgb"] = spaces.Box(0, 255, (height, width, 3), np.uint8)
+            if use_depth:
+                sp["depth"] = spaces.Box(0.0, 1.0, (height, width, 1), np.float32)
+            sp[GOAL_UUID] = spaces.Box(fmin, fmax, (2,), np.float32)
         self.observation_space = spaces.Dict(sp)
         self.action_space = spaces.Discrete(num_actions)
         self.original_action_space = self.action_space
@@ -56,6 +67,13 @@ class HostSyntheticNavEnv:
 
     def _obs(self):
         o = {}
+        if self._task == "rearrange":
+            o["head_depth"] = self._rng.random((self._h, self._w, 1), dtype=np.float32)
+            o["arm_depth"] = self._rng.random((self._h, self._w, 1), dtype=np.float32)
+            o["joint"] = self._rng.uniform(-np.pi, np.pi, 7).astype(np.float32)
+            o["is_holding"] = np.array([float(self._rng.random() < 0.5)], dtype=np.float32)
+            o["goal_to_agent_gps_compass"] = np.array([self._rng.uniform(0.0, 10.0), self._rng.uniform(-np.pi, np.pi)], dtype=np.float32)
+            return o
         if self._use_rgb:
             o["rgb"] = self._rng.integers(0, 256, (self._h, self._w, 3), dtype=np.uint8)
         if self._use_depth:
@@ -90,6 +108,11 @@ class HostSyntheticNavEnv:
         pass
 
 
-def make_host_env(seed, height, width, use_rgb, use_depth, num_actions, max_episode_steps, work_us=0, num_episodes=0):
+def make_host_env(seed, height, width, use_rgb, use_depth, num_actions, max_episode_steps, work_us=0, num_episodes=0, task="pointnav"):
     return HostSyntheticNavEnv(seed=seed, height=height, width=width, use_rgb=use_rgb, use_depth=use_depth, num_actions=num_actions,
-                               max_episode_steps=max_episode_steps, work_us=work_us, num_episodes=num_episodes)
+                               max_episode_steps=max_episode_steps, work_us=work_us, num_episodes=num_episodes, task=task)
+
+
+def make_rearrange_host_env(seed, height, width, use_rgb, use_depth, num_actions, max_episode_steps, work_us=0, num_episodes=0):
+    """`vector_env_factory.make_env_fn` form of `task="rearrange"` (the sensor sizes come from the configured simulator sensors)."""
+    return make_host_env(seed, height, width, use_rgb, use_depth, num_actions, max_episode_steps, work_us, num_episodes, task="rearrange")

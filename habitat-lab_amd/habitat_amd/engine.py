@@ -107,19 +107,75 @@ class DevicePackInfo:
         return self
 
 
+def _read_param_table(L, h):
+    """[(name, shape, offset in floats)] of an engine handle, in the reference's state_dict() order."""
+    specs = []
+    name = C.create_string_buffer(256)
+    shape = (C.c_int64 * 4)()
+    nd, off = C.c_int(0), C.c_int64(0)
+    for i in range(L.hab_policy_num_params(h)):
+        check(L.hab_policy_param_info(h, i, name, 256, shape, C.byref(nd), C.byref(off)), "hab_policy_param_info")
+        specs.append((name.value.decode(), tuple(int(shape[k]) for k in range(nd.value)), int(off.value)))
+    return specs
+
+
+def policy_param_table(**engine_kwargs):
+    """The flat parameter arena's layout [(name, shape, offset)] for a set of PolicyEngine arguments.  Creating an engine handle and
+    reading its table touches no device, so this works on a machine without a GPU."""
+    L = _lib.lib()
+    d = PolicyEngine.make_desc(**{k: v for k, v in engine_kwargs.items() if k not in ("device", "with_grads")})
+    h = C.c_void_p()
+    check(L.hab_policy_create(C.byref(d), C.byref(h)), "hab_policy_create")
+    try:
+        return _read_param_table(L, h)
+    finally:
+        L.hab_policy_destroy(h)
+
+
 class PolicyEngine:
-    def __init__(self, *, arch="simple_cnn", backbone=18, baseplanes=32, normalize_visual_inputs=False, rnn_type="GRU",
-                 rnn_layers=1, hidden=512, num_actions=4, H=256, W=256, has_rgb=True, has_depth=True, goal_dim=2,
-                 max_frames=4096, max_envs=64, device="cuda", with_grads=True, visual_order=("rgb", "depth", "semantic"),
-                 has_semantic=False, num_object_categories=0, has_compass=False, has_gps=False, action_dist="categorical",
-                 gauss_flags=0, gauss_min_std=0.0, gauss_max_std=0.0, pointgoal_dim=0, proximity_dim=0):
-        L = _lib.lib()
-        self.L = L
+    @staticmethod
+    def make_desc(*, arch="simple_cnn", backbone=18, baseplanes=32, normalize_visual_inputs=False, rnn_type="GRU",
+                  rnn_layers=1, hidden=512, num_actions=4, H=256, W=256, has_rgb=True, has_depth=True, goal_dim=2,
+                  max_frames=4096, max_envs=64, visual_order=("rgb", "depth", "semantic"),
+                  has_semantic=False, num_object_categories=0, has_compass=False, has_gps=False, action_dist="categorical",
+                  gauss_flags=0, gauss_min_std=0.0, gauss_max_std=0.0, pointgoal_dim=0, proximity_dim=0, visual_table=(),
+                  fused_widths=()) -> PolicyDesc:
+        """hab_policy_desc of these arguments (see __init__)."""
         d = PolicyDesc(ARCH[arch], backbone, baseplanes, int(normalize_visual_inputs), RNN[rnn_type.upper()], rnn_layers, hidden,
                        num_actions, H, W, int(has_rgb), int(has_depth), goal_dim, max_frames, max_envs,
                        sum({"rgb": 1, "depth": 2, "semantic": 3}[k] << (2 * i) for i, k in enumerate(visual_order)), int(has_semantic),
                        int(num_object_categories), int(has_compass), int(has_gps), {"categorical": 0, "gaussian": 1}[action_dist],
                        int(gauss_flags), float(gauss_min_std), float(gauss_max_std), int(pointgoal_dim), int(proximity_dim))
+        if len(visual_table) > _lib.MAX_VISUAL or len(fused_widths) > _lib.MAX_FUSED:
+            raise _lib.HabError(f"at most {_lib.MAX_VISUAL} visual sensors and {_lib.MAX_FUSED} fused 1-D sensors")
+        if visual_table:
+            d.has_rgb = d.has_depth = d.has_semantic = d.visual_order = 0
+        d.num_visual = len(visual_table)
+        for i, (dt, ch, scale) in enumerate(visual_table):
+            d.visual_dtype[i], d.visual_channels[i], d.visual_scale[i] = int(dt), int(ch), float(scale)
+        d.num_fused = len(fused_widths)
+        for i, w in enumerate(fused_widths):
+            d.fused_width[i] = int(w)
+        return d
+
+    def __init__(self, *, arch="simple_cnn", backbone=18, baseplanes=32, normalize_visual_inputs=False, rnn_type="GRU",
+                 rnn_layers=1, hidden=512, num_actions=4, H=256, W=256, has_rgb=True, has_depth=True, goal_dim=2,
+                 max_frames=4096, max_envs=64, device="cuda", with_grads=True, visual_order=("rgb", "depth", "semantic"),
+                 has_semantic=False, num_object_categories=0, has_compass=False, has_gps=False, action_dist="categorical",
+                 gauss_flags=0, gauss_min_std=0.0, gauss_max_std=0.0, pointgoal_dim=0, proximity_dim=0, visual_table=(),
+                 fused_widths=()):
+        """visual_table: named visual sensors as (HAB_DTYPE_* code, channels, uint8 scale) in concatenation order -- given INSTEAD of
+        has_rgb / has_depth / has_semantic / visual_order; fused_widths: widths of the raw 1-D sensors fused into the recurrent
+        encoder's input, in order (hab_policy_desc)."""
+        L = _lib.lib()
+        self.L = L
+        d = self.make_desc(arch=arch, backbone=backbone, baseplanes=baseplanes, normalize_visual_inputs=normalize_visual_inputs,
+                           rnn_type=rnn_type, rnn_layers=rnn_layers, hidden=hidden, num_actions=num_actions, H=H, W=W, has_rgb=has_rgb,
+                           has_depth=has_depth, goal_dim=goal_dim, max_frames=max_frames, max_envs=max_envs, visual_order=visual_order,
+                           has_semantic=has_semantic, num_object_categories=num_object_categories, has_compass=has_compass,
+                           has_gps=has_gps, action_dist=action_dist, gauss_flags=gauss_flags, gauss_min_std=gauss_min_std,
+                           gauss_max_std=gauss_max_std, pointgoal_dim=pointgoal_dim, proximity_dim=proximity_dim,
+                           visual_table=visual_table, fused_widths=fused_widths)
         self.action_dist = action_dist
         self.desc = d
         h = C.c_void_p()
@@ -131,13 +187,7 @@ class PolicyEngine:
         self.num_actions = num_actions
         n = L.hab_policy_num_params(h)
         self.param_floats = L.hab_policy_param_floats(h)
-        self.specs = []
-        name = C.create_string_buffer(256)
-        shape = (C.c_int64 * 4)()
-        nd, off = C.c_int(0), C.c_int64(0)
-        for i in range(n):
-            check(L.hab_policy_param_info(h, i, name, 256, shape, C.byref(nd), C.byref(off)), "hab_policy_param_info")
-            self.specs.append((name.value.decode(), tuple(int(shape[k]) for k in range(nd.value)), int(off.value)))
+        self.specs = _read_param_table(L, h)
         self.buffer_names = {self.specs[i][0] for i in range(n) if L.hab_policy_param_is_buffer(h, i) == 1}
         dev = self.device
         self.params_flat = torch.zeros(self.param_floats, dtype=torch.float32, device=dev)
@@ -247,11 +297,17 @@ class PolicyEngine:
     @staticmethod
     def _obs(rgb, depth, goal, prev_actions=None, extra=None):
         """extra: optional dict with the ObjectNav sensors `semantic` (int32), `objectgoal` (int64), `compass`, `gps`, and the further
-        1-D goal sensors `pointgoal`, `proximity` (float)."""
+        1-D goal sensors `pointgoal`, `proximity` (float); `visual` / `fused`: the tensors of the descriptor's sensor tables, in table
+        order."""
         dp = lambda t: t.data_ptr() if t is not None else None
         e = extra or {}
-        return Obs(dp(rgb), dp(depth), dp(goal), dp(prev_actions), dp(e.get("semantic")), dp(e.get("objectgoal")), dp(e.get("compass")),
-                   dp(e.get("gps")), dp(e.get("visual_features")), dp(e.get("pointgoal")), dp(e.get("proximity")))
+        o = Obs(dp(rgb), dp(depth), dp(goal), dp(prev_actions), dp(e.get("semantic")), dp(e.get("objectgoal")), dp(e.get("compass")),
+                dp(e.get("gps")), dp(e.get("visual_features")), dp(e.get("pointgoal")), dp(e.get("proximity")))
+        for i, t in enumerate(e.get("visual", ())):
+            o.visual[i] = t.data_ptr()
+        for i, t in enumerate(e.get("fused", ())):
+            o.fused[i] = t.data_ptr()
+        return o
 
     def visual_feature_shape(self):
         """(C, Hf, Wf) = ResNetEncoder.output_shape (resnet_policy.py:235-253)."""

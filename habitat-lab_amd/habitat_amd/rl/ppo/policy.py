@@ -132,8 +132,7 @@ class _EvaluateFn(torch.autograd.Function):
         # visual embedding (ReLU(visual fc); absent for a blind net) -- copies of the engine's activations, differentiable through backward()
         eng, B, H = policy.engine, call["B"], policy.recurrent_hidden_size
         feats = eng.tap(4)[:B * H].view(B, H).clone()                                  # HAB_TAP_RNN_OUT
-        blind = getattr(policy, "is_blind", False) or not (policy._engine_kwargs.get("has_rgb") or policy._engine_kwargs.get("has_depth")
-                                                          or policy._engine_kwargs.get("has_semantic"))
+        blind = getattr(policy, "is_blind", False) or not policy._reads_images()
         ctx.has_perc = not blind
         ctx.use_extra = len(policy.aux_loss_modules) > 0  # (decided here: no device read-back to find out whether a gradient is zero)
         perc = eng.tap(3).view(B, -1)[:, :H].clone() if not blind else v.new_zeros(B, 0)  # HAB_TAP_RNN_IN[:, :hidden]
@@ -195,6 +194,11 @@ class NetPolicy(nn.Module, Policy):
     def _get_policy_components(self) -> List[nn.Module]:
         return [self._modules["net"], self._modules["critic"], self._modules["action_distribution"]]
 
+    def _reads_images(self) -> bool:
+        """The net has a visual encoder: legacy rgb / depth / semantic flags or a table of named visual sensors."""
+        kw = self._engine_kwargs
+        return bool(kw.get("has_rgb") or kw.get("has_depth") or kw.get("has_semantic") or kw.get("visual_table"))
+
     def aux_loss_parameters(self): return {k: v.parameters() for k, v in self.aux_loss_modules.items()}
 
     def _build_aux_modules(self, aux_loss_config, action_space) -> None:
@@ -208,7 +212,7 @@ class NetPolicy(nn.Module, Policy):
         net = self._modules["net"]
         net.output_size = net.recurrent_hidden_size = net.perception_embedding_size = self._hidden
         net.num_recurrent_layers = self.num_recurrent_layers
-        net.is_blind = not (self._engine_kwargs.get("has_rgb") or self._engine_kwargs.get("has_depth") or self._engine_kwargs.get("has_semantic"))
+        net.is_blind = not self._reads_images()
         items = aux_loss_config.items() if hasattr(aux_loss_config, "items") else aux_loss_config
         for name, cfg in items:
             cls = baseline_registry.get_auxiliary_loss(str(name))
@@ -269,9 +273,7 @@ class NetPolicy(nn.Module, Policy):
         self.engine, self.device = eng, device
         eng.set_training(self.training)
         ve = self.visual_encoder
-        if ve is not None and self._engine_kwargs.get("arch") == "resnet" and (self._engine_kwargs.get("has_rgb") or
-                                                                               self._engine_kwargs.get("has_depth") or
-                                                                               self._engine_kwargs.get("has_semantic")):
+        if ve is not None and self._engine_kwargs.get("arch") == "resnet" and self._reads_images():
             # the reference calls `actor_critic.visual_encoder(batch)` and reads `.output_shape` (ppo_trainer.py:271-279)
             ve.output_shape = eng.visual_feature_shape()
             ve.forward = self.encode_visual
@@ -284,7 +286,7 @@ class NetPolicy(nn.Module, Policy):
         eng = self._require_engine()
         obs = {k: v for k, v in observations.items() if k != VISUAL_FEATURES_KEY}
         rgb, depth, _, extra = self._obs_ptrs(obs)
-        ref = rgb if rgb is not None else depth
+        ref = next(t for t in (rgb, depth, extra.get("semantic"), *extra.get("visual", ())) if t is not None)
         n = ref.shape[0]
         if out is None:
             out = torch.empty((n,) + tuple(eng.visual_feature_shape()), device=self.device)
@@ -332,11 +334,23 @@ class NetPolicy(nn.Module, Policy):
             extra["proximity"] = observations["proximity"]
         if VISUAL_FEATURES_KEY in observations:  # frozen encoder: the rollout holds its output (resnet_policy.py:636-646)
             extra["visual_features"] = observations[VISUAL_FEATURES_KEY]
+        # named visual sensors and fused 1-D sensors (PointNavResNetPolicy): the tensors in the order of the engine's tables
+        for slot, table, dtypes in (("visual", getattr(self, "visual_sensors", ()), _TORCH_DTYPE), ("fused", getattr(self, "fused_sensors", ()), None)):
+            if not table or (slot == "visual" and not kw.get("visual_table")):
+                continue
+            ts = [observations[entry[0]] for entry in table]
+            for entry, t in zip(table, ts):
+                want_dt = dtypes[entry[1]] if dtypes else torch.float32
+                if t.dtype != want_dt:
+                    raise _lib.HabError(f"observation '{entry[0]}' must be {want_dt} (got {t.dtype})")
+                if not t.is_contiguous():
+                    raise _lib.HabError("observation tensors must be contiguous NHWC")
+            extra[slot] = ts
         want = {"rgb": torch.uint8, "depth": torch.float32, "goal": torch.float32, "semantic": torch.int32, "objectgoal": torch.int64,
                 "compass": torch.float32, "gps": torch.float32, "visual_features": torch.float32, "pointgoal": torch.float32,
                 "proximity": torch.float32}
         for name, t in dict(rgb=rgb, depth=depth, goal=goal, **extra).items():
-            if t is None:
+            if t is None or name in ("visual", "fused"):
                 continue
             if t.dtype != want[name]:
                 raise _lib.HabError(f"observation '{name}' must be {want[name]} (got {t.dtype})")
@@ -523,7 +537,7 @@ BACKBONES = {"resnet18": (18, "basic", [2, 2, 2, 2], False, False), "resnet50": 
 
 
 def _resnet_init(n_in, hidden, num_actions, rnn_type, rnn_layers, backbone, baseplanes, H, W, normalize, has_goal=True, n_obj=0,
-                 has_gps=False, has_compass=False, gauss=None, pointgoal_dim=0, proximity_dim=0, blind=False):
+                 has_gps=False, has_compass=False, gauss=None, pointgoal_dim=0, proximity_dim=0, blind=False, fused_dim=0):
     """Parameter / buffer values exactly as PointNavResNetPolicy.__init__ produces them: the torch modules are created in
     the reference's order (resnet_policy.py:389-396 embedding, :454-456 tgt_embeding, :578-585 ResNetEncoder [default
     Conv2d / GroupNorm initialisers -- ResNetEncoder.layer_init is never called], :588-595 visual_fc, :597-602 state encoder
@@ -617,7 +631,8 @@ def _resnet_init(n_in, hidden, num_actions, rnn_type, rnn_layers, backbone, base
         fc = nn.Linear(ncomp * fh * fw, hidden)
         out["net.visual_fc.1.weight"], out["net.visual_fc.1.bias"] = fc.weight.detach(), fc.bias.detach()
     rnn_cls = nn.LSTM if rnn_type == "LSTM" else nn.GRU
-    rnn = rnn_cls(input_size=(0 if blind else hidden) + 32 * n_slots, hidden_size=hidden, num_layers=rnn_layers)
+    # rnn_input_size: visual_fc's output, the raw fused 1-D sensors, the embeddings (resnet_policy.py:560-571,597-602)
+    rnn = rnn_cls(input_size=(0 if blind else hidden) + fused_dim + 32 * n_slots, hidden_size=hidden, num_layers=rnn_layers)
     for name, param in rnn.named_parameters():
         if "weight" in name:
             nn.init.orthogonal_(param)
@@ -669,11 +684,71 @@ def _gaussian_options(ad):
             dict(action_dist="gaussian", gauss_flags=flags, gauss_min_std=lo, gauss_max_std=hi))
 
 
+# Sensors with an embedding of their own in PointNavResNetNet (resnet_policy.py:441-545): never part of the default `fuse_keys` (:560-571)
+GOAL_SENSOR_KEYS = (GOAL_UUID, POINTGOAL_UUID, "objectgoal", "gps", "compass", "heading", "proximity", "imagegoal", "instance_imagegoal")
+MAX_VISUAL_CHANNELS = 8  # the encoder input is padded to 4 or 8 channels
+_TORCH_DTYPE = {_lib.DTYPE_U8: torch.uint8, _lib.DTYPE_F32: torch.float32, _lib.DTYPE_I32: torch.int32}
+_LEGACY_VISUAL = {"rgb": (_lib.DTYPE_U8, 3), "depth": (_lib.DTYPE_F32, 1), "semantic": (_lib.DTYPE_I32, 1)}
+
+
+def resolve_sensors(observation_space, fuse_keys=None, force_blind: bool = False):
+    """Which observations PointNavResNetNet reads beside its goal sensors (resnet_policy.py:178-199,560-571,648-660), as the engine's
+    two tables:
+      visual: [(key, HAB_DTYPE_* code, channels, scale)] -- the `fuse_keys` entries of rank 3 in `fuse_keys` order, what ResNetEncoder
+              concatenates; scale = np.float32(1 / high.max()) for uint8 sensors (multiplied, :185-199,263-265), 1 otherwise;
+      fused:  [(key, width)] -- the `fuse_keys` entries of rank 1, float32, whose raw values go into the recurrent encoder's input.
+    `fuse_keys` None: every key of the observation space in its order except the goal sensors.  `force_blind` empties the visual
+    table; the 1-D sensors are fused all the same."""
+    sp = observation_space.spaces
+    if fuse_keys is None:
+        keys = [k for k in sp.keys() if k not in GOAL_SENSOR_KEYS]
+    else:
+        keys = list(fuse_keys)
+        for k in keys:
+            sp[k]  # KeyError for a name the observation space does not have, like the reference's observation_space.spaces[k]
+        twice = [k for k in keys if k in GOAL_SENSOR_KEYS]
+        if twice:
+            raise _lib.HabError(f"fuse_keys names the goal sensor(s) {twice}: they already reach the recurrent encoder through their "
+                                "embeddings and would be fed twice")
+    visual, fused = [], []
+    for k in keys:
+        space = sp[k]
+        rank = len(space.shape)
+        dt = np.dtype(space.dtype)
+        if rank == 3:
+            code = {np.dtype(np.uint8): _lib.DTYPE_U8, np.dtype(np.float32): _lib.DTYPE_F32, np.dtype(np.int32): _lib.DTYPE_I32}.get(dt)
+            if code is None:
+                raise _lib.HabError(f"visual sensor '{k}' is {dt}: the accelerated path reads uint8, float32 and int32 images")
+            scale = float(np.float32(1.0 / space.high.max())) if code == _lib.DTYPE_U8 else 1.0
+            visual.append((k, code, int(space.shape[2]), scale))
+        elif rank == 1:
+            if dt != np.dtype(np.float32):
+                raise _lib.HabError(f"fused 1-D sensor '{k}' is {dt}: only float32 sensors are fused into the recurrent encoder's input")
+            fused.append((k, int(space.shape[0])))
+        else:
+            raise _lib.HabError(f"sensor '{k}' has rank {rank}: PointNavResNetPolicy reads (H, W, C) images and 1-D vectors")
+    if force_blind:
+        visual = []
+    if len(visual) > _lib.MAX_VISUAL:
+        raise _lib.HabError(f"{len(visual)} visual sensors {[v[0] for v in visual]}: the accelerated path takes at most {_lib.MAX_VISUAL}")
+    if sum(v[2] for v in visual) > MAX_VISUAL_CHANNELS:
+        raise _lib.HabError(f"{sum(v[2] for v in visual)} visual channels in {[v[0] for v in visual]}: the accelerated path takes at most "
+                            f"{MAX_VISUAL_CHANNELS} in total")
+    sizes = {tuple(sp[v[0]].shape[:2]) for v in visual}
+    if len(sizes) > 1:
+        raise _lib.HabError(f"visual sensors {[v[0] for v in visual]} differ in height x width {sorted(sizes)}: they are concatenated "
+                            "along the channels")
+    if len(fused) > _lib.MAX_FUSED:
+        raise _lib.HabError(f"{len(fused)} fused 1-D sensors {[f[0] for f in fused]}: the accelerated path takes at most {_lib.MAX_FUSED}")
+    return visual, fused
+
+
 @baseline_registry.register_policy
 class PointNavResNetPolicy(NetPolicy):
     """GroupNorm-ResNet + GRU/LSTM policy (rl/ddppo/policy/resnet_policy.py:50-162,391-767) on the HIP engine.
-    Supported on the accelerated path: backbones resnet18 / resnet50, rgb and/or depth visual sensors, the
-    pointgoal_with_gps_compass goal (2-D polar), discrete actions."""
+    Visual sensors under any name (up to 4 sensors / 8 channels of uint8, float32 or int32, concatenated in `fuse_keys` order) and raw
+    float32 1-D sensors fused into the recurrent encoder's input (`fuse_keys`, see resolve_sensors) beside the goal sensors
+    pointgoal_with_gps_compass (2-D polar), pointgoal, proximity, objectgoal, compass, gps; discrete or Gaussian actions."""
 
     def __init__(self, observation_space, action_space, hidden_size: int = 512, num_recurrent_layers: int = 1,
                  rnn_type: str = "GRU", resnet_baseplanes: int = 32, backbone: str = "resnet18",
@@ -688,27 +763,31 @@ class PointNavResNetPolicy(NetPolicy):
             gauss, gauss_kw = _gaussian_options(policy_config.action_dist)
         elif dist != "categorical":
             raise ValueError(f"Action distribution {dist} not supported.")
-        visual_keys = [k for k, v in sp.items() if len(v.shape) > 1]  # observation-space order (resnet_policy.py:178-182)
+        # `heading` is refused: the reference's forward embeds sensor_observations[0] -- the FIRST ROW of the batch (:705-713) -- which only
+        # type-checks for one environment; `imagegoal` / `instance_imagegoal` build a second ResNetEncoder for the goal image (:517-545)
+        refused = [k for k in ("heading", "imagegoal", "instance_imagegoal") if k in sp]
+        if refused:
+            raise _lib.HabError(f"PointNavResNetPolicy on habitat_amd does not take the {refused} sensor(s): the accelerated path has the "
+                                f"pointgoal_with_gps_compass, pointgoal, proximity, objectgoal, compass, gps goal sensors (got {list(sp.keys())})")
+        visual_tab, fused_tab = resolve_sensors(observation_space, fuse_keys, force_blind_policy)
+        visual_keys = [v[0] for v in visual_tab]  # `fuse_keys` order = observation-space order by default (resnet_policy.py:178-182)
         # force_blind_policy (resnet_policy.py:553-554): the visual encoder is built on an EMPTY observation space -- the images stay in
         # the observation dict (the rollout still stores them) but no backbone, compression or visual_fc exists and the recurrent
         # encoder's input is the embeddings alone.  An observation space without images gives the same net.
-        blind = bool(force_blind_policy) or not visual_keys
-        image_keys, visual_keys = visual_keys, ([] if blind else visual_keys)
+        blind = not visual_keys
         if blind and normalize_visual_inputs:
             # the reference builds RunningMeanAndVar(0) there and fails its `assert n_channels > 0` (running_mean_and_var.py:16): a blind
             # policy exists only without input normalisation (from_config turns it on when the observation space has "rgb")
             raise AssertionError("normalize_visual_inputs needs at least one visual channel (blind policy)")
-        # 1-D sensors with an embedding on the accelerated path (resnet_policy.py:454-515,662-734).  `heading` is refused: the reference's
-        # forward embeds sensor_observations[0] -- the FIRST ROW of the batch (:705-713) -- which only type-checks for one environment;
-        # `imagegoal` / `instance_imagegoal` build a second ResNetEncoder for the goal image (:517-545)
-        known_1d = {GOAL_UUID, POINTGOAL_UUID, "proximity", "objectgoal", "compass", "gps"}
-        other = [k for k in sp.keys() if k not in image_keys and k not in known_1d]
-        if any(k not in ("rgb", "depth", "semantic") for k in image_keys) or other:
-            raise _lib.HabError("PointNavResNetPolicy on habitat_amd supports the rgb / depth / semantic visual sensors and the "
-                                f"pointgoal_with_gps_compass, pointgoal, proximity, objectgoal, compass, gps 1-D sensors (got {list(sp.keys())})")
-        has_rgb, has_depth, has_sem = "rgb" in visual_keys, "depth" in visual_keys, "semantic" in visual_keys
+        # The rgb / depth / semantic triple in its classic form and nothing fused is described to the engine by the flags it has always
+        # taken; every other set of sensors by the two tables.
+        legacy = not fused_tab and all(k in _LEGACY_VISUAL and (c, ch) == _LEGACY_VISUAL[k] and (c != _lib.DTYPE_U8 or sc == float(np.float32(1.0 / 255.0)))
+                                       for k, c, ch, sc in visual_tab)
+        has_rgb, has_depth, has_sem = (legacy and "rgb" in visual_keys), (legacy and "depth" in visual_keys), (legacy and "semantic" in visual_keys)
         H, W = (int(sp[visual_keys[0]].shape[0]), int(sp[visual_keys[0]].shape[1])) if visual_keys else (0, 0)
-        n_in = (3 if has_rgb else 0) + (1 if has_depth else 0) + (1 if has_sem else 0)
+        n_in = sum(v[2] for v in visual_tab)
+        fused_dim = sum(f[1] for f in fused_tab)
+        table_kw = {} if legacy else dict(visual_table=tuple(v[1:] for v in visual_tab), fused_widths=tuple(f[1] for f in fused_tab))
         na = get_num_actions(action_space)
         rnn_type = rnn_type.upper()
         has_goal = GOAL_UUID in sp
@@ -728,13 +807,15 @@ class PointNavResNetPolicy(NetPolicy):
                               normalize_visual_inputs=bool(normalize_visual_inputs), rnn_type=rnn_type,
                               rnn_layers=num_recurrent_layers, hidden=hidden_size, H=H, W=W, has_rgb=has_rgb, has_depth=has_depth,
                               goal_dim=2 if has_goal else 0, max_frames=max_frames, max_envs=max_envs,
-                              visual_order=tuple(visual_keys), has_semantic=has_sem, num_object_categories=n_obj,
-                              has_compass=has_compass, has_gps=has_gps, pointgoal_dim=pg_dim, proximity_dim=px_dim, **(gauss_kw or {})),
+                              visual_order=tuple(visual_keys) if legacy else (), has_semantic=has_sem, num_object_categories=n_obj,
+                              has_compass=has_compass, has_gps=has_gps, pointgoal_dim=pg_dim, proximity_dim=px_dim, **table_kw,
+                              **(gauss_kw or {})),
                          lambda: _resnet_init(n_in, hidden_size, na, rnn_type, num_recurrent_layers, backbone, resnet_baseplanes,
                                               H, W, normalize_visual_inputs, has_goal, n_obj, has_gps, has_compass, gauss,
-                                              pointgoal_dim=pg_dim, proximity_dim=px_dim, blind=blind),
+                                              pointgoal_dim=pg_dim, proximity_dim=px_dim, blind=blind, fused_dim=fused_dim),
                          buffer_names=bufs)
         self.is_blind = blind
+        self.visual_sensors, self.fused_sensors = tuple(visual_tab), tuple(fused_tab)
         self._build_aux_modules(aux_loss_config, action_space)
 
     @classmethod

@@ -223,10 +223,26 @@ int hab_transpose2d(const float* w, float* wt, int R, int C, hipStream_t stream)
  * running_mean_and_var.py:24-78).  All NHWC fp32, channel counts multiples of 4.
  * ------------------------------------------------------------------------------------------- */
 /* Ingest: per visual key permute -> uint8 * fp32(1/255) -> cat (rgb,depth or depth,rgb) -> avg_pool2d(2); channels
- * zero-padded to cpad (4 or 8); observations read in place through rows[] (resnet_policy.py:259-271). */
+ * zero-padded to cpad (4 or 8); observations read in place through rows[] (resnet_policy.py:259-271).  The rgb / depth / semantic
+ * form of hab_obs_ingest_pool_sensors below (an adapter onto it: the keys that are present, ordered by their output channels). */
 int hab_obs_ingest_pool(const uint8_t* rgb, const float* depth, const int32_t* semantic, const int* rows, float* y, int B, int H, int W,
                         int cpad, int c_rgb, int c_depth, int c_sem /* first output channel of each key, -1 = absent */,
                         hipStream_t stream);
+/* The same for a table of n <= 4 visual sensors under any name (resnet_policy.py:178-199,259-271): sensor i is (rows, H, W,
+ * channels[i]) of dtypes[i] (HAB_DTYPE_*) and lands at output channel sum(channels[:i]); uint8 values are multiplied with scales[i] =
+ * fp32(1 / high.max()), int32 values are cast.  sum(channels) <= cpad (4 or 8), padding channels are written as zeros.  The arithmetic
+ * is F.avg_pool2d's on the scaled fp32 values, bit for bit: taps added in the order (0,0), (0,1), (1,0), (1,1), then * 0.25.
+ *   norm_mean / norm_var (nullable, together): the evaluation-mode RunningMeanAndVar affine is applied to the result.
+ *   mom_partial (nullable; with pivot, and without norm_*): training mode -- the pass also leaves per-workgroup partial sums of
+ *   (x - pivot[c]) and (x - pivot[c])^2 per channel, [*mom_blocks][16] doubles (room for 2048 x 16). */
+int hab_obs_ingest_pool_sensors(const void* const* sensors, const int32_t* dtypes, const int32_t* channels, const float* scales, int n,
+                                const int* rows, float* y, int B, int H, int W, int cpad, const float* norm_mean, const float* norm_var,
+                                const float* pivot, double* mom_partial, int* mom_blocks, hipStream_t stream);
+/* Raw 1-D sensors into the recurrent encoder's input (PointNavResNetNet.forward, resnet_policy.py:648-660: torch.cat of the `fuse_keys`
+ * values): dst[f][col0 + off_i + c] = sensors[i][rows ? rows[f] : f][c] for the n <= 8 float32 sensors of widths[i] values (off_i =
+ * sum(widths[:i])), and dst[f][pad0 .. pad0 + npad) = 0 (the row's padding up to its leading dimension), in ONE launch. */
+int hab_fused_gather(const float* const* sensors, const int32_t* widths, int n, const int* rows, float* dst, int ld, int col0, int pad0,
+                     int npad, int B, hipStream_t stream);
 /* Channel moments over all pixels: mode 0 -> out[c] = mean, mode 1 -> out[c] = mean((x - mean[c])^2)
  * (running_mean_and_var.py:33-45).  scratch: >= 1024*cpad doubles. */
 int hab_channel_moments(const float* x, int64_t npix, int cpad, int mode, const float* mean, float* out, double* scratch,
@@ -356,7 +372,7 @@ typedef struct hab_policy_desc {
     int32_t hidden;        /* 512 */
     int32_t num_actions;   /* Discrete(n) */
     int32_t H, W;          /* observation size */
-    int32_t has_rgb, has_depth;
+    int32_t has_rgb, has_depth;    /* (arch 1: the legacy way of naming the visual sensors; num_visual below is the general one) */
     int32_t goal_dim;      /* pointgoal_with_gps_compass dims (2) */
     int32_t max_frames;    /* largest T*n of an evaluate call */
     int32_t max_envs;      /* largest n of an act call */
@@ -375,7 +391,23 @@ typedef struct hab_policy_desc {
     /* further 1-D goal sensors (resnet_policy.py:489-494,510-515,694-700): dims of the PointGoalSensor / ProximitySensor vectors, 0 = absent.
      * arch 0 (PointNavBaselinePolicy): a `pointgoal` sensor is passed as `goal` (policy.py:509-514), these stay 0. */
     int32_t pointgoal_dim, proximity_dim;
+    /* arch 1, named sensors (ResNetEncoder takes every rank-3 observation under any name, resnet_policy.py:178-199,259-271;
+     * PointNavResNetNet concatenates the raw values of the other 1-D `fuse_keys`, :560-571,648-660).  Both counts 0: the legacy flags
+     * above say what the net reads, exactly as before.  num_visual > 0: the visual sensors are THIS table, in concatenation order
+     * (has_rgb / has_depth / has_semantic / visual_order must be 0): element type HAB_DTYPE_*, channels, and the factor a uint8
+     * sensor is multiplied with (fp32(1 / high.max()); ignored for the other types).  At most HAB_MAX_VISUAL sensors and 8 channels
+     * in total, all (H, W, channels).  num_fused > 0: that many float32 1-D sensors of fused_width[i] values each are copied, in
+     * table order, into the recurrent encoder's input behind visual_fc's output (behind nothing for a blind net) and in front of the
+     * embeddings; weight_ih_l0 has sum(fused_width) more columns there.  No parameter is added. */
+    int32_t num_visual;
+    int32_t visual_dtype[4];
+    int32_t visual_channels[4];
+    float visual_scale[4];
+    int32_t num_fused;
+    int32_t fused_width[8];
 } hab_policy_desc;
+#define HAB_MAX_VISUAL 4
+#define HAB_MAX_FUSED 8
 /* rl/ddppo/policy/resnet.py:296-345 */
 #define HAB_BACKBONE_RESNET18 18
 #define HAB_BACKBONE_RESNET50 50
@@ -406,6 +438,8 @@ typedef struct hab_obs {   /* arena base pointers; frame f lives at row rows[f] 
                                     the encoder and backward stops at visual_fc (no encoder gradients are written). */
     const float* pointgoal;      /* (rows, pointgoal_dim)  PointGoalSensor, arch 1 */
     const float* proximity;      /* (rows, proximity_dim)  ProximitySensor, arch 1 */
+    const void* visual[4];       /* (rows, H, W, visual_channels[i]) of visual_dtype[i]: the descriptor's visual table, in its order */
+    const float* fused[8];       /* (rows, fused_width[i]): the descriptor's fused table, in its order */
 } hab_obs;
 
 typedef struct hab_pack_info { /* int32 copies of hab_build_pack_info's arrays */
@@ -531,7 +565,7 @@ int hab_policy_probe_work(hab_policy* p, int tag, double* flops, double* bytes);
 #define HAB_TAP_CONV3 2
 #define HAB_TAP_RNN_IN 3
 #define HAB_TAP_RNN_OUT 4
-#define HAB_TAP_ENC_IN 5       /* arch 1: avg-pooled, normalised encoder input (NHWC, channels padded to 4) */
+#define HAB_TAP_ENC_IN 5       /* arch 1: avg-pooled, normalised encoder input (NHWC, channels padded to 4, or to 8 for 5 .. 8 channels) */
 #define HAB_TAP_STEM 6
 #define HAB_TAP_POOL 7
 #define HAB_TAP_COMPRESSION 8
