@@ -233,6 +233,271 @@ static int launch_resize_crop(const ResizeCropArgs& a, hipStream_t stream) {
     return HAB_OK;
 }
 
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// CubeMap2Equirect / CubeMap2Fisheye (N6).  Reference: habitat_baselines/common/obs_transformers.py:239-1199: stack of
+// the six face sensors -> permute -> float -> (depth: * z-factor) -> F.grid_sample(bilinear, zeros, align_corners=True) against six
+// precomputed grids -> view(...).sum(1) -> cast -> permute, eight launches and about seven full-size temporaries per sensor group.
+// The six grids are disjoint (a pixel is assigned to the first face that sees its ray), so the sum has one non-zero term: the table
+// holds that face and its grid coordinates, and ONE gather launch reads the six NHWC sensors where they lie and writes the output
+// once in the sensor dtype.  One thread owns an output pixel (all channels) for a run of frames: the table entry, the four tap
+// offsets and the four weights are computed once and reused over the run.  Neighbouring output pixels map to neighbouring texels of
+// one face, so the reads are locally coherent without LDS.
+//
+// Arithmetic is ATen's grid_sampler_2d (fp32, contraction off): ix = ((gx + 1) / 2) * (W - 1); x0 = floor(ix), x1 = x0 + 1; weights
+// (x1-ix)*(y1-iy), (ix-x0)*(y1-iy), (x1-ix)*(iy-y0), (ix-x0)*(iy-y0); result = sum over nw, ne, sw, se in that order of value * weight;
+// a tap outside the face contributes nothing, and nothing outside the face is read: the address of such a tap is moved onto a texel
+// of the face and the value is discarded (gx = +1 gives x1 = W: the last face of the last frame must not be read past its end).
+// With a z-factor each tap value is first multiplied by zfactor[y_tap * W + x_tap] (the reference multiplies the batch before it
+// samples).
+struct ProjEntry { int32_t face; float gx, gy; };
+static_assert(sizeof(ProjEntry) == 12, "table entry = {int32 face; float gx; float gy}");
+
+constexpr int PROJ_MAX_SRC = 6;
+struct ProjectArgs {
+    const void* src[PROJ_MAX_SRC];
+    void* dst;
+    const ProjEntry* table;
+    const float* zf;
+    int n_src, N, H, W;
+    int out_h, out_w;
+    int frames_per_thread;
+};
+
+template <class T, int C>
+struct PixIO {  // one pixel = C elements
+    static __device__ void load(const T* p, float (&v)[C]) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) v[c] = (float)p[c];
+    }
+    static __device__ void store(T* p, const float (&v)[C]) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) p[c] = PixCast<T>::from(v[c]);
+    }
+};
+
+// What one output pixel needs of its face, the same for every frame: ATen's unnormalised coordinates, corner weights and bounds.
+struct ProjTaps {
+    float w[4];                      // nw, ne, sw, se
+    bool okx0, okx1, oky0, oky1;     // column x0 / x1 and row y0 / y1 inside the face
+    int xi0, xi1, yi0, yi1;          // the same as integers, 0 where outside (a texel of the face whose value is discarded)
+};
+
+__device__ inline ProjTaps proj_taps(float gx, float gy, int H, int W) {
+    ProjTaps t;
+    const float ix = ((gx + 1.f) / 2.f) * (float)(W - 1);
+    const float iy = ((gy + 1.f) / 2.f) * (float)(H - 1);
+    const float x0 = floorf(ix), y0 = floorf(iy), x1 = x0 + 1.f, y1 = y0 + 1.f;
+    t.w[0] = (x1 - ix) * (y1 - iy); t.w[1] = (ix - x0) * (y1 - iy); t.w[2] = (x1 - ix) * (iy - y0); t.w[3] = (ix - x0) * (iy - y0);
+    // bounds in the float domain: a NaN or huge coordinate fails every comparison and no tap is used
+    const float xmax = (float)(W - 1), ymax = (float)(H - 1);
+    t.okx0 = x0 >= 0.f && x0 <= xmax; t.okx1 = x1 >= 0.f && x1 <= xmax;
+    t.oky0 = y0 >= 0.f && y0 <= ymax; t.oky1 = y1 >= 0.f && y1 <= ymax;
+    t.xi0 = t.okx0 ? (int)x0 : 0; t.xi1 = t.okx1 ? (int)x1 : 0; t.yi0 = t.oky0 ? (int)y0 : 0; t.yi1 = t.oky1 ? (int)y1 : 0;
+    return t;
+}
+
+__device__ inline const void* proj_face(const ProjectArgs& a, int face) {
+    const void* base = nullptr;  // select, not index: a runtime index into the by-value pointer array would put it in scratch
+#pragma unroll
+    for (int f = 0; f < PROJ_MAX_SRC; ++f)
+        if (face == f) base = a.src[f];
+    return base;
+}
+
+constexpr int PROJ_UNROLL = 4;  // frames in flight per thread
+// A workgroup owns a 32 x 8 tile of output pixels: rows that are neighbours in the output read the same rows of the face, and inside
+// one workgroup the second reader finds them in the CU's vector cache (row-major strips of 256 pixels put vertical neighbours on
+// different XCDs, each of which fetched the face rows into its own L2).
+constexpr int PROJ_TW = 32, PROJ_TH = 8;
+
+// Any dtype and channel count: four taps, each read on its own.
+template <class T, int C, bool ZF>
+__global__ void __launch_bounds__(256) obs_project_kernel(const ProjectArgs a) {
+    const int ox = blockIdx.x * PROJ_TW + threadIdx.x % PROJ_TW, oy = blockIdx.y * PROJ_TH + threadIdx.x / PROJ_TW;
+    if (ox >= a.out_w || oy >= a.out_h) return;
+    const int p = oy * a.out_w + ox, out_px = a.out_h * a.out_w;
+    const int n0 = blockIdx.z * a.frames_per_thread;
+    const int n1 = min(n0 + a.frames_per_thread, a.N);
+    const size_t frame = (size_t)a.H * a.W * C;
+    T* out = static_cast<T*>(a.dst) + ((size_t)n0 * out_px + p) * C;
+    const size_t out_stride = (size_t)out_px * C;
+    const ProjEntry e = a.table[p];
+    float zero[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) zero[c] = 0.f;
+    if (e.face < 0 || e.face >= a.n_src) {  // no source: 0 in every channel
+        for (int n = n0; n < n1; ++n, out += out_stride) PixIO<T, C>::store(out, zero);
+        return;
+    }
+    const ProjTaps t = proj_taps(e.gx, e.gy, a.H, a.W);
+    const bool ok[4] = {t.okx0 && t.oky0, t.okx1 && t.oky0, t.okx0 && t.oky1, t.okx1 && t.oky1};
+    const int tex[4] = {t.yi0 * a.W + t.xi0, t.yi0 * a.W + t.xi1, t.yi1 * a.W + t.xi0, t.yi1 * a.W + t.xi1};
+    float z[4] = {1.f, 1.f, 1.f, 1.f};
+    if (ZF) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) z[k] = a.zf[tex[k]];
+    }
+    const T* face = static_cast<const T*>(proj_face(a, e.face));
+    for (int n = n0; n < n1; n += PROJ_UNROLL) {
+        float v[PROJ_UNROLL][4][C];
+#pragma unroll
+        for (int u = 0; u < PROJ_UNROLL; ++u) {  // every load of the batch is issued before the first use; the tail repeats frame n1 - 1
+            const T* img = face + (size_t)min(n + u, n1 - 1) * frame;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) PixIO<T, C>::load(img + (size_t)tex[k] * C, v[u][k]);
+        }
+#pragma unroll
+        for (int u = 0; u < PROJ_UNROLL; ++u) {
+            if (n + u >= n1) break;
+            float r[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                r[c] = 0.f;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) r[c] = r[c] + (ok[k] ? (ZF ? v[u][k][c] * z[k] : v[u][k][c]) * t.w[k] : 0.f);
+            }
+            PixIO<T, C>::store(out + (size_t)(n + u - n0) * out_stride, r);
+        }
+    }
+}
+
+// The two flagship sensors, float32 depth (C = 1) and packed uint8 rgb (C = 3): the taps x0 and x1 of a row are neighbours in
+// memory, so ONE load per row fetches both -- two loads per frame instead of four dword or twelve byte loads.  The pair starts at
+// column xb = min(x0, W - 2) (0 when x0 is outside), so it lies inside the row also when x0 or x1 does not; which half holds x0 and
+// which x1 is the same for every frame.
+typedef float f32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+typedef uint32_t u32x3_a4 __attribute__((ext_vector_type(3), aligned(4)));
+
+template <class T>
+struct PairFetch;
+template <>
+struct PairFetch<float> {  // dwordx2 at texel (y, xb)
+    static constexpr int C = 1;
+    int off;
+    __device__ PairFetch(int y, int xb, int W, int) : off(y * W + xb) {}
+    __device__ void load(const float* img, float (&px)[2][1]) const {
+        const f32x2_a4 d = *reinterpret_cast<const f32x2_a4*>(img + off);
+        px[0][0] = d.x; px[1][0] = d.y;
+    }
+};
+template <>
+struct PairFetch<uint8_t> {  // the six bytes of (y, xb), (y, xb + 1) inside three aligned dwords that do not leave the frame
+    static constexpr int C = 3;
+    int base;        // byte offset of the first dword inside the frame (frames are a multiple of 4 bytes, checked by the launcher)
+    uint32_t shift;  // position of the first byte in the dwords, 0..6
+    __device__ PairFetch(int y, int xb, int W, int frame_bytes) {
+        const int addr = (y * W + xb) * 3;
+        base = min(addr & ~3, frame_bytes - 12);
+        shift = (uint32_t)(addr - base);
+    }
+    __device__ void load(const uint8_t* img, float (&px)[2][3]) const {
+        const u32x3_a4 d = *reinterpret_cast<const u32x3_a4*>(img + base);
+        const bool hi = shift >= 4;
+        const uint32_t d0 = hi ? d.y : d.x, d1 = hi ? d.z : d.y;
+        const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, shift & 3);   // bytes 0..3 of the pair
+        const uint32_t w1 = __builtin_amdgcn_alignbyte(d.z, d1, shift & 3);  // bytes 4..5 (hi: shift & 3 <= 2, they come from d1)
+        px[0][0] = (float)(w0 & 255u); px[0][1] = (float)((w0 >> 8) & 255u); px[0][2] = (float)((w0 >> 16) & 255u);
+        px[1][0] = (float)(w0 >> 24); px[1][1] = (float)(w1 & 255u); px[1][2] = (float)((w1 >> 8) & 255u);
+    }
+};
+
+template <class T, bool ZF>
+__global__ void __launch_bounds__(256) obs_project_pair_kernel(const ProjectArgs a) {
+    constexpr int C = PairFetch<T>::C;
+    const int ox = blockIdx.x * PROJ_TW + threadIdx.x % PROJ_TW, oy = blockIdx.y * PROJ_TH + threadIdx.x / PROJ_TW;
+    if (ox >= a.out_w || oy >= a.out_h) return;
+    const int p = oy * a.out_w + ox, out_px = a.out_h * a.out_w;
+    const int n0 = blockIdx.z * a.frames_per_thread;
+    const int n1 = min(n0 + a.frames_per_thread, a.N);
+    const int frame = a.H * a.W * C;
+    T* out = static_cast<T*>(a.dst) + ((size_t)n0 * out_px + p) * C;
+    const size_t out_stride = (size_t)out_px * C;
+    const ProjEntry e = a.table[p];
+    float zero[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) zero[c] = 0.f;
+    if (e.face < 0 || e.face >= a.n_src) {
+        for (int n = n0; n < n1; ++n, out += out_stride) PixIO<T, C>::store(out, zero);
+        return;
+    }
+    const ProjTaps t = proj_taps(e.gx, e.gy, a.H, a.W);
+    const bool ok[4] = {t.okx0 && t.oky0, t.okx1 && t.oky0, t.okx0 && t.oky1, t.okx1 && t.oky1};
+    const int xb = t.okx0 ? min(t.xi0, a.W - 2) : 0;                   // W >= 2, checked by the launcher
+    const bool s0 = t.okx0 && t.xi0 != xb, s1 = t.okx1 && t.xi1 != xb;  // x0 / x1 is the SECOND texel of the pair
+    const PairFetch<T> f0(t.yi0, xb, a.W, frame * (int)sizeof(T)), f1(t.yi1, xb, a.W, frame * (int)sizeof(T));
+    float z[4] = {1.f, 1.f, 1.f, 1.f};
+    if (ZF) {
+        const int tex[4] = {t.yi0 * a.W + t.xi0, t.yi0 * a.W + t.xi1, t.yi1 * a.W + t.xi0, t.yi1 * a.W + t.xi1};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) z[k] = a.zf[tex[k]];
+    }
+    const T* face = static_cast<const T*>(proj_face(a, e.face));
+    for (int n = n0; n < n1; n += PROJ_UNROLL) {
+        float top[PROJ_UNROLL][2][C], bot[PROJ_UNROLL][2][C];
+#pragma unroll
+        for (int u = 0; u < PROJ_UNROLL; ++u) {  // every load of the batch is issued before the first use; the tail repeats frame n1 - 1
+            const T* img = face + (size_t)min(n + u, n1 - 1) * frame;
+            f0.load(img, top[u]);
+            f1.load(img, bot[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < PROJ_UNROLL; ++u) {
+            if (n + u >= n1) break;
+            float r[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float v[4] = {s0 ? top[u][1][c] : top[u][0][c], s1 ? top[u][1][c] : top[u][0][c],
+                                    s0 ? bot[u][1][c] : bot[u][0][c], s1 ? bot[u][1][c] : bot[u][0][c]};
+                r[c] = 0.f;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) r[c] = r[c] + (ok[k] ? (ZF ? v[k] * z[k] : v[k]) * t.w[k] : 0.f);
+            }
+            PixIO<T, C>::store(out + (size_t)(n + u - n0) * out_stride, r);
+        }
+    }
+}
+
+template <class T, int C>
+static int launch_project_c(const ProjectArgs& a0, hipStream_t stream) {
+    ProjectArgs a = a0;
+    const int tiles_x = cdiv(a.out_w, PROJ_TW), tiles_y = cdiv(a.out_h, PROJ_TH);
+    if (tiles_y > 65535) return HAB_ERR_UNSUPPORTED;
+    // enough workgroups to fill the chip (about 8 per CU), then as many frames per thread as that leaves
+    int chunks = (int)cdivl(2048, (long long)tiles_x * tiles_y);
+    if (chunks > a.N) chunks = a.N;
+    a.frames_per_thread = cdiv(a.N, chunks);
+    chunks = cdiv(a.N, a.frames_per_thread);
+    dim3 grid(tiles_x, tiles_y, chunks);
+    const bool zf = a.zf != nullptr;
+    if constexpr ((std::is_same_v<T, float> && C == 1) || (std::is_same_v<T, uint8_t> && C == 3)) {
+        const long long frame_bytes = (long long)a.H * a.W * C * sizeof(T);
+        bool aligned = (reinterpret_cast<uintptr_t>(a.dst) & 3) == 0;
+        for (int f = 0; f < a.n_src; ++f) aligned = aligned && (reinterpret_cast<uintptr_t>(a.src[f]) & 3) == 0;
+        if (a.W >= 2 && frame_bytes % 4 == 0 && frame_bytes >= 12 && aligned) {
+            if (zf) obs_project_pair_kernel<T, true><<<grid, 256, 0, stream>>>(a);
+            else obs_project_pair_kernel<T, false><<<grid, 256, 0, stream>>>(a);
+            HAB_LAUNCH_CHECK();
+            return HAB_OK;
+        }
+    }
+    if (zf) obs_project_kernel<T, C, true><<<grid, 256, 0, stream>>>(a);
+    else obs_project_kernel<T, C, false><<<grid, 256, 0, stream>>>(a);
+    HAB_LAUNCH_CHECK();
+    return HAB_OK;
+}
+
+template <class T>
+static int launch_project(const ProjectArgs& a, int C, hipStream_t stream) {
+    switch (C) {
+    case 1: return launch_project_c<T, 1>(a, stream);
+    case 2: return launch_project_c<T, 2>(a, stream);
+    case 3: return launch_project_c<T, 3>(a, stream);
+    case 4: return launch_project_c<T, 4>(a, stream);
+    default: return HAB_ERR_ARG;
+    }
+}
+
 }  // namespace hab
 
 extern "C" int hab_obs_resize_crop(const void* src, void* dst, int dtype, int N, int H, int W, int C, int resized_h, int resized_w,
@@ -249,4 +514,26 @@ extern "C" int hab_obs_resize_crop(const void* src, void* dst, int dtype, int N,
     case HAB_DTYPE_I32: return launch_resize_crop<int32_t>(a, stream);
     default: return HAB_ERR_UNSUPPORTED;
     }
+}
+
+
+extern "C" int hab_obs_project(const void* const* src, int n_src, void* dst, int dtype, int N, int H, int W, int C, const void* table,
+                               const float* zfactor, int out_h, int out_w, hipStream_t stream) {
+    using namespace hab;
+    if (!src || !dst || !table || n_src < 1 || n_src > PROJ_MAX_SRC || N <= 0 || H <= 0 || W <= 0 || C < 1 || C > 4 || out_h <= 0 ||
+        out_w <= 0)
+        return HAB_ERR_ARG;
+    for (int f = 0; f < n_src; ++f)
+        if (!src[f]) return HAB_ERR_ARG;
+    if (dtype != HAB_DTYPE_U8 && dtype != HAB_DTYPE_F32) return HAB_ERR_UNSUPPORTED;
+    // texel offsets inside a face and the output pixel index are 32-bit in the kernel; frame offsets are 64-bit
+    if ((long long)H * W * C > 0x7fffffffLL || (long long)out_h * out_w > 0x7fffff00LL) return HAB_ERR_UNSUPPORTED;
+    ProjectArgs a{};
+    for (int f = 0; f < n_src; ++f) a.src[f] = src[f];
+    a.dst = dst;
+    a.table = static_cast<const ProjEntry*>(table);
+    a.zf = zfactor;
+    a.n_src = n_src; a.N = N; a.H = H; a.W = W;
+    a.out_h = out_h; a.out_w = out_w;
+    return dtype == HAB_DTYPE_U8 ? launch_project<uint8_t>(a, C, stream) : launch_project<float>(a, C, stream);
 }

@@ -2,7 +2,9 @@
 numpy-generated RGB-D + pointgoal observations of the benchmark's sizes, Bernoulli episode ends, a step budget.  It exists so
 that the process-per-env transport (core/vector_env.py) and the trainer's host path can be exercised and timed end to end
 without habitat-sim; it makes no attempt to be a navigation task.  `task="rearrange"` emits the observation set of a rearrangement
-skill instead (two named depth cameras and raw 1-D robot-state sensors, no goal sensor with an embedding; discrete actions)."""
+skill instead (two named depth cameras and raw 1-D robot-state sensors, no goal sensor with an embedding; discrete actions).
+`task="cubemap"` emits the six cube-face cameras of a 360-degree agent (`rgb_back` ... `rgb_up`, `depth_back` ... `depth_up`, the
+face order of CubeMap2Equirect / CubeMap2Fisheye) plus the pointgoal sensor."""
 from __future__ import annotations
 
 import numpy as np
@@ -10,6 +12,7 @@ import numpy as np
 from habitat_amd.common import spaces
 
 GOAL_UUID = "pointgoal_with_gps_compass"
+CUBE_FACES = ("back", "down", "front", "left", "right", "up")  # the sensor order of the cube-map obs transformers
 
 
 class Episode:
@@ -29,7 +32,7 @@ class HostSyntheticNavEnv:
     def __init__(self, seed: int = 0, height: int = 256, width: int = 256, use_rgb: bool = True, use_depth: bool = True,
                  num_actions: int = 4, max_episode_steps: int = 500, p_done: float = 1.0 / 25.0, work_us: int = 0,
                  num_episodes: int = 0, task: str = "pointnav"):
-        assert task in ("pointnav", "rearrange"), task
+        assert task in ("pointnav", "rearrange", "cubemap"), task
         self._task = task
         self._rng = np.random.default_rng(seed)
         self._seed = seed
@@ -43,6 +46,12 @@ class HostSyntheticNavEnv:
             sp["joint"] = spaces.Box(fmin, fmax, (7,), np.float32)
             sp["is_holding"] = spaces.Box(0.0, 1.0, (1,), np.float32)
             sp["goal_to_agent_gps_compass"] = spaces.Box(fmin, fmax, (2,), np.float32)
+        elif task == "cubemap":
+            for face in CUBE_FACES:
+                sp[f"rgb_{face}"] = spaces.Box(0, 255, (height, width, 3), np.uint8)
+            for face in CUBE_FACES:
+                sp[f"depth_{face}"] = spaces.Box(0.0, 1.0, (height, width, 1), np.float32)
+            sp[GOAL_UUID] = spaces.Box(fmin, fmax, (2,), np.float32)
         else:
             if use_rgb:
                 sp["rgb"] = spaces.Box(0, 255, (height, width, 3), np.uint8)
@@ -73,6 +82,13 @@ class HostSyntheticNavEnv:
             o["joint"] = self._rng.uniform(-np.pi, np.pi, 7).astype(np.float32)
             o["is_holding"] = np.array([float(self._rng.random() < 0.5)], dtype=np.float32)
             o["goal_to_agent_gps_compass"] = np.array([self._rng.uniform(0.0, 10.0), self._rng.uniform(-np.pi, np.pi)], dtype=np.float32)
+            return o
+        if self._task == "cubemap":
+            for face in CUBE_FACES:
+                o[f"rgb_{face}"] = self._rng.integers(0, 256, (self._h, self._w, 3), dtype=np.uint8)
+            for face in CUBE_FACES:
+                o[f"depth_{face}"] = self._rng.random((self._h, self._w, 1), dtype=np.float32)
+            o[GOAL_UUID] = np.array([self._rng.uniform(0.0, 10.0), self._rng.uniform(-np.pi, np.pi)], dtype=np.float32)
             return o
         if self._use_rgb:
             o["rgb"] = self._rng.integers(0, 256, (self._h, self._w, 3), dtype=np.uint8)
@@ -116,3 +132,8 @@ def make_host_env(seed, height, width, use_rgb, use_depth, num_actions, max_epis
 def make_rearrange_host_env(seed, height, width, use_rgb, use_depth, num_actions, max_episode_steps, work_us=0, num_episodes=0):
     """`vector_env_factory.make_env_fn` form of `task="rearrange"` (the sensor sizes come from the configured simulator sensors)."""
     return make_host_env(seed, height, width, use_rgb, use_depth, num_actions, max_episode_steps, work_us, num_episodes, task="rearrange")
+
+
+def make_cubemap_host_env(seed, height, width, use_rgb, use_depth, num_actions, max_episode_steps, work_us=0, num_episodes=0):
+    """`vector_env_factory.make_env_fn` form of `task="cubemap"` (the face size comes from the configured simulator sensors)."""
+    return make_host_env(seed, height, width, use_rgb, use_depth, num_actions, max_episode_steps, work_us, num_episodes, task="cubemap")

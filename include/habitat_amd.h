@@ -65,6 +65,17 @@ int hab_synth_objectnav_sensors(int32_t* semantic, int64_t* objectgoal, float* c
 int hab_obs_resize_crop(const void* src, void* dst, int dtype, int N, int H, int W, int C, int resized_h, int resized_w,
                         int crop_y0, int crop_x0, int out_h, int out_w, int mode, hipStream_t stream);
 
+/* CubeMap2Equirect / CubeMap2Fisheye (habitat_baselines/common/obs_transformers.py:239-1199: stack of six face sensors -> permute ->
+ * float -> depth z-factor multiply -> F.grid_sample(bilinear, padding zeros, align_corners=True) against six grids -> sum over the
+ * faces -> cast -> permute), one gather launch.  src: HOST array of n_src (1..6) device pointers, each an (N,H,W,C) contiguous
+ * sensor of `dtype` (HAB_DTYPE_U8 | HAB_DTYPE_F32; anything else returns HAB_ERR_UNSUPPORTED), C in 1..4; the array is read during
+ * the call only.  table (device): out_h*out_w entries {int32 face; float gx; float gy}: face = -1 writes 0 in every channel,
+ * otherwise face in [0, n_src) and (gx, gy) are grid_sample coordinates in [-1, 1].  zfactor (device, H*W floats) or NULL: every tap
+ * value is multiplied by zfactor[y_tap*W + x_tap] before it is weighted.  fp32 arithmetic in ATen's order; a tap outside the face
+ * contributes 0 and is not read.  dst (N,out_h,out_w,C) of `dtype` (uint8: truncation).  No allocation, no synchronisation. */
+int hab_obs_project(const void* const* src, int n_src, void* dst, int dtype, int N, int H, int W, int C, const void* table,
+                    const float* zfactor, int out_h, int out_w, hipStream_t stream);
+
 /* Per-step episode bookkeeping of the rollout loop, fused (rl/ppo/ppo_trainer.py:417-446: current_episode_reward += rewards;
  * running_episode_stats["reward"] += current_episode_reward.where(done, 0); ["count"] += done;
  * current_episode_reward.masked_fill_(done, 0)) plus RolloutStorage.insert's prev_actions[t+1] = actions[t]
