@@ -135,19 +135,57 @@ __global__ void __launch_bounds__(256) obs_resize_crop_tile_kernel(const ResizeC
     for (int c = 0; c < C; ++c) out[c] = PixCast<T>::from(__fdiv_rn(__fdiv_rn(sum[c], kh), kw));
 }
 
+// Which kernel runs a call.  ONE function decides, from what the call's source side fixes (pointer, dtype, shape, resized extent,
+// mode) and the two environment switches; the launcher and hab_obs_resize_crop_form both ask it.
+struct ResizeCropChoice {
+    int form;
+    int words_max;       // tile: LDS row pitch in dwords
+    size_t lds_bytes;    // tile: dynamic LDS of the launch
+};
+
 template <class T, int C>
-static int try_tile_launch(const ResizeCropArgs& a, hipStream_t stream) {
-    const long long pitch = (long long)a.W * C * sizeof(T), frame_bytes = pitch * a.H;
-    if (pitch % 4 || (reinterpret_cast<uintptr_t>(a.src) & 3) || a.N > 65535) return -1;
+static bool tile_fits(const ResizeCropArgs& a, ResizeCropChoice& ch) {
+    const long long pitch = (long long)a.W * C * sizeof(T);
+    if (pitch % 4 || (reinterpret_cast<uintptr_t>(a.src) & 3) || a.N > 65535) return false;
     // upper bounds of the tile's source footprint
     const int rows_max = (int)(((long long)RC_TH * a.H + a.rh - 1) / a.rh) + 2;
     const int px_max = (int)(((long long)RC_TW * a.W + a.rw - 1) / a.rw) + 2;
-    const int words_max = (int)((px_max * C * sizeof(T) + 3) / 4) + 2;
-    const size_t lds_bytes = (size_t)rows_max * words_max * 4;
-    if (lds_bytes > 48 * 1024) return -1;
+    ch.words_max = (int)((px_max * C * sizeof(T) + 3) / 4) + 2;
+    ch.lds_bytes = (size_t)rows_max * ch.words_max * 4;
+    if (ch.lds_bytes > 48 * 1024) return false;
+    // grid.y = tile rows of the window <= tile rows of the resized image: the bound does not depend on the crop
+    return cdiv(a.rh, RC_TH) <= 65535;
+}
+
+// -> HAB_RESIZE_FORM_* or a negative HAB_ERR_*.  Uses a.src, a.N, a.H, a.W, a.C, a.rh, a.rw, a.mode only.
+template <class T>
+static int choose_resize_crop(const ResizeCropArgs& a, ResizeCropChoice& ch) {
+    static const bool no_tile = hab_env_flag("HAB_OBS_NO_TILE");
+    ch = ResizeCropChoice{HAB_RESIZE_FORM_GENERIC, 0, 0};
+    if (a.C > 4) return HAB_ERR_UNSUPPORTED;
+    if constexpr (std::is_same_v<T, uint8_t>) {
+        static const bool no_rgb8 = hab_env_flag("HAB_OBS_NO_RGB8");
+        const long long bytes = (long long)a.N * a.H * a.W * 3;
+        // widest window = ceil(W / rw) + 1 pixels
+        if (a.mode == HAB_RESIZE_AREA && a.C == 3 && !no_rgb8 && (a.W + a.rw - 1) / a.rw + 1 <= 4 && bytes % 4 == 0 &&
+            (reinterpret_cast<uintptr_t>(a.src) & 3) == 0)
+            return ch.form = HAB_RESIZE_FORM_RGB8;
+    }
+    if (a.mode == HAB_RESIZE_AREA && !no_tile) {
+        bool fits = false;
+        if (a.C == 1) fits = tile_fits<T, 1>(a, ch);
+        else if (a.C == 3) fits = tile_fits<T, 3>(a, ch);
+        else if (a.C == 4) fits = tile_fits<T, 4>(a, ch);
+        if (fits) return ch.form = HAB_RESIZE_FORM_TILE;
+    }
+    return ch.form = HAB_RESIZE_FORM_GENERIC;
+}
+
+template <class T, int C>
+static int tile_launch(const ResizeCropArgs& a, const ResizeCropChoice& ch, hipStream_t stream) {
+    const long long frame_bytes = (long long)a.W * C * sizeof(T) * a.H;
     dim3 grid(cdiv(a.ow, RC_TW), cdiv(a.oh, RC_TH), a.N);
-    if (grid.y > 65535) return -1;
-    obs_resize_crop_tile_kernel<T, C><<<grid, 256, lds_bytes, stream>>>(a, words_max, frame_bytes);
+    obs_resize_crop_tile_kernel<T, C><<<grid, 256, ch.lds_bytes, stream>>>(a, ch.words_max, frame_bytes);
     HAB_LAUNCH_CHECK();
     return HAB_OK;
 }
@@ -200,14 +238,13 @@ __global__ void __launch_bounds__(256) obs_resize_crop_rgb8_kernel(const ResizeC
 
 template <class T>
 static int launch_resize_crop(const ResizeCropArgs& a, hipStream_t stream) {
-    static const bool no_tile = hab_env_flag("HAB_OBS_NO_TILE");
+    ResizeCropChoice ch;
+    const int form = choose_resize_crop<T>(a, ch);
+    if (form < 0) return form;
+    const long long total = (long long)a.N * a.oh * a.ow;
     if constexpr (std::is_same_v<T, uint8_t>) {
-        static const bool no_rgb8 = hab_env_flag("HAB_OBS_NO_RGB8");
-        const long long bytes = (long long)a.N * a.H * a.W * 3;
-        // widest window = ceil(W / rw) + 1 pixels
-        if (a.mode == HAB_RESIZE_AREA && a.C == 3 && !no_rgb8 && (a.W + a.rw - 1) / a.rw + 1 <= 4 && bytes % 4 == 0 &&
-            (reinterpret_cast<uintptr_t>(a.src) & 3) == 0) {
-            const long long total = (long long)a.N * a.oh * a.ow;
+        if (form == HAB_RESIZE_FORM_RGB8) {
+            const long long bytes = (long long)a.N * a.H * a.W * 3;
             int blocks = (int)cdivl(total, 256);
             if (blocks > 65536) blocks = 65536;
             obs_resize_crop_rgb8_kernel<<<blocks, 256, 0, stream>>>(a, bytes / 4 - 1);
@@ -215,20 +252,14 @@ static int launch_resize_crop(const ResizeCropArgs& a, hipStream_t stream) {
             return HAB_OK;
         }
     }
-    if (a.mode == HAB_RESIZE_AREA && !no_tile) {
-        int rc = -1;
-        if (a.C == 1) rc = try_tile_launch<T, 1>(a, stream);
-        else if (a.C == 3) rc = try_tile_launch<T, 3>(a, stream);
-        else if (a.C == 4) rc = try_tile_launch<T, 4>(a, stream);
-        if (rc >= 0) return rc;
+    if (form == HAB_RESIZE_FORM_TILE) {
+        if (a.C == 1) return tile_launch<T, 1>(a, ch, stream);
+        if (a.C == 3) return tile_launch<T, 3>(a, ch, stream);
+        return tile_launch<T, 4>(a, ch, stream);
     }
-    const long long total = (long long)a.N * a.oh * a.ow;
     int blocks = (int)cdivl(total, 256);
     if (blocks > 16384) blocks = 16384;
-    if (a.C <= 4)
-        obs_resize_crop_kernel<T, 4><<<blocks, 256, 0, stream>>>(a);
-    else
-        return HAB_ERR_UNSUPPORTED;
+    obs_resize_crop_kernel<T, 4><<<blocks, 256, 0, stream>>>(a);
     HAB_LAUNCH_CHECK();
     return HAB_OK;
 }
@@ -512,6 +543,21 @@ extern "C" int hab_obs_resize_crop(const void* src, void* dst, int dtype, int N,
     case HAB_DTYPE_U8: return launch_resize_crop<uint8_t>(a, stream);
     case HAB_DTYPE_F32: return launch_resize_crop<float>(a, stream);
     case HAB_DTYPE_I32: return launch_resize_crop<int32_t>(a, stream);
+    default: return HAB_ERR_UNSUPPORTED;
+    }
+}
+
+
+extern "C" int hab_obs_resize_crop_form(const void* src, int dtype, int N, int H, int W, int C, int resized_h, int resized_w, int mode) {
+    using namespace hab;
+    if (!src || N <= 0 || H <= 0 || W <= 0 || C <= 0 || resized_h <= 0 || resized_w <= 0) return HAB_ERR_ARG;
+    if (mode != HAB_RESIZE_AREA && mode != HAB_RESIZE_NEAREST) return HAB_ERR_ARG;
+    ResizeCropArgs a{src, nullptr, N, H, W, C, resized_h, resized_w, 0, 0, resized_h, resized_w, mode};
+    ResizeCropChoice ch;
+    switch (dtype) {
+    case HAB_DTYPE_U8: return choose_resize_crop<uint8_t>(a, ch);
+    case HAB_DTYPE_F32: return choose_resize_crop<float>(a, ch);
+    case HAB_DTYPE_I32: return choose_resize_crop<int32_t>(a, ch);
     default: return HAB_ERR_UNSUPPORTED;
     }
 }

@@ -66,6 +66,7 @@ SIGNATURES = {
     "hab_synth_step": (c_int, [vp, vp, vp, vp, vp, vp, vp, c_uint32, c_uint32, c_int, c_int, c_int, c_int, vp]),
     "hab_synth_objectnav_sensors": (c_int, [vp, vp, vp, vp, vp, c_uint32, c_uint32, c_int, c_int, c_int, vp]),
     "hab_obs_resize_crop": (c_int, [vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp]),
+    "hab_obs_resize_crop_form": (c_int, [vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "hab_obs_project": (c_int, [vp, c_int, vp, c_int, c_int, c_int, c_int, c_int, vp, vp, c_int, c_int, vp]),
     "hab_rollout_step_stats": (c_int, [vp, vp, vp, vp, vp, vp, vp, c_int, c_int, vp]),
     "hab_compute_returns": (c_int, [vp, vp, vp, vp, vp, c_int, c_int, c_float, c_float, c_int, c_int, vp]),

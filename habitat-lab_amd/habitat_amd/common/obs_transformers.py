@@ -9,7 +9,8 @@ The reference resizes with permute -> float -> F.interpolate("area" | "nearest")
 sensor at a time.  Here every (sensor, transform) is one `hab_obs_resize_crop` launch, and `apply_obs_transforms_batch` FUSES a
 ResizeShortestEdge that is directly followed by a CenterCropper on the same sensor into a single launch that only computes the
 pixels surviving the crop (640x480 -> 341x256 -> 256x256 for the ObjectNav sensors).  Results are bit-identical to the
-reference's CPU output (tests/test_gpu_kernels.py::test_obs_resize_crop).
+reference's CPU output for each of the three kernels the launcher chooses among (tests/test_gpu_resize_crop.py, against the plain
+restatement of tests/resize_crop_reference.py; tests/test_obs_transformers.py against the reference's golden outputs).
 
 Projection transformers (N6): `CubeMap2Equirect` and `CubeMap2Fisheye` (:239-1199) turn six cube-face cameras into one panorama or
 one fisheye frame.  The reference stacks the six sensors, permutes, converts to float, multiplies depth by a z-factor, runs
@@ -170,6 +171,9 @@ class ResizeShortestEdge(ObservationTransformer):
 
 @baseline_registry.register_obs_transformer()
 class CenterCropper(ObservationTransformer):
+    """obs_transformers.py:151-231.  One difference, on purpose: a crop larger than the image is refused with a `HabError` (alone or
+    fused behind a ResizeShortestEdge).  The reference's slice silently returns an image smaller than the observation space says."""
+
     def __init__(self, size: Union[numbers.Integral, Tuple[int, int]], channels_last: bool = True,
                  trans_keys: Tuple[str, ...] = ("rgb", "depth", "semantic")):
         super().__init__()

@@ -64,6 +64,14 @@ int hab_synth_objectnav_sensors(int32_t* semantic, int64_t* objectgoal, float* c
 #define HAB_RESIZE_NEAREST 1
 int hab_obs_resize_crop(const void* src, void* dst, int dtype, int N, int H, int W, int C, int resized_h, int resized_w,
                         int crop_y0, int crop_x0, int out_h, int out_w, int mode, hipStream_t stream);
+/* Which kernel hab_obs_resize_crop runs for such a call: 0 the generic grid-stride kernel, 1 the LDS-staged tile kernel, 2 the packed
+ * uint8 rgb kernel, or a negative HAB_ERR_* where the call itself would be refused for these arguments.  Host only: nothing is
+ * launched and `src` is not read (only its alignment counts).  The launcher asks the same function, so the answer holds for every
+ * crop window of that resized image; it includes the HAB_OBS_NO_TILE / HAB_OBS_NO_RGB8 switches.  For tests and tools. */
+#define HAB_RESIZE_FORM_GENERIC 0
+#define HAB_RESIZE_FORM_TILE 1
+#define HAB_RESIZE_FORM_RGB8 2
+int hab_obs_resize_crop_form(const void* src, int dtype, int N, int H, int W, int C, int resized_h, int resized_w, int mode);
 
 /* CubeMap2Equirect / CubeMap2Fisheye (habitat_baselines/common/obs_transformers.py:239-1199: stack of six face sensors -> permute ->
  * float -> depth z-factor multiply -> F.grid_sample(bilinear, padding zeros, align_corners=True) against six grids -> sum over the
