@@ -1,0 +1,346 @@
+// Nav2D-v0: a 2-D point-goal world simulated and rendered on the device, written straight into rollout rows.
+// Definition: habitat_amd/common/env_factory.py (Nav2DVectorEnv); specification: tests/nav2d_reference.py, which these
+// kernels reproduce bit for bit (phi = atan2f excepted).  Every float operation below is one fp32 rounding: contraction is off
+// for the whole file and division / square root are the correctly rounded forms (`__fdiv_rn` = `x / y`, `sqrt_rn` below); angles come from host-built tables.
+#include <cstddef>
+#include "hab_common.h"
+#include "../../include/habitat_amd.h"
+
+#pragma clang fp contract(off)
+
+using namespace hab;
+
+namespace nav2d {
+
+__host__ __device__ inline uint32_t mix32(uint32_t x) {
+    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
+    return x;
+}
+__host__ __device__ inline uint32_t stream_key(uint32_t seed, uint32_t sensor, uint32_t env, uint32_t t) {
+    uint32_t h = mix32(seed + 0x9E3779B9u * (sensor + 1u));
+    h = mix32(h ^ env);
+    return mix32(h ^ t);
+}
+__device__ inline float u01(uint32_t w) { return (float)(w >> 8) * 5.9604644775390625e-08f; }
+
+constexpr uint32_t S_OBST = 16u, S_START = 17u, S_GOAL = 18u, S_HEAD = 19u, S_COLOR = 20u;
+constexpr int MAX_K = HAB_NAV2D_MAX_OBSTACLES, CANDIDATES = 16;
+constexpr float ARENA = 8.0f, RADIUS = 0.1f, LO = 0.1f, HI = 7.9f, FORWARD = 0.25f;
+
+// One env's state (HAB_NAV2D_STATE_BYTES = 224 bytes = 56 words; the layout is part of the C ABI, see the header).
+struct Nav2DState {
+    float px, py, gx, gy;
+    float d_prev, d_start, path;
+    int32_t heading, steps, collisions, episode, ended;
+    float last[4];              // success, spl, distance_to_goal, collisions of the episode that ended last
+    float rect[MAX_K][4];       // x0, y0, x1, y1
+    uint32_t color[MAX_K];      // r | g << 8 | b << 16
+};
+static_assert(sizeof(Nav2DState) == HAB_NAV2D_STATE_BYTES, "Nav2DState layout");
+// the words the header names for the host side
+static_assert(offsetof(Nav2DState, px) == 4 * HAB_NAV2D_W_PX && offsetof(Nav2DState, py) == 4 * HAB_NAV2D_W_PY, "Nav2DState layout");
+static_assert(offsetof(Nav2DState, gx) == 4 * HAB_NAV2D_W_GX && offsetof(Nav2DState, gy) == 4 * HAB_NAV2D_W_GY, "Nav2DState layout");
+static_assert(offsetof(Nav2DState, heading) == 4 * HAB_NAV2D_W_HEADING && offsetof(Nav2DState, steps) == 4 * HAB_NAV2D_W_STEPS,
+              "Nav2DState layout");
+static_assert(offsetof(Nav2DState, collisions) == 4 * HAB_NAV2D_W_COLLISIONS && offsetof(Nav2DState, episode) == 4 * HAB_NAV2D_W_EPISODE,
+              "Nav2DState layout");
+static_assert(offsetof(Nav2DState, ended) == 4 * HAB_NAV2D_W_ENDED && offsetof(Nav2DState, last) == 4 * HAB_NAV2D_W_LAST_MEASURES,
+              "Nav2DState layout");
+
+// Correctly rounded square root.  NOT `__fsqrt_rn`: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers define that name as the
+// native (1 ulp) square root; `sqrtf` is the IEEE one under hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt.
+__device__ inline float sqrt_rn(float x) { return __builtin_sqrtf(x); }
+
+__device__ inline bool is_free(float x, float y, const Nav2DState& s, int K) {
+    if (!(x >= LO && x <= HI && y >= LO && y <= HI)) return false;
+    for (int k = 0; k < K; ++k)
+        if (x > s.rect[k][0] - RADIUS && x < s.rect[k][2] + RADIUS && y > s.rect[k][1] - RADIUS && y < s.rect[k][3] + RADIUS)
+            return false;
+    return true;
+}
+__device__ inline float dist(float ax, float ay, float bx, float by) {
+    const float dx = bx - ax, dy = by - ay;
+    return sqrt_rn(dx * dx + dy * dy);
+}
+
+__device__ void begin_episode(Nav2DState& s, uint32_t seed, uint32_t env, int K, int nh) {
+    const uint32_t ep = (uint32_t)s.episode;
+    const uint32_t ko = stream_key(seed, S_OBST, env, ep), kc = stream_key(seed, S_COLOR, env, ep);
+    for (int k = 0; k < K; ++k) {
+        const float cx = 2.0f + 4.0f * u01(mix32(ko ^ (uint32_t)(4 * k))), cy = 2.0f + 4.0f * u01(mix32(ko ^ (uint32_t)(4 * k + 1)));
+        const float hx = 0.25f + 0.75f * u01(mix32(ko ^ (uint32_t)(4 * k + 2))), hy = 0.25f + 0.75f * u01(mix32(ko ^ (uint32_t)(4 * k + 3)));
+        s.rect[k][0] = cx - hx; s.rect[k][1] = cy - hy; s.rect[k][2] = cx + hx; s.rect[k][3] = cy + hy;
+        const uint32_t c = mix32(kc ^ (uint32_t)k);
+        s.color[k] = (64u + (c & 127u)) | ((64u + ((c >> 8) & 127u)) << 8) | ((64u + ((c >> 16) & 127u)) << 16);
+    }
+    const uint32_t ks = stream_key(seed, S_START, env, ep), kg = stream_key(seed, S_GOAL, env, ep);
+    float sx = 0.5f, sy = 0.5f;
+    for (int j = 0; j < CANDIDATES; ++j) {
+        const float x = LO + 7.8f * u01(mix32(ks ^ (uint32_t)(2 * j))), y = LO + 7.8f * u01(mix32(ks ^ (uint32_t)(2 * j + 1)));
+        if (is_free(x, y, s, K)) { sx = x; sy = y; break; }
+    }
+    float gx = 7.5f, gy = 7.5f;
+    for (int j = 0; j < CANDIDATES; ++j) {
+        const float x = LO + 7.8f * u01(mix32(kg ^ (uint32_t)(2 * j))), y = LO + 7.8f * u01(mix32(kg ^ (uint32_t)(2 * j + 1)));
+        if (is_free(x, y, s, K) && dist(sx, sy, x, y) >= 1.0f) { gx = x; gy = y; break; }
+    }
+    s.px = sx; s.py = sy; s.gx = gx; s.gy = gy;
+    s.heading = (int32_t)(mix32(stream_key(seed, S_HEAD, env, ep) ^ 0u) % (uint32_t)nh);
+    s.d_start = s.d_prev = dist(sx, sy, gx, gy);
+    s.path = 0.0f;
+    s.steps = 0;
+    s.collisions = 0;
+}
+
+// One thread per env.  advance = 0: episode 0 of every selected env; advance = 1: one step with actions[n].  Then the goal sensor.
+__global__ void nav2d_step_kernel(Nav2DState* __restrict__ states, const float* __restrict__ dirs, const int64_t* __restrict__ actions,
+                                  const uint8_t* __restrict__ mask, float* __restrict__ goal, float* __restrict__ reward,
+                                  uint8_t* __restrict__ not_done, float* __restrict__ sums, uint32_t seed, uint32_t env_offset, int N,
+                                  int K, int nh, int max_steps, int advance) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N || (mask && !mask[n])) return;
+    Nav2DState& s = states[n];  // worked on in place: a private copy indexed by k would live in scratch memory
+    const uint32_t env = env_offset + (uint32_t)n;
+    if (!advance) {
+        s.episode = 0;
+        s.ended = 0;
+        s.last[0] = s.last[1] = s.last[2] = s.last[3] = 0.0f;
+        begin_episode(s, seed, env, K, nh);
+    } else {
+        const int64_t a = actions[n];  // anything outside 0..3 moves nothing (the host-side entry points refuse it)
+        if (a == 1) {
+            const float nx = s.px + FORWARD * dirs[2 * s.heading], ny = s.py + FORWARD * dirs[2 * s.heading + 1];
+            if (is_free(nx, ny, s, K)) { s.px = nx; s.py = ny; s.path = s.path + FORWARD; }
+            else s.collisions += 1;
+        } else if (a == 2) {
+            s.heading = (s.heading + 1) % nh;
+        } else if (a == 3) {
+            s.heading = (s.heading + nh - 1) % nh;
+        }
+        const float d = dist(s.px, s.py, s.gx, s.gy);
+        const bool success = (a == 0) && (d < 0.2f);
+        reward[n] = (-0.01f + (s.d_prev - d)) + (success ? 2.5f : 0.0f);
+        s.d_prev = d;
+        s.steps += 1;
+        const bool done = (a == 0) || (s.steps >= max_steps);
+        not_done[n] = done ? 0 : 1;
+        s.ended = done ? 1 : 0;
+        if (done) {
+            s.last[0] = success ? 1.0f : 0.0f;
+            s.last[1] = success ? __fdiv_rn(s.d_start, fmaxf(s.d_start, s.path)) : 0.0f;
+            s.last[2] = d;
+            s.last[3] = (float)s.collisions;
+            if (sums)
+                for (int m = 0; m < 4; ++m) sums[(size_t)m * N + n] = sums[(size_t)m * N + n] + s.last[m];
+            s.episode += 1;
+            begin_episode(s, seed, env, K, nh);
+        }
+    }
+    if (goal) {
+        const float c = dirs[2 * s.heading], sn = dirs[2 * s.heading + 1];
+        const float dx = s.gx - s.px, dy = s.gy - s.py;
+        const float dot = dx * c + dy * sn, cross = c * dy - sn * dx;
+        goal[2 * n + 0] = dist(s.px, s.py, s.gx, s.gy);
+        goal[2 * n + 1] = atan2f(cross, dot);
+    }
+}
+
+// ---- rendering ---------------------------------------------------------------------------------------------------------------
+// Entry / exit of the ray p + t d through [lo, hi] on one axis.
+__device__ inline void slab(float lo, float hi, float p, float d, float inv, float& tmin, float& tmax) {
+    if (d == 0.0f) {
+        const bool inside = p > lo && p < hi;
+        tmin = inside ? -INFINITY : INFINITY;
+        tmax = inside ? INFINITY : -INFINITY;
+        return;
+    }
+    const float t0 = (lo - p) * inv, t1 = (hi - p) * inv;
+    tmin = fminf(t0, t1);
+    tmax = fmaxf(t0, t1);
+}
+__device__ inline uint32_t shade(uint32_t rgb, float depth01) {
+    const float s = 1.0f - depth01;
+    const uint32_t r = (uint32_t)((float)(rgb & 255u) * s), g = (uint32_t)((float)((rgb >> 8) & 255u) * s),
+                   b = (uint32_t)((float)((rgb >> 16) & 255u) * s);
+    return r | (g << 8) | (b << 16);
+}
+constexpr uint32_t pack_rgb(uint32_t r, uint32_t g, uint32_t b) { return r | (g << 8) | (b << 16); }
+
+struct alignas(4) U32x3 { uint32_t a, b, c; };
+struct alignas(16) RowRec { float z, depth; uint32_t color, pad; };  // floor / ceiling of one row: z, its depth value, its shaded colour
+
+constexpr int RENDER_THREADS = 256;
+constexpr int RENDER_MAX_ROWS = 1024;  // rows of one tile
+
+// grid (row tiles, N), RENDER_THREADS threads.  Phase 1: the W column hits and the tile's row constants, once per workgroup, into
+// LDS.  Phase 2: the tile's pixels are one contiguous range of the image; it is swept in groups of four pixels placed so that the
+// depth group is one aligned 16-byte store and the rgb group three whole dwords; the up to three pixels before the first and
+// after the last group are written one by one.
+// LDS: four per-column arrays (z_wall, depth of the wall, z seen by rgb, shaded wall colour) and row[r] = (z of floor / ceiling, its
+// depth, its shaded colour, as a RowRec).  Colours are packed integers and stay uint32_t from LDS to the store.  A lane's four pixels
+// are four consecutive columns, so the lanes of a wave read the column arrays at a stride of four dwords; column u sits at
+// u + (u >> 5), which spreads a half wave's 32 reads over the 32 banks.
+__host__ __device__ inline int col_slot(int u) { return u + (u >> 5); }
+__host__ __device__ inline int col_pitch(int W) { return (col_slot(W) + 4) & ~3; }  // a multiple of 4: `row` stays 16-byte aligned
+__global__ void __launch_bounds__(RENDER_THREADS)
+nav2d_render_kernel(const Nav2DState* __restrict__ states, const float* __restrict__ ray, const float* __restrict__ col_cos,
+                    const float* __restrict__ tanv, const uint8_t* __restrict__ mask, uint8_t* __restrict__ rgb,
+                    float* __restrict__ depth, int H, int W, int K, int rows_per_tile) {
+    extern __shared__ uint4 lds[];
+    const int n = blockIdx.y;
+    if (mask && !mask[n]) return;
+    const int P = col_pitch(W);
+    float* c_zd = reinterpret_cast<float*>(lds);
+    float* c_dw = c_zd + P;
+    float* c_zr = c_dw + P;
+    uint32_t* c_cw = reinterpret_cast<uint32_t*>(c_zr + P);
+    RowRec* row = reinterpret_cast<RowRec*>(lds + P);
+    const Nav2DState& s = states[n];
+    const int v0 = blockIdx.x * rows_per_tile, v1 = min(H, v0 + rows_per_tile);
+    const float px = s.px, py = s.py;
+    const float* rayh = ray + (size_t)s.heading * W * 2;
+    for (int u = threadIdx.x; u < W; u += RENDER_THREADS) {
+        const float dx = rayh[2 * u], dy = rayh[2 * u + 1];
+        const float ix = __fdiv_rn(1.0f, dx), iy = __fdiv_rn(1.0f, dy);
+        const float tx = dx > 0.0f ? (ARENA - px) * ix : (dx < 0.0f ? (0.0f - px) * ix : INFINITY);
+        const float ty = dy > 0.0f ? (ARENA - py) * iy : (dy < 0.0f ? (0.0f - py) * iy : INFINITY);
+        float t = tx <= ty ? tx : ty;
+        int hit = tx <= ty ? (dx > 0.0f ? 0 : 1) : (dy > 0.0f ? 2 : 3);
+        for (int k = 0; k < K; ++k) {
+            float axn, axx, ayn, ayx;
+            slab(s.rect[k][0], s.rect[k][2], px, dx, ix, axn, axx);
+            slab(s.rect[k][1], s.rect[k][3], py, dy, iy, ayn, ayx);
+            const float tn = fmaxf(axn, ayn), tm = fminf(axx, ayx);
+            if (tn <= tm && tn > 0.0f && tn < t) { t = tn; hit = 4 + k; }
+        }
+        const float cf = col_cos[u];
+        const float z_wall = t * cf;
+        const float ox = px - s.gx, oy = py - s.gy;
+        const float b = ox * dx + oy * dy;
+        const float c = (ox * ox + oy * oy) - 0.2f * 0.2f;
+        const float disc = b * b - c;
+        const float tmk = -b - sqrt_rn(fmaxf(disc, 0.0f));
+        const bool marker = disc >= 0.0f && tmk > 0.0f && tmk < t;
+        const float z_rgb = marker ? tmk * cf : z_wall;
+        uint32_t base;
+        if (marker) base = pack_rgb(255, 32, 32);
+        else if (hit >= 4) base = s.color[hit - 4];
+        else base = hit == 0 ? pack_rgb(200, 180, 150) : hit == 1 ? pack_rgb(150, 200, 180) : hit == 2 ? pack_rgb(180, 150, 200)
+                                                                                                        : pack_rgb(200, 200, 150);
+        const float d_wall = fminf(__fdiv_rn(z_wall, 10.0f), 1.0f), d_rgbw = fminf(__fdiv_rn(z_rgb, 10.0f), 1.0f);
+        const int q = col_slot(u);
+        c_zd[q] = z_wall;
+        c_dw[q] = d_wall;
+        c_zr[q] = z_rgb;
+        c_cw[q] = shade(base, d_rgbw);
+    }
+    for (int r = threadIdx.x; r < v1 - v0; r += RENDER_THREADS) {
+        const float tv = tanv[v0 + r];
+        const float zf = __fdiv_rn(1.25f, fabsf(tv));
+        const float d_flat = fminf(__fdiv_rn(zf, 10.0f), 1.0f);
+        row[r] = RowRec{zf, d_flat, shade(tv > 0.0f ? pack_rgb(230, 230, 240) : pack_rgb(110, 100, 90), d_flat), 0u};
+    }
+    __syncthreads();
+
+    const long long img = (long long)n * H * W;   // first pixel of this env's image, in pixels from the tensor base
+    const int s_px = v0 * W, e_px = v1 * W;       // this tile's pixel range within the image
+    if (depth) {
+        float* dimg = depth + img;
+        // first pixel i >= s_px whose address is 16-byte aligned
+        const int mis = (int)(((uintptr_t)(dimg + s_px) >> 2) & 3);
+        const int first = min(e_px, s_px + ((4 - mis) & 3));
+        const int groups = (e_px - first) >> 2, last = first + (groups << 2);
+        for (int g = threadIdx.x; g < groups; g += RENDER_THREADS) {
+            const int i = first + (g << 2);
+            int v = i / W, u = i - v * W;
+            float o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int q = col_slot(u);
+                const RowRec rv = row[v - v0];
+                o[j] = c_zd[q] <= rv.z ? c_dw[q] : rv.depth;
+                if (++u == W) { u = 0; ++v; }
+            }
+            *reinterpret_cast<float4*>(dimg + i) = make_float4(o[0], o[1], o[2], o[3]);
+        }
+        const int edge = (first - s_px) + (e_px - last);
+        if ((int)threadIdx.x < edge) {
+            const int i = (int)threadIdx.x < first - s_px ? s_px + (int)threadIdx.x : last + ((int)threadIdx.x - (first - s_px));
+            const int v = i / W, u = i - v * W;
+            const int q = col_slot(u);
+            const RowRec rv = row[v - v0];
+            dimg[i] = c_zd[q] <= rv.z ? c_dw[q] : rv.depth;
+        }
+    }
+    if (rgb) {
+        uint8_t* cimg = rgb + img * 3;
+        // first pixel i >= s_px whose byte address is dword aligned: (base + 3 i) % 4 == 0  <=>  i % 4 == base % 4
+        const int mis = (int)(((uintptr_t)cimg - (uintptr_t)s_px) & 3);   // (base - s_px) mod 4
+        const int first = min(e_px, s_px + mis);
+        const int groups = (e_px - first) >> 2, last = first + (groups << 2);
+        for (int g = threadIdx.x; g < groups; g += RENDER_THREADS) {
+            const int i = first + (g << 2);
+            int v = i / W, u = i - v * W;
+            uint32_t p[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int q = col_slot(u);
+                const RowRec rv = row[v - v0];
+                p[j] = c_zr[q] <= rv.z ? c_cw[q] : rv.color;
+                if (++u == W) { u = 0; ++v; }
+            }
+            U32x3 w;
+            w.a = p[0] | (p[1] << 24);
+            w.b = (p[1] >> 8) | (p[2] << 16);
+            w.c = (p[2] >> 16) | (p[3] << 8);
+            *reinterpret_cast<U32x3*>(cimg + (size_t)i * 3) = w;
+        }
+        const int edge = (first - s_px) + (e_px - last);
+        if ((int)threadIdx.x < edge) {
+            const int i = (int)threadIdx.x < first - s_px ? s_px + (int)threadIdx.x : last + ((int)threadIdx.x - (first - s_px));
+            const int v = i / W, u = i - v * W;
+            const int q = col_slot(u);
+            const RowRec rv = row[v - v0];
+            const uint32_t p = c_zr[q] <= rv.z ? c_cw[q] : rv.color;
+            cimg[(size_t)i * 3 + 0] = (uint8_t)(p & 255u);
+            cimg[(size_t)i * 3 + 1] = (uint8_t)((p >> 8) & 255u);
+            cimg[(size_t)i * 3 + 2] = (uint8_t)((p >> 16) & 255u);
+        }
+    }
+}
+
+}  // namespace nav2d
+
+using namespace nav2d;
+
+extern "C" int hab_nav2d_state_bytes(void) { return (int)sizeof(Nav2DState); }
+
+extern "C" int hab_nav2d_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                              const int64_t* actions, const uint8_t* mask, uint8_t* rgb, float* depth, float* goal, float* reward,
+                              uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
+                              int num_obstacles, int num_headings, int max_episode_steps, int advance, hipStream_t stream) {
+    if (!state || !dirs || N <= 0 || num_headings <= 0 || max_episode_steps <= 0) return HAB_ERR_ARG;
+    if (num_obstacles < 0 || num_obstacles > MAX_K) return HAB_ERR_ARG;
+    if (advance && (!actions || !reward || !not_done)) return HAB_ERR_ARG;
+    if ((rgb || depth) && (!ray || !col_cos || !tanv || H <= 0 || W <= 0)) return HAB_ERR_ARG;
+    if ((rgb || depth) && (W > HAB_NAV2D_MAX_WIDTH || (long long)H * W > (1ll << 24))) return HAB_ERR_UNSUPPORTED;
+    if ((rgb || depth) && N > 65535) return HAB_ERR_UNSUPPORTED;  // the render's grid.y is the env
+    if (depth && ((uintptr_t)depth & 3)) return HAB_ERR_ARG;
+    nav2d_step_kernel<<<cdiv(N, 64), 64, 0, stream>>>((Nav2DState*)state, dirs, actions, mask, goal, reward, not_done, measure_sums,
+                                                      seed, env_offset, N, num_obstacles, num_headings, max_episode_steps, advance);
+    HAB_LAUNCH_CHECK();
+    if (rgb || depth) {
+        // a tile is at least ~16 KiB of stores per workgroup, so that the W column hits are a small part of its work
+        // and at most RENDER_MAX_ROWS, which keeps the dynamic LDS below 64 KiB for every accepted W
+        int rows = cdiv(4096, W);
+        if (rows < 4) rows = 4;
+        if (rows > RENDER_MAX_ROWS) rows = RENDER_MAX_ROWS;
+        if (rows > H) rows = H;
+        dim3 grid(cdiv(H, rows), N);
+        const size_t lds = (size_t)(col_pitch(W) + rows) * sizeof(uint4);
+        nav2d_render_kernel<<<grid, RENDER_THREADS, lds, stream>>>((const Nav2DState*)state, ray, col_cos, tanv, mask, rgb, depth, H, W,
+                                                                    num_obstacles, rows);
+        HAB_LAUNCH_CHECK();
+    }
+    return HAB_OK;
+}

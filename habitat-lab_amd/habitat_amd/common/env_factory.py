@@ -213,9 +213,194 @@ class SyntheticVectorEnv:
         pass
 
 
+NAV2D_MEASURES = ("success", "spl", "distance_to_goal", "collisions")
+NAV2D_MAX_OBSTACLES = 8
+# 4-byte words of a state record (include/habitat_amd.h: HAB_NAV2D_W_EPISODE, _ENDED, _LAST_MEASURES), the ones this module
+# reads; csrc/nav2d.hip asserts the record's member offsets against the header's
+_W_EPISODE, _W_ENDED, _W_LAST = 10, 11, 12
+
+
+def nav2d_num_headings(turn_angle) -> int:
+    if isinstance(turn_angle, bool) or not isinstance(turn_angle, (int, np.integer)) or turn_angle <= 0 or 360 % int(turn_angle) != 0:
+        raise _lib.HabError(f"Nav2D: turn_angle {turn_angle!r} must be a positive whole number of degrees that divides 360")
+    return 360 // int(turn_angle)
+
+
+def nav2d_tables(turn_angle: int, height: int, width: int):
+    """The host tables of the Nav2D kernels, computed in float64 and rounded once: dirs (nh, 2) = (cos, sin) of heading h; and, for
+    a rendered env, ray (nh, W, 2) = world direction of column u's ray at heading h (column 0 leftmost, 90 degree horizontal field of
+    view), col_cos (W,) = cosine between that ray and the optical axis, tanv (H,) = tangent of row v's elevation (row 0 on top, square
+    pixels).  No angle is evaluated on the device."""
+    nh = nav2d_num_headings(turn_angle)
+    a = np.arange(nh, dtype=np.float64) * (2.0 * np.pi / nh)
+    dirs = np.stack([np.cos(a), np.sin(a)], 1).astype(np.float32)
+    if height <= 0 or width <= 0:
+        return dirs, None, None, None
+    au = np.arctan(1.0 - 2.0 * (np.arange(width, dtype=np.float64) + 0.5) / width)
+    th = a[:, None] + au[None, :]
+    ray = np.stack([np.cos(th), np.sin(th)], 2).astype(np.float32)
+    tanv = ((1.0 - 2.0 * (np.arange(height, dtype=np.float64) + 0.5) / height) * (height / width)).astype(np.float32)
+    return dirs, ray, np.cos(au).astype(np.float32), tanv
+
+
+class Nav2DVectorEnv(SyntheticVectorEnv):
+    """Nav2D-v0: a small 2-D point-goal world whose reward depends on the actions, simulated and rendered on the device
+    (csrc/nav2d.hip) and written straight into rollout rows.  It is a measurement source like the hashed tasks, not a simulator port.
+    tests/nav2d_reference.py restates all of the following in numpy; the kernels match it bit for bit, phi excepted.
+
+    World.  One per (env, episode), a function of (seed, env_offset + env, episode index) through mix32 / stream_key / u01 with the
+    stream ids 16 (obstacles), 17 (start), 18 (goal), 19 (heading), 20 (obstacle colours); word i of a stream is
+    mix32(stream_key(seed, id, env, episode) ^ i) and u_i its u01.
+      * Arena: the square [0, 8] x [0, 8] m.  K = num_obstacles in 0..8 axis-aligned rectangles; rectangle k has the centre
+        (2 + 4 u_4k, 2 + 4 u_4k+1) and the half extents (0.25 + 0.75 u_4k+2, 0.25 + 0.75 u_4k+3), so the outer ring of width 1 m
+        is always free.
+      * The agent is a disc of radius 0.1 m.  A position is free when it lies in [0.1, 7.9]^2 and not strictly inside any rectangle
+        grown by 0.1 on every side (a box test: corners are not rounded).
+      * Start: the first free candidate (0.1 + 7.8 u_2j, 0.1 + 7.8 u_2j+1), j = 0..15, of the start stream, else (0.5, 0.5).
+        Goal: the first candidate of the goal stream that is free and at least 1 m from the start, else (7.5, 7.5).
+      * Heading: an index h in [0, 360 / turn_angle), initially word 0 of the heading stream modulo that count; turn_angle is a
+        whole number of degrees dividing 360 (default 10).  The direction of h is row h of a (cos, sin) table of h * turn_angle
+        computed in float64 on the host and rounded to float32.
+    Actions.  Discrete(4) in habitat's order: 0 STOP, 1 MOVE_FORWARD, 2 TURN_LEFT (h + 1), 3 TURN_RIGHT (h - 1).  Forward:
+      p' = p + 0.25 * dir (a float32 multiply, then a separate float32 add), taken if p' is free; otherwise the agent stays and a
+      collision is counted.  The episode ends on STOP or when its step count reaches habitat.environment.max_episode_steps.
+    Reward and measures (habitat's PointNav defaults).  d = float32 Euclidean distance to the goal, sqrt(dx * dx + dy * dy);
+      success = STOP and d < 0.2; reward = (-0.01 + (d_prev - d_new)) + 2.5 * success; path_length grows by 0.25 per accepted
+      forward.  At the episode's end spl = success * d_start / max(d_start, path_length) -- the STRAIGHT-LINE SPL: d_start is the
+      Euclidean distance, not a geodesic one, so with obstacles it overstates habitat's -- distance_to_goal = d and collisions = the
+      count.  On done the next episode's world is generated, its first observation is what the step returns and not_done = 0.
+    Sensors.
+      * pointgoal_with_gps_compass = (rho, phi): rho = d; phi = atan2f(cross, dot) of the goal offset in the agent frame, left
+        positive: dot = dx * c + dy * s, cross = c * dy - s * dx.  phi is the one quantity that is not bitwise (atan2f is not
+        correctly rounded).
+      * depth (H, W, 1) float32 in [0, 1]: pinhole camera, 90 degree horizontal field of view, square pixels, 1.25 m above the floor
+        under a 2.5 m ceiling.  Per column a ray-vs-slab intersection against the four walls and the K rectangles gives the hit
+        distance t; z_wall = t * cos(column angle).  depth = min(z_wall(u), 1.25 / |tan_v|) / 10, clipped to 1.
+      * rgb (H, W, 3) uint8: floor and ceiling constants, a colour per wall, obstacle k's colour from word k of the colour stream; a
+        red goal marker, a cylinder of radius 0.2 m around the goal from floor to ceiling, drawn in rgb ONLY (depth stays what the
+        agent collides with); each colour is scaled by 1 - z / 10 and truncated.
+      * Without rgb and depth nothing is rendered and the observation space is the goal sensor alone.
+
+    Besides the VectorEnv API this env consumes actions (`consumes_actions`): `step_into_obs(obs, reward, not_done, actions=...)`
+    on the device path; `async_step_at(i, a)` records a, and `advance_on_device` steps exactly the pending envs with their recorded
+    actions through the kernels' per-env mask.  `measure_sums` holds the device-side running sums of the four measures."""
+
+    consumes_actions = True
+    measure_names = NAV2D_MEASURES
+
+    def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
+                 use_depth: bool = True, num_actions: int = 4, device="cuda", num_obstacles: int = 3, turn_angle: int = 10,
+                 max_episode_steps: int = 500):
+        self.num_headings = nav2d_num_headings(turn_angle)
+        if not 0 <= int(num_obstacles) <= NAV2D_MAX_OBSTACLES:
+            raise _lib.HabError(f"Nav2D: num_obstacles {num_obstacles} outside 0..{NAV2D_MAX_OBSTACLES}")
+        if num_actions != 4:
+            raise _lib.HabError(f"Nav2D: the action space is Discrete(4) (STOP, MOVE_FORWARD, TURN_LEFT, TURN_RIGHT), got {num_actions}")
+        if int(max_episode_steps) <= 0:
+            raise _lib.HabError(f"Nav2D: max_episode_steps {max_episode_steps} must be positive")
+        if not (use_rgb or use_depth):
+            height = width = 0
+        super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth,
+                         num_actions=num_actions, device=device, task="nav2d")
+        self.num_obstacles, self.turn_angle, self.max_episode_steps = int(num_obstacles), int(turn_angle), int(max_episode_steps)
+        dev = self.device
+        self._tables = [None if t is None else torch.from_numpy(t).to(dev) for t in nav2d_tables(self.turn_angle, height, width)]
+        words = _lib.lib().hab_nav2d_state_bytes() // 4
+        self._state = torch.zeros(num_envs, words, dtype=torch.int32, device=dev)
+        self.measure_sums = torch.zeros(len(NAV2D_MEASURES), num_envs, device=dev)
+        self._actions_host = np.zeros(num_envs, dtype=np.int64)
+        self._infos: List[dict] = [{} for _ in range(num_envs)]
+        self.number_of_episodes = [1 << 30] * num_envs  # episodes are generated, never repeated
+
+    # ---- device fast path ---------------------------------------------------------------------
+    def _launch(self, obs, reward, not_done, actions, mask, advance: int):
+        if actions is not None and (actions.dtype != torch.int64 or actions.numel() != self.num_envs or not actions.is_contiguous()
+                                    or not actions.is_cuda):
+            raise _lib.HabError("Nav2D: actions must be a contiguous int64 device tensor of shape (N,) or (N, 1)")
+        dirs, ray, col_cos, tanv = self._tables
+        check(_lib.lib().hab_nav2d_step(ptr(self._state), ptr(dirs), ptr(ray), ptr(col_cos), ptr(tanv), ptr(actions), ptr(mask),
+                                        ptr(obs.get("rgb")), ptr(obs.get("depth")), ptr(obs.get(GOAL_UUID)), ptr(reward), ptr(not_done),
+                                        ptr(self.measure_sums), self.seed, self.env_offset, self.num_envs, self.H, self.W,
+                                        self.num_obstacles, self.num_headings, self.max_episode_steps, advance, stream_ptr()),
+              "hab_nav2d_step")
+
+    def reset_into_obs(self, obs):
+        self._launch(obs, None, None, None, None, 0)
+
+    def step_into_obs(self, obs, reward, not_done, actions=None, mask=None):
+        """One step of every env (or of the envs whose `mask` byte is set) with `actions` int64 (N,) / (N, 1): the new observations,
+        rewards (N,) and not-done bytes (N,) go straight into the given device tensors."""
+        if actions is None:
+            raise _lib.HabError("Nav2D: step_into_obs needs the actions of the step")
+        self._launch(obs, reward, not_done, actions, mask, 1)
+
+    def reset_into(self, rgb, depth, goal):
+        self.reset_into_obs({k: v for k, v in (("rgb", rgb), ("depth", depth), (GOAL_UUID, goal)) if v is not None})
+
+    def step_into(self, rgb, depth, goal, reward, not_done, actions=None, mask=None):
+        self.step_into_obs({k: v for k, v in (("rgb", rgb), ("depth", depth), (GOAL_UUID, goal)) if v is not None}, reward, not_done,
+                           actions=actions, mask=mask)
+
+    # ---- VectorEnv API (host path) ----------------------------------------------------------------
+    def async_step_at(self, index_env: int, action) -> None:
+        if isinstance(action, dict):
+            action = action["action"]
+        a = np.asarray(action)
+        if a.size != 1 or not (np.issubdtype(a.dtype, np.integer) or float(a.item()).is_integer()) or not 0 <= int(a.item()) <= 3:
+            raise _lib.HabError(f"Nav2D: env {index_env}: action {action!r} outside 0..3")
+        super().async_step_at(index_env, action)
+        self._actions_host[int(index_env)] = int(a.item())
+
+    def advance_on_device(self) -> List[int]:
+        """Steps exactly the envs whose step was requested, with their recorded actions, through the kernels' per-env mask: no
+        scratch copies, untouched envs keep state and observations.  Returns the ids."""
+        ids = sorted(self._pending)
+        self._pending.clear()
+        if ids:
+            actions = torch.from_numpy(self._actions_host.copy()).to(self.device)
+            mask = None
+            if len(ids) != self.num_envs:
+                m = np.zeros(self.num_envs, dtype=np.uint8)
+                m[ids] = 1
+                mask = torch.from_numpy(m).to(self.device)
+            self.step_into_obs(self._own_obs(), self._rew, self._nd, actions=actions, mask=mask)
+        return ids
+
+    def step_infos_host(self, ids) -> List[dict]:
+        """The scalar infos of the last step of envs `ids`: the four measures where that step ended an episode, else {}."""
+        rec = self._state[:, _W_ENDED:_W_LAST + len(NAV2D_MEASURES)].cpu()
+        last = rec[:, 1:].contiguous().view(torch.float32).numpy()
+        return [dict(zip(NAV2D_MEASURES, (float(x) for x in last[i]))) if int(rec[i, 0]) else {} for i in ids]
+
+    def _advance_pending(self):
+        ids = sorted(self._pending)
+        super()._advance_pending()
+        for i, info in zip(ids, self.step_infos_host(ids)):
+            self._infos[i] = info
+
+    def wait_step_at(self, index_env: int):
+        obs, rew, done, _ = super().wait_step_at(index_env)
+        return obs, rew, done, dict(self._infos[index_env])
+
+    def step(self, actions):
+        """VectorEnv.step: all envs, one action each."""
+        for i, a in enumerate(actions):
+            self.async_step_at(i, a)
+        return [self.wait_step_at(i) for i in range(self.num_envs)]
+
+    def current_episodes(self):
+        ep = self._state[:, _W_EPISODE].cpu().numpy()
+        return [dict(scene_id="nav2d", episode_id=f"{self.env_offset + i}:{int(ep[i])}") for i in range(self.num_envs)]
+
+    def pause_at(self, index: int):
+        raise _lib.HabError("Nav2D: episodes are generated and never repeat, so no env is ever paused")
+
+
 class SyntheticVectorEnvFactory(VectorEnvFactory):
     """Default `_target_`: N synthetic PointNav envs sized from habitat.simulator.sensors.*; per-rank env ids are
-    offset by rank * num_environments exactly like the reference offsets the seed (ppo_trainer.py:208-211)."""
+    offset by rank * num_environments exactly like the reference offsets the seed (ppo_trainer.py:208-211).  A
+    `habitat.task.type` starting with "nav2d" (any case) selects the Nav2D-v0 task, whose num_obstacles / turn_angle come from
+    `habitat.synthetic` and whose episode limit from `habitat.environment.max_episode_steps`."""
 
     def __init__(self, use_rgb: bool = True, use_depth: bool = True):
         self.use_rgb, self.use_depth = use_rgb, use_depth
@@ -226,6 +411,13 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
         sens = hab.simulator.sensors
         use_rgb = self.use_rgb and "rgb" in sens
         use_depth = self.use_depth and "depth" in sens
+        if str(hab.task.type).lower().startswith("nav2d"):
+            ref = sens["rgb"] if use_rgb else (sens["depth"] if use_depth else dict(height=0, width=0))
+            syn = getattr(hab, "synthetic", {})
+            return Nav2DVectorEnv(int(hb.num_environments), int(ref["height"]), int(ref["width"]), seed=int(hab.seed),
+                                  env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, num_actions=len(hab.task.actions),
+                                  device=device, num_obstacles=getattr(syn, "num_obstacles", 3), turn_angle=getattr(syn, "turn_angle", 10),
+                                  max_episode_steps=getattr(hab.environment, "max_episode_steps", 500))
         ref = sens["rgb"] if use_rgb else sens["depth"]
         task = "objectnav" if str(hab.task.type).lower().startswith("objectnav") else "pointnav"
         return SyntheticVectorEnv(int(hb.num_environments), int(ref.height), int(ref.width), seed=int(hab.seed),

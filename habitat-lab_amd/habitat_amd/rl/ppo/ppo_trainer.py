@@ -65,7 +65,7 @@ def batch_obs(observations, device):
 @baseline_registry.register_trainer(name="ddppo")
 @baseline_registry.register_trainer(name="ppo")
 class PPOTrainer(BaseRLTrainer):
-    supported_tasks = ["Nav-v0", "ObjectNav-v1"]
+    supported_tasks = ["Nav-v0", "ObjectNav-v1", "Nav2D-v0"]
     SHORT_ROLLOUT_THRESHOLD: float = 0.25
 
     def __init__(self, config=None):
@@ -179,6 +179,7 @@ class PPOTrainer(BaseRLTrainer):
         self.current_episode_reward = torch.zeros(N, 1, device=stat_dev)
         self.running_episode_stats = dict(count=torch.zeros(N, 1, device=stat_dev), reward=torch.zeros(N, 1, device=stat_dev))
         self.window_episode_stats = defaultdict(lambda: deque(maxlen=self._ppo_cfg.reward_window_size))
+        self._measure_base = None  # see _coalesce_post_step
         self.t_start = time.time()
 
     # ---- checkpoints ---------------------------------------------------------------------------------------
@@ -228,8 +229,11 @@ class PPOTrainer(BaseRLTrainer):
                    out=dict(values=B["value_preds"][t], actions=B["actions"][t], action_log_probs=B["action_log_probs"][t],
                             rnn_hidden_states=B["recurrent_hidden_states"][t + 1]))
         with g_timer.avg_time("trainer.step_env"):
+            # an env whose observations depend on the actions (consumes_actions, e.g. Nav2DVectorEnv) is handed the row the policy
+            # just wrote for THIS step
+            kw = dict(actions=B["actions"][t]) if getattr(self.envs, "consumes_actions", False) else {}
             self._device_obs_into({k: v[t + 1] for k, v in obs.items() if k != VISUAL_FEATURES_KEY},
-                                  lambda rows: self.envs.step_into_obs(rows, B["rewards"][t], B["masks"][t + 1]))
+                                  lambda rows: self.envs.step_into_obs(rows, B["rewards"][t], B["masks"][t + 1], **kw))
             if self._is_static_encoder:  # ppo_trainer.py:467-471
                 ac.encode_visual({k: v[t + 1] for k, v in obs.items()}, out=obs[VISUAL_FEATURES_KEY][t + 1])
         with g_timer.avg_time("trainer.update_stats"):
@@ -291,8 +295,10 @@ class PPOTrainer(BaseRLTrainer):
             cur = self.current_episode_reward[env_slice]
             self.running_episode_stats["reward"][env_slice] += cur.where(done_masks, cur.new_zeros(()))
             self.running_episode_stats["count"][env_slice] += done_masks.float()
-            for k in (infos[0] or {}):
-                vals = [i.get(k) for i in infos]
+            # the keys of every env's info, not only of env 0's: an env may report its measures only with the step that ends an
+            # episode (Nav2DVectorEnv) and {} otherwise; a missing value counts 0 and is masked out below unless that env is done
+            for k in dict.fromkeys(k for i in infos for k in (i or {})):
+                vals = [(i or {}).get(k, 0.0) for i in infos]
                 if all(isinstance(v, (int, float)) for v in vals):
                     v = torch.tensor(vals, dtype=torch.float, device=cdev).unsqueeze(1)
                     if k not in self.running_episode_stats:
@@ -319,6 +325,15 @@ class PPOTrainer(BaseRLTrainer):
         return losses
 
     def _coalesce_post_step(self, losses: Dict[str, float], count_steps_delta: int) -> Dict[str, float]:
+        sums = getattr(getattr(self, "envs", None), "measure_sums", None) if getattr(self, "_device_envs", False) else None
+        if sums is not None:  # device path: the env accumulates its episode measures itself (the host path reads them from infos)
+            count = self.running_episode_stats["count"]
+            if getattr(self, "_measure_base", None) is None:
+                # the env's sums count from its construction; what the statistics held before that (restored by a resume, else
+                # nothing) stays underneath them, so that the window's differences never run backwards
+                self._measure_base = {k: self.running_episode_stats.get(k, torch.zeros_like(count)).clone() for k in self.envs.measure_names}
+            for i, k in enumerate(self.envs.measure_names):
+                self.running_episode_stats[k] = self._measure_base[k] + sums[i].to(count).unsqueeze(1)
         order = sorted(self.running_episode_stats.keys())
         stats = torch.stack([self.running_episode_stats[k] for k in order], 0)
         stats = self._all_reduce(stats)

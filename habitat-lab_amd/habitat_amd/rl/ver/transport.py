@@ -78,6 +78,7 @@ class DeviceEnvTransport(_Records):
         self._outstanding = np.zeros(self.num_envs, bool)
         self._speeds = np.ones(self.num_envs) if speeds is None else np.asarray(speeds, dtype=np.float64)
         self._rng = np.random.RandomState(seed)
+        self._actions: Dict[int, Any] = {}  # the action of every outstanding step: an env that consumes actions gets it at arrival
 
     def start_experience_collection(self) -> List[int]:
         self.envs.reset_into_obs(self.envs._own_obs())
@@ -89,6 +90,8 @@ class DeviceEnvTransport(_Records):
 
     def send_action(self, env_idx, action):
         self._outstanding[env_idx] = True
+        a = np.asarray(action)
+        self._actions[env_idx] = a.item() if a.size == 1 else a
 
     def poll(self, timeout, max_messages):
         cand = np.nonzero(self._outstanding)[0]
@@ -98,10 +101,11 @@ class DeviceEnvTransport(_Records):
         if not arrived:
             return []
         for e in arrived:
-            self.envs.async_step_at(e, 0)
+            self.envs.async_step_at(e, self._actions.pop(e))
         self.envs.advance_on_device()               # observations are generated in HBM and stay there
         rew, nd = self.envs.step_results_host()     # two N-element vectors for the host-side episode accounting
-        for e in arrived:
+        infos = self.envs.step_infos_host(arrived) if hasattr(self.envs, "step_infos_host") else [{}] * len(arrived)
+        for e, info in zip(arrived, infos):
             self._outstanding[e] = False
-            self._record(e, float(rew[e]), not bool(nd[e]), {})
+            self._record(e, float(rew[e]), not bool(nd[e]), info)
         return arrived

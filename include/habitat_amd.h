@@ -50,6 +50,44 @@ int hab_synth_objectnav_sensors(int32_t* semantic, int64_t* objectgoal, float* c
                                 uint32_t seed, uint32_t env_offset, int N, int H, int W, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Nav2D-v0: a 2-D point-goal world whose reward depends on the actions, simulated and rendered on the
+ * device and written straight into rollout rows (definition: habitat_amd/common/env_factory.py;
+ * bit-identical to tests/nav2d_reference.py except phi = atan2f).  `state` is N records of
+ * HAB_NAV2D_STATE_BYTES, owned by the caller and opaque to it except for the 4-byte words named
+ * below.  Host-built fp32 tables: dirs (num_headings,2) = (cos, sin) of each heading; ray
+ * (num_headings,W,2) = world direction of column u's ray; col_cos (W) = cosine between that ray and
+ * the optical axis; tanv (H) = tangent of row v's elevation.  advance=0: every selected env starts
+ * episode 0 and its first observation is written (actions / reward / not_done unused);
+ * advance=1: one step with actions int64 (N) or (N,1) in 0..3 (STOP, MOVE_FORWARD, TURN_LEFT,
+ * TURN_RIGHT; any other value moves nothing), then reward, not_done and the observation of the new
+ * state -- the next episode's first one where the step ended an episode.  mask: one byte per env,
+ * only envs with a non-zero byte are touched (state and outputs); NULL = all.  rgb / depth / goal
+ * may be NULL; with either image N <= 65535.  measure_sums (4,N) f32 or NULL: success, spl,
+ * distance_to_goal, collisions of every episode that ends are added to row m, column n.
+ * ------------------------------------------------------------------------------------------- */
+#define HAB_NAV2D_STATE_BYTES 224
+#define HAB_NAV2D_MAX_OBSTACLES 8
+#define HAB_NAV2D_MAX_WIDTH 2048
+/* words of a state record: position, goal, heading index, steps and collisions of the running episode, episode index, whether the
+ * last step ended an episode, and the four measures of the episode that ended last */
+#define HAB_NAV2D_W_PX 0
+#define HAB_NAV2D_W_PY 1
+#define HAB_NAV2D_W_GX 2
+#define HAB_NAV2D_W_GY 3
+#define HAB_NAV2D_W_HEADING 7
+#define HAB_NAV2D_W_STEPS 8
+#define HAB_NAV2D_W_COLLISIONS 9
+#define HAB_NAV2D_W_EPISODE 10
+#define HAB_NAV2D_W_ENDED 11
+#define HAB_NAV2D_W_LAST_MEASURES 12
+int hab_nav2d_state_bytes(void);
+int hab_nav2d_step(void* state /*N,HAB_NAV2D_STATE_BYTES*/, const float* dirs, const float* ray, const float* col_cos,
+                   const float* tanv, const int64_t* actions /*N*/, const uint8_t* mask /*N*/, uint8_t* rgb /*N,H,W,3*/,
+                   float* depth /*N,H,W,1*/, float* goal /*N,2*/, float* reward /*N*/, uint8_t* not_done /*N*/,
+                   float* measure_sums /*4,N*/, uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles,
+                   int num_headings, int max_episode_steps, int advance, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Observation transformers, fused: ResizeShortestEdge followed by CenterCropper
  * (habitat_baselines/common/obs_transformers.py:70-231; utils/common.py:481-557: F.interpolate(mode="area") -- "nearest" for
  * the semantic sensor -- on the float NCHW view, cast back to the sensor dtype, then a center slice).  src (N,H,W,C) NHWC of

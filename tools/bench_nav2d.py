@@ -1,0 +1,71 @@
+#!/usr/bin/env python3
+"""Nav2D-v0 step + render (hab_nav2d_step: 64 envs, 256x256 rgb u8 + depth f32, 8 obstacles) beside hab_synth_step at the same shape.
+hab_synth_step is a pure store kernel that writes the same bytes (a hash per word, nothing read), so it is the yardstick for a render
+that is meant to be store-bound.  Both are warmed up and then alternated in one process; every window of INNER calls is timed with
+device events and the median and the range of the windows are printed, with the bytes written per second.  The Nav2D actions are a
+fixed random sequence (all four actions), so episodes end and worlds are regenerated inside the timed windows, as in a rollout; the
+reset (advance = 0) is timed separately.
+usage: python tools/bench_nav2d.py [envs] [size] [windows]"""
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "habitat-lab_amd"))
+from habitat_amd.common.env_factory import GOAL_UUID, Nav2DVectorEnv, SyntheticVectorEnv  # noqa: E402
+
+INNER = 10  # calls per timed window: a single launch of a few microseconds would time the enqueue
+
+
+def timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for i in range(INNER):
+        fn(i)
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3 / INNER  # us per call
+
+
+def main():
+    n = int(sys.argv[1]) if len(sys.argv) > 1 else 64
+    size = int(sys.argv[2]) if len(sys.argv) > 2 else 256
+    windows = int(sys.argv[3]) if len(sys.argv) > 3 else 30
+    assert torch.cuda.is_available(), "bench_nav2d needs a GPU"
+    dev = "cuda"
+    nav = Nav2DVectorEnv(n, size, size, seed=100, num_obstacles=8, turn_angle=10, max_episode_steps=500, device=dev)
+    syn = SyntheticVectorEnv(n, size, size, seed=100, device=dev)
+    obs = {"rgb": torch.empty(n, size, size, 3, dtype=torch.uint8, device=dev), "depth": torch.empty(n, size, size, 1, device=dev),
+           GOAL_UUID: torch.empty(n, 2, device=dev)}
+    rew, nd = torch.empty(n, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
+    g = torch.Generator().manual_seed(0)
+    # mostly moving actions, a STOP now and then: episodes of a few dozen steps
+    acts = torch.multinomial(torch.tensor([0.02, 0.58, 0.2, 0.2]), INNER * n, replacement=True, generator=g).view(INNER, n).to(dev)
+    runs = {
+        "nav2d step+render": lambda i: nav.step_into_obs(obs, rew, nd, actions=acts[i]),
+        "nav2d reset+render": lambda i: nav.reset_into_obs(obs),
+        "hab_synth_step": lambda i: syn.step_into_obs(obs, rew, nd),
+    }
+    nav.reset_into_obs(obs)
+    syn.reset_into_obs(obs)
+    for _ in range(3):
+        for fn in runs.values():
+            timed(fn)
+    times = {k: [] for k in runs}
+    for _ in range(windows):
+        for k, fn in runs.items():  # alternated: drift of the clocks hits all of them alike
+            times[k].append(timed(fn))
+    nbytes = n * size * size * 7
+    print(f"# {n} envs, {size}x{size} rgb + depth, {nbytes / 1e6:.1f} MB written per call, {windows} windows of {INNER} calls")
+    med = {}
+    for k, v in times.items():
+        med[k] = statistics.median(v)
+        print(f"{k:20s} median {med[k]:8.1f} us  range [{min(v):.1f}, {max(v):.1f}] us  {nbytes / med[k] / 1e3:7.1f} GB/s written")
+    print(f"ratio nav2d step+render / hab_synth_step: {med['nav2d step+render'] / med['hab_synth_step']:.2f}")
+
+
+if __name__ == "__main__":
+    main()
