@@ -92,6 +92,47 @@ __device__ void begin_episode(Nav2DState& s, uint32_t seed, uint32_t env, int K,
     s.collisions = 0;
 }
 
+// Episode 0 of one env (advance = 0 of both step kernels).
+__device__ inline void first_episode(Nav2DState& s, uint32_t seed, uint32_t env, int K, int nh) {
+    s.episode = 0;
+    s.ended = 0;
+    s.last[0] = s.last[1] = s.last[2] = s.last[3] = 0.0f;
+    begin_episode(s, seed, env, K, nh);
+}
+
+// What follows the move of one step, the same for both action spaces: reward, step count, done, and on done the measures, their
+// sums and the next episode's world.  `stop` is the action's request to end the episode (STOP / both speeds below their minima).
+__device__ inline void end_step(Nav2DState& s, bool stop, float* __restrict__ reward, uint8_t* __restrict__ not_done,
+                                float* __restrict__ sums, uint32_t seed, uint32_t env, int n, int N, int K, int nh, int max_steps) {
+    const float d = dist(s.px, s.py, s.gx, s.gy);
+    const bool success = stop && (d < 0.2f);
+    reward[n] = (-0.01f + (s.d_prev - d)) + (success ? 2.5f : 0.0f);
+    s.d_prev = d;
+    s.steps += 1;
+    const bool done = stop || (s.steps >= max_steps);
+    not_done[n] = done ? 0 : 1;
+    s.ended = done ? 1 : 0;
+    if (done) {
+        s.last[0] = success ? 1.0f : 0.0f;
+        s.last[1] = success ? __fdiv_rn(s.d_start, fmaxf(s.d_start, s.path)) : 0.0f;
+        s.last[2] = d;
+        s.last[3] = (float)s.collisions;
+        if (sums)
+            for (int m = 0; m < 4; ++m) sums[(size_t)m * N + n] = sums[(size_t)m * N + n] + s.last[m];
+        s.episode += 1;
+        begin_episode(s, seed, env, K, nh);
+    }
+}
+
+// pointgoal_with_gps_compass of the current state.
+__device__ inline void write_goal(const Nav2DState& s, const float* __restrict__ dirs, float* __restrict__ goal, int n) {
+    const float c = dirs[2 * s.heading], sn = dirs[2 * s.heading + 1];
+    const float dx = s.gx - s.px, dy = s.gy - s.py;
+    const float dot = dx * c + dy * sn, cross = c * dy - sn * dx;
+    goal[2 * n + 0] = dist(s.px, s.py, s.gx, s.gy);
+    goal[2 * n + 1] = atan2f(cross, dot);
+}
+
 // One thread per env.  advance = 0: episode 0 of every selected env; advance = 1: one step with actions[n].  Then the goal sensor.
 __global__ void nav2d_step_kernel(Nav2DState* __restrict__ states, const float* __restrict__ dirs, const int64_t* __restrict__ actions,
                                   const uint8_t* __restrict__ mask, float* __restrict__ goal, float* __restrict__ reward,
@@ -102,10 +143,7 @@ __global__ void nav2d_step_kernel(Nav2DState* __restrict__ states, const float* 
     Nav2DState& s = states[n];  // worked on in place: a private copy indexed by k would live in scratch memory
     const uint32_t env = env_offset + (uint32_t)n;
     if (!advance) {
-        s.episode = 0;
-        s.ended = 0;
-        s.last[0] = s.last[1] = s.last[2] = s.last[3] = 0.0f;
-        begin_episode(s, seed, env, K, nh);
+        first_episode(s, seed, env, K, nh);
     } else {
         const int64_t a = actions[n];  // anything outside 0..3 moves nothing (the host-side entry points refuse it)
         if (a == 1) {
@@ -117,32 +155,50 @@ __global__ void nav2d_step_kernel(Nav2DState* __restrict__ states, const float* 
         } else if (a == 3) {
             s.heading = (s.heading + nh - 1) % nh;
         }
-        const float d = dist(s.px, s.py, s.gx, s.gy);
-        const bool success = (a == 0) && (d < 0.2f);
-        reward[n] = (-0.01f + (s.d_prev - d)) + (success ? 2.5f : 0.0f);
-        s.d_prev = d;
-        s.steps += 1;
-        const bool done = (a == 0) || (s.steps >= max_steps);
-        not_done[n] = done ? 0 : 1;
-        s.ended = done ? 1 : 0;
-        if (done) {
-            s.last[0] = success ? 1.0f : 0.0f;
-            s.last[1] = success ? __fdiv_rn(s.d_start, fmaxf(s.d_start, s.path)) : 0.0f;
-            s.last[2] = d;
-            s.last[3] = (float)s.collisions;
-            if (sums)
-                for (int m = 0; m < 4; ++m) sums[(size_t)m * N + n] = sums[(size_t)m * N + n] + s.last[m];
-            s.episode += 1;
-            begin_episode(s, seed, env, K, nh);
+        end_step(s, a == 0, reward, not_done, sums, seed, env, n, N, K, nh, max_steps);
+    }
+    if (goal) write_goal(s, dirs, goal, n);
+}
+
+// Nav2DVel-v0 (Nav2DVelVectorEnv; specification: tests/nav2d_vel_reference.py): the same record, world, reward, measures and sensors,
+// with a continuous action (a_lin, a_ang), one 8-byte row of an (N, 2) float32 tensor.  Each component is clamped to [-1, 1], a
+// non-finite one acts as 0; the step length is (c_lin + 1) * 0.125, the turn rint(c_ang * max_turn) heading quanta (left positive),
+// and both below their minima is the stop.  A blocked target counts one collision and, with sliding, the agent takes the x or else
+// the y component of the move alone where that is free.  The heading stays an index into `dirs`: no angle is evaluated here.
+__global__ void nav2d_vel_step_kernel(Nav2DState* __restrict__ states, const float* __restrict__ dirs, const float2* __restrict__ actions,
+                                      const uint8_t* __restrict__ mask, float* __restrict__ goal, float* __restrict__ reward,
+                                      uint8_t* __restrict__ not_done, float* __restrict__ sums, uint32_t seed, uint32_t env_offset,
+                                      int N, int K, int nh, int max_steps, int max_turn, int stop_turn, float min_lin, int sliding,
+                                      int advance) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N || (mask && !mask[n])) return;
+    Nav2DState& s = states[n];
+    const uint32_t env = env_offset + (uint32_t)n;
+    if (!advance) {
+        first_episode(s, seed, env, K, nh);
+    } else {
+        const float2 a = actions[n];
+        const float c_lin = isfinite(a.x) ? fminf(fmaxf(a.x, -1.0f), 1.0f) : 0.0f;
+        const float c_ang = isfinite(a.y) ? fminf(fmaxf(a.y, -1.0f), 1.0f) : 0.0f;
+        const float l = (c_lin + 1.0f) * 0.125f;
+        const int dh = (int)rintf(c_ang * (float)max_turn);  // |dh| <= max_turn <= nh / 2
+        const bool stop = (l < min_lin) && (abs(dh) < stop_turn);
+        if (!stop) {
+            s.heading = (s.heading + dh + nh) % nh;
+            const float nx = s.px + l * dirs[2 * s.heading], ny = s.py + l * dirs[2 * s.heading + 1];
+            if (is_free(nx, ny, s, K)) {
+                s.px = nx; s.py = ny; s.path = s.path + l;
+            } else {
+                s.collisions += 1;
+                if (sliding) {
+                    if (is_free(nx, s.py, s, K)) { s.path = s.path + fabsf(nx - s.px); s.px = nx; }
+                    else if (is_free(s.px, ny, s, K)) { s.path = s.path + fabsf(ny - s.py); s.py = ny; }
+                }
+            }
         }
+        end_step(s, stop, reward, not_done, sums, seed, env, n, N, K, nh, max_steps);
     }
-    if (goal) {
-        const float c = dirs[2 * s.heading], sn = dirs[2 * s.heading + 1];
-        const float dx = s.gx - s.px, dy = s.gy - s.py;
-        const float dot = dx * c + dy * sn, cross = c * dy - sn * dx;
-        goal[2 * n + 0] = dist(s.px, s.py, s.gx, s.gy);
-        goal[2 * n + 1] = atan2f(cross, dot);
-    }
+    if (goal) write_goal(s, dirs, goal, n);
 }
 
 // ---- rendering ---------------------------------------------------------------------------------------------------------------
@@ -315,10 +371,10 @@ using namespace nav2d;
 
 extern "C" int hab_nav2d_state_bytes(void) { return (int)sizeof(Nav2DState); }
 
-extern "C" int hab_nav2d_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
-                              const int64_t* actions, const uint8_t* mask, uint8_t* rgb, float* depth, float* goal, float* reward,
-                              uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
-                              int num_obstacles, int num_headings, int max_episode_steps, int advance, hipStream_t stream) {
+// The argument checks both step entries share.
+static int check_step_args(const void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                           const void* actions, const uint8_t* rgb, const float* depth, const float* reward, const uint8_t* not_done,
+                           int N, int H, int W, int num_obstacles, int num_headings, int max_episode_steps, int advance) {
     if (!state || !dirs || N <= 0 || num_headings <= 0 || max_episode_steps <= 0) return HAB_ERR_ARG;
     if (num_obstacles < 0 || num_obstacles > MAX_K) return HAB_ERR_ARG;
     if (advance && (!actions || !reward || !not_done)) return HAB_ERR_ARG;
@@ -326,21 +382,55 @@ extern "C" int hab_nav2d_step(void* state, const float* dirs, const float* ray, 
     if ((rgb || depth) && (W > HAB_NAV2D_MAX_WIDTH || (long long)H * W > (1ll << 24))) return HAB_ERR_UNSUPPORTED;
     if ((rgb || depth) && N > 65535) return HAB_ERR_UNSUPPORTED;  // the render's grid.y is the env
     if (depth && ((uintptr_t)depth & 3)) return HAB_ERR_ARG;
+    return HAB_OK;
+}
+
+static int launch_render(const void* state, const float* ray, const float* col_cos, const float* tanv, const uint8_t* mask, uint8_t* rgb,
+                         float* depth, int N, int H, int W, int num_obstacles, hipStream_t stream) {
+    // a tile is at least ~16 KiB of stores per workgroup, so that the W column hits are a small part of its work
+    // and at most RENDER_MAX_ROWS, which keeps the dynamic LDS below 64 KiB for every accepted W
+    int rows = cdiv(4096, W);
+    if (rows < 4) rows = 4;
+    if (rows > RENDER_MAX_ROWS) rows = RENDER_MAX_ROWS;
+    if (rows > H) rows = H;
+    dim3 grid(cdiv(H, rows), N);
+    const size_t lds = (size_t)(col_pitch(W) + rows) * sizeof(uint4);
+    nav2d_render_kernel<<<grid, RENDER_THREADS, lds, stream>>>((const Nav2DState*)state, ray, col_cos, tanv, mask, rgb, depth, H, W,
+                                                                num_obstacles, rows);
+    HAB_LAUNCH_CHECK();
+    return HAB_OK;
+}
+
+extern "C" int hab_nav2d_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                              const int64_t* actions, const uint8_t* mask, uint8_t* rgb, float* depth, float* goal, float* reward,
+                              uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
+                              int num_obstacles, int num_headings, int max_episode_steps, int advance, hipStream_t stream) {
+    const int rc = check_step_args(state, dirs, ray, col_cos, tanv, actions, rgb, depth, reward, not_done, N, H, W, num_obstacles,
+                                   num_headings, max_episode_steps, advance);
+    if (rc != HAB_OK) return rc;
     nav2d_step_kernel<<<cdiv(N, 64), 64, 0, stream>>>((Nav2DState*)state, dirs, actions, mask, goal, reward, not_done, measure_sums,
                                                       seed, env_offset, N, num_obstacles, num_headings, max_episode_steps, advance);
     HAB_LAUNCH_CHECK();
-    if (rgb || depth) {
-        // a tile is at least ~16 KiB of stores per workgroup, so that the W column hits are a small part of its work
-        // and at most RENDER_MAX_ROWS, which keeps the dynamic LDS below 64 KiB for every accepted W
-        int rows = cdiv(4096, W);
-        if (rows < 4) rows = 4;
-        if (rows > RENDER_MAX_ROWS) rows = RENDER_MAX_ROWS;
-        if (rows > H) rows = H;
-        dim3 grid(cdiv(H, rows), N);
-        const size_t lds = (size_t)(col_pitch(W) + rows) * sizeof(uint4);
-        nav2d_render_kernel<<<grid, RENDER_THREADS, lds, stream>>>((const Nav2DState*)state, ray, col_cos, tanv, mask, rgb, depth, H, W,
-                                                                    num_obstacles, rows);
-        HAB_LAUNCH_CHECK();
-    }
+    if (rgb || depth) return launch_render(state, ray, col_cos, tanv, mask, rgb, depth, N, H, W, num_obstacles, stream);
+    return HAB_OK;
+}
+
+extern "C" int hab_nav2d_vel_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                                  const float* actions, const uint8_t* mask, uint8_t* rgb, float* depth, float* goal, float* reward,
+                                  uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
+                                  int num_obstacles, int num_headings, int max_episode_steps, int max_turn_steps, int stop_turn_steps,
+                                  float min_abs_lin_speed, int allow_sliding, int advance, hipStream_t stream) {
+    const int rc = check_step_args(state, dirs, ray, col_cos, tanv, actions, rgb, depth, reward, not_done, N, H, W, num_obstacles,
+                                   num_headings, max_episode_steps, advance);
+    if (rc != HAB_OK) return rc;
+    if ((uintptr_t)actions & 7) return HAB_ERR_ARG;  // a row is read as one float2
+    if (max_turn_steps < 1 || max_turn_steps > num_headings / 2 || stop_turn_steps < 1 || stop_turn_steps > max_turn_steps)
+        return HAB_ERR_ARG;
+    nav2d_vel_step_kernel<<<cdiv(N, 64), 64, 0, stream>>>((Nav2DState*)state, dirs, (const float2*)actions, mask, goal, reward, not_done,
+                                                          measure_sums, seed, env_offset, N, num_obstacles, num_headings,
+                                                          max_episode_steps, max_turn_steps, stop_turn_steps, min_abs_lin_speed,
+                                                          allow_sliding, advance);
+    HAB_LAUNCH_CHECK();
+    if (rgb || depth) return launch_render(state, ray, col_cos, tanv, mask, rgb, depth, N, H, W, num_obstacles, stream);
     return HAB_OK;
 }

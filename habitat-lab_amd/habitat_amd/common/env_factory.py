@@ -396,11 +396,108 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
         raise _lib.HabError("Nav2D: episodes are generated and never repeat, so no env is ever paused")
 
 
+def nav2d_vel_parameters(turn_angle, max_turn_angle, min_abs_lin_speed, min_abs_ang_speed):
+    """Checks the `habitat.synthetic` keys of Nav2DVel-v0 and returns (num_headings, M, S): the largest turn of one step and the
+    smallest turn that is not a stop, both in heading quanta."""
+    nh = nav2d_num_headings(turn_angle)
+    whole = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    if not whole(max_turn_angle) or max_turn_angle <= 0 or max_turn_angle % turn_angle != 0 or max_turn_angle > 180:
+        raise _lib.HabError(f"Nav2DVel: max_turn_angle {max_turn_angle!r} must be a positive multiple of turn_angle {turn_angle} "
+                            "(whole degrees), at most 180")
+    if not whole(min_abs_ang_speed) or min_abs_ang_speed <= 0 or min_abs_ang_speed % turn_angle != 0 or min_abs_ang_speed > max_turn_angle:
+        raise _lib.HabError(f"Nav2DVel: min_abs_ang_speed {min_abs_ang_speed!r} must be a positive multiple of turn_angle {turn_angle} "
+                            f"(whole degrees), at most max_turn_angle {max_turn_angle}")
+    if (isinstance(min_abs_lin_speed, bool) or not isinstance(min_abs_lin_speed, (int, float, np.integer, np.floating))
+            or not 0.0 < float(min_abs_lin_speed) <= 0.25):
+        raise _lib.HabError(f"Nav2DVel: min_abs_lin_speed {min_abs_lin_speed!r} must be a length in (0, 0.25] metres")
+    return nh, int(max_turn_angle) // int(turn_angle), int(min_abs_ang_speed) // int(turn_angle)
+
+
+class Nav2DVelVectorEnv(Nav2DVectorEnv):
+    """Nav2DVel-v0: Nav2D-v0 under velocity control, the source whose reward depends on CONTINUOUS actions.  World generation, the
+    free-space test, sensors, rendering, the reward formula, the four measures, the state record and the (seed, env, episode) streams
+    are Nav2D-v0's (see Nav2DVectorEnv); only the action and the physics of one step differ.  The parameter names follow habitat's
+    `velocity_control` action (inputs in [-1, 1] scaled to a linear and an angular range, a stop when both speeds are below their
+    minima, sliding along obstacles); the reference's source is not at hand, so the statement below IS this project's specification.
+    tests/nav2d_vel_reference.py restates it in numpy and `nav2d_vel_step_kernel` (csrc/nav2d.hip) matches it bit for bit, phi excepted.
+    No angle is evaluated on the device: the heading stays an index into the host tables.
+
+    Parameters (`habitat.synthetic`): turn_angle (default 1), the heading quantum, whole degrees dividing 360; max_turn_angle (10), a
+    positive multiple of turn_angle, at most 180, M = max_turn_angle / turn_angle; min_abs_lin_speed (0.025) metres in (0, 0.25];
+    min_abs_ang_speed (5) degrees, a positive multiple of turn_angle, at most max_turn_angle, S = min_abs_ang_speed / turn_angle;
+    allow_sliding (true).
+    Action space: Box(-1, 1, (2,), float32), a = (a_lin, a_ang).
+    One step (every written operation one float32 rounding, no fused multiply-add):
+      1. per component c = min(max(a, -1), 1), and c = 0 for a non-finite a;
+      2. step length l = (c_lin + 1) * 0.125: one add, then one multiply, so l is in [0, 0.25];
+      3. turn dh = (int) rint(c_ang * M): one float32 multiply rounded half to even; positive is left (TURN_LEFT is h + 1);
+      4. stop = (l < min_abs_lin_speed) and (|dh| < S); on stop nothing moves;
+      5. otherwise h = (h + dh) mod num_headings and, with (c, s) = dirs[h], the target is nx = px + l * c, ny = py + l * s.  A free
+         target is taken and path_length grows by l.  A blocked one counts one collision; then, with sliding, (nx, py) is taken if free
+         (path_length grows by |nx - px|), else (px, ny) if free (by |ny - py|), else the agent stays;
+      6. distance, reward ((-0.01 + (d_prev - d)) + 2.5 * success, success = stop and d < 0.2), step count,
+         done = stop or steps >= max_episode_steps, the measures and their sums, the next episode's world on done and the goal sensor
+         are exactly Nav2D-v0's with `stop` in the place of STOP.
+
+    `step_into_obs(obs, reward, not_done, actions=...)` takes the (N, 2) float32 row the policy stored; the env clamps, so the stored
+    action stays unclipped.  `async_step_at(i, a)` takes a length-2 array (or {"action": array})."""
+
+    def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
+                 use_depth: bool = True, num_actions: int = 1, device="cuda", num_obstacles: int = 3, turn_angle: int = 1,
+                 max_episode_steps: int = 500, max_turn_angle: int = 10, min_abs_lin_speed: float = 0.025, min_abs_ang_speed: int = 5,
+                 allow_sliding: bool = True):
+        _, self.max_turn_steps, self.stop_turn_steps = nav2d_vel_parameters(turn_angle, max_turn_angle, min_abs_lin_speed,
+                                                                            min_abs_ang_speed)
+        if not isinstance(allow_sliding, (bool, np.bool_)):
+            raise _lib.HabError(f"Nav2DVel: allow_sliding {allow_sliding!r} must be true or false")
+        if num_actions != 1:
+            raise _lib.HabError(f"Nav2DVel: the task has the one action velocity_control, got {num_actions} actions")
+        super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
+                         num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps)
+        self.max_turn_angle, self.min_abs_ang_speed = int(max_turn_angle), int(min_abs_ang_speed)
+        self.min_abs_lin_speed, self.allow_sliding = float(min_abs_lin_speed), bool(allow_sliding)
+        self.action_spaces = [spaces.Box(-1.0, 1.0, (2,), np.float32) for _ in range(num_envs)]
+        self.orig_action_spaces = self.action_spaces
+        self._actions_host = np.zeros((num_envs, 2), dtype=np.float32)
+
+    def _launch(self, obs, reward, not_done, actions, mask, advance: int):
+        if actions is not None and (actions.dtype != torch.float32 or tuple(actions.shape) != (self.num_envs, 2)
+                                    or not actions.is_contiguous() or not actions.is_cuda):
+            raise _lib.HabError("Nav2DVel: actions must be a contiguous float32 device tensor of shape (N, 2)")
+        dirs, ray, col_cos, tanv = self._tables
+        check(_lib.lib().hab_nav2d_vel_step(ptr(self._state), ptr(dirs), ptr(ray), ptr(col_cos), ptr(tanv), ptr(actions), ptr(mask),
+                                            ptr(obs.get("rgb")), ptr(obs.get("depth")), ptr(obs.get(GOAL_UUID)), ptr(reward),
+                                            ptr(not_done), ptr(self.measure_sums), self.seed, self.env_offset, self.num_envs, self.H,
+                                            self.W, self.num_obstacles, self.num_headings, self.max_episode_steps, self.max_turn_steps,
+                                            self.stop_turn_steps, self.min_abs_lin_speed, int(self.allow_sliding), advance,
+                                            stream_ptr()), "hab_nav2d_vel_step")
+
+    def step_into_obs(self, obs, reward, not_done, actions=None, mask=None):
+        """One step of every env (or of the envs whose `mask` byte is set) with `actions` float32 (N, 2), rows (a_lin, a_ang): the new
+        observations, rewards (N,) and not-done bytes (N,) go straight into the given device tensors."""
+        if actions is None:
+            raise _lib.HabError("Nav2DVel: step_into_obs needs the actions of the step")
+        self._launch(obs, reward, not_done, actions, mask, 1)
+
+    def async_step_at(self, index_env: int, action) -> None:
+        if isinstance(action, dict):
+            action = action["action"]
+        try:
+            a = np.asarray(action, dtype=np.float32)
+        except (TypeError, ValueError):
+            a = None
+        if a is None or a.shape != (2,):
+            raise _lib.HabError(f"Nav2DVel: env {index_env}: action {action!r} is not a length-2 array (a_lin, a_ang)")
+        SyntheticVectorEnv.async_step_at(self, index_env, action)
+        self._actions_host[int(index_env)] = a
+
+
 class SyntheticVectorEnvFactory(VectorEnvFactory):
     """Default `_target_`: N synthetic PointNav envs sized from habitat.simulator.sensors.*; per-rank env ids are
     offset by rank * num_environments exactly like the reference offsets the seed (ppo_trainer.py:208-211).  A
     `habitat.task.type` starting with "nav2d" (any case) selects the Nav2D-v0 task, whose num_obstacles / turn_angle come from
-    `habitat.synthetic` and whose episode limit from `habitat.environment.max_episode_steps`."""
+    `habitat.synthetic` and whose episode limit from `habitat.environment.max_episode_steps`; one starting with "nav2dvel" selects
+    Nav2DVel-v0, its velocity-controlled variant (Nav2DVelVectorEnv), with the further `habitat.synthetic` keys named there."""
 
     def __init__(self, use_rgb: bool = True, use_depth: bool = True):
         self.use_rgb, self.use_depth = use_rgb, use_depth
@@ -411,9 +508,20 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
         sens = hab.simulator.sensors
         use_rgb = self.use_rgb and "rgb" in sens
         use_depth = self.use_depth and "depth" in sens
-        if str(hab.task.type).lower().startswith("nav2d"):
+        task_type = str(hab.task.type).lower()
+        if task_type.startswith("nav2d"):
             ref = sens["rgb"] if use_rgb else (sens["depth"] if use_depth else dict(height=0, width=0))
             syn = getattr(hab, "synthetic", {})
+            if task_type.startswith("nav2dvel"):
+                return Nav2DVelVectorEnv(int(hb.num_environments), int(ref["height"]), int(ref["width"]), seed=int(hab.seed),
+                                         env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, num_actions=len(hab.task.actions),
+                                         device=device, num_obstacles=getattr(syn, "num_obstacles", 3),
+                                         turn_angle=getattr(syn, "turn_angle", 1),
+                                         max_episode_steps=getattr(hab.environment, "max_episode_steps", 500),
+                                         max_turn_angle=getattr(syn, "max_turn_angle", 10),
+                                         min_abs_lin_speed=getattr(syn, "min_abs_lin_speed", 0.025),
+                                         min_abs_ang_speed=getattr(syn, "min_abs_ang_speed", 5),
+                                         allow_sliding=getattr(syn, "allow_sliding", True))
             return Nav2DVectorEnv(int(hb.num_environments), int(ref["height"]), int(ref["width"]), seed=int(hab.seed),
                                   env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, num_actions=len(hab.task.actions),
                                   device=device, num_obstacles=getattr(syn, "num_obstacles", 3), turn_angle=getattr(syn, "turn_angle", 10),

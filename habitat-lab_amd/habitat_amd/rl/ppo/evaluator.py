@@ -65,7 +65,7 @@ class Evaluator(abc.ABC):
 
 class HabitatEvaluator(Evaluator):
     def evaluate_agent(self, agent, envs, config, checkpoint_index, step_id, writer, device, obs_transforms, env_spec, rank0_keys):
-        from habitat_amd.rl.ppo.ppo_trainer import batch_obs
+        from habitat_amd.rl.ppo.ppo_trainer import batch_obs, host_env_action
         hb = config.habitat_baselines
         if len(hb.eval.video_option) > 0:
             raise _lib.HabError("eval.video_option: video generation needs the simulator's renderer and is not part of this path")
@@ -103,7 +103,8 @@ class HabitatEvaluator(Evaluator):
                     prev_actions.copy_(action_data.actions)
                 else:
                     ac.update_hidden_state(test_recurrent_hidden_states, prev_actions, action_data)
-            step_data = [a.item() for a in action_data.env_actions.cpu()]  # host copies: workers must never see device tensors
+            # host copies: workers must never see device tensors; a continuous action is clipped to the Box (habitat_evaluator.py:179-188)
+            step_data = [host_env_action(a, ac.policy_action_space) for a in action_data.env_actions.cpu()]
             outputs = envs.step(step_data)
             observations, rewards_l, dones, infos = [list(x) for x in zip(*outputs)]
             policy_infos = ac.get_extra(action_data, infos, dones)

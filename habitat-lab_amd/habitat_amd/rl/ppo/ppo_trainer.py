@@ -28,6 +28,7 @@ from habitat_amd.common.baseline_registry import baseline_registry
 from habitat_amd.common.env_factory import instantiate
 from habitat_amd.common.obs_transformers import (apply_obs_transforms_batch, apply_obs_transforms_obs_space,
                                                  get_active_obs_transforms)
+from habitat_amd.common.spaces import is_continuous_action_space
 from habitat_amd.config.default import read_write
 from habitat_amd.rl.ddppo.ddp_utils import (EXIT, StoreCounterPoller, get_distrib_size, init_distrib_slurm, load_resume_state, pin_rank_affinity, rank0_only,
                                             requeue_job, save_resume_state)
@@ -40,6 +41,14 @@ import habitat_amd.rl.ddppo  # noqa: F401  (registers DDPPO)
 import habitat_amd.rl.ppo  # noqa: F401  (registers policies / PPO)
 import habitat_amd.rl.ppo.single_agent_access_mgr  # noqa: F401
 import habitat_amd.rl.ver  # noqa: F401  (registers VERRolloutStorage)
+
+
+def host_env_action(act: torch.Tensor, action_space):
+    """What the host path hands an env for one env's action row (ppo_trainer.py, _compute_actions_and_step_envs): a continuous action
+    clipped to the Box as a numpy array, a discrete one as a Python int.  The rollout keeps the unclipped action."""
+    if is_continuous_action_space(action_space):
+        return np.clip(act.numpy(), action_space.low, action_space.high)
+    return act.item()
 
 
 def batch_obs(observations, device):
@@ -262,7 +271,7 @@ class PPOTrainer(BaseRLTrainer):
                 step_batch["prev_actions"], step_batch["masks"])
         with g_timer.avg_time("trainer.obs_insert"):
             for index_env, act in zip(range(env_slice.start, env_slice.stop), action_data.env_actions.cpu().unbind(0)):
-                self.envs.async_step_at(index_env, act.item())
+                self.envs.async_step_at(index_env, host_env_action(act, self._env_spec.action_space))
             self._agent.rollouts.insert(next_recurrent_hidden_states=action_data.rnn_hidden_states, actions=action_data.actions,
                                         action_log_probs=action_data.action_log_probs, value_preds=action_data.values,
                                         buffer_index=buffer_index)

@@ -86,6 +86,20 @@ int hab_nav2d_step(void* state /*N,HAB_NAV2D_STATE_BYTES*/, const float* dirs, c
                    float* depth /*N,H,W,1*/, float* goal /*N,2*/, float* reward /*N*/, uint8_t* not_done /*N*/,
                    float* measure_sums /*4,N*/, uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles,
                    int num_headings, int max_episode_steps, int advance, hipStream_t stream);
+/* Nav2DVel-v0: the same world, record, reward, measures, sensors and render with a continuous action (definition:
+ * habitat_amd/common/env_factory.py, Nav2DVelVectorEnv; bit-identical to tests/nav2d_vel_reference.py except phi = atan2f; the
+ * parameter names follow habitat's velocity_control action, habitat/tasks/nav/nav.py VelocityAction).  Every argument of
+ * hab_nav2d_step keeps its meaning and its checks, except actions: f32 (N,2) rows (a_lin, a_ang), 8-byte aligned.  Each component is
+ * clamped to [-1, 1], a non-finite one acts as 0; step length (c_lin + 1) * 0.125 m, turn rint(c_ang * max_turn_steps) headings
+ * (1 <= max_turn_steps <= num_headings / 2); the step is the stop when the length is below min_abs_lin_speed and the turn below
+ * stop_turn_steps (1 <= stop_turn_steps <= max_turn_steps); allow_sliding != 0 lets a blocked agent take the x, else the y,
+ * component of its move alone. */
+int hab_nav2d_vel_step(void* state /*N,HAB_NAV2D_STATE_BYTES*/, const float* dirs, const float* ray, const float* col_cos,
+                       const float* tanv, const float* actions /*N,2*/, const uint8_t* mask /*N*/, uint8_t* rgb /*N,H,W,3*/,
+                       float* depth /*N,H,W,1*/, float* goal /*N,2*/, float* reward /*N*/, uint8_t* not_done /*N*/,
+                       float* measure_sums /*4,N*/, uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles,
+                       int num_headings, int max_episode_steps, int max_turn_steps, int stop_turn_steps, float min_abs_lin_speed,
+                       int allow_sliding, int advance, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Observation transformers, fused: ResizeShortestEdge followed by CenterCropper

@@ -5,7 +5,11 @@ that is meant to be store-bound.  Both are warmed up and then alternated in one 
 device events and the median and the range of the windows are printed, with the bytes written per second.  The Nav2D actions are a
 fixed random sequence (all four actions), so episodes end and worlds are regenerated inside the timed windows, as in a rollout; the
 reset (advance = 0) is timed separately.
-usage: python tools/bench_nav2d.py [envs] [size] [windows]"""
+With --vel the pair is instead Nav2DVel-v0 (hab_nav2d_vel_step, turn_angle 1: a 360-heading ray table) beside hab_nav2d_step at the same
+shape: the render kernel is shared, so the medians are expected to agree within the spread of the windows.  Its actions are uniform in
+[-0.9, 1] x [-1, 1], which stops about as often as the discrete sequence does.  Three more runs separate the parts: the velocity task
+on 36 headings (the discrete task's ray table size) and both step kernels without images.
+usage: python tools/bench_nav2d.py [--vel] [envs] [size] [windows]"""
 import os
 import statistics
 import sys
@@ -15,7 +19,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "habitat-lab_amd"))
-from habitat_amd.common.env_factory import GOAL_UUID, Nav2DVectorEnv, SyntheticVectorEnv  # noqa: E402
+from habitat_amd.common.env_factory import GOAL_UUID, Nav2DVectorEnv, Nav2DVelVectorEnv, SyntheticVectorEnv  # noqa: E402
 
 INNER = 10  # calls per timed window: a single launch of a few microseconds would time the enqueue
 
@@ -31,9 +35,11 @@ def timed(fn):
 
 
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-    size = int(sys.argv[2]) if len(sys.argv) > 2 else 256
-    windows = int(sys.argv[3]) if len(sys.argv) > 3 else 30
+    argv = [a for a in sys.argv[1:] if a != "--vel"]
+    vel = "--vel" in sys.argv[1:]
+    n = int(argv[0]) if len(argv) > 0 else 64
+    size = int(argv[1]) if len(argv) > 1 else 256
+    windows = int(argv[2]) if len(argv) > 2 else 30
     assert torch.cuda.is_available(), "bench_nav2d needs a GPU"
     dev = "cuda"
     nav = Nav2DVectorEnv(n, size, size, seed=100, num_obstacles=8, turn_angle=10, max_episode_steps=500, device=dev)
@@ -49,6 +55,25 @@ def main():
         "nav2d reset+render": lambda i: nav.reset_into_obs(obs),
         "hab_synth_step": lambda i: syn.step_into_obs(obs, rew, nd),
     }
+    if vel:
+        kw = dict(seed=100, num_obstacles=8, max_episode_steps=500, device=dev)
+        nvel = Nav2DVelVectorEnv(n, size, size, **kw)
+        # the same task on Nav2D-v0's 36 headings (M = S = 1), and both steps without images: what the ray table and the step cost
+        nvel36 = Nav2DVelVectorEnv(n, size, size, turn_angle=10, max_turn_angle=10, min_abs_ang_speed=10, **kw)
+        nav0 = Nav2DVectorEnv(n, 0, 0, use_rgb=False, use_depth=False, turn_angle=10, **kw)
+        nvel0 = Nav2DVelVectorEnv(n, 0, 0, use_rgb=False, use_depth=False, **kw)
+        goal = {GOAL_UUID: obs[GOAL_UUID]}
+        lo = torch.tensor([-0.9, -1.0])
+        vacts = (lo + (1.0 - lo) * torch.rand(INNER, n, 2, generator=g)).to(dev)
+        runs = {"nav2d step+render": runs["nav2d step+render"],
+                "nav2dvel step+render": lambda i: nvel.step_into_obs(obs, rew, nd, actions=vacts[i]),
+                "nav2dvel, 36 headings": lambda i: nvel36.step_into_obs(obs, rew, nd, actions=vacts[i]),
+                "nav2d step only": lambda i: nav0.step_into_obs(goal, rew, nd, actions=acts[i]),
+                "nav2dvel step only": lambda i: nvel0.step_into_obs(goal, rew, nd, actions=vacts[i])}
+        for e in (nvel, nvel36):
+            e.reset_into_obs(obs)
+        for e in (nav0, nvel0):
+            e.reset_into_obs(goal)
     nav.reset_into_obs(obs)
     syn.reset_into_obs(obs)
     for _ in range(3):
@@ -63,8 +88,11 @@ def main():
     med = {}
     for k, v in times.items():
         med[k] = statistics.median(v)
-        print(f"{k:20s} median {med[k]:8.1f} us  range [{min(v):.1f}, {max(v):.1f}] us  {nbytes / med[k] / 1e3:7.1f} GB/s written")
-    print(f"ratio nav2d step+render / hab_synth_step: {med['nav2d step+render'] / med['hab_synth_step']:.2f}")
+        print(f"{k:22s} median {med[k]:8.1f} us  range [{min(v):.1f}, {max(v):.1f}] us  {nbytes / med[k] / 1e3:7.1f} GB/s written")
+    if vel:
+        print(f"ratio nav2dvel step+render / nav2d step+render: {med['nav2dvel step+render'] / med['nav2d step+render']:.3f}")
+    else:
+        print(f"ratio nav2d step+render / hab_synth_step: {med['nav2d step+render'] / med['hab_synth_step']:.2f}")
 
 
 if __name__ == "__main__":
