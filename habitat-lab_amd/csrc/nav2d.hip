@@ -2,6 +2,8 @@
 // Definition: habitat_amd/common/env_factory.py (Nav2DVectorEnv); specification: tests/nav2d_reference.py, which these
 // kernels reproduce bit for bit (phi = atan2f excepted).  Every float operation below is one fp32 rounding: contraction is off
 // for the whole file and division / square root are the correctly rounded forms (`__fdiv_rn` = `x / y`, `sqrt_rn` below); angles come from host-built tables.
+// Nav2DVel-v0 (continuous actions) and Nav2DObj-v0 (objects, a target category, the ObjectNav sensor set) share the world, the end of
+// a step and the render; their specifications are tests/nav2d_vel_reference.py and tests/nav2d_obj_reference.py.
 #include <cstddef>
 #include "hab_common.h"
 #include "../../include/habitat_amd.h"
@@ -24,7 +26,10 @@ __host__ __device__ inline uint32_t stream_key(uint32_t seed, uint32_t sensor, u
 __device__ inline float u01(uint32_t w) { return (float)(w >> 8) * 5.9604644775390625e-08f; }
 
 constexpr uint32_t S_OBST = 16u, S_START = 17u, S_GOAL = 18u, S_HEAD = 19u, S_COLOR = 20u;
+constexpr uint32_t S_OBJ_POS = 21u, S_OBJ_CAT = 22u, S_OBJ_TARGET = 23u;  // Nav2DObj-v0
 constexpr int MAX_K = HAB_NAV2D_MAX_OBSTACLES, CANDIDATES = 16;
+constexpr int MAX_M = HAB_NAV2D_MAX_OBJECTS, RING_SLOTS = 28;
+constexpr float OBJ_R = 0.3f, OBJ_BLOCK = 0.4f, OBJ_LO = 0.5f, OBJ_HI = 7.5f, OBJ_APART = 1.0f, OBJ_SUCCESS = 1.0f;
 constexpr float ARENA = 8.0f, RADIUS = 0.1f, LO = 0.1f, HI = 7.9f, FORWARD = 0.25f;
 
 // One env's state (HAB_NAV2D_STATE_BYTES = 224 bytes = 56 words; the layout is part of the C ABI, see the header).
@@ -47,6 +52,23 @@ static_assert(offsetof(Nav2DState, collisions) == 4 * HAB_NAV2D_W_COLLISIONS && 
 static_assert(offsetof(Nav2DState, ended) == 4 * HAB_NAV2D_W_ENDED && offsetof(Nav2DState, last) == 4 * HAB_NAV2D_W_LAST_MEASURES,
               "Nav2DState layout");
 
+// One env of Nav2DObj-v0: a Nav2D-v0 record (gx, gy = the centre of the nearest object of the target category), then the start pose
+// the gps / compass sensors refer to, the target category and the objects.
+struct Nav2DObjState {
+    Nav2DState base;
+    float sx, sy;
+    int32_t h0, target;
+    float obj[MAX_M][2];        // centre x, y
+    int32_t cat[MAX_M];
+};
+static_assert(sizeof(Nav2DObjState) == HAB_NAV2D_OBJ_STATE_BYTES && offsetof(Nav2DObjState, base) == 0, "Nav2DObjState layout");
+static_assert(offsetof(Nav2DObjState, sx) == 4 * HAB_NAV2D_OBJ_W_START_X && offsetof(Nav2DObjState, sy) == 4 * HAB_NAV2D_OBJ_W_START_Y,
+              "Nav2DObjState layout");
+static_assert(offsetof(Nav2DObjState, h0) == 4 * HAB_NAV2D_OBJ_W_START_HEADING && offsetof(Nav2DObjState, target) == 4 * HAB_NAV2D_OBJ_W_TARGET,
+              "Nav2DObjState layout");
+static_assert(offsetof(Nav2DObjState, obj) == 4 * HAB_NAV2D_OBJ_W_OBJECTS && offsetof(Nav2DObjState, cat) == 4 * HAB_NAV2D_OBJ_W_CATEGORIES,
+              "Nav2DObjState layout");
+
 // Correctly rounded square root.  NOT `__fsqrt_rn`: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers define that name as the
 // native (1 ulp) square root; `sqrtf` is the IEEE one under hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt.
 __device__ inline float sqrt_rn(float x) { return __builtin_sqrtf(x); }
@@ -63,6 +85,9 @@ __device__ inline float dist(float ax, float ay, float bx, float by) {
     return sqrt_rn(dx * dx + dy * dy);
 }
 
+// A new episode's world.  GOAL (Nav2D-v0, Nav2DVel-v0): rectangles, their colours, the start, the goal, the heading, the distances and
+// the counters.  Without GOAL (Nav2DObj-v0) the goal and the distances are left to the caller, which places its objects afterwards.
+template <bool GOAL = true>
 __device__ void begin_episode(Nav2DState& s, uint32_t seed, uint32_t env, int K, int nh) {
     const uint32_t ep = (uint32_t)s.episode;
     const uint32_t ko = stream_key(seed, S_OBST, env, ep), kc = stream_key(seed, S_COLOR, env, ep);
@@ -80,13 +105,16 @@ __device__ void begin_episode(Nav2DState& s, uint32_t seed, uint32_t env, int K,
         if (is_free(x, y, s, K)) { sx = x; sy = y; break; }
     }
     float gx = 7.5f, gy = 7.5f;
-    for (int j = 0; j < CANDIDATES; ++j) {
-        const float x = LO + 7.8f * u01(mix32(kg ^ (uint32_t)(2 * j))), y = LO + 7.8f * u01(mix32(kg ^ (uint32_t)(2 * j + 1)));
-        if (is_free(x, y, s, K) && dist(sx, sy, x, y) >= 1.0f) { gx = x; gy = y; break; }
+    if constexpr (GOAL) {
+        for (int j = 0; j < CANDIDATES; ++j) {
+            const float x = LO + 7.8f * u01(mix32(kg ^ (uint32_t)(2 * j))), y = LO + 7.8f * u01(mix32(kg ^ (uint32_t)(2 * j + 1)));
+            if (is_free(x, y, s, K) && dist(sx, sy, x, y) >= 1.0f) { gx = x; gy = y; break; }
+        }
     }
-    s.px = sx; s.py = sy; s.gx = gx; s.gy = gy;
+    s.px = sx; s.py = sy;
+    if constexpr (GOAL) { s.gx = gx; s.gy = gy; }
     s.heading = (int32_t)(mix32(stream_key(seed, S_HEAD, env, ep) ^ 0u) % (uint32_t)nh);
-    s.d_start = s.d_prev = dist(sx, sy, gx, gy);
+    if constexpr (GOAL) s.d_start = s.d_prev = dist(sx, sy, gx, gy);
     s.path = 0.0f;
     s.steps = 0;
     s.collisions = 0;
@@ -100,12 +128,16 @@ __device__ inline void first_episode(Nav2DState& s, uint32_t seed, uint32_t env,
     begin_episode(s, seed, env, K, nh);
 }
 
-// What follows the move of one step, the same for both action spaces: reward, step count, done, and on done the measures, their
-// sums and the next episode's world.  `stop` is the action's request to end the episode (STOP / both speeds below their minima).
-__device__ inline void end_step(Nav2DState& s, bool stop, float* __restrict__ reward, uint8_t* __restrict__ not_done,
+// What follows the move of one step, the same for every task: reward, step count, done, and on done the measures, their sums and
+// the next episode's world (`begin_episode<GOAL>`; the object task then adds its objects where `ended` is set).  `stop` is the
+// action's request to end the episode (STOP / both speeds below their minima), `success_dist` the task's success radius; the
+// distance is the one to (gx, gy).  A form that took the next world as a callable compiled to a velocity kernel whose distance was
+// that of the previous position; this form gives the Nav2D-v0 and Nav2DVel-v0 kernels the instructions they had before the object task.
+template <bool GOAL = true>
+__device__ inline void end_step(Nav2DState& s, bool stop, float success_dist, float* __restrict__ reward, uint8_t* __restrict__ not_done,
                                 float* __restrict__ sums, uint32_t seed, uint32_t env, int n, int N, int K, int nh, int max_steps) {
     const float d = dist(s.px, s.py, s.gx, s.gy);
-    const bool success = stop && (d < 0.2f);
+    const bool success = stop && (d < success_dist);
     reward[n] = (-0.01f + (s.d_prev - d)) + (success ? 2.5f : 0.0f);
     s.d_prev = d;
     s.steps += 1;
@@ -120,7 +152,7 @@ __device__ inline void end_step(Nav2DState& s, bool stop, float* __restrict__ re
         if (sums)
             for (int m = 0; m < 4; ++m) sums[(size_t)m * N + n] = sums[(size_t)m * N + n] + s.last[m];
         s.episode += 1;
-        begin_episode(s, seed, env, K, nh);
+        begin_episode<GOAL>(s, seed, env, K, nh);
     }
 }
 
@@ -155,7 +187,7 @@ __global__ void nav2d_step_kernel(Nav2DState* __restrict__ states, const float* 
         } else if (a == 3) {
             s.heading = (s.heading + nh - 1) % nh;
         }
-        end_step(s, a == 0, reward, not_done, sums, seed, env, n, N, K, nh, max_steps);
+        end_step(s, a == 0, 0.2f, reward, not_done, sums, seed, env, n, N, K, nh, max_steps);
     }
     if (goal) write_goal(s, dirs, goal, n);
 }
@@ -196,9 +228,117 @@ __global__ void nav2d_vel_step_kernel(Nav2DState* __restrict__ states, const flo
                 }
             }
         }
-        end_step(s, stop, reward, not_done, sums, seed, env, n, N, K, nh, max_steps);
+        end_step(s, stop, 0.2f, reward, not_done, sums, seed, env, n, N, K, nh, max_steps);
     }
     if (goal) write_goal(s, dirs, goal, n);
+}
+
+// ---- Nav2DObj-v0 (Nav2DObjVectorEnv; specification: tests/nav2d_obj_reference.py) -----------------------------------------------------
+__device__ inline bool is_free_obj(float x, float y, const Nav2DObjState& s, int K, int M) {
+    if (!is_free(x, y, s.base, K)) return false;
+    for (int j = 0; j < M; ++j)
+        if (dist(x, y, s.obj[j][0], s.obj[j][1]) < OBJ_BLOCK) return false;
+    return true;
+}
+// Whether (x, y) can take object j: clear of the start and of the objects before it.
+__device__ inline bool object_fits(float x, float y, const Nav2DObjState& s, int j) {
+    if (!(dist(s.sx, s.sy, x, y) >= OBJ_APART)) return false;
+    for (int i = 0; i < j; ++i)
+        if (!(dist(s.obj[i][0], s.obj[i][1], x, y) >= OBJ_APART)) return false;
+    return true;
+}
+// Slot q of the fallback ring: the 28 points one metre apart on the square through (0.5, 0.5) and (7.5, 7.5), counter-clockwise
+// from (0.5, 0.5).  No rectangle grown by 0.3 reaches them.
+__device__ inline void ring_slot(int q, float& x, float& y) {
+    const int side = q / 7;
+    const float i = (float)(q - 7 * side);
+    x = side == 0 ? 0.5f + i : side == 1 ? 7.5f : side == 2 ? 7.5f - i : 0.5f;
+    y = side == 0 ? 0.5f : side == 1 ? 0.5f + i : side == 2 ? 7.5f : 7.5f - i;
+}
+// The nearest centre of the target category becomes (gx, gy); returns its distance.  The first of equally near ones wins.
+__device__ inline float nearest_target(Nav2DObjState& s, int M) {
+    float best = INFINITY;
+    for (int j = 0; j < M; ++j) {
+        if (s.cat[j] != s.target) continue;
+        const float d = dist(s.base.px, s.base.py, s.obj[j][0], s.obj[j][1]);
+        if (d < best) { best = d; s.base.gx = s.obj[j][0]; s.base.gy = s.obj[j][1]; }
+    }
+    return best;
+}
+// What Nav2DObj-v0 adds to a world that `begin_episode<false>` has just generated: the start pose the gps / compass sensors refer to,
+// the objects, the target, and the distances.
+__device__ void place_objects(Nav2DObjState& s, uint32_t seed, uint32_t env, int K, int M, int C) {
+    const uint32_t ep = (uint32_t)s.base.episode;
+    s.sx = s.base.px; s.sy = s.base.py; s.h0 = s.base.heading;
+    const uint32_t kp = stream_key(seed, S_OBJ_POS, env, ep), kc = stream_key(seed, S_OBJ_CAT, env, ep);
+    for (int j = 0; j < M; ++j) {
+        bool placed = false;
+        for (int i = 0; i < CANDIDATES && !placed; ++i) {
+            const uint32_t w = (uint32_t)(2 * (CANDIDATES * j + i));
+            const float x = LO + 7.8f * u01(mix32(kp ^ w)), y = LO + 7.8f * u01(mix32(kp ^ (w + 1u)));
+            if (!(x >= OBJ_LO && x <= OBJ_HI && y >= OBJ_LO && y <= OBJ_HI)) continue;
+            bool in_rect = false;
+            for (int k = 0; k < K; ++k)
+                in_rect = in_rect || (x > s.base.rect[k][0] - OBJ_R && x < s.base.rect[k][2] + OBJ_R && y > s.base.rect[k][1] - OBJ_R &&
+                                      y < s.base.rect[k][3] + OBJ_R);
+            if (in_rect || !object_fits(x, y, s, j)) continue;
+            s.obj[j][0] = x; s.obj[j][1] = y;
+            placed = true;
+        }
+        for (int q = 0; q < RING_SLOTS && !placed; ++q) {  // a fitting slot always exists, see the restatement
+            float x, y;
+            ring_slot(q, x, y);
+            s.obj[j][0] = x; s.obj[j][1] = y;
+            placed = object_fits(x, y, s, j);
+        }
+        s.cat[j] = (int32_t)(mix32(kc ^ (uint32_t)j) % (uint32_t)C);
+    }
+    for (int j = M; j < MAX_M; ++j) { s.obj[j][0] = 0.0f; s.obj[j][1] = 0.0f; s.cat[j] = -1; }
+    s.target = s.cat[mix32(stream_key(seed, S_OBJ_TARGET, env, ep) ^ 0u) % (uint32_t)M];
+    s.base.d_start = s.base.d_prev = nearest_target(s, M);
+}
+
+// One thread per env, as nav2d_step_kernel.  Then objectgoal, gps (the offset from the start in the start heading's frame, written
+// term by term like write_goal's dot and cross) and compass (a row of the host table).
+__global__ void nav2d_obj_step_kernel(Nav2DObjState* __restrict__ states, const float* __restrict__ dirs, const float* __restrict__ ctab,
+                                      const int64_t* __restrict__ actions, const uint8_t* __restrict__ mask,
+                                      int64_t* __restrict__ objectgoal, float* __restrict__ gps, float* __restrict__ compass,
+                                      float* __restrict__ reward, uint8_t* __restrict__ not_done, float* __restrict__ sums, uint32_t seed,
+                                      uint32_t env_offset, int N, int K, int nh, int max_steps, int M, int C, int advance) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N || (mask && !mask[n])) return;
+    Nav2DObjState& o = states[n];
+    Nav2DState& s = o.base;
+    const uint32_t env = env_offset + (uint32_t)n;
+    if (!advance) {
+        s.episode = 0;
+        s.ended = 0;
+        s.last[0] = s.last[1] = s.last[2] = s.last[3] = 0.0f;
+        begin_episode<false>(s, seed, env, K, nh);
+        place_objects(o, seed, env, K, M, C);
+    } else {
+        const int64_t a = actions[n];  // 4, 5 (LOOK_UP, LOOK_DOWN) and anything outside 0..5 move nothing
+        if (a == 1) {
+            const float nx = s.px + FORWARD * dirs[2 * s.heading], ny = s.py + FORWARD * dirs[2 * s.heading + 1];
+            if (is_free_obj(nx, ny, o, K, M)) { s.px = nx; s.py = ny; s.path = s.path + FORWARD; }
+            else s.collisions += 1;
+        } else if (a == 2) {
+            s.heading = (s.heading + 1) % nh;
+        } else if (a == 3) {
+            s.heading = (s.heading + nh - 1) % nh;
+        }
+        nearest_target(o, M);  // (gx, gy) of this step, which end_step measures the distance to
+        end_step<false>(s, a == 0, OBJ_SUCCESS, reward, not_done, sums, seed, env, n, N, K, nh, max_steps);
+        if (s.ended) place_objects(o, seed, env, K, M, C);
+    }
+    if (objectgoal) objectgoal[n] = (int64_t)o.target;
+    if (gps) {
+        const float c = dirs[2 * o.h0], sn = dirs[2 * o.h0 + 1];
+        const float dx = s.px - o.sx, dy = s.py - o.sy;
+        gps[2 * n + 0] = dx * c + dy * sn;
+        gps[2 * n + 1] = c * dy - sn * dx;
+    }
+    if (compass) compass[n] = ctab[(s.heading - o.h0 + nh) % nh];
 }
 
 // ---- rendering ---------------------------------------------------------------------------------------------------------------
@@ -223,10 +363,55 @@ __device__ inline uint32_t shade(uint32_t rgb, float depth01) {
 constexpr uint32_t pack_rgb(uint32_t r, uint32_t g, uint32_t b) { return r | (g << 8) | (b << 16); }
 
 struct alignas(4) U32x3 { uint32_t a, b, c; };
-struct alignas(16) RowRec { float z, depth; uint32_t color, pad; };  // floor / ceiling of one row: z, its depth value, its shaded colour
+// floor / ceiling of one row: z, its depth value, its shaded colour, its semantic id (Nav2DObj-v0; 0 otherwise)
+struct alignas(16) RowRec { float z, depth; uint32_t color, sem; };
 
 constexpr int RENDER_THREADS = 256;
 constexpr int RENDER_MAX_ROWS = 1024;  // rows of one tile
+constexpr uint32_t SEM_FLOOR = 0u, SEM_CEILING = 1u, SEM_WALL = 2u, SEM_RECT = 3u, SEM_OBJECT = 4u;
+
+// The colour of an object of one category, the same in every episode.
+__device__ inline uint32_t category_color(int32_t cat) {
+    const uint32_t c = mix32(0x0B7EC700u + (uint32_t)cat);
+    return (128u + (c & 127u)) | ((128u + ((c >> 8) & 127u)) << 8) | ((128u + ((c >> 16) & 127u)) << 16);
+}
+
+__host__ __device__ inline int col_slot(int u) { return u + (u >> 5); }
+__host__ __device__ inline int col_pitch(int W) { return (col_slot(W) + 4) & ~3; }  // a multiple of 4: `row` stays 16-byte aligned
+
+// One plane of 4-byte pixels (depth, semantic) of the tile [s_px, e_px): pixel (v, u) is wall[col_slot(u)] where the column's hit is
+// no farther than the row's floor / ceiling, else flat(row).  Groups of four pixels are one aligned 16-byte store; the up to three
+// pixels before the first and after the last group are written one by one.
+template <class T, class Flat>
+__device__ inline void sweep_dwords(T* __restrict__ img, int s_px, int e_px, int W, int v0, const float* __restrict__ c_z,
+                                    const T* __restrict__ wall, const RowRec* __restrict__ row, Flat flat) {
+    struct alignas(16) T4 { T x, y, z, w; };
+    // first pixel i >= s_px whose address is 16-byte aligned
+    const int mis = (int)(((uintptr_t)(img + s_px) >> 2) & 3);
+    const int first = min(e_px, s_px + ((4 - mis) & 3));
+    const int groups = (e_px - first) >> 2, last = first + (groups << 2);
+    for (int g = threadIdx.x; g < groups; g += RENDER_THREADS) {
+        const int i = first + (g << 2);
+        int v = i / W, u = i - v * W;
+        T o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int q = col_slot(u);
+            const RowRec rv = row[v - v0];
+            o[j] = c_z[q] <= rv.z ? wall[q] : flat(rv);
+            if (++u == W) { u = 0; ++v; }
+        }
+        *reinterpret_cast<T4*>(img + i) = T4{o[0], o[1], o[2], o[3]};
+    }
+    const int edge = (first - s_px) + (e_px - last);
+    if ((int)threadIdx.x < edge) {
+        const int i = (int)threadIdx.x < first - s_px ? s_px + (int)threadIdx.x : last + ((int)threadIdx.x - (first - s_px));
+        const int v = i / W, u = i - v * W;
+        const int q = col_slot(u);
+        const RowRec rv = row[v - v0];
+        img[i] = c_z[q] <= rv.z ? wall[q] : flat(rv);
+    }
+}
 
 // grid (row tiles, N), RENDER_THREADS threads.  Phase 1: the W column hits and the tile's row constants, once per workgroup, into
 // LDS.  Phase 2: the tile's pixels are one contiguous range of the image; it is swept in groups of four pixels placed so that the
@@ -236,12 +421,15 @@ constexpr int RENDER_MAX_ROWS = 1024;  // rows of one tile
 // depth, its shaded colour, as a RowRec).  Colours are packed integers and stay uint32_t from LDS to the store.  A lane's four pixels
 // are four consecutive columns, so the lanes of a wave read the column arrays at a stride of four dwords; column u sits at
 // u + (u >> 5), which spreads a half wave's 32 reads over the 32 banks.
-__host__ __device__ inline int col_slot(int u) { return u + (u >> 5); }
-__host__ __device__ inline int col_pitch(int W) { return (col_slot(W) + 4) & ~3; }  // a multiple of 4: `row` stays 16-byte aligned
+// OBJ (Nav2DObj-v0): `states` are Nav2DObjState records; the M cylinders are geometry that depth, rgb and semantic see alike and
+// there is no goal marker; a fifth per-column array holds the semantic id of the column's hit and a third sweep writes `semantic`
+// like depth.  LDS is (4 or 5) * col_pitch(W) dwords + 16 bytes per tile row: at most 20 * 2116 + 16 * 4 bytes (W = 2048) or
+// 16 * 1024 + 20 * 4 (W = 1), under 64 KiB for every accepted width.
+template <bool OBJ>
 __global__ void __launch_bounds__(RENDER_THREADS)
-nav2d_render_kernel(const Nav2DState* __restrict__ states, const float* __restrict__ ray, const float* __restrict__ col_cos,
+nav2d_render_kernel(const void* __restrict__ states, const float* __restrict__ ray, const float* __restrict__ col_cos,
                     const float* __restrict__ tanv, const uint8_t* __restrict__ mask, uint8_t* __restrict__ rgb,
-                    float* __restrict__ depth, int H, int W, int K, int rows_per_tile) {
+                    float* __restrict__ depth, int32_t* __restrict__ semantic, int H, int W, int K, int M, int rows_per_tile) {
     extern __shared__ uint4 lds[];
     const int n = blockIdx.y;
     if (mask && !mask[n]) return;
@@ -250,8 +438,10 @@ nav2d_render_kernel(const Nav2DState* __restrict__ states, const float* __restri
     float* c_dw = c_zd + P;
     float* c_zr = c_dw + P;
     uint32_t* c_cw = reinterpret_cast<uint32_t*>(c_zr + P);
-    RowRec* row = reinterpret_cast<RowRec*>(lds + P);
-    const Nav2DState& s = states[n];
+    int32_t* c_sem = reinterpret_cast<int32_t*>(c_cw + P);  // OBJ only
+    RowRec* row = reinterpret_cast<RowRec*>(lds + P) + (OBJ ? P / 4 : 0);
+    const Nav2DObjState* os = OBJ ? static_cast<const Nav2DObjState*>(states) + n : nullptr;
+    const Nav2DState& s = OBJ ? os->base : static_cast<const Nav2DState*>(states)[n];
     const int v0 = blockIdx.x * rows_per_tile, v1 = min(H, v0 + rows_per_tile);
     const float px = s.px, py = s.py;
     const float* rayh = ray + (size_t)s.heading * W * 2;
@@ -269,17 +459,33 @@ nav2d_render_kernel(const Nav2DState* __restrict__ states, const float* __restri
             const float tn = fmaxf(axn, ayn), tm = fminf(axx, ayx);
             if (tn <= tm && tn > 0.0f && tn < t) { t = tn; hit = 4 + k; }
         }
+        if constexpr (OBJ) {
+            // the cylinders: the goal marker's ray-circle test (nearest intersection, ray direction taken as unit length)
+            for (int j = 0; j < M; ++j) {
+                const float ox = px - os->obj[j][0], oy = py - os->obj[j][1];
+                const float b = ox * dx + oy * dy;
+                const float c = (ox * ox + oy * oy) - OBJ_R * OBJ_R;
+                const float disc = b * b - c;
+                const float to = -b - sqrt_rn(fmaxf(disc, 0.0f));
+                if (disc >= 0.0f && to > 0.0f && to < t) { t = to; hit = 4 + MAX_K + j; }
+            }
+        }
         const float cf = col_cos[u];
         const float z_wall = t * cf;
-        const float ox = px - s.gx, oy = py - s.gy;
-        const float b = ox * dx + oy * dy;
-        const float c = (ox * ox + oy * oy) - 0.2f * 0.2f;
-        const float disc = b * b - c;
-        const float tmk = -b - sqrt_rn(fmaxf(disc, 0.0f));
-        const bool marker = disc >= 0.0f && tmk > 0.0f && tmk < t;
-        const float z_rgb = marker ? tmk * cf : z_wall;
+        float z_rgb = z_wall;
+        bool marker = false;
+        if constexpr (!OBJ) {
+            const float ox = px - s.gx, oy = py - s.gy;
+            const float b = ox * dx + oy * dy;
+            const float c = (ox * ox + oy * oy) - 0.2f * 0.2f;
+            const float disc = b * b - c;
+            const float tmk = -b - sqrt_rn(fmaxf(disc, 0.0f));
+            marker = disc >= 0.0f && tmk > 0.0f && tmk < t;
+            z_rgb = marker ? tmk * cf : z_wall;
+        }
         uint32_t base;
         if (marker) base = pack_rgb(255, 32, 32);
+        else if (OBJ && hit >= 4 + MAX_K) base = category_color(os->cat[hit - (4 + MAX_K)]);
         else if (hit >= 4) base = s.color[hit - 4];
         else base = hit == 0 ? pack_rgb(200, 180, 150) : hit == 1 ? pack_rgb(150, 200, 180) : hit == 2 ? pack_rgb(180, 150, 200)
                                                                                                         : pack_rgb(200, 200, 150);
@@ -289,45 +495,21 @@ nav2d_render_kernel(const Nav2DState* __restrict__ states, const float* __restri
         c_dw[q] = d_wall;
         c_zr[q] = z_rgb;
         c_cw[q] = shade(base, d_rgbw);
+        if constexpr (OBJ)
+            c_sem[q] = hit >= 4 + MAX_K ? (int32_t)SEM_OBJECT + os->cat[hit - (4 + MAX_K)] : (int32_t)(hit >= 4 ? SEM_RECT : SEM_WALL);
     }
     for (int r = threadIdx.x; r < v1 - v0; r += RENDER_THREADS) {
         const float tv = tanv[v0 + r];
         const float zf = __fdiv_rn(1.25f, fabsf(tv));
         const float d_flat = fminf(__fdiv_rn(zf, 10.0f), 1.0f);
-        row[r] = RowRec{zf, d_flat, shade(tv > 0.0f ? pack_rgb(230, 230, 240) : pack_rgb(110, 100, 90), d_flat), 0u};
+        row[r] = RowRec{zf, d_flat, shade(tv > 0.0f ? pack_rgb(230, 230, 240) : pack_rgb(110, 100, 90), d_flat),
+                        OBJ ? (tv > 0.0f ? SEM_CEILING : SEM_FLOOR) : 0u};
     }
     __syncthreads();
 
     const long long img = (long long)n * H * W;   // first pixel of this env's image, in pixels from the tensor base
     const int s_px = v0 * W, e_px = v1 * W;       // this tile's pixel range within the image
-    if (depth) {
-        float* dimg = depth + img;
-        // first pixel i >= s_px whose address is 16-byte aligned
-        const int mis = (int)(((uintptr_t)(dimg + s_px) >> 2) & 3);
-        const int first = min(e_px, s_px + ((4 - mis) & 3));
-        const int groups = (e_px - first) >> 2, last = first + (groups << 2);
-        for (int g = threadIdx.x; g < groups; g += RENDER_THREADS) {
-            const int i = first + (g << 2);
-            int v = i / W, u = i - v * W;
-            float o[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int q = col_slot(u);
-                const RowRec rv = row[v - v0];
-                o[j] = c_zd[q] <= rv.z ? c_dw[q] : rv.depth;
-                if (++u == W) { u = 0; ++v; }
-            }
-            *reinterpret_cast<float4*>(dimg + i) = make_float4(o[0], o[1], o[2], o[3]);
-        }
-        const int edge = (first - s_px) + (e_px - last);
-        if ((int)threadIdx.x < edge) {
-            const int i = (int)threadIdx.x < first - s_px ? s_px + (int)threadIdx.x : last + ((int)threadIdx.x - (first - s_px));
-            const int v = i / W, u = i - v * W;
-            const int q = col_slot(u);
-            const RowRec rv = row[v - v0];
-            dimg[i] = c_zd[q] <= rv.z ? c_dw[q] : rv.depth;
-        }
-    }
+    if (depth) sweep_dwords(depth + img, s_px, e_px, W, v0, c_zd, c_dw, row, [](const RowRec& rv) { return rv.depth; });
     if (rgb) {
         uint8_t* cimg = rgb + img * 3;
         // first pixel i >= s_px whose byte address is dword aligned: (base + 3 i) % 4 == 0  <=>  i % 4 == base % 4
@@ -363,6 +545,9 @@ nav2d_render_kernel(const Nav2DState* __restrict__ states, const float* __restri
             cimg[(size_t)i * 3 + 2] = (uint8_t)((p >> 16) & 255u);
         }
     }
+    if constexpr (OBJ)
+        if (semantic)
+            sweep_dwords(semantic + img, s_px, e_px, W, v0, c_zd, c_sem, row, [](const RowRec& rv) { return (int32_t)rv.sem; });
 }
 
 }  // namespace nav2d
@@ -371,22 +556,26 @@ using namespace nav2d;
 
 extern "C" int hab_nav2d_state_bytes(void) { return (int)sizeof(Nav2DState); }
 
-// The argument checks both step entries share.
+extern "C" int hab_nav2d_obj_state_bytes(void) { return (int)sizeof(Nav2DObjState); }
+
+// The argument checks the step entries share; `image` is whether any image destination is given.
 static int check_step_args(const void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
-                           const void* actions, const uint8_t* rgb, const float* depth, const float* reward, const uint8_t* not_done,
+                           const void* actions, bool image, const float* depth, const float* reward, const uint8_t* not_done,
                            int N, int H, int W, int num_obstacles, int num_headings, int max_episode_steps, int advance) {
     if (!state || !dirs || N <= 0 || num_headings <= 0 || max_episode_steps <= 0) return HAB_ERR_ARG;
     if (num_obstacles < 0 || num_obstacles > MAX_K) return HAB_ERR_ARG;
     if (advance && (!actions || !reward || !not_done)) return HAB_ERR_ARG;
-    if ((rgb || depth) && (!ray || !col_cos || !tanv || H <= 0 || W <= 0)) return HAB_ERR_ARG;
-    if ((rgb || depth) && (W > HAB_NAV2D_MAX_WIDTH || (long long)H * W > (1ll << 24))) return HAB_ERR_UNSUPPORTED;
-    if ((rgb || depth) && N > 65535) return HAB_ERR_UNSUPPORTED;  // the render's grid.y is the env
+    if (image && (!ray || !col_cos || !tanv || H <= 0 || W <= 0)) return HAB_ERR_ARG;
+    if (image && (W > HAB_NAV2D_MAX_WIDTH || (long long)H * W > (1ll << 24))) return HAB_ERR_UNSUPPORTED;
+    if (image && N > 65535) return HAB_ERR_UNSUPPORTED;  // the render's grid.y is the env
     if (depth && ((uintptr_t)depth & 3)) return HAB_ERR_ARG;
     return HAB_OK;
 }
 
+// `semantic` and `num_objects` are used by the Nav2DObj-v0 instantiation alone.
+template <bool OBJ>
 static int launch_render(const void* state, const float* ray, const float* col_cos, const float* tanv, const uint8_t* mask, uint8_t* rgb,
-                         float* depth, int N, int H, int W, int num_obstacles, hipStream_t stream) {
+                         float* depth, int32_t* semantic, int N, int H, int W, int num_obstacles, int num_objects, hipStream_t stream) {
     // a tile is at least ~16 KiB of stores per workgroup, so that the W column hits are a small part of its work
     // and at most RENDER_MAX_ROWS, which keeps the dynamic LDS below 64 KiB for every accepted W
     int rows = cdiv(4096, W);
@@ -394,9 +583,9 @@ static int launch_render(const void* state, const float* ray, const float* col_c
     if (rows > RENDER_MAX_ROWS) rows = RENDER_MAX_ROWS;
     if (rows > H) rows = H;
     dim3 grid(cdiv(H, rows), N);
-    const size_t lds = (size_t)(col_pitch(W) + rows) * sizeof(uint4);
-    nav2d_render_kernel<<<grid, RENDER_THREADS, lds, stream>>>((const Nav2DState*)state, ray, col_cos, tanv, mask, rgb, depth, H, W,
-                                                                num_obstacles, rows);
+    const size_t lds = (size_t)(col_pitch(W) + rows) * sizeof(uint4) + (OBJ ? (size_t)col_pitch(W) * sizeof(int32_t) : 0);
+    nav2d_render_kernel<OBJ><<<grid, RENDER_THREADS, lds, stream>>>(state, ray, col_cos, tanv, mask, rgb, depth, semantic, H, W,
+                                                                     num_obstacles, num_objects, rows);
     HAB_LAUNCH_CHECK();
     return HAB_OK;
 }
@@ -405,13 +594,13 @@ extern "C" int hab_nav2d_step(void* state, const float* dirs, const float* ray, 
                               const int64_t* actions, const uint8_t* mask, uint8_t* rgb, float* depth, float* goal, float* reward,
                               uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
                               int num_obstacles, int num_headings, int max_episode_steps, int advance, hipStream_t stream) {
-    const int rc = check_step_args(state, dirs, ray, col_cos, tanv, actions, rgb, depth, reward, not_done, N, H, W, num_obstacles,
+    const int rc = check_step_args(state, dirs, ray, col_cos, tanv, actions, rgb || depth, depth, reward, not_done, N, H, W, num_obstacles,
                                    num_headings, max_episode_steps, advance);
     if (rc != HAB_OK) return rc;
     nav2d_step_kernel<<<cdiv(N, 64), 64, 0, stream>>>((Nav2DState*)state, dirs, actions, mask, goal, reward, not_done, measure_sums,
                                                       seed, env_offset, N, num_obstacles, num_headings, max_episode_steps, advance);
     HAB_LAUNCH_CHECK();
-    if (rgb || depth) return launch_render(state, ray, col_cos, tanv, mask, rgb, depth, N, H, W, num_obstacles, stream);
+    if (rgb || depth) return launch_render<false>(state, ray, col_cos, tanv, mask, rgb, depth, nullptr, N, H, W, num_obstacles, 0, stream);
     return HAB_OK;
 }
 
@@ -420,7 +609,7 @@ extern "C" int hab_nav2d_vel_step(void* state, const float* dirs, const float* r
                                   uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
                                   int num_obstacles, int num_headings, int max_episode_steps, int max_turn_steps, int stop_turn_steps,
                                   float min_abs_lin_speed, int allow_sliding, int advance, hipStream_t stream) {
-    const int rc = check_step_args(state, dirs, ray, col_cos, tanv, actions, rgb, depth, reward, not_done, N, H, W, num_obstacles,
+    const int rc = check_step_args(state, dirs, ray, col_cos, tanv, actions, rgb || depth, depth, reward, not_done, N, H, W, num_obstacles,
                                    num_headings, max_episode_steps, advance);
     if (rc != HAB_OK) return rc;
     if ((uintptr_t)actions & 7) return HAB_ERR_ARG;  // a row is read as one float2
@@ -431,6 +620,29 @@ extern "C" int hab_nav2d_vel_step(void* state, const float* dirs, const float* r
                                                           max_episode_steps, max_turn_steps, stop_turn_steps, min_abs_lin_speed,
                                                           allow_sliding, advance);
     HAB_LAUNCH_CHECK();
-    if (rgb || depth) return launch_render(state, ray, col_cos, tanv, mask, rgb, depth, N, H, W, num_obstacles, stream);
+    if (rgb || depth) return launch_render<false>(state, ray, col_cos, tanv, mask, rgb, depth, nullptr, N, H, W, num_obstacles, 0, stream);
+    return HAB_OK;
+}
+
+extern "C" int hab_nav2d_obj_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                                  const int64_t* actions, const uint8_t* mask, uint8_t* rgb, float* depth, int32_t* semantic,
+                                  int64_t* objectgoal, float* gps, float* compass, const float* compass_table, float* reward,
+                                  uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
+                                  int num_obstacles, int num_headings, int max_episode_steps, int num_objects, int num_categories,
+                                  int num_actions, int advance, hipStream_t stream) {
+    const bool image = rgb || depth || semantic;
+    const int rc = check_step_args(state, dirs, ray, col_cos, tanv, actions, image, depth, reward, not_done, N, H, W, num_obstacles,
+                                   num_headings, max_episode_steps, advance);
+    if (rc != HAB_OK) return rc;
+    if (semantic && ((uintptr_t)semantic & 3)) return HAB_ERR_ARG;
+    if (compass && !compass_table) return HAB_ERR_ARG;
+    if (num_objects < 1 || num_objects > MAX_M || num_categories < 1 || num_categories > HAB_NAV2D_MAX_CATEGORIES) return HAB_ERR_ARG;
+    if (num_actions != 4 && num_actions != 6) return HAB_ERR_ARG;
+    nav2d_obj_step_kernel<<<cdiv(N, 64), 64, 0, stream>>>((Nav2DObjState*)state, dirs, compass_table, actions, mask, objectgoal, gps,
+                                                          compass, reward, not_done, measure_sums, seed, env_offset, N, num_obstacles,
+                                                          num_headings, max_episode_steps, num_objects, num_categories, advance);
+    HAB_LAUNCH_CHECK();
+    if (image)
+        return launch_render<true>(state, ray, col_cos, tanv, mask, rgb, depth, semantic, N, H, W, num_obstacles, num_objects, stream);
     return HAB_OK;
 }

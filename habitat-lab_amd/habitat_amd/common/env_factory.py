@@ -287,6 +287,12 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
 
     consumes_actions = True
     measure_names = NAV2D_MEASURES
+    # what a subclass with another sensor set changes: the observation set SyntheticVectorEnv builds, whether an image is rendered
+    # without rgb and depth, and the size of a state record
+    _sensor_set = "nav2d"
+    _renders_without_rgb_depth = False
+    _state_bytes = "hab_nav2d_state_bytes"
+    num_actions = 4
 
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
                  use_depth: bool = True, num_actions: int = 4, device="cuda", num_obstacles: int = 3, turn_angle: int = 10,
@@ -298,14 +304,14 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
             raise _lib.HabError(f"Nav2D: the action space is Discrete(4) (STOP, MOVE_FORWARD, TURN_LEFT, TURN_RIGHT), got {num_actions}")
         if int(max_episode_steps) <= 0:
             raise _lib.HabError(f"Nav2D: max_episode_steps {max_episode_steps} must be positive")
-        if not (use_rgb or use_depth):
+        if not (use_rgb or use_depth or self._renders_without_rgb_depth):
             height = width = 0
         super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth,
-                         num_actions=num_actions, device=device, task="nav2d")
+                         num_actions=num_actions, device=device, task=self._sensor_set)
         self.num_obstacles, self.turn_angle, self.max_episode_steps = int(num_obstacles), int(turn_angle), int(max_episode_steps)
         dev = self.device
         self._tables = [None if t is None else torch.from_numpy(t).to(dev) for t in nav2d_tables(self.turn_angle, height, width)]
-        words = _lib.lib().hab_nav2d_state_bytes() // 4
+        words = getattr(_lib.lib(), self._state_bytes)() // 4
         self._state = torch.zeros(num_envs, words, dtype=torch.int32, device=dev)
         self.measure_sums = torch.zeros(len(NAV2D_MEASURES), num_envs, device=dev)
         self._actions_host = np.zeros(num_envs, dtype=np.int64)
@@ -346,8 +352,9 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
         if isinstance(action, dict):
             action = action["action"]
         a = np.asarray(action)
-        if a.size != 1 or not (np.issubdtype(a.dtype, np.integer) or float(a.item()).is_integer()) or not 0 <= int(a.item()) <= 3:
-            raise _lib.HabError(f"Nav2D: env {index_env}: action {action!r} outside 0..3")
+        top = self.num_actions - 1
+        if a.size != 1 or not (np.issubdtype(a.dtype, np.integer) or float(a.item()).is_integer()) or not 0 <= int(a.item()) <= top:
+            raise _lib.HabError(f"Nav2D: env {index_env}: action {action!r} outside 0..{top}")
         super().async_step_at(index_env, action)
         self._actions_host[int(index_env)] = int(a.item())
 
@@ -492,12 +499,104 @@ class Nav2DVelVectorEnv(Nav2DVectorEnv):
         self._actions_host[int(index_env)] = a
 
 
+NAV2D_MAX_OBJECTS, NAV2D_MAX_CATEGORIES = 8, NUM_OBJECT_CATEGORIES
+
+
+def nav2d_compass_table(turn_angle: int):
+    """(num_headings,) float32: the compass reading after k left turns, k * turn_angle in (-pi, pi] (k above the half turn counts as
+    k - num_headings), computed in float64 and rounded once."""
+    nh = nav2d_num_headings(turn_angle)
+    k = np.arange(nh, dtype=np.int64)
+    k = np.where(2 * k > nh, k - nh, k)
+    return (k.astype(np.float64) * (2.0 * np.pi / nh)).astype(np.float32)
+
+
+class Nav2DObjVectorEnv(Nav2DVectorEnv):
+    """Nav2DObj-v0: Nav2D-v0's world with objects in it and the ObjectNav sensor set, the source on which a policy can only learn by
+    looking.  There is no goal position and no goal sensor: the agent is told a category (`objectgoal`) and has to STOP within 1 m of
+    the centre of an object of that category, which it can find in `semantic` / `depth` / `rgb` alone.  Arena, rectangles, start,
+    heading, the box free test, streams 16-20 and the 0.25 m forward step are Nav2D-v0's (see Nav2DVectorEnv).
+    tests/nav2d_obj_reference.py restates the task in numpy; `nav2d_obj_step_kernel` and the object form of `nav2d_render_kernel`
+    (csrc/nav2d.hip) match it bit for bit on every output -- no angle function runs on the device.
+
+    Parameters (`habitat.synthetic`): num_objects M in 1..8 (default 3), num_categories C in 1..21 (default 4), besides Nav2D-v0's.
+    Objects.  Upright cylinders of radius 0.3 m from floor to ceiling, placed after the start from the streams 21 (positions, 16
+      candidates (0.1 + 7.8 u, 0.1 + 7.8 u') per object), 22 (categories) and 23 (target).  Object j takes its first candidate that
+      lies in [0.5, 7.5]^2, is not strictly inside a rectangle grown by 0.3 m, is at least 1 m from the start and at least 1 m from
+      every earlier object; failing all 16, the first of 28 fixed points one metre apart on the square through (0.5, 0.5) and
+      (7.5, 7.5) that keeps the two distances (one always does, see the restatement).  Its category is word j of stream 22 modulo C.
+      A position closer than 0.4 m to a centre is not free.
+    Target.  The category of object (word 0 of stream 23 modulo M).  d = the distance to the nearest centre of that category; the
+      nearest instance may change during an episode.
+    Actions.  Discrete(4) or Discrete(6) in habitat's order; LOOK_UP and LOOK_DOWN change nothing and cost a step.
+    Reward, end of an episode and the four measures are Nav2D-v0's with this d; success = STOP and d < 1.0.
+    Sensors.  objectgoal int64 (1,); gps float32 (2,) = (dot, cross) of position - start in the start heading's frame; compass
+      float32 (1,) = (heading - start heading) * turn_angle in (-pi, pi] from a host table; depth and rgb as Nav2D-v0 with the
+      cylinders as geometry (a fixed colour per category) and no goal marker; semantic int32 (H, W, 1): floor 0, ceiling 1, walls 2,
+      rectangles 3, an object 4 + category.  The observation-space ranges are the hashed ObjectNav task's, so the same policy is built.
+      `semantic` is always rendered, also without rgb and depth."""
+
+    _sensor_set = "objectnav"
+    _renders_without_rgb_depth = True
+    _state_bytes = "hab_nav2d_obj_state_bytes"
+
+    def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
+                 use_depth: bool = True, num_actions: int = 6, device="cuda", num_obstacles: int = 3, turn_angle: int = 10,
+                 max_episode_steps: int = 500, num_objects: int = 3, num_categories: int = 4):
+        whole = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        if not whole(num_objects) or not 1 <= num_objects <= NAV2D_MAX_OBJECTS:
+            raise _lib.HabError(f"Nav2DObj: num_objects {num_objects!r} outside 1..{NAV2D_MAX_OBJECTS}")
+        if not whole(num_categories) or not 1 <= num_categories <= NAV2D_MAX_CATEGORIES:
+            raise _lib.HabError(f"Nav2DObj: num_categories {num_categories!r} outside 1..{NAV2D_MAX_CATEGORIES}")
+        if num_actions not in (4, 6):
+            raise _lib.HabError("Nav2DObj: the action space is Discrete(4) (STOP, MOVE_FORWARD, TURN_LEFT, TURN_RIGHT) or Discrete(6) "
+                                f"(with LOOK_UP, LOOK_DOWN), got {num_actions}")
+        if int(height) <= 0 or int(width) <= 0:
+            raise _lib.HabError(f"Nav2DObj: the semantic image is always rendered, so the image size {height} x {width} must be positive")
+        super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
+                         num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps)
+        self.task = "nav2dobj"
+        self.num_objects, self.num_categories, self.num_actions = int(num_objects), int(num_categories), int(num_actions)
+        self.action_spaces = [spaces.Discrete(self.num_actions) for _ in range(num_envs)]
+        self.orig_action_spaces = self.action_spaces
+        self._compass_table = torch.from_numpy(nav2d_compass_table(self.turn_angle)).to(self.device)
+
+    def _launch(self, obs, reward, not_done, actions, mask, advance: int):
+        if actions is not None and (actions.dtype != torch.int64 or actions.numel() != self.num_envs or not actions.is_contiguous()
+                                    or not actions.is_cuda):
+            raise _lib.HabError("Nav2DObj: actions must be a contiguous int64 device tensor of shape (N,) or (N, 1)")
+        dirs, ray, col_cos, tanv = self._tables
+        check(_lib.lib().hab_nav2d_obj_step(ptr(self._state), ptr(dirs), ptr(ray), ptr(col_cos), ptr(tanv), ptr(actions), ptr(mask),
+                                            ptr(obs.get("rgb")), ptr(obs.get("depth")), ptr(obs.get("semantic")),
+                                            ptr(obs.get("objectgoal")), ptr(obs.get("gps")), ptr(obs.get("compass")),
+                                            ptr(self._compass_table), ptr(reward), ptr(not_done), ptr(self.measure_sums), self.seed,
+                                            self.env_offset, self.num_envs, self.H, self.W, self.num_obstacles, self.num_headings,
+                                            self.max_episode_steps, self.num_objects, self.num_categories, self.num_actions, advance,
+                                            stream_ptr()), "hab_nav2d_obj_step")
+
+    def step_into_obs(self, obs, reward, not_done, actions=None, mask=None):
+        """One step of every env (or of the envs whose `mask` byte is set) with `actions` int64 (N,) / (N, 1): the new observations
+        (any of rgb, depth, semantic, objectgoal, gps, compass), rewards (N,) and not-done bytes (N,) go straight into the given
+        device tensors."""
+        if actions is None:
+            raise _lib.HabError("Nav2DObj: step_into_obs needs the actions of the step")
+        self._launch(obs, reward, not_done, actions, mask, 1)
+
+    def reset_into(self, rgb, depth, goal):
+        raise _lib.HabError("Nav2DObj: the task has no pointgoal sensor; use reset_into_obs with the ObjectNav sensor rows")
+
+    def step_into(self, rgb, depth, goal, reward, not_done, actions=None, mask=None):
+        raise _lib.HabError("Nav2DObj: the task has no pointgoal sensor; use step_into_obs with the ObjectNav sensor rows")
+
+
 class SyntheticVectorEnvFactory(VectorEnvFactory):
     """Default `_target_`: N synthetic PointNav envs sized from habitat.simulator.sensors.*; per-rank env ids are
     offset by rank * num_environments exactly like the reference offsets the seed (ppo_trainer.py:208-211).  A
     `habitat.task.type` starting with "nav2d" (any case) selects the Nav2D-v0 task, whose num_obstacles / turn_angle come from
     `habitat.synthetic` and whose episode limit from `habitat.environment.max_episode_steps`; one starting with "nav2dvel" selects
-    Nav2DVel-v0, its velocity-controlled variant (Nav2DVelVectorEnv), with the further `habitat.synthetic` keys named there."""
+    Nav2DVel-v0, its velocity-controlled variant (Nav2DVelVectorEnv), with the further `habitat.synthetic` keys named there; one
+    starting with "nav2dobj" selects Nav2DObj-v0 (Nav2DObjVectorEnv: objects, a target category, the ObjectNav sensor set), which
+    reads num_objects / num_categories too and takes its image size from the rgb, else the depth, else the semantic sensor."""
 
     def __init__(self, use_rgb: bool = True, use_depth: bool = True):
         self.use_rgb, self.use_depth = use_rgb, use_depth
@@ -512,6 +611,17 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
         if task_type.startswith("nav2d"):
             ref = sens["rgb"] if use_rgb else (sens["depth"] if use_depth else dict(height=0, width=0))
             syn = getattr(hab, "synthetic", {})
+            if task_type.startswith("nav2dobj"):
+                if not (use_rgb or use_depth):
+                    if "semantic" not in sens:
+                        raise _lib.HabError("Nav2DObj: no rgb, depth or semantic sensor gives the image size")
+                    ref = sens["semantic"]
+                return Nav2DObjVectorEnv(int(hb.num_environments), int(ref["height"]), int(ref["width"]), seed=int(hab.seed),
+                                         env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, num_actions=len(hab.task.actions),
+                                         device=device, num_obstacles=getattr(syn, "num_obstacles", 3),
+                                         turn_angle=getattr(syn, "turn_angle", 10),
+                                         max_episode_steps=getattr(hab.environment, "max_episode_steps", 500),
+                                         num_objects=getattr(syn, "num_objects", 3), num_categories=getattr(syn, "num_categories", 4))
             if task_type.startswith("nav2dvel"):
                 return Nav2DVelVectorEnv(int(hb.num_environments), int(ref["height"]), int(ref["width"]), seed=int(hab.seed),
                                          env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, num_actions=len(hab.task.actions),

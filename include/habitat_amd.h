@@ -100,6 +100,36 @@ int hab_nav2d_vel_step(void* state /*N,HAB_NAV2D_STATE_BYTES*/, const float* dir
                        float* measure_sums /*4,N*/, uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles,
                        int num_headings, int max_episode_steps, int max_turn_steps, int stop_turn_steps, float min_abs_lin_speed,
                        int allow_sliding, int advance, hipStream_t stream);
+/* Nav2DObj-v0: the same arena, rectangles, start, heading and forward step with num_objects (1..HAB_NAV2D_MAX_OBJECTS) cylinders of
+ * radius 0.3 m, each of one of num_categories (1..HAB_NAV2D_MAX_CATEGORIES) categories; the agent is told a category and has to
+ * STOP within 1 m of the nearest centre of it (definition: habitat_amd/common/env_factory.py, Nav2DObjVectorEnv; bit-identical to
+ * tests/nav2d_obj_reference.py on every output, no angle function runs on the device).  `state` is N records of
+ * HAB_NAV2D_OBJ_STATE_BYTES whose first HAB_NAV2D_STATE_BYTES are a Nav2D-v0 record: the words named above keep their meaning, with
+ * (GX, GY) the centre of the nearest object of the target category.  Every argument of hab_nav2d_step keeps its meaning and its
+ * checks; there is no goal sensor.  actions int64 in 0..num_actions-1, num_actions 4 or 6 (4, 5 = LOOK_UP, LOOK_DOWN, which move
+ * nothing and cost a step).  semantic int32 (N,H,W,1), 4-byte aligned: 0 floor, 1 ceiling, 2 wall, 3 rectangle, 4 + category an
+ * object; objectgoal int64 (N,1): the target category; gps f32 (N,2): the offset from the start in the start heading's frame;
+ * compass f32 (N,1): row (heading - start heading) mod num_headings of compass_table (num_headings) f32, the host-built angles in
+ * (-pi, pi].  Every destination may be NULL (compass_table only together with compass); with any image N <= 65535. */
+#define HAB_NAV2D_OBJ_STATE_BYTES 336
+#define HAB_NAV2D_MAX_OBJECTS 8
+#define HAB_NAV2D_MAX_CATEGORIES 21
+/* further words of a Nav2DObj-v0 record: start position, start heading index, target category, object centres (x, y) x
+ * HAB_NAV2D_MAX_OBJECTS, object categories x HAB_NAV2D_MAX_OBJECTS */
+#define HAB_NAV2D_OBJ_W_START_X 56
+#define HAB_NAV2D_OBJ_W_START_Y 57
+#define HAB_NAV2D_OBJ_W_START_HEADING 58
+#define HAB_NAV2D_OBJ_W_TARGET 59
+#define HAB_NAV2D_OBJ_W_OBJECTS 60
+#define HAB_NAV2D_OBJ_W_CATEGORIES 76
+int hab_nav2d_obj_state_bytes(void);
+int hab_nav2d_obj_step(void* state /*N,HAB_NAV2D_OBJ_STATE_BYTES*/, const float* dirs, const float* ray, const float* col_cos,
+                       const float* tanv, const int64_t* actions /*N*/, const uint8_t* mask /*N*/, uint8_t* rgb /*N,H,W,3*/,
+                       float* depth /*N,H,W,1*/, int32_t* semantic /*N,H,W,1*/, int64_t* objectgoal /*N,1*/, float* gps /*N,2*/,
+                       float* compass /*N,1*/, const float* compass_table /*num_headings*/, float* reward /*N*/,
+                       uint8_t* not_done /*N*/, float* measure_sums /*4,N*/, uint32_t seed, uint32_t env_offset, int N, int H, int W,
+                       int num_obstacles, int num_headings, int max_episode_steps, int num_objects, int num_categories,
+                       int num_actions, int advance, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Observation transformers, fused: ResizeShortestEdge followed by CenterCropper

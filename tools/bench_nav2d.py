@@ -9,7 +9,9 @@ With --vel the pair is instead Nav2DVel-v0 (hab_nav2d_vel_step, turn_angle 1: a 
 shape: the render kernel is shared, so the medians are expected to agree within the spread of the windows.  Its actions are uniform in
 [-0.9, 1] x [-1, 1], which stops about as often as the discrete sequence does.  Three more runs separate the parts: the velocity task
 on 36 headings (the discrete task's ray table size) and both step kernels without images.
-usage: python tools/bench_nav2d.py [--vel] [envs] [size] [windows]"""
+With --obj the runs are Nav2DObj-v0 (hab_nav2d_obj_step, 8 obstacles, 8 objects of 4 categories, six actions) with and without the
+`semantic` plane (11 against 7 bytes per pixel), beside hab_nav2d_step: the same render kernel in its object form.
+usage: python tools/bench_nav2d.py [--vel | --obj] [envs] [size] [windows]"""
 import os
 import statistics
 import sys
@@ -19,7 +21,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "habitat-lab_amd"))
-from habitat_amd.common.env_factory import GOAL_UUID, Nav2DVectorEnv, Nav2DVelVectorEnv, SyntheticVectorEnv  # noqa: E402
+from habitat_amd.common.env_factory import (GOAL_UUID, Nav2DObjVectorEnv, Nav2DVectorEnv, Nav2DVelVectorEnv,  # noqa: E402
+                                            SyntheticVectorEnv)
 
 INNER = 10  # calls per timed window: a single launch of a few microseconds would time the enqueue
 
@@ -35,8 +38,8 @@ def timed(fn):
 
 
 def main():
-    argv = [a for a in sys.argv[1:] if a != "--vel"]
-    vel = "--vel" in sys.argv[1:]
+    argv = [a for a in sys.argv[1:] if a not in ("--vel", "--obj")]
+    vel, objects = "--vel" in sys.argv[1:], "--obj" in sys.argv[1:]
     n = int(argv[0]) if len(argv) > 0 else 64
     size = int(argv[1]) if len(argv) > 1 else 256
     windows = int(argv[2]) if len(argv) > 2 else 30
@@ -74,6 +77,19 @@ def main():
             e.reset_into_obs(obs)
         for e in (nav0, nvel0):
             e.reset_into_obs(goal)
+    if objects:
+        nobj = Nav2DObjVectorEnv(n, size, size, seed=100, num_obstacles=8, turn_angle=10, max_episode_steps=500, num_objects=8,
+                                 num_categories=4, num_actions=6, device=dev)
+        oobs = {"rgb": obs["rgb"], "depth": obs["depth"], "semantic": torch.empty(n, size, size, 1, dtype=torch.int32, device=dev),
+                "objectgoal": torch.empty(n, 1, dtype=torch.int64, device=dev), "gps": torch.empty(n, 2, device=dev),
+                "compass": torch.empty(n, 1, device=dev)}
+        no_sem = {k: v for k, v in oobs.items() if k != "semantic"}
+        oacts = torch.multinomial(torch.tensor([0.02, 0.5, 0.2, 0.2, 0.04, 0.04]), INNER * n, replacement=True,
+                                  generator=g).view(INNER, n).to(dev)
+        runs = {"nav2d step+render": runs["nav2d step+render"],
+                "nav2dobj with semantic": lambda i: nobj.step_into_obs(oobs, rew, nd, actions=oacts[i]),
+                "nav2dobj without": lambda i: nobj.step_into_obs(no_sem, rew, nd, actions=oacts[i])}
+        nobj.reset_into_obs(oobs)
     nav.reset_into_obs(obs)
     syn.reset_into_obs(obs)
     for _ in range(3):
@@ -89,7 +105,11 @@ def main():
     for k, v in times.items():
         med[k] = statistics.median(v)
         print(f"{k:22s} median {med[k]:8.1f} us  range [{min(v):.1f}, {max(v):.1f}] us  {nbytes / med[k] / 1e3:7.1f} GB/s written")
-    if vel:
+    if objects:
+        print("bytes per pixel: 11 with semantic, 7 without (the GB/s column counts 7 for every row)")
+        print(f"ratio nav2dobj with semantic / without: {med['nav2dobj with semantic'] / med['nav2dobj without']:.3f}")
+        print(f"ratio nav2dobj without semantic / nav2d step+render: {med['nav2dobj without'] / med['nav2d step+render']:.3f}")
+    elif vel:
         print(f"ratio nav2dvel step+render / nav2d step+render: {med['nav2dvel step+render'] / med['nav2d step+render']:.3f}")
     else:
         print(f"ratio nav2d step+render / hab_synth_step: {med['nav2d step+render'] / med['hab_synth_step']:.2f}")
