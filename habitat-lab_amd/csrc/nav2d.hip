@@ -4,6 +4,8 @@
 // for the whole file and division / square root are the correctly rounded forms (`__fdiv_rn` = `x / y`, `sqrt_rn` below); angles come from host-built tables.
 // Nav2DVel-v0 (continuous actions) and Nav2DObj-v0 (objects, a target category, the ObjectNav sensor set) share the world, the end of
 // a step and the render; their specifications are tests/nav2d_vel_reference.py and tests/nav2d_obj_reference.py.
+// The geodesic distance mode of the first two tasks (nav2d_geo_build_kernel, the GEO forms of the step kernels) is specified by
+// tests/nav2d_geo_reference.py.
 #include <cstddef>
 #include "hab_common.h"
 #include "../../include/habitat_amd.h"
@@ -51,6 +53,9 @@ static_assert(offsetof(Nav2DState, collisions) == 4 * HAB_NAV2D_W_COLLISIONS && 
               "Nav2DState layout");
 static_assert(offsetof(Nav2DState, ended) == 4 * HAB_NAV2D_W_ENDED && offsetof(Nav2DState, last) == 4 * HAB_NAV2D_W_LAST_MEASURES,
               "Nav2DState layout");
+static_assert(offsetof(Nav2DState, d_prev) == 4 * HAB_NAV2D_W_D_PREV && offsetof(Nav2DState, d_start) == 4 * HAB_NAV2D_W_D_START,
+              "Nav2DState layout");
+static_assert(offsetof(Nav2DState, path) == 4 * HAB_NAV2D_W_PATH && offsetof(Nav2DState, rect) == 4 * HAB_NAV2D_W_RECTS, "Nav2DState layout");
 
 // One env of Nav2DObj-v0: a Nav2D-v0 record (gx, gy = the centre of the nearest object of the target category), then the start pose
 // the gps / compass sensors refer to, the target category and the objects.
@@ -83,6 +88,83 @@ __device__ inline bool is_free(float x, float y, const Nav2DState& s, int K) {
 __device__ inline float dist(float ax, float ay, float bx, float by) {
     const float dx = bx - ax, dy = by - ay;
     return sqrt_rn(dx * dx + dy * dy);
+}
+
+// ---- geodesic distance (distance = "geodesic" of Nav2D-v0 and Nav2DVel-v0; specification: tests/nav2d_geo_reference.py) ------------
+// The field of one env's running episode (HAB_NAV2D_GEO_BYTES): D[4k + j] = the shortest-path length from corner j of obstacle k's
+// inflated box to the goal over the visibility graph of those corners, +inf for a corner that is no node; whether the start reached
+// the goal; the sweeps the build took; the steps of the episode at which the agent saw neither the goal nor a node.
+constexpr int GEO_NODES = 4 * MAX_K;
+constexpr float GEO_E = 0.0009765625f;  // 2^-10: what a visibility box is shrunk by
+struct GeoField {
+    float D[GEO_NODES];
+    int32_t reachable, sweeps, lost_steps, zero[5];
+};
+static_assert(sizeof(GeoField) == HAB_NAV2D_GEO_BYTES, "GeoField layout");
+static_assert(offsetof(GeoField, reachable) == 4 * HAB_NAV2D_GEO_W_REACHABLE && offsetof(GeoField, sweeps) == 4 * HAB_NAV2D_GEO_W_SWEEPS &&
+              offsetof(GeoField, lost_steps) == 4 * HAB_NAV2D_GEO_W_LOST_STEPS, "GeoField layout");
+
+// Corner j of obstacle k's inflated box, in the order (X0, Y0), (X1, Y0), (X0, Y1), (X1, Y1): the expressions of is_free.
+__device__ inline void geo_corner(const Nav2DState& s, int k, int j, float& x, float& y) {
+    x = (j & 1) ? s.rect[k][2] + RADIUS : s.rect[k][0] - RADIUS;
+    y = (j & 2) ? s.rect[k][3] + RADIUS : s.rect[k][1] - RADIUS;
+}
+// Obstacle k's visibility box as centre and half extent per axis.
+struct GeoBox { float cx, ex, cy, ey; };
+__device__ inline GeoBox geo_box(const Nav2DState& s, int k) {
+    const float lx = (s.rect[k][0] - RADIUS) + GEO_E, ly = (s.rect[k][1] - RADIUS) + GEO_E;
+    const float hx = (s.rect[k][2] + RADIUS) - GEO_E, hy = (s.rect[k][3] + RADIUS) - GEO_E;
+    return GeoBox{(lx + hx) * 0.5f, (hx - lx) * 0.5f, (ly + hy) * 0.5f, (hy - ly) * 0.5f};
+}
+// Whether the segment a-b meets the open box: the separating-axis test.
+__device__ inline bool geo_blocked(const GeoBox& b, float ax, float ay, float bx, float by) {
+    const float mx = (ax + bx) * 0.5f - b.cx, sx = (bx - ax) * 0.5f;
+    const float my = (ay + by) * 0.5f - b.cy, sy = (by - ay) * 0.5f;
+    return fabsf(mx) < b.ex + fabsf(sx) && fabsf(my) < b.ey + fabsf(sy) &&
+           fabsf(sx * my - sy * mx) < b.ex * fabsf(sy) + b.ey * fabsf(sx);
+}
+// Whether a-b misses all K boxes; `boxes` is the build kernel's LDS array.
+__device__ inline bool geo_visible(const GeoBox* boxes, int K, float ax, float ay, float bx, float by) {
+    for (int k = 0; k < K; ++k)
+        if (geo_blocked(boxes[k], ax, ay, bx, by)) return false;
+    return true;
+}
+// geo(p) of one env by one thread: the goal if p sees it, and the nodes p sees, each with its field value.  The K inflated boxes and
+// visibility boxes are computed once into registers: the loops over k are unrolled over MAX_K with the uniform k < K as a guard, so
+// every index is static, and a visibility test is straight-line arithmetic over the boxes with no load and no branch in it: the
+// 64 envs of a workgroup are one wave, so a test that reads a box through the state pointer costs a memory latency each time.
+__device__ inline float geo_query(const Nav2DState& s, const GeoField& g, int K) {
+    float X0[MAX_K], Y0[MAX_K], X1[MAX_K], Y1[MAX_K];
+    GeoBox box[MAX_K];
+#pragma unroll
+    for (int k = 0; k < MAX_K; ++k) {
+        if (k < K) {
+            X0[k] = s.rect[k][0] - RADIUS; Y0[k] = s.rect[k][1] - RADIUS; X1[k] = s.rect[k][2] + RADIUS; Y1[k] = s.rect[k][3] + RADIUS;
+            box[k] = geo_box(s, k);
+        }
+    }
+    const float px = s.px, py = s.py;
+    auto sees = [&](float x, float y) {
+        bool blocked = false;
+#pragma unroll
+        for (int k = 0; k < MAX_K; ++k)
+            if (k < K) blocked |= geo_blocked(box[k], px, py, x, y);
+        return !blocked;
+    };
+    float best = sees(s.gx, s.gy) ? dist(px, py, s.gx, s.gy) : INFINITY;
+#pragma unroll
+    for (int k = 0; k < MAX_K; ++k) {
+        if (k < K) {
+#pragma unroll 1
+            for (int j = 0; j < 4; ++j) {
+                const float Di = g.D[4 * k + j];
+                if (!(Di < INFINITY)) continue;
+                const float x = (j & 1) ? X1[k] : X0[k], y = (j & 2) ? Y1[k] : Y0[k];
+                if (sees(x, y)) best = fminf(best, dist(px, py, x, y) + Di);
+            }
+        }
+    }
+    return best;
 }
 
 // A new episode's world.  GOAL (Nav2D-v0, Nav2DVel-v0): rectangles, their colours, the start, the goal, the heading, the distances and
@@ -133,10 +215,18 @@ __device__ inline void first_episode(Nav2DState& s, uint32_t seed, uint32_t env,
 // action's request to end the episode (STOP / both speeds below their minima), `success_dist` the task's success radius; the
 // distance is the one to (gx, gy).  A form that took the next world as a callable compiled to a velocity kernel whose distance was
 // that of the previous position; this form gives the Nav2D-v0 and Nav2DVel-v0 kernels the instructions they had before the object task.
-template <bool GOAL = true>
+// GEO: `geo` is the env's field; in a reachable episode the distance is geo(p), and d_prev where p sees nothing (a lost step).
+template <bool GOAL = true, bool GEO = false>
 __device__ inline void end_step(Nav2DState& s, bool stop, float success_dist, float* __restrict__ reward, uint8_t* __restrict__ not_done,
-                                float* __restrict__ sums, uint32_t seed, uint32_t env, int n, int N, int K, int nh, int max_steps) {
-    const float d = dist(s.px, s.py, s.gx, s.gy);
+                                float* __restrict__ sums, uint32_t seed, uint32_t env, int n, int N, int K, int nh, int max_steps,
+                                GeoField* geo = nullptr) {
+    float d = dist(s.px, s.py, s.gx, s.gy);
+    if constexpr (GEO) {
+        if (geo->reachable) {
+            d = geo_query(s, *geo, K);
+            if (!(d < INFINITY)) { d = s.d_prev; geo->lost_steps += 1; }
+        }
+    }
     const bool success = stop && (d < success_dist);
     reward[n] = (-0.01f + (s.d_prev - d)) + (success ? 2.5f : 0.0f);
     s.d_prev = d;
@@ -166,10 +256,12 @@ __device__ inline void write_goal(const Nav2DState& s, const float* __restrict__
 }
 
 // One thread per env.  advance = 0: episode 0 of every selected env; advance = 1: one step with actions[n].  Then the goal sensor.
-__global__ void nav2d_step_kernel(Nav2DState* __restrict__ states, const float* __restrict__ dirs, const int64_t* __restrict__ actions,
+// GEO: launched with 64 threads a workgroup, and told so: the query keeps the boxes of the world in registers.
+template <bool GEO>
+__global__ void __launch_bounds__(GEO ? 64 : 1024) nav2d_step_kernel(Nav2DState* __restrict__ states, const float* __restrict__ dirs, const int64_t* __restrict__ actions,
                                   const uint8_t* __restrict__ mask, float* __restrict__ goal, float* __restrict__ reward,
                                   uint8_t* __restrict__ not_done, float* __restrict__ sums, uint32_t seed, uint32_t env_offset, int N,
-                                  int K, int nh, int max_steps, int advance) {
+                                  int K, int nh, int max_steps, int advance, GeoField* __restrict__ geo) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N || (mask && !mask[n])) return;
     Nav2DState& s = states[n];  // worked on in place: a private copy indexed by k would live in scratch memory
@@ -187,7 +279,7 @@ __global__ void nav2d_step_kernel(Nav2DState* __restrict__ states, const float* 
         } else if (a == 3) {
             s.heading = (s.heading + nh - 1) % nh;
         }
-        end_step(s, a == 0, 0.2f, reward, not_done, sums, seed, env, n, N, K, nh, max_steps);
+        end_step<true, GEO>(s, a == 0, 0.2f, reward, not_done, sums, seed, env, n, N, K, nh, max_steps, GEO ? geo + n : nullptr);
     }
     if (goal) write_goal(s, dirs, goal, n);
 }
@@ -197,11 +289,12 @@ __global__ void nav2d_step_kernel(Nav2DState* __restrict__ states, const float* 
 // non-finite one acts as 0; the step length is (c_lin + 1) * 0.125, the turn rint(c_ang * max_turn) heading quanta (left positive),
 // and both below their minima is the stop.  A blocked target counts one collision and, with sliding, the agent takes the x or else
 // the y component of the move alone where that is free.  The heading stays an index into `dirs`: no angle is evaluated here.
-__global__ void nav2d_vel_step_kernel(Nav2DState* __restrict__ states, const float* __restrict__ dirs, const float2* __restrict__ actions,
+template <bool GEO>
+__global__ void __launch_bounds__(GEO ? 64 : 1024) nav2d_vel_step_kernel(Nav2DState* __restrict__ states, const float* __restrict__ dirs, const float2* __restrict__ actions,
                                       const uint8_t* __restrict__ mask, float* __restrict__ goal, float* __restrict__ reward,
                                       uint8_t* __restrict__ not_done, float* __restrict__ sums, uint32_t seed, uint32_t env_offset,
                                       int N, int K, int nh, int max_steps, int max_turn, int stop_turn, float min_lin, int sliding,
-                                      int advance) {
+                                      int advance, GeoField* __restrict__ geo) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N || (mask && !mask[n])) return;
     Nav2DState& s = states[n];
@@ -228,9 +321,100 @@ __global__ void nav2d_vel_step_kernel(Nav2DState* __restrict__ states, const flo
                 }
             }
         }
-        end_step(s, stop, 0.2f, reward, not_done, sums, seed, env, n, N, K, nh, max_steps);
+        end_step<true, GEO>(s, stop, 0.2f, reward, not_done, sums, seed, env, n, N, K, nh, max_steps, GEO ? geo + n : nullptr);
     }
     if (goal) write_goal(s, dirs, goal, n);
+}
+
+// The field of one env per 64-thread workgroup (one wavefront).  Selected are the envs whose `mask` byte is set (NULL: all) and, with
+// `only_ended`, whose last step ended an episode; every other workgroup leaves before the first barrier.  LDS: the 32 nodes, the K
+// visibility boxes, the symmetric 32 x 32 weight matrix (4 KiB) and two copies of D.  The 496 node pairs go round the lanes, 8 rounds;
+// the 32 last hops take one lane each.  For the sweeps lane l owns half h = l & 1 of row i = l >> 1, its 16 weights in registers
+// (read as column i of rows 16 h + t: 32 banks, the two halves 2-way); a sweep reads D from one copy, joins the two halves of a row
+// with one lane exchange and writes the other copy, and the wave votes on whether any row changed.  The query of the current
+// position takes one node per lane and a wave-wide minimum, which is exact and so the same as the step kernels' serial one.
+__global__ void __launch_bounds__(64)
+nav2d_geo_build_kernel(char* __restrict__ states, size_t state_stride, GeoField* __restrict__ geo, const uint8_t* __restrict__ mask,
+                       int only_ended, int K) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    if (mask && !mask[n]) return;
+    Nav2DState& s = *reinterpret_cast<Nav2DState*>(states + (size_t)n * state_stride);
+    if (only_ended && !s.ended) return;
+    __shared__ float node_x[GEO_NODES], node_y[GEO_NODES];
+    __shared__ int node_ok[GEO_NODES];
+    __shared__ GeoBox boxes[MAX_K];
+    __shared__ float W[GEO_NODES * GEO_NODES];
+    __shared__ float D[2][GEO_NODES];
+    if (lane < GEO_NODES) {
+        float x = 0.0f, y = 0.0f;
+        bool ok = false;
+        if (lane < 4 * K) {
+            geo_corner(s, lane >> 2, lane & 3, x, y);
+            ok = is_free(x, y, s, K);
+        }
+        node_x[lane] = x; node_y[lane] = y; node_ok[lane] = ok ? 1 : 0;
+        W[lane * GEO_NODES + lane] = INFINITY;
+    } else if (lane - GEO_NODES < K) {
+        boxes[lane - GEO_NODES] = geo_box(s, lane - GEO_NODES);
+    }
+    __syncthreads();
+    // pair p of the 496: rows a and 30 - a hold 32 pairs together (row 15 alone 16)
+    for (int p = lane; p < GEO_NODES * (GEO_NODES - 1) / 2; p += 64) {
+        const int a = p >> 5, c = p & 31;
+        const int i = c < 31 - a ? a : 30 - a;
+        const int j = c < 31 - a ? a + 1 + c : i + 1 + (c - (31 - a));
+        float w = INFINITY;
+        if (node_ok[i] && node_ok[j] && geo_visible(boxes, K, node_x[i], node_y[i], node_x[j], node_y[j]))
+            w = dist(node_x[i], node_y[i], node_x[j], node_y[j]);
+        W[i * GEO_NODES + j] = w;
+        W[j * GEO_NODES + i] = w;
+    }
+    const float gx = s.gx, gy = s.gy;
+    if (lane < GEO_NODES) {
+        float d = INFINITY;
+        if (node_ok[lane] && geo_visible(boxes, K, node_x[lane], node_y[lane], gx, gy)) d = dist(node_x[lane], node_y[lane], gx, gy);
+        D[0][lane] = d;
+    }
+    __syncthreads();
+    const int row = lane >> 1, half = lane & 1;
+    float w[GEO_NODES / 2];
+#pragma unroll
+    for (int t = 0; t < GEO_NODES / 2; ++t) w[t] = W[(half * (GEO_NODES / 2) + t) * GEO_NODES + row];
+    int cur = 0, sweeps = 0;
+    while (sweeps < 4 * K) {  // the loop is uniform over the wave: K is an argument, the exit a vote
+        sweeps += 1;
+        float m = INFINITY;
+#pragma unroll
+        for (int t = 0; t < GEO_NODES / 2; ++t) m = fminf(m, w[t] + D[cur][half * (GEO_NODES / 2) + t]);
+        m = fminf(m, __shfl_xor(m, 1));
+        const float before = D[cur][row];
+        const float after = fminf(before, m);
+        if (half == 0) D[cur ^ 1][row] = after;
+        const bool changed = __ballot(after != before) != 0;
+        __syncthreads();
+        cur ^= 1;
+        if (!changed) break;
+    }
+    // g0 = geo(current position): the goal on lane 32, node l on lane l
+    const float px = s.px, py = s.py;
+    float v = INFINITY;
+    if (lane < GEO_NODES) {
+        const float Di = D[cur][lane];
+        geo[n].D[lane] = Di;
+        if (Di < INFINITY && geo_visible(boxes, K, px, py, node_x[lane], node_y[lane])) v = dist(px, py, node_x[lane], node_y[lane]) + Di;
+    } else if (lane == GEO_NODES) {
+        if (geo_visible(boxes, K, px, py, gx, gy)) v = dist(px, py, gx, gy);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+    if (lane == 0) {
+        const bool reachable = v < INFINITY;
+        geo[n].reachable = reachable ? 1 : 0;
+        geo[n].sweeps = sweeps;
+        geo[n].lost_steps = 0;
+        for (int z = 0; z < 5; ++z) geo[n].zero[z] = 0;
+        if (reachable) s.d_start = s.d_prev = v;
+    }
 }
 
 // ---- Nav2DObj-v0 (Nav2DObjVectorEnv; specification: tests/nav2d_obj_reference.py) -----------------------------------------------------
@@ -597,8 +781,45 @@ extern "C" int hab_nav2d_step(void* state, const float* dirs, const float* ray, 
     const int rc = check_step_args(state, dirs, ray, col_cos, tanv, actions, rgb || depth, depth, reward, not_done, N, H, W, num_obstacles,
                                    num_headings, max_episode_steps, advance);
     if (rc != HAB_OK) return rc;
-    nav2d_step_kernel<<<cdiv(N, 64), 64, 0, stream>>>((Nav2DState*)state, dirs, actions, mask, goal, reward, not_done, measure_sums,
-                                                      seed, env_offset, N, num_obstacles, num_headings, max_episode_steps, advance);
+    nav2d_step_kernel<false><<<cdiv(N, 64), 64, 0, stream>>>((Nav2DState*)state, dirs, actions, mask, goal, reward, not_done, measure_sums,
+                                                             seed, env_offset, N, num_obstacles, num_headings, max_episode_steps,
+                                                             advance, nullptr);
+    HAB_LAUNCH_CHECK();
+    if (rgb || depth) return launch_render<false>(state, ray, col_cos, tanv, mask, rgb, depth, nullptr, N, H, W, num_obstacles, 0, stream);
+    return HAB_OK;
+}
+
+extern "C" int hab_nav2d_geo_bytes(void) { return (int)sizeof(GeoField); }
+
+static int check_geo_args(const void* state, size_t state_stride_bytes, const void* geo, int N, int num_obstacles) {
+    if (!state || !geo || ((uintptr_t)geo & 3) || ((uintptr_t)state & 3) || N <= 0) return HAB_ERR_ARG;
+    if (state_stride_bytes < sizeof(Nav2DState) || (state_stride_bytes & 3)) return HAB_ERR_ARG;
+    if (num_obstacles < 0 || num_obstacles > MAX_K) return HAB_ERR_ARG;
+    return HAB_OK;
+}
+
+extern "C" int hab_nav2d_geo_build(void* state, size_t state_stride_bytes, void* geo, const uint8_t* mask, int only_ended, int N,
+                                   int num_obstacles, hipStream_t stream) {
+    const int rc = check_geo_args(state, state_stride_bytes, geo, N, num_obstacles);
+    if (rc != HAB_OK) return rc;
+    nav2d_geo_build_kernel<<<N, 64, 0, stream>>>((char*)state, state_stride_bytes, (GeoField*)geo, mask, only_ended, num_obstacles);
+    HAB_LAUNCH_CHECK();
+    return HAB_OK;
+}
+
+extern "C" int hab_nav2d_step_geo(void* state, void* geo, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                                  const int64_t* actions, const uint8_t* mask, uint8_t* rgb, float* depth, float* goal, float* reward,
+                                  uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
+                                  int num_obstacles, int num_headings, int max_episode_steps, int advance, hipStream_t stream) {
+    int rc = check_step_args(state, dirs, ray, col_cos, tanv, actions, rgb || depth, depth, reward, not_done, N, H, W, num_obstacles,
+                             num_headings, max_episode_steps, advance);
+    if (rc == HAB_OK) rc = check_geo_args(state, sizeof(Nav2DState), geo, N, num_obstacles);
+    if (rc != HAB_OK) return rc;
+    nav2d_step_kernel<true><<<cdiv(N, 64), 64, 0, stream>>>((Nav2DState*)state, dirs, actions, mask, goal, reward, not_done, measure_sums,
+                                                            seed, env_offset, N, num_obstacles, num_headings, max_episode_steps,
+                                                            advance, (GeoField*)geo);
+    HAB_LAUNCH_CHECK();
+    nav2d_geo_build_kernel<<<N, 64, 0, stream>>>((char*)state, sizeof(Nav2DState), (GeoField*)geo, mask, advance ? 1 : 0, num_obstacles);
     HAB_LAUNCH_CHECK();
     if (rgb || depth) return launch_render<false>(state, ray, col_cos, tanv, mask, rgb, depth, nullptr, N, H, W, num_obstacles, 0, stream);
     return HAB_OK;
@@ -615,10 +836,34 @@ extern "C" int hab_nav2d_vel_step(void* state, const float* dirs, const float* r
     if ((uintptr_t)actions & 7) return HAB_ERR_ARG;  // a row is read as one float2
     if (max_turn_steps < 1 || max_turn_steps > num_headings / 2 || stop_turn_steps < 1 || stop_turn_steps > max_turn_steps)
         return HAB_ERR_ARG;
-    nav2d_vel_step_kernel<<<cdiv(N, 64), 64, 0, stream>>>((Nav2DState*)state, dirs, (const float2*)actions, mask, goal, reward, not_done,
-                                                          measure_sums, seed, env_offset, N, num_obstacles, num_headings,
-                                                          max_episode_steps, max_turn_steps, stop_turn_steps, min_abs_lin_speed,
-                                                          allow_sliding, advance);
+    nav2d_vel_step_kernel<false><<<cdiv(N, 64), 64, 0, stream>>>((Nav2DState*)state, dirs, (const float2*)actions, mask, goal, reward,
+                                                                 not_done, measure_sums, seed, env_offset, N, num_obstacles,
+                                                                 num_headings, max_episode_steps, max_turn_steps, stop_turn_steps,
+                                                                 min_abs_lin_speed, allow_sliding, advance, nullptr);
+    HAB_LAUNCH_CHECK();
+    if (rgb || depth) return launch_render<false>(state, ray, col_cos, tanv, mask, rgb, depth, nullptr, N, H, W, num_obstacles, 0, stream);
+    return HAB_OK;
+}
+
+extern "C" int hab_nav2d_vel_step_geo(void* state, void* geo, const float* dirs, const float* ray, const float* col_cos,
+                                      const float* tanv, const float* actions, const uint8_t* mask, uint8_t* rgb, float* depth,
+                                      float* goal, float* reward, uint8_t* not_done, float* measure_sums, uint32_t seed,
+                                      uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings,
+                                      int max_episode_steps, int max_turn_steps, int stop_turn_steps, float min_abs_lin_speed,
+                                      int allow_sliding, int advance, hipStream_t stream) {
+    int rc = check_step_args(state, dirs, ray, col_cos, tanv, actions, rgb || depth, depth, reward, not_done, N, H, W, num_obstacles,
+                             num_headings, max_episode_steps, advance);
+    if (rc == HAB_OK) rc = check_geo_args(state, sizeof(Nav2DState), geo, N, num_obstacles);
+    if (rc != HAB_OK) return rc;
+    if ((uintptr_t)actions & 7) return HAB_ERR_ARG;  // a row is read as one float2
+    if (max_turn_steps < 1 || max_turn_steps > num_headings / 2 || stop_turn_steps < 1 || stop_turn_steps > max_turn_steps)
+        return HAB_ERR_ARG;
+    nav2d_vel_step_kernel<true><<<cdiv(N, 64), 64, 0, stream>>>((Nav2DState*)state, dirs, (const float2*)actions, mask, goal, reward,
+                                                                not_done, measure_sums, seed, env_offset, N, num_obstacles,
+                                                                num_headings, max_episode_steps, max_turn_steps, stop_turn_steps,
+                                                                min_abs_lin_speed, allow_sliding, advance, (GeoField*)geo);
+    HAB_LAUNCH_CHECK();
+    nav2d_geo_build_kernel<<<N, 64, 0, stream>>>((char*)state, sizeof(Nav2DState), (GeoField*)geo, mask, advance ? 1 : 0, num_obstacles);
     HAB_LAUNCH_CHECK();
     if (rgb || depth) return launch_render<false>(state, ray, col_cos, tanv, mask, rgb, depth, nullptr, N, H, W, num_obstacles, 0, stream);
     return HAB_OK;

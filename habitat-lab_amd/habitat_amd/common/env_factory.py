@@ -220,6 +220,15 @@ NAV2D_MAX_OBSTACLES = 8
 _W_EPISODE, _W_ENDED, _W_LAST = 10, 11, 12
 
 
+NAV2D_DISTANCES = ("euclidean", "geodesic")
+
+
+def nav2d_distance(distance, who: str = "Nav2D") -> str:
+    if not isinstance(distance, str) or distance not in NAV2D_DISTANCES:
+        raise _lib.HabError(f"{who}: distance {distance!r} must be one of {', '.join(map(repr, NAV2D_DISTANCES))}")
+    return distance
+
+
 def nav2d_num_headings(turn_angle) -> int:
     if isinstance(turn_angle, bool) or not isinstance(turn_angle, (int, np.integer)) or turn_angle <= 0 or 360 % int(turn_angle) != 0:
         raise _lib.HabError(f"Nav2D: turn_angle {turn_angle!r} must be a positive whole number of degrees that divides 360")
@@ -266,9 +275,9 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
       collision is counted.  The episode ends on STOP or when its step count reaches habitat.environment.max_episode_steps.
     Reward and measures (habitat's PointNav defaults).  d = float32 Euclidean distance to the goal, sqrt(dx * dx + dy * dy);
       success = STOP and d < 0.2; reward = (-0.01 + (d_prev - d_new)) + 2.5 * success; path_length grows by 0.25 per accepted
-      forward.  At the episode's end spl = success * d_start / max(d_start, path_length) -- the STRAIGHT-LINE SPL: d_start is the
-      Euclidean distance, not a geodesic one, so with obstacles it overstates habitat's -- distance_to_goal = d and collisions = the
-      count.  On done the next episode's world is generated, its first observation is what the step returns and not_done = 0.
+      forward.  At the episode's end spl = success * d_start / max(d_start, path_length) -- in the default distance mode the
+      STRAIGHT-LINE SPL: d_start is the Euclidean distance, so with obstacles it overstates habitat's; see Distance below --
+      distance_to_goal = d and collisions = the count.  On done the next episode's world is generated, its first observation is what the step returns and not_done = 0.
     Sensors.
       * pointgoal_with_gps_compass = (rho, phi): rho = d; phi = atan2f(cross, dot) of the goal offset in the agent frame, left
         positive: dot = dx * c + dy * s, cross = c * dy - s * dx.  phi is the one quantity that is not bitwise (atan2f is not
@@ -280,6 +289,30 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
         red goal marker, a cylinder of radius 0.2 m around the goal from floor to ceiling, drawn in rgb ONLY (depth stays what the
         agent collides with); each colour is scaled by 1 - z / 10 and truncated.
       * Without rgb and depth nothing is rendered and the observation space is the goal sensor alone.
+
+    Distance (`distance`, from `habitat.synthetic.distance_to_goal`).  "euclidean", the default, is all of the above.  "geodesic"
+      changes the d of the reward, the success test, distance_to_goal and the SPL numerator -- nothing else: the world, the goal
+      sensor and the render stay -- to the shortest path round the obstacles, as habitat defines these measures.
+      tests/nav2d_geo_reference.py restates it in numpy; `nav2d_geo_build_kernel` and the geodesic forms of the step kernels match it
+      bit for bit.  Every operation is one float32 rounding in the written order.
+      * Boxes.  Obstacle k has the inflated box X0 = x0 - 0.1, Y0 = y0 - 0.1, X1 = x1 + 0.1, Y1 = y1 + 0.1 (the expressions of the
+        free test) and the visibility box, that box shrunk by E = 2^-10 m: lx = X0 + E, ly = Y0 + E, hx = X1 - E, hy = Y1 - E.
+      * visible(a, b) unless the segment meets the open visibility box of some obstacle, by the separating-axis test
+        cx = (lx + hx) * 0.5, ex = (hx - lx) * 0.5, mx = (ax + bx) * 0.5 - cx, sx = (bx - ax) * 0.5, the same for y; blocked iff
+        |mx| < ex + |sx| and |my| < ey + |sy| and |sx * my - sy * mx| < ex * |sy| + ey * |sx|.  A shortest path touches inflated
+        boxes only at corners and along sides, so it clears every shrunk box by E, about a thousand times the test's rounding
+        error: no valid edge is lost, and the result lies between the exact geodesic of the world shrunk by E and the world's own.
+        The arena walls never block: free space is inside the convex [0.1, 7.9]^2 and no inflated box reaches a wall.
+      * Nodes.  Node 4k + j is corner j of inflated box k in the order (X0, Y0), (X1, Y0), (X0, Y1), (X1, Y1), valid iff free.
+      * Field.  D[i] = +inf for invalid nodes; else the least over node paths i -> ... -> goal of the sum rounded from the goal
+        outwards, fl(w(i, j) + D[j]) with w = the Euclidean d where visible; the last hop is d(node, goal) where visible.  It is
+        the fixed point of Jacobi sweeps D <- min(D, min_j fl(w[i][j] + D[j])), run until one changes nothing, at most 4K.
+      * geo(p) = the least of d(p, goal) if visible and fl(d(p, c_i) + D[i]) over the nodes with finite D[i] that p sees; +inf
+        if there is none.
+      * When an episode begins the field is built and g0 = geo(start).  g0 finite: d_start = d_prev = g0 and every step's d is
+        geo(p); where that is +inf (the agent hopped across a sliver into an enclosed pocket) d = d_prev and the episode's
+        lost-step counter goes up.  g0 infinite (the goal is walled off): the episode keeps the Euclidean d throughout.
+      The field records (`_geo`, (N, 40) int32: D, reachable, sweeps, lost steps) exist in this mode only.
 
     Besides the VectorEnv API this env consumes actions (`consumes_actions`): `step_into_obs(obs, reward, not_done, actions=...)`
     on the device path; `async_step_at(i, a)` records a, and `advance_on_device` steps exactly the pending envs with their recorded
@@ -296,8 +329,9 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
 
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
                  use_depth: bool = True, num_actions: int = 4, device="cuda", num_obstacles: int = 3, turn_angle: int = 10,
-                 max_episode_steps: int = 500):
+                 max_episode_steps: int = 500, distance: str = "euclidean"):
         self.num_headings = nav2d_num_headings(turn_angle)
+        self.distance = nav2d_distance(distance)
         if not 0 <= int(num_obstacles) <= NAV2D_MAX_OBSTACLES:
             raise _lib.HabError(f"Nav2D: num_obstacles {num_obstacles} outside 0..{NAV2D_MAX_OBSTACLES}")
         if num_actions != 4:
@@ -314,6 +348,9 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
         words = getattr(_lib.lib(), self._state_bytes)() // 4
         self._state = torch.zeros(num_envs, words, dtype=torch.int32, device=dev)
         self.measure_sums = torch.zeros(len(NAV2D_MEASURES), num_envs, device=dev)
+        self._geo = None
+        if self.distance == "geodesic":
+            self._geo = torch.zeros(num_envs, _lib.lib().hab_nav2d_geo_bytes() // 4, dtype=torch.int32, device=dev)
         self._actions_host = np.zeros(num_envs, dtype=np.int64)
         self._infos: List[dict] = [{} for _ in range(num_envs)]
         self.number_of_episodes = [1 << 30] * num_envs  # episodes are generated, never repeated
@@ -324,11 +361,13 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
                                     or not actions.is_cuda):
             raise _lib.HabError("Nav2D: actions must be a contiguous int64 device tensor of shape (N,) or (N, 1)")
         dirs, ray, col_cos, tanv = self._tables
-        check(_lib.lib().hab_nav2d_step(ptr(self._state), ptr(dirs), ptr(ray), ptr(col_cos), ptr(tanv), ptr(actions), ptr(mask),
-                                        ptr(obs.get("rgb")), ptr(obs.get("depth")), ptr(obs.get(GOAL_UUID)), ptr(reward), ptr(not_done),
-                                        ptr(self.measure_sums), self.seed, self.env_offset, self.num_envs, self.H, self.W,
-                                        self.num_obstacles, self.num_headings, self.max_episode_steps, advance, stream_ptr()),
-              "hab_nav2d_step")
+        rest = (ptr(dirs), ptr(ray), ptr(col_cos), ptr(tanv), ptr(actions), ptr(mask), ptr(obs.get("rgb")), ptr(obs.get("depth")),
+                ptr(obs.get(GOAL_UUID)), ptr(reward), ptr(not_done), ptr(self.measure_sums), self.seed, self.env_offset, self.num_envs,
+                self.H, self.W, self.num_obstacles, self.num_headings, self.max_episode_steps, advance, stream_ptr())
+        if self._geo is not None:
+            check(_lib.lib().hab_nav2d_step_geo(ptr(self._state), ptr(self._geo), *rest), "hab_nav2d_step_geo")
+        else:
+            check(_lib.lib().hab_nav2d_step(ptr(self._state), *rest), "hab_nav2d_step")
 
     def reset_into_obs(self, obs):
         self._launch(obs, None, None, None, None, 0)
@@ -446,13 +485,16 @@ class Nav2DVelVectorEnv(Nav2DVectorEnv):
          done = stop or steps >= max_episode_steps, the measures and their sums, the next episode's world on done and the goal sensor
          are exactly Nav2D-v0's with `stop` in the place of STOP.
 
+    `distance="geodesic"` is Nav2D-v0's geodesic mode, word for word (see Nav2DVectorEnv, Distance): the d of step 6 becomes the
+    shortest path round the obstacles; tests/nav2d_geo_reference.py restates it for this task too.
+
     `step_into_obs(obs, reward, not_done, actions=...)` takes the (N, 2) float32 row the policy stored; the env clamps, so the stored
     action stays unclipped.  `async_step_at(i, a)` takes a length-2 array (or {"action": array})."""
 
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
                  use_depth: bool = True, num_actions: int = 1, device="cuda", num_obstacles: int = 3, turn_angle: int = 1,
                  max_episode_steps: int = 500, max_turn_angle: int = 10, min_abs_lin_speed: float = 0.025, min_abs_ang_speed: int = 5,
-                 allow_sliding: bool = True):
+                 allow_sliding: bool = True, distance: str = "euclidean"):
         _, self.max_turn_steps, self.stop_turn_steps = nav2d_vel_parameters(turn_angle, max_turn_angle, min_abs_lin_speed,
                                                                             min_abs_ang_speed)
         if not isinstance(allow_sliding, (bool, np.bool_)):
@@ -460,7 +502,8 @@ class Nav2DVelVectorEnv(Nav2DVectorEnv):
         if num_actions != 1:
             raise _lib.HabError(f"Nav2DVel: the task has the one action velocity_control, got {num_actions} actions")
         super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
-                         num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps)
+                         num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps,
+                         distance=nav2d_distance(distance, "Nav2DVel"))
         self.max_turn_angle, self.min_abs_ang_speed = int(max_turn_angle), int(min_abs_ang_speed)
         self.min_abs_lin_speed, self.allow_sliding = float(min_abs_lin_speed), bool(allow_sliding)
         self.action_spaces = [spaces.Box(-1.0, 1.0, (2,), np.float32) for _ in range(num_envs)]
@@ -472,12 +515,14 @@ class Nav2DVelVectorEnv(Nav2DVectorEnv):
                                     or not actions.is_contiguous() or not actions.is_cuda):
             raise _lib.HabError("Nav2DVel: actions must be a contiguous float32 device tensor of shape (N, 2)")
         dirs, ray, col_cos, tanv = self._tables
-        check(_lib.lib().hab_nav2d_vel_step(ptr(self._state), ptr(dirs), ptr(ray), ptr(col_cos), ptr(tanv), ptr(actions), ptr(mask),
-                                            ptr(obs.get("rgb")), ptr(obs.get("depth")), ptr(obs.get(GOAL_UUID)), ptr(reward),
-                                            ptr(not_done), ptr(self.measure_sums), self.seed, self.env_offset, self.num_envs, self.H,
-                                            self.W, self.num_obstacles, self.num_headings, self.max_episode_steps, self.max_turn_steps,
-                                            self.stop_turn_steps, self.min_abs_lin_speed, int(self.allow_sliding), advance,
-                                            stream_ptr()), "hab_nav2d_vel_step")
+        rest = (ptr(dirs), ptr(ray), ptr(col_cos), ptr(tanv), ptr(actions), ptr(mask), ptr(obs.get("rgb")), ptr(obs.get("depth")),
+                ptr(obs.get(GOAL_UUID)), ptr(reward), ptr(not_done), ptr(self.measure_sums), self.seed, self.env_offset, self.num_envs,
+                self.H, self.W, self.num_obstacles, self.num_headings, self.max_episode_steps, self.max_turn_steps,
+                self.stop_turn_steps, self.min_abs_lin_speed, int(self.allow_sliding), advance, stream_ptr())
+        if self._geo is not None:
+            check(_lib.lib().hab_nav2d_vel_step_geo(ptr(self._state), ptr(self._geo), *rest), "hab_nav2d_vel_step_geo")
+        else:
+            check(_lib.lib().hab_nav2d_vel_step(ptr(self._state), *rest), "hab_nav2d_vel_step")
 
     def step_into_obs(self, obs, reward, not_done, actions=None, mask=None):
         """One step of every env (or of the envs whose `mask` byte is set) with `actions` float32 (N, 2), rows (a_lin, a_ang): the new
@@ -542,8 +587,11 @@ class Nav2DObjVectorEnv(Nav2DVectorEnv):
 
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
                  use_depth: bool = True, num_actions: int = 6, device="cuda", num_obstacles: int = 3, turn_angle: int = 10,
-                 max_episode_steps: int = 500, num_objects: int = 3, num_categories: int = 4):
+                 max_episode_steps: int = 500, num_objects: int = 3, num_categories: int = 4, distance: str = "euclidean"):
         whole = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        if nav2d_distance(distance, "Nav2DObj") != "euclidean":
+            raise _lib.HabError("Nav2DObj: distance 'geodesic' is not available for this task: the distance is the one to the nearest "
+                                "object of the target category, which needs a field with several targets")
         if not whole(num_objects) or not 1 <= num_objects <= NAV2D_MAX_OBJECTS:
             raise _lib.HabError(f"Nav2DObj: num_objects {num_objects!r} outside 1..{NAV2D_MAX_OBJECTS}")
         if not whole(num_categories) or not 1 <= num_categories <= NAV2D_MAX_CATEGORIES:
@@ -596,7 +644,9 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
     `habitat.synthetic` and whose episode limit from `habitat.environment.max_episode_steps`; one starting with "nav2dvel" selects
     Nav2DVel-v0, its velocity-controlled variant (Nav2DVelVectorEnv), with the further `habitat.synthetic` keys named there; one
     starting with "nav2dobj" selects Nav2DObj-v0 (Nav2DObjVectorEnv: objects, a target category, the ObjectNav sensor set), which
-    reads num_objects / num_categories too and takes its image size from the rgb, else the depth, else the semantic sensor."""
+    reads num_objects / num_categories too and takes its image size from the rgb, else the depth, else the semantic sensor.
+    `habitat.synthetic.distance_to_goal` ("euclidean", the default, or "geodesic") is the distance mode of the Nav2D tasks; the
+    object task refuses "geodesic"."""
 
     def __init__(self, use_rgb: bool = True, use_depth: bool = True):
         self.use_rgb, self.use_depth = use_rgb, use_depth
@@ -611,6 +661,7 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
         if task_type.startswith("nav2d"):
             ref = sens["rgb"] if use_rgb else (sens["depth"] if use_depth else dict(height=0, width=0))
             syn = getattr(hab, "synthetic", {})
+            distance = getattr(syn, "distance_to_goal", "euclidean")
             if task_type.startswith("nav2dobj"):
                 if not (use_rgb or use_depth):
                     if "semantic" not in sens:
@@ -621,7 +672,8 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
                                          device=device, num_obstacles=getattr(syn, "num_obstacles", 3),
                                          turn_angle=getattr(syn, "turn_angle", 10),
                                          max_episode_steps=getattr(hab.environment, "max_episode_steps", 500),
-                                         num_objects=getattr(syn, "num_objects", 3), num_categories=getattr(syn, "num_categories", 4))
+                                         num_objects=getattr(syn, "num_objects", 3), num_categories=getattr(syn, "num_categories", 4),
+                                         distance=distance)
             if task_type.startswith("nav2dvel"):
                 return Nav2DVelVectorEnv(int(hb.num_environments), int(ref["height"]), int(ref["width"]), seed=int(hab.seed),
                                          env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, num_actions=len(hab.task.actions),
@@ -631,11 +683,11 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
                                          max_turn_angle=getattr(syn, "max_turn_angle", 10),
                                          min_abs_lin_speed=getattr(syn, "min_abs_lin_speed", 0.025),
                                          min_abs_ang_speed=getattr(syn, "min_abs_ang_speed", 5),
-                                         allow_sliding=getattr(syn, "allow_sliding", True))
+                                         allow_sliding=getattr(syn, "allow_sliding", True), distance=distance)
             return Nav2DVectorEnv(int(hb.num_environments), int(ref["height"]), int(ref["width"]), seed=int(hab.seed),
                                   env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, num_actions=len(hab.task.actions),
                                   device=device, num_obstacles=getattr(syn, "num_obstacles", 3), turn_angle=getattr(syn, "turn_angle", 10),
-                                  max_episode_steps=getattr(hab.environment, "max_episode_steps", 500))
+                                  max_episode_steps=getattr(hab.environment, "max_episode_steps", 500), distance=distance)
         ref = sens["rgb"] if use_rgb else sens["depth"]
         task = "objectnav" if str(hab.task.type).lower().startswith("objectnav") else "pointnav"
         return SyntheticVectorEnv(int(hb.num_environments), int(ref.height), int(ref.width), seed=int(hab.seed),

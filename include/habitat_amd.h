@@ -80,6 +80,12 @@ int hab_synth_objectnav_sensors(int32_t* semantic, int64_t* objectgoal, float* c
 #define HAB_NAV2D_W_EPISODE 10
 #define HAB_NAV2D_W_ENDED 11
 #define HAB_NAV2D_W_LAST_MEASURES 12
+/* further words: the distance to the goal after the last step, at the episode's start, the path length so far, and the rectangles
+ * (x0, y0, x1, y1) x HAB_NAV2D_MAX_OBSTACLES */
+#define HAB_NAV2D_W_D_PREV 4
+#define HAB_NAV2D_W_D_START 5
+#define HAB_NAV2D_W_PATH 6
+#define HAB_NAV2D_W_RECTS 16
 int hab_nav2d_state_bytes(void);
 int hab_nav2d_step(void* state /*N,HAB_NAV2D_STATE_BYTES*/, const float* dirs, const float* ray, const float* col_cos,
                    const float* tanv, const int64_t* actions /*N*/, const uint8_t* mask /*N*/, uint8_t* rgb /*N,H,W,3*/,
@@ -100,6 +106,38 @@ int hab_nav2d_vel_step(void* state /*N,HAB_NAV2D_STATE_BYTES*/, const float* dir
                        float* measure_sums /*4,N*/, uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles,
                        int num_headings, int max_episode_steps, int max_turn_steps, int stop_turn_steps, float min_abs_lin_speed,
                        int allow_sliding, int advance, hipStream_t stream);
+/* Geodesic distance to goal for Nav2D-v0 and Nav2DVel-v0 (definition: habitat_amd/common/env_factory.py, Nav2DVectorEnv, distance =
+ * "geodesic"; bit-identical to tests/nav2d_geo_reference.py).  The world, start, goal, heading, goal sensor and render are those of
+ * the entries above; the distance of the reward, the success test, distance_to_goal and SPL is the shortest path round the
+ * rectangles grown by the agent radius, over the visibility graph of their corners.  `geo` is N field records of HAB_NAV2D_GEO_BYTES,
+ * 4-byte aligned, owned by the caller: words 0..31 the distance from corner j of rectangle k (word 4k + j; corners in the order
+ * (x0, y0), (x1, y0), (x0, y1), (x1, y1)) to the goal, +inf where the corner is no node; then the words named below; words 35..39
+ * are zero.  hab_nav2d_geo_build builds the field of every env that `mask` selects (NULL = all) and, with only_ended != 0, whose
+ * ENDED word is set, from the record's rectangles and goal; where the record's position reaches the goal it writes that distance
+ * to D_START and D_PREV and sets REACHABLE, otherwise the episode keeps the straight-line distance.  `state` may be records of any
+ * stride >= HAB_NAV2D_STATE_BYTES (a multiple of 4) that begin with a Nav2D-v0 record.  hab_nav2d_step_geo / hab_nav2d_vel_step_geo
+ * are hab_nav2d_step / hab_nav2d_vel_step with `geo`: the step, then the build for the envs whose episode ended (advance = 0: for
+ * every selected env), then the render.  A step at which the agent sees neither the goal nor a node keeps D_PREV as its distance
+ * and counts in LOST_STEPS.  Refused besides the checks above: geo NULL or not 4-byte aligned. */
+#define HAB_NAV2D_GEO_BYTES 160
+#define HAB_NAV2D_GEO_W_REACHABLE 32
+#define HAB_NAV2D_GEO_W_SWEEPS 33   /* relaxation sweeps of the build, the one that changed nothing included */
+#define HAB_NAV2D_GEO_W_LOST_STEPS 34
+int hab_nav2d_geo_bytes(void);
+int hab_nav2d_geo_build(void* state, size_t state_stride_bytes, void* geo /*N,HAB_NAV2D_GEO_BYTES*/, const uint8_t* mask /*N*/,
+                        int only_ended, int N, int num_obstacles, hipStream_t stream);
+int hab_nav2d_step_geo(void* state /*N,HAB_NAV2D_STATE_BYTES*/, void* geo /*N,HAB_NAV2D_GEO_BYTES*/, const float* dirs, const float* ray,
+                       const float* col_cos, const float* tanv, const int64_t* actions /*N*/, const uint8_t* mask /*N*/,
+                       uint8_t* rgb /*N,H,W,3*/, float* depth /*N,H,W,1*/, float* goal /*N,2*/, float* reward /*N*/,
+                       uint8_t* not_done /*N*/, float* measure_sums /*4,N*/, uint32_t seed, uint32_t env_offset, int N, int H, int W,
+                       int num_obstacles, int num_headings, int max_episode_steps, int advance, hipStream_t stream);
+int hab_nav2d_vel_step_geo(void* state /*N,HAB_NAV2D_STATE_BYTES*/, void* geo /*N,HAB_NAV2D_GEO_BYTES*/, const float* dirs,
+                           const float* ray, const float* col_cos, const float* tanv, const float* actions /*N,2*/,
+                           const uint8_t* mask /*N*/, uint8_t* rgb /*N,H,W,3*/, float* depth /*N,H,W,1*/, float* goal /*N,2*/,
+                           float* reward /*N*/, uint8_t* not_done /*N*/, float* measure_sums /*4,N*/, uint32_t seed,
+                           uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings, int max_episode_steps,
+                           int max_turn_steps, int stop_turn_steps, float min_abs_lin_speed, int allow_sliding, int advance,
+                           hipStream_t stream);
 /* Nav2DObj-v0: the same arena, rectangles, start, heading and forward step with num_objects (1..HAB_NAV2D_MAX_OBJECTS) cylinders of
  * radius 0.3 m, each of one of num_categories (1..HAB_NAV2D_MAX_CATEGORIES) categories; the agent is told a category and has to
  * STOP within 1 m of the nearest centre of it (definition: habitat_amd/common/env_factory.py, Nav2DObjVectorEnv; bit-identical to
