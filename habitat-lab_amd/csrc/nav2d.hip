@@ -202,12 +202,13 @@ __device__ void begin_episode(Nav2DState& s, uint32_t seed, uint32_t env, int K,
     s.collisions = 0;
 }
 
-// Episode 0 of one env (advance = 0 of both step kernels).
+// Episode 0 of one env (advance = 0 of every step kernel; GOAL as in begin_episode).
+template <bool GOAL = true>
 __device__ inline void first_episode(Nav2DState& s, uint32_t seed, uint32_t env, int K, int nh) {
     s.episode = 0;
     s.ended = 0;
     s.last[0] = s.last[1] = s.last[2] = s.last[3] = 0.0f;
-    begin_episode(s, seed, env, K, nh);
+    begin_episode<GOAL>(s, seed, env, K, nh);
 }
 
 // What follows the move of one step, the same for every task: reward, step count, done, and on done the measures, their sums and
@@ -495,10 +496,7 @@ __global__ void nav2d_obj_step_kernel(Nav2DObjState* __restrict__ states, const 
     Nav2DState& s = o.base;
     const uint32_t env = env_offset + (uint32_t)n;
     if (!advance) {
-        s.episode = 0;
-        s.ended = 0;
-        s.last[0] = s.last[1] = s.last[2] = s.last[3] = 0.0f;
-        begin_episode<false>(s, seed, env, K, nh);
+        first_episode<false>(s, seed, env, K, nh);
         place_objects(o, seed, env, K, M, C);
     } else {
         const int64_t a = actions[n];  // 4, 5 (LOOK_UP, LOOK_DOWN) and anything outside 0..5 move nothing
@@ -742,54 +740,24 @@ extern "C" int hab_nav2d_state_bytes(void) { return (int)sizeof(Nav2DState); }
 
 extern "C" int hab_nav2d_obj_state_bytes(void) { return (int)sizeof(Nav2DObjState); }
 
-// The argument checks the step entries share; `image` is whether any image destination is given.
-static int check_step_args(const void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
-                           const void* actions, bool image, const float* depth, const float* reward, const uint8_t* not_done,
-                           int N, int H, int W, int num_obstacles, int num_headings, int max_episode_steps, int advance) {
-    if (!state || !dirs || N <= 0 || num_headings <= 0 || max_episode_steps <= 0) return HAB_ERR_ARG;
-    if (num_obstacles < 0 || num_obstacles > MAX_K) return HAB_ERR_ARG;
-    if (advance && (!actions || !reward || !not_done)) return HAB_ERR_ARG;
-    if (image && (!ray || !col_cos || !tanv || H <= 0 || W <= 0)) return HAB_ERR_ARG;
-    if (image && (W > HAB_NAV2D_MAX_WIDTH || (long long)H * W > (1ll << 24))) return HAB_ERR_UNSUPPORTED;
-    if (image && N > 65535) return HAB_ERR_UNSUPPORTED;  // the render's grid.y is the env
-    if (depth && ((uintptr_t)depth & 3)) return HAB_ERR_ARG;
-    return HAB_OK;
-}
-
-// `semantic` and `num_objects` are used by the Nav2DObj-v0 instantiation alone.
-template <bool OBJ>
-static int launch_render(const void* state, const float* ray, const float* col_cos, const float* tanv, const uint8_t* mask, uint8_t* rgb,
-                         float* depth, int32_t* semantic, int N, int H, int W, int num_obstacles, int num_objects, hipStream_t stream) {
-    // a tile is at least ~16 KiB of stores per workgroup, so that the W column hits are a small part of its work
-    // and at most RENDER_MAX_ROWS, which keeps the dynamic LDS below 64 KiB for every accepted W
-    int rows = cdiv(4096, W);
-    if (rows < 4) rows = 4;
-    if (rows > RENDER_MAX_ROWS) rows = RENDER_MAX_ROWS;
-    if (rows > H) rows = H;
-    dim3 grid(cdiv(H, rows), N);
-    const size_t lds = (size_t)(col_pitch(W) + rows) * sizeof(uint4) + (OBJ ? (size_t)col_pitch(W) * sizeof(int32_t) : 0);
-    nav2d_render_kernel<OBJ><<<grid, RENDER_THREADS, lds, stream>>>(state, ray, col_cos, tanv, mask, rgb, depth, semantic, H, W,
-                                                                     num_obstacles, num_objects, rows);
-    HAB_LAUNCH_CHECK();
-    return HAB_OK;
-}
-
-extern "C" int hab_nav2d_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
-                              const int64_t* actions, const uint8_t* mask, uint8_t* rgb, float* depth, float* goal, float* reward,
-                              uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
-                              int num_obstacles, int num_headings, int max_episode_steps, int advance, hipStream_t stream) {
-    const int rc = check_step_args(state, dirs, ray, col_cos, tanv, actions, rgb || depth, depth, reward, not_done, N, H, W, num_obstacles,
-                                   num_headings, max_episode_steps, advance);
-    if (rc != HAB_OK) return rc;
-    nav2d_step_kernel<false><<<cdiv(N, 64), 64, 0, stream>>>((Nav2DState*)state, dirs, actions, mask, goal, reward, not_done, measure_sums,
-                                                             seed, env_offset, N, num_obstacles, num_headings, max_episode_steps,
-                                                             advance, nullptr);
-    HAB_LAUNCH_CHECK();
-    if (rgb || depth) return launch_render<false>(state, ray, col_cos, tanv, mask, rgb, depth, nullptr, N, H, W, num_obstacles, 0, stream);
-    return HAB_OK;
-}
-
-extern "C" int hab_nav2d_geo_bytes(void) { return (int)sizeof(GeoField); }
+// What every step entry is given, in the order of the C signatures.  NULL where the entry has none: `geo`, the field of a `_geo`
+// entry; `goal`, the sensor row of the point-goal tasks; `semantic`, Nav2DObj-v0's image.
+struct StepArgs {
+    void *state, *geo;
+    const float *dirs, *ray, *col_cos, *tanv;
+    const void* actions;
+    const uint8_t* mask;
+    uint8_t* rgb;
+    float *depth, *goal;
+    int32_t* semantic;
+    float* reward;
+    uint8_t* not_done;
+    float* measure_sums;
+    uint32_t seed, env_offset;
+    int N, H, W, num_obstacles, num_headings, max_episode_steps, advance;
+    hipStream_t stream;
+    bool image() const { return rgb || depth || semantic; }  // whether any image destination is given
+};
 
 static int check_geo_args(const void* state, size_t state_stride_bytes, const void* geo, int N, int num_obstacles) {
     if (!state || !geo || ((uintptr_t)geo & 3) || ((uintptr_t)state & 3) || N <= 0) return HAB_ERR_ARG;
@@ -797,6 +765,79 @@ static int check_geo_args(const void* state, size_t state_stride_bytes, const vo
     if (num_obstacles < 0 || num_obstacles > MAX_K) return HAB_ERR_ARG;
     return HAB_OK;
 }
+
+// The argument checks the step entries share, then, for a `_geo` entry, those of the field.
+static int check_step_args(const StepArgs& a, bool geo_entry) {
+    if (!a.state || !a.dirs || a.N <= 0 || a.num_headings <= 0 || a.max_episode_steps <= 0) return HAB_ERR_ARG;
+    if (a.num_obstacles < 0 || a.num_obstacles > MAX_K) return HAB_ERR_ARG;
+    if (a.advance && (!a.actions || !a.reward || !a.not_done)) return HAB_ERR_ARG;
+    if (a.image() && (!a.ray || !a.col_cos || !a.tanv || a.H <= 0 || a.W <= 0)) return HAB_ERR_ARG;
+    if (a.image() && (a.W > HAB_NAV2D_MAX_WIDTH || (long long)a.H * a.W > (1ll << 24))) return HAB_ERR_UNSUPPORTED;
+    if (a.image() && a.N > 65535) return HAB_ERR_UNSUPPORTED;  // the render's grid.y is the env
+    if (a.depth && ((uintptr_t)a.depth & 3)) return HAB_ERR_ARG;
+    return geo_entry ? check_geo_args(a.state, sizeof(Nav2DState), a.geo, a.N, a.num_obstacles) : HAB_OK;
+}
+
+// The render, where an image destination is given.  `semantic` and `num_objects` are used by the Nav2DObj-v0 instantiation alone.
+template <bool OBJ>
+static int launch_render(const StepArgs& a, int num_objects) {
+    if (!a.image()) return HAB_OK;
+    // a tile is at least ~16 KiB of stores per workgroup, so that the W column hits are a small part of its work
+    // and at most RENDER_MAX_ROWS, which keeps the dynamic LDS below 64 KiB for every accepted W
+    int rows = cdiv(4096, a.W);
+    if (rows < 4) rows = 4;
+    if (rows > RENDER_MAX_ROWS) rows = RENDER_MAX_ROWS;
+    if (rows > a.H) rows = a.H;
+    dim3 grid(cdiv(a.H, rows), a.N);
+    const size_t lds = (size_t)(col_pitch(a.W) + rows) * sizeof(uint4) + (OBJ ? (size_t)col_pitch(a.W) * sizeof(int32_t) : 0);
+    nav2d_render_kernel<OBJ><<<grid, RENDER_THREADS, lds, a.stream>>>(a.state, a.ray, a.col_cos, a.tanv, a.mask, a.rgb, a.depth, a.semantic,
+                                                                       a.H, a.W, a.num_obstacles, num_objects, rows);
+    HAB_LAUNCH_CHECK();
+    return HAB_OK;
+}
+
+// What follows the step kernel of a point-goal task: for a `_geo` entry the fields of the episodes that began (at a reset, of every
+// env the mask selects), then the render.
+template <bool GEO>
+static int finish_goal_step(const StepArgs& a) {
+    if (GEO) {
+        nav2d_geo_build_kernel<<<a.N, 64, 0, a.stream>>>((char*)a.state, sizeof(Nav2DState), (GeoField*)a.geo, a.mask, a.advance ? 1 : 0,
+                                                         a.num_obstacles);
+        HAB_LAUNCH_CHECK();
+    }
+    return launch_render<false>(a, 0);
+}
+
+// Nav2D-v0.  hab_nav2d_step is <false> with geo = NULL, which is what its kernel is given; hab_nav2d_step_geo is <true>.
+template <bool GEO>
+static int step(const StepArgs& a) {
+    const int rc = check_step_args(a, GEO);
+    if (rc != HAB_OK) return rc;
+    nav2d_step_kernel<GEO><<<cdiv(a.N, 64), 64, 0, a.stream>>>((Nav2DState*)a.state, a.dirs, (const int64_t*)a.actions, a.mask, a.goal,
+                                                                a.reward, a.not_done, a.measure_sums, a.seed, a.env_offset, a.N,
+                                                                a.num_obstacles, a.num_headings, a.max_episode_steps, a.advance,
+                                                                GEO ? (GeoField*)a.geo : nullptr);
+    HAB_LAUNCH_CHECK();
+    return finish_goal_step<GEO>(a);
+}
+
+extern "C" int hab_nav2d_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                              const int64_t* actions, const uint8_t* mask, uint8_t* rgb, float* depth, float* goal, float* reward,
+                              uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
+                              int num_obstacles, int num_headings, int max_episode_steps, int advance, hipStream_t stream) {
+    return step<false>({state, nullptr, dirs, ray, col_cos, tanv, actions, mask, rgb, depth, goal, nullptr, reward, not_done, measure_sums,
+                        seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream});
+}
+
+extern "C" int hab_nav2d_step_geo(void* state, void* geo, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                                  const int64_t* actions, const uint8_t* mask, uint8_t* rgb, float* depth, float* goal, float* reward,
+                                  uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
+                                  int num_obstacles, int num_headings, int max_episode_steps, int advance, hipStream_t stream) {
+    return step<true>({state, geo, dirs, ray, col_cos, tanv, actions, mask, rgb, depth, goal, nullptr, reward, not_done, measure_sums,
+                       seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream});
+}
+
+extern "C" int hab_nav2d_geo_bytes(void) { return (int)sizeof(GeoField); }
 
 extern "C" int hab_nav2d_geo_build(void* state, size_t state_stride_bytes, void* geo, const uint8_t* mask, int only_ended, int N,
                                    int num_obstacles, hipStream_t stream) {
@@ -807,22 +848,21 @@ extern "C" int hab_nav2d_geo_build(void* state, size_t state_stride_bytes, void*
     return HAB_OK;
 }
 
-extern "C" int hab_nav2d_step_geo(void* state, void* geo, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
-                                  const int64_t* actions, const uint8_t* mask, uint8_t* rgb, float* depth, float* goal, float* reward,
-                                  uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
-                                  int num_obstacles, int num_headings, int max_episode_steps, int advance, hipStream_t stream) {
-    int rc = check_step_args(state, dirs, ray, col_cos, tanv, actions, rgb || depth, depth, reward, not_done, N, H, W, num_obstacles,
-                             num_headings, max_episode_steps, advance);
-    if (rc == HAB_OK) rc = check_geo_args(state, sizeof(Nav2DState), geo, N, num_obstacles);
+// Nav2DVel-v0, its two entries like Nav2D-v0's.
+template <bool GEO>
+static int vel_step(const StepArgs& a, int max_turn_steps, int stop_turn_steps, float min_abs_lin_speed, int allow_sliding) {
+    const int rc = check_step_args(a, GEO);
     if (rc != HAB_OK) return rc;
-    nav2d_step_kernel<true><<<cdiv(N, 64), 64, 0, stream>>>((Nav2DState*)state, dirs, actions, mask, goal, reward, not_done, measure_sums,
-                                                            seed, env_offset, N, num_obstacles, num_headings, max_episode_steps,
-                                                            advance, (GeoField*)geo);
+    if ((uintptr_t)a.actions & 7) return HAB_ERR_ARG;  // a row is read as one float2
+    if (max_turn_steps < 1 || max_turn_steps > a.num_headings / 2 || stop_turn_steps < 1 || stop_turn_steps > max_turn_steps)
+        return HAB_ERR_ARG;
+    nav2d_vel_step_kernel<GEO><<<cdiv(a.N, 64), 64, 0, a.stream>>>((Nav2DState*)a.state, a.dirs, (const float2*)a.actions, a.mask, a.goal,
+                                                                    a.reward, a.not_done, a.measure_sums, a.seed, a.env_offset, a.N,
+                                                                    a.num_obstacles, a.num_headings, a.max_episode_steps, max_turn_steps,
+                                                                    stop_turn_steps, min_abs_lin_speed, allow_sliding, a.advance,
+                                                                    GEO ? (GeoField*)a.geo : nullptr);
     HAB_LAUNCH_CHECK();
-    nav2d_geo_build_kernel<<<N, 64, 0, stream>>>((char*)state, sizeof(Nav2DState), (GeoField*)geo, mask, advance ? 1 : 0, num_obstacles);
-    HAB_LAUNCH_CHECK();
-    if (rgb || depth) return launch_render<false>(state, ray, col_cos, tanv, mask, rgb, depth, nullptr, N, H, W, num_obstacles, 0, stream);
-    return HAB_OK;
+    return finish_goal_step<GEO>(a);
 }
 
 extern "C" int hab_nav2d_vel_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
@@ -830,19 +870,9 @@ extern "C" int hab_nav2d_vel_step(void* state, const float* dirs, const float* r
                                   uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
                                   int num_obstacles, int num_headings, int max_episode_steps, int max_turn_steps, int stop_turn_steps,
                                   float min_abs_lin_speed, int allow_sliding, int advance, hipStream_t stream) {
-    const int rc = check_step_args(state, dirs, ray, col_cos, tanv, actions, rgb || depth, depth, reward, not_done, N, H, W, num_obstacles,
-                                   num_headings, max_episode_steps, advance);
-    if (rc != HAB_OK) return rc;
-    if ((uintptr_t)actions & 7) return HAB_ERR_ARG;  // a row is read as one float2
-    if (max_turn_steps < 1 || max_turn_steps > num_headings / 2 || stop_turn_steps < 1 || stop_turn_steps > max_turn_steps)
-        return HAB_ERR_ARG;
-    nav2d_vel_step_kernel<false><<<cdiv(N, 64), 64, 0, stream>>>((Nav2DState*)state, dirs, (const float2*)actions, mask, goal, reward,
-                                                                 not_done, measure_sums, seed, env_offset, N, num_obstacles,
-                                                                 num_headings, max_episode_steps, max_turn_steps, stop_turn_steps,
-                                                                 min_abs_lin_speed, allow_sliding, advance, nullptr);
-    HAB_LAUNCH_CHECK();
-    if (rgb || depth) return launch_render<false>(state, ray, col_cos, tanv, mask, rgb, depth, nullptr, N, H, W, num_obstacles, 0, stream);
-    return HAB_OK;
+    return vel_step<false>({state, nullptr, dirs, ray, col_cos, tanv, actions, mask, rgb, depth, goal, nullptr, reward, not_done,
+                            measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream},
+                           max_turn_steps, stop_turn_steps, min_abs_lin_speed, allow_sliding);
 }
 
 extern "C" int hab_nav2d_vel_step_geo(void* state, void* geo, const float* dirs, const float* ray, const float* col_cos,
@@ -851,22 +881,9 @@ extern "C" int hab_nav2d_vel_step_geo(void* state, void* geo, const float* dirs,
                                       uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings,
                                       int max_episode_steps, int max_turn_steps, int stop_turn_steps, float min_abs_lin_speed,
                                       int allow_sliding, int advance, hipStream_t stream) {
-    int rc = check_step_args(state, dirs, ray, col_cos, tanv, actions, rgb || depth, depth, reward, not_done, N, H, W, num_obstacles,
-                             num_headings, max_episode_steps, advance);
-    if (rc == HAB_OK) rc = check_geo_args(state, sizeof(Nav2DState), geo, N, num_obstacles);
-    if (rc != HAB_OK) return rc;
-    if ((uintptr_t)actions & 7) return HAB_ERR_ARG;  // a row is read as one float2
-    if (max_turn_steps < 1 || max_turn_steps > num_headings / 2 || stop_turn_steps < 1 || stop_turn_steps > max_turn_steps)
-        return HAB_ERR_ARG;
-    nav2d_vel_step_kernel<true><<<cdiv(N, 64), 64, 0, stream>>>((Nav2DState*)state, dirs, (const float2*)actions, mask, goal, reward,
-                                                                not_done, measure_sums, seed, env_offset, N, num_obstacles,
-                                                                num_headings, max_episode_steps, max_turn_steps, stop_turn_steps,
-                                                                min_abs_lin_speed, allow_sliding, advance, (GeoField*)geo);
-    HAB_LAUNCH_CHECK();
-    nav2d_geo_build_kernel<<<N, 64, 0, stream>>>((char*)state, sizeof(Nav2DState), (GeoField*)geo, mask, advance ? 1 : 0, num_obstacles);
-    HAB_LAUNCH_CHECK();
-    if (rgb || depth) return launch_render<false>(state, ray, col_cos, tanv, mask, rgb, depth, nullptr, N, H, W, num_obstacles, 0, stream);
-    return HAB_OK;
+    return vel_step<true>({state, geo, dirs, ray, col_cos, tanv, actions, mask, rgb, depth, goal, nullptr, reward, not_done, measure_sums,
+                           seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream},
+                          max_turn_steps, stop_turn_steps, min_abs_lin_speed, allow_sliding);
 }
 
 extern "C" int hab_nav2d_obj_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
@@ -875,9 +892,9 @@ extern "C" int hab_nav2d_obj_step(void* state, const float* dirs, const float* r
                                   uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
                                   int num_obstacles, int num_headings, int max_episode_steps, int num_objects, int num_categories,
                                   int num_actions, int advance, hipStream_t stream) {
-    const bool image = rgb || depth || semantic;
-    const int rc = check_step_args(state, dirs, ray, col_cos, tanv, actions, image, depth, reward, not_done, N, H, W, num_obstacles,
-                                   num_headings, max_episode_steps, advance);
+    const StepArgs a{state, nullptr, dirs, ray, col_cos, tanv, actions, mask, rgb, depth, nullptr, semantic, reward, not_done,
+                     measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream};
+    const int rc = check_step_args(a, false);
     if (rc != HAB_OK) return rc;
     if (semantic && ((uintptr_t)semantic & 3)) return HAB_ERR_ARG;
     if (compass && !compass_table) return HAB_ERR_ARG;
@@ -887,7 +904,5 @@ extern "C" int hab_nav2d_obj_step(void* state, const float* dirs, const float* r
                                                           compass, reward, not_done, measure_sums, seed, env_offset, N, num_obstacles,
                                                           num_headings, max_episode_steps, num_objects, num_categories, advance);
     HAB_LAUNCH_CHECK();
-    if (image)
-        return launch_render<true>(state, ray, col_cos, tanv, mask, rgb, depth, semantic, N, H, W, num_obstacles, num_objects, stream);
-    return HAB_OK;
+    return launch_render<true>(a, num_objects);
 }

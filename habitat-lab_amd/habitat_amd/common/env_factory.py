@@ -229,8 +229,13 @@ def nav2d_distance(distance, who: str = "Nav2D") -> str:
     return distance
 
 
+def whole(v) -> bool:
+    """Whether v is a whole number (a bool is none)."""
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
 def nav2d_num_headings(turn_angle) -> int:
-    if isinstance(turn_angle, bool) or not isinstance(turn_angle, (int, np.integer)) or turn_angle <= 0 or 360 % int(turn_angle) != 0:
+    if not whole(turn_angle) or turn_angle <= 0 or 360 % int(turn_angle) != 0:
         raise _lib.HabError(f"Nav2D: turn_angle {turn_angle!r} must be a positive whole number of degrees that divides 360")
     return 360 // int(turn_angle)
 
@@ -326,6 +331,11 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
     _renders_without_rgb_depth = False
     _state_bytes = "hab_nav2d_state_bytes"
     num_actions = 4
+    # what a subclass with another step changes: the name in the refusals, the library's entries (Euclidean, geodesic), what
+    # `actions` has to be (with _actions_shaped), and the two hooks _sensor_rows and _task_parameters
+    _name = "Nav2D"
+    _entries = ("hab_nav2d_step", "hab_nav2d_step_geo")
+    _action_dtype, _action_text = torch.int64, "int64 device tensor of shape (N,) or (N, 1)"
 
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
                  use_depth: bool = True, num_actions: int = 4, device="cuda", num_obstacles: int = 3, turn_angle: int = 10,
@@ -354,29 +364,41 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
         self._actions_host = np.zeros(num_envs, dtype=np.int64)
         self._infos: List[dict] = [{} for _ in range(num_envs)]
         self.number_of_episodes = [1 << 30] * num_envs  # episodes are generated, never repeated
+        # the step entry and the arguments that no call changes, before and after the ones _launch is given
+        self._entry = self._entries[0] if self._geo is None else self._entries[1]
+        self._step = getattr(_lib.lib(), self._entry)
+        field = () if self._geo is None else (ptr(self._geo),)
+        self._head = (ptr(self._state), *field, *map(ptr, self._tables))
+        self._tail = (ptr(self.measure_sums), self.seed, self.env_offset, self.num_envs, self.H, self.W, self.num_obstacles,
+                      self.num_headings, self.max_episode_steps, *self._task_parameters())
 
     # ---- device fast path ---------------------------------------------------------------------
+    def _actions_shaped(self, actions) -> bool:
+        return actions.numel() == self.num_envs
+
+    def _sensor_rows(self, obs):
+        """The pointers of the entry's sensor destinations, in its order."""
+        return ptr(obs.get("rgb")), ptr(obs.get("depth")), ptr(obs.get(GOAL_UUID))
+
+    def _task_parameters(self):
+        """The entry's arguments between max_episode_steps and advance; read once, when the env is built."""
+        return ()
+
     def _launch(self, obs, reward, not_done, actions, mask, advance: int):
-        if actions is not None and (actions.dtype != torch.int64 or actions.numel() != self.num_envs or not actions.is_contiguous()
-                                    or not actions.is_cuda):
-            raise _lib.HabError("Nav2D: actions must be a contiguous int64 device tensor of shape (N,) or (N, 1)")
-        dirs, ray, col_cos, tanv = self._tables
-        rest = (ptr(dirs), ptr(ray), ptr(col_cos), ptr(tanv), ptr(actions), ptr(mask), ptr(obs.get("rgb")), ptr(obs.get("depth")),
-                ptr(obs.get(GOAL_UUID)), ptr(reward), ptr(not_done), ptr(self.measure_sums), self.seed, self.env_offset, self.num_envs,
-                self.H, self.W, self.num_obstacles, self.num_headings, self.max_episode_steps, advance, stream_ptr())
-        if self._geo is not None:
-            check(_lib.lib().hab_nav2d_step_geo(ptr(self._state), ptr(self._geo), *rest), "hab_nav2d_step_geo")
-        else:
-            check(_lib.lib().hab_nav2d_step(ptr(self._state), *rest), "hab_nav2d_step")
+        if actions is not None and not (actions.dtype == self._action_dtype and self._actions_shaped(actions) and actions.is_contiguous()
+                                        and actions.is_cuda):
+            raise _lib.HabError(f"{self._name}: actions must be a contiguous {self._action_text}")
+        check(self._step(*self._head, ptr(actions), ptr(mask), *self._sensor_rows(obs), ptr(reward), ptr(not_done), *self._tail, advance,
+                         stream_ptr()), self._entry)
 
     def reset_into_obs(self, obs):
         self._launch(obs, None, None, None, None, 0)
 
     def step_into_obs(self, obs, reward, not_done, actions=None, mask=None):
-        """One step of every env (or of the envs whose `mask` byte is set) with `actions` int64 (N,) / (N, 1): the new observations,
-        rewards (N,) and not-done bytes (N,) go straight into the given device tensors."""
+        """One step of every env (or of the envs whose `mask` byte is set) with the task's `actions` (Nav2D-v0: int64 (N,) / (N, 1)):
+        the new observations, rewards (N,) and not-done bytes (N,) go straight into the given device tensors."""
         if actions is None:
-            raise _lib.HabError("Nav2D: step_into_obs needs the actions of the step")
+            raise _lib.HabError(f"{self._name}: step_into_obs needs the actions of the step")
         self._launch(obs, reward, not_done, actions, mask, 1)
 
     def reset_into(self, rgb, depth, goal):
@@ -446,7 +468,6 @@ def nav2d_vel_parameters(turn_angle, max_turn_angle, min_abs_lin_speed, min_abs_
     """Checks the `habitat.synthetic` keys of Nav2DVel-v0 and returns (num_headings, M, S): the largest turn of one step and the
     smallest turn that is not a stop, both in heading quanta."""
     nh = nav2d_num_headings(turn_angle)
-    whole = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
     if not whole(max_turn_angle) or max_turn_angle <= 0 or max_turn_angle % turn_angle != 0 or max_turn_angle > 180:
         raise _lib.HabError(f"Nav2DVel: max_turn_angle {max_turn_angle!r} must be a positive multiple of turn_angle {turn_angle} "
                             "(whole degrees), at most 180")
@@ -488,8 +509,12 @@ class Nav2DVelVectorEnv(Nav2DVectorEnv):
     `distance="geodesic"` is Nav2D-v0's geodesic mode, word for word (see Nav2DVectorEnv, Distance): the d of step 6 becomes the
     shortest path round the obstacles; tests/nav2d_geo_reference.py restates it for this task too.
 
-    `step_into_obs(obs, reward, not_done, actions=...)` takes the (N, 2) float32 row the policy stored; the env clamps, so the stored
-    action stays unclipped.  `async_step_at(i, a)` takes a length-2 array (or {"action": array})."""
+    `step_into_obs(obs, reward, not_done, actions=...)` takes the (N, 2) float32 rows (a_lin, a_ang) the policy stored; the env clamps,
+    so the stored action stays unclipped.  `async_step_at(i, a)` takes a length-2 array (or {"action": array})."""
+
+    _name = "Nav2DVel"
+    _entries = ("hab_nav2d_vel_step", "hab_nav2d_vel_step_geo")
+    _action_dtype, _action_text = torch.float32, "float32 device tensor of shape (N, 2)"
 
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
                  use_depth: bool = True, num_actions: int = 1, device="cuda", num_obstacles: int = 3, turn_angle: int = 1,
@@ -501,35 +526,20 @@ class Nav2DVelVectorEnv(Nav2DVectorEnv):
             raise _lib.HabError(f"Nav2DVel: allow_sliding {allow_sliding!r} must be true or false")
         if num_actions != 1:
             raise _lib.HabError(f"Nav2DVel: the task has the one action velocity_control, got {num_actions} actions")
+        self.max_turn_angle, self.min_abs_ang_speed = int(max_turn_angle), int(min_abs_ang_speed)
+        self.min_abs_lin_speed, self.allow_sliding = float(min_abs_lin_speed), bool(allow_sliding)
         super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
                          num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps,
                          distance=nav2d_distance(distance, "Nav2DVel"))
-        self.max_turn_angle, self.min_abs_ang_speed = int(max_turn_angle), int(min_abs_ang_speed)
-        self.min_abs_lin_speed, self.allow_sliding = float(min_abs_lin_speed), bool(allow_sliding)
         self.action_spaces = [spaces.Box(-1.0, 1.0, (2,), np.float32) for _ in range(num_envs)]
         self.orig_action_spaces = self.action_spaces
         self._actions_host = np.zeros((num_envs, 2), dtype=np.float32)
 
-    def _launch(self, obs, reward, not_done, actions, mask, advance: int):
-        if actions is not None and (actions.dtype != torch.float32 or tuple(actions.shape) != (self.num_envs, 2)
-                                    or not actions.is_contiguous() or not actions.is_cuda):
-            raise _lib.HabError("Nav2DVel: actions must be a contiguous float32 device tensor of shape (N, 2)")
-        dirs, ray, col_cos, tanv = self._tables
-        rest = (ptr(dirs), ptr(ray), ptr(col_cos), ptr(tanv), ptr(actions), ptr(mask), ptr(obs.get("rgb")), ptr(obs.get("depth")),
-                ptr(obs.get(GOAL_UUID)), ptr(reward), ptr(not_done), ptr(self.measure_sums), self.seed, self.env_offset, self.num_envs,
-                self.H, self.W, self.num_obstacles, self.num_headings, self.max_episode_steps, self.max_turn_steps,
-                self.stop_turn_steps, self.min_abs_lin_speed, int(self.allow_sliding), advance, stream_ptr())
-        if self._geo is not None:
-            check(_lib.lib().hab_nav2d_vel_step_geo(ptr(self._state), ptr(self._geo), *rest), "hab_nav2d_vel_step_geo")
-        else:
-            check(_lib.lib().hab_nav2d_vel_step(ptr(self._state), *rest), "hab_nav2d_vel_step")
+    def _actions_shaped(self, actions) -> bool:
+        return tuple(actions.shape) == (self.num_envs, 2)
 
-    def step_into_obs(self, obs, reward, not_done, actions=None, mask=None):
-        """One step of every env (or of the envs whose `mask` byte is set) with `actions` float32 (N, 2), rows (a_lin, a_ang): the new
-        observations, rewards (N,) and not-done bytes (N,) go straight into the given device tensors."""
-        if actions is None:
-            raise _lib.HabError("Nav2DVel: step_into_obs needs the actions of the step")
-        self._launch(obs, reward, not_done, actions, mask, 1)
+    def _task_parameters(self):
+        return self.max_turn_steps, self.stop_turn_steps, self.min_abs_lin_speed, int(self.allow_sliding)
 
     def async_step_at(self, index_env: int, action) -> None:
         if isinstance(action, dict):
@@ -579,8 +589,11 @@ class Nav2DObjVectorEnv(Nav2DVectorEnv):
       float32 (1,) = (heading - start heading) * turn_angle in (-pi, pi] from a host table; depth and rgb as Nav2D-v0 with the
       cylinders as geometry (a fixed colour per category) and no goal marker; semantic int32 (H, W, 1): floor 0, ceiling 1, walls 2,
       rectangles 3, an object 4 + category.  The observation-space ranges are the hashed ObjectNav task's, so the same policy is built.
-      `semantic` is always rendered, also without rgb and depth."""
+      `semantic` is always rendered, also without rgb and depth.  `step_into_obs` writes any of rgb, depth, semantic, objectgoal, gps,
+      compass, whichever rows `obs` holds; `actions` is int64 (N,) / (N, 1) as for Nav2D-v0."""
 
+    _name = "Nav2DObj"
+    _entries = ("hab_nav2d_obj_step",)  # the mode with a field is refused
     _sensor_set = "objectnav"
     _renders_without_rgb_depth = True
     _state_bytes = "hab_nav2d_obj_state_bytes"
@@ -588,7 +601,6 @@ class Nav2DObjVectorEnv(Nav2DVectorEnv):
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
                  use_depth: bool = True, num_actions: int = 6, device="cuda", num_obstacles: int = 3, turn_angle: int = 10,
                  max_episode_steps: int = 500, num_objects: int = 3, num_categories: int = 4, distance: str = "euclidean"):
-        whole = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
         if nav2d_distance(distance, "Nav2DObj") != "euclidean":
             raise _lib.HabError("Nav2DObj: distance 'geodesic' is not available for this task: the distance is the one to the nearest "
                                 "object of the target category, which needs a field with several targets")
@@ -601,34 +613,20 @@ class Nav2DObjVectorEnv(Nav2DVectorEnv):
                                 f"(with LOOK_UP, LOOK_DOWN), got {num_actions}")
         if int(height) <= 0 or int(width) <= 0:
             raise _lib.HabError(f"Nav2DObj: the semantic image is always rendered, so the image size {height} x {width} must be positive")
+        self.num_objects, self.num_categories, self.num_actions = int(num_objects), int(num_categories), int(num_actions)
         super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
                          num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps)
         self.task = "nav2dobj"
-        self.num_objects, self.num_categories, self.num_actions = int(num_objects), int(num_categories), int(num_actions)
         self.action_spaces = [spaces.Discrete(self.num_actions) for _ in range(num_envs)]
         self.orig_action_spaces = self.action_spaces
         self._compass_table = torch.from_numpy(nav2d_compass_table(self.turn_angle)).to(self.device)
 
-    def _launch(self, obs, reward, not_done, actions, mask, advance: int):
-        if actions is not None and (actions.dtype != torch.int64 or actions.numel() != self.num_envs or not actions.is_contiguous()
-                                    or not actions.is_cuda):
-            raise _lib.HabError("Nav2DObj: actions must be a contiguous int64 device tensor of shape (N,) or (N, 1)")
-        dirs, ray, col_cos, tanv = self._tables
-        check(_lib.lib().hab_nav2d_obj_step(ptr(self._state), ptr(dirs), ptr(ray), ptr(col_cos), ptr(tanv), ptr(actions), ptr(mask),
-                                            ptr(obs.get("rgb")), ptr(obs.get("depth")), ptr(obs.get("semantic")),
-                                            ptr(obs.get("objectgoal")), ptr(obs.get("gps")), ptr(obs.get("compass")),
-                                            ptr(self._compass_table), ptr(reward), ptr(not_done), ptr(self.measure_sums), self.seed,
-                                            self.env_offset, self.num_envs, self.H, self.W, self.num_obstacles, self.num_headings,
-                                            self.max_episode_steps, self.num_objects, self.num_categories, self.num_actions, advance,
-                                            stream_ptr()), "hab_nav2d_obj_step")
+    def _sensor_rows(self, obs):
+        return (ptr(obs.get("rgb")), ptr(obs.get("depth")), ptr(obs.get("semantic")), ptr(obs.get("objectgoal")), ptr(obs.get("gps")),
+                ptr(obs.get("compass")), ptr(self._compass_table))
 
-    def step_into_obs(self, obs, reward, not_done, actions=None, mask=None):
-        """One step of every env (or of the envs whose `mask` byte is set) with `actions` int64 (N,) / (N, 1): the new observations
-        (any of rgb, depth, semantic, objectgoal, gps, compass), rewards (N,) and not-done bytes (N,) go straight into the given
-        device tensors."""
-        if actions is None:
-            raise _lib.HabError("Nav2DObj: step_into_obs needs the actions of the step")
-        self._launch(obs, reward, not_done, actions, mask, 1)
+    def _task_parameters(self):
+        return self.num_objects, self.num_categories, self.num_actions
 
     def reset_into(self, rgb, depth, goal):
         raise _lib.HabError("Nav2DObj: the task has no pointgoal sensor; use reset_into_obs with the ObjectNav sensor rows")
@@ -662,32 +660,23 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
             ref = sens["rgb"] if use_rgb else (sens["depth"] if use_depth else dict(height=0, width=0))
             syn = getattr(hab, "synthetic", {})
             distance = getattr(syn, "distance_to_goal", "euclidean")
+            kw = dict(seed=int(hab.seed), env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, num_actions=len(hab.task.actions),
+                      device=device, num_obstacles=getattr(syn, "num_obstacles", 3), turn_angle=getattr(syn, "turn_angle", 10),
+                      max_episode_steps=getattr(hab.environment, "max_episode_steps", 500), distance=distance)
+            make = Nav2DVectorEnv
             if task_type.startswith("nav2dobj"):
                 if not (use_rgb or use_depth):
                     if "semantic" not in sens:
                         raise _lib.HabError("Nav2DObj: no rgb, depth or semantic sensor gives the image size")
                     ref = sens["semantic"]
-                return Nav2DObjVectorEnv(int(hb.num_environments), int(ref["height"]), int(ref["width"]), seed=int(hab.seed),
-                                         env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, num_actions=len(hab.task.actions),
-                                         device=device, num_obstacles=getattr(syn, "num_obstacles", 3),
-                                         turn_angle=getattr(syn, "turn_angle", 10),
-                                         max_episode_steps=getattr(hab.environment, "max_episode_steps", 500),
-                                         num_objects=getattr(syn, "num_objects", 3), num_categories=getattr(syn, "num_categories", 4),
-                                         distance=distance)
-            if task_type.startswith("nav2dvel"):
-                return Nav2DVelVectorEnv(int(hb.num_environments), int(ref["height"]), int(ref["width"]), seed=int(hab.seed),
-                                         env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, num_actions=len(hab.task.actions),
-                                         device=device, num_obstacles=getattr(syn, "num_obstacles", 3),
-                                         turn_angle=getattr(syn, "turn_angle", 1),
-                                         max_episode_steps=getattr(hab.environment, "max_episode_steps", 500),
-                                         max_turn_angle=getattr(syn, "max_turn_angle", 10),
-                                         min_abs_lin_speed=getattr(syn, "min_abs_lin_speed", 0.025),
-                                         min_abs_ang_speed=getattr(syn, "min_abs_ang_speed", 5),
-                                         allow_sliding=getattr(syn, "allow_sliding", True), distance=distance)
-            return Nav2DVectorEnv(int(hb.num_environments), int(ref["height"]), int(ref["width"]), seed=int(hab.seed),
-                                  env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, num_actions=len(hab.task.actions),
-                                  device=device, num_obstacles=getattr(syn, "num_obstacles", 3), turn_angle=getattr(syn, "turn_angle", 10),
-                                  max_episode_steps=getattr(hab.environment, "max_episode_steps", 500), distance=distance)
+                make = Nav2DObjVectorEnv
+                kw.update(num_objects=getattr(syn, "num_objects", 3), num_categories=getattr(syn, "num_categories", 4))
+            elif task_type.startswith("nav2dvel"):
+                make = Nav2DVelVectorEnv
+                kw.update(turn_angle=getattr(syn, "turn_angle", 1), max_turn_angle=getattr(syn, "max_turn_angle", 10),
+                          min_abs_lin_speed=getattr(syn, "min_abs_lin_speed", 0.025),
+                          min_abs_ang_speed=getattr(syn, "min_abs_ang_speed", 5), allow_sliding=getattr(syn, "allow_sliding", True))
+            return make(int(hb.num_environments), int(ref["height"]), int(ref["width"]), **kw)
         ref = sens["rgb"] if use_rgb else sens["depth"]
         task = "objectnav" if str(hab.task.type).lower().startswith("objectnav") else "pointnav"
         return SyntheticVectorEnv(int(hb.num_environments), int(ref.height), int(ref.width), seed=int(hab.seed),
