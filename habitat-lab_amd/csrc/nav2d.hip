@@ -5,7 +5,8 @@
 // Nav2DVel-v0 (continuous actions) and Nav2DObj-v0 (objects, a target category, the ObjectNav sensor set) share the world, the end of
 // a step and the render; their specifications are tests/nav2d_vel_reference.py and tests/nav2d_obj_reference.py.
 // The geodesic distance mode of the first two tasks (nav2d_geo_build_kernel, the GEO forms of the step kernels) is specified by
-// tests/nav2d_geo_reference.py.
+// tests/nav2d_geo_reference.py, that of Nav2DObj-v0 (nav2d_obj_geo_build_kernel, nav2d_obj_geo_step_kernel: the distance to the
+// nearest instance of the target category) by tests/nav2d_obj_geo_reference.py.
 #include <cstddef>
 #include "hab_common.h"
 #include "../../include/habitat_amd.h"
@@ -523,6 +524,236 @@ __global__ void nav2d_obj_step_kernel(Nav2DObjState* __restrict__ states, const 
     if (compass) compass[n] = ctab[(s.heading - o.h0 + nh) % nh];
 }
 
+// ---- geodesic distance of Nav2DObj-v0 (distance = "geodesic"; specification: tests/nav2d_obj_geo_reference.py) ---------------------
+// The distance to the nearest instance of the target category along the shortest path.  Obstacles of the graph: the K rectangles
+// grown by the agent radius and, for each object, the bounding square of its keep-out disc, up to 16 boxes; 64 nodes, 4k + j corner j
+// of rectangle box k, 32 + 4m + j corner j of object m's square; targets, the centres of the objects of the target category, each
+// seen through its own square.  The field of one env's running episode (HAB_NAV2D_OBJ_GEO_BYTES) is laid out like GeoField.
+constexpr int OBJ_GEO_NODES = GEO_NODES + 4 * MAX_M, OBJ_GEO_BOXES = MAX_K + MAX_M;
+static_assert(OBJ_GEO_NODES == 64, "one node per lane of a wavefront");
+struct ObjGeoField {
+    float D[OBJ_GEO_NODES];
+    int32_t reachable, sweeps, lost_steps, zero[5];
+};
+static_assert(sizeof(ObjGeoField) == HAB_NAV2D_OBJ_GEO_BYTES, "ObjGeoField layout");
+static_assert(offsetof(ObjGeoField, reachable) == 4 * HAB_NAV2D_OBJ_GEO_W_REACHABLE &&
+              offsetof(ObjGeoField, sweeps) == 4 * HAB_NAV2D_OBJ_GEO_W_SWEEPS &&
+              offsetof(ObjGeoField, lost_steps) == 4 * HAB_NAV2D_OBJ_GEO_W_LOST_STEPS, "ObjGeoField layout");
+
+// Node i of the graph; false where it does not exist (k >= K, m >= M).
+__device__ inline bool obj_geo_node(const Nav2DObjState& o, int i, int K, int M, float& x, float& y) {
+    x = 0.0f; y = 0.0f;
+    if (i < GEO_NODES) {
+        if (i >= 4 * K) return false;
+        geo_corner(o.base, i >> 2, i & 3, x, y);
+        return true;
+    }
+    const int m = (i - GEO_NODES) >> 2, j = i & 3;
+    if (m >= M) return false;
+    x = (j & 1) ? o.obj[m][0] + OBJ_BLOCK : o.obj[m][0] - OBJ_BLOCK;
+    y = (j & 2) ? o.obj[m][1] + OBJ_BLOCK : o.obj[m][1] - OBJ_BLOCK;
+    return true;
+}
+// Object m's visibility box: its square shrunk by GEO_E, with geo_box's expressions.
+__device__ inline GeoBox obj_geo_box(const Nav2DObjState& o, int m) {
+    const float lx = (o.obj[m][0] - OBJ_BLOCK) + GEO_E, ly = (o.obj[m][1] - OBJ_BLOCK) + GEO_E;
+    const float hx = (o.obj[m][0] + OBJ_BLOCK) - GEO_E, hy = (o.obj[m][1] + OBJ_BLOCK) - GEO_E;
+    return GeoBox{(lx + hx) * 0.5f, (hx - lx) * 0.5f, (ly + hy) * 0.5f, (hy - ly) * 0.5f};
+}
+// The K + M visibility boxes into the wave's LDS array, rectangles first; the caller puts the barrier after it.
+__device__ inline void obj_geo_fill_boxes(GeoBox* boxes, const Nav2DObjState& o, int K, int M, int lane) {
+    if (lane < K) boxes[lane] = geo_box(o.base, lane);
+    else if (lane >= MAX_K && lane - MAX_K < M) boxes[K + (lane - MAX_K)] = obj_geo_box(o, lane - MAX_K);
+}
+// Whether a-b misses the B boxes, box `skip` left out.
+__device__ inline bool geo_visible_but(const GeoBox* boxes, int B, int skip, float ax, float ay, float bx, float by) {
+    for (int b = 0; b < B; ++b)
+        if (b != skip && geo_blocked(boxes[b], ax, ay, bx, by)) return false;
+    return true;
+}
+// geo(p) by one wavefront: lane i takes node i = (x, y) with field value Di (+inf: no candidate), lane t < M also the centre of
+// object t where it is a target, seen with its own box left out; then the minimum over the wave, which is exact and so the
+// restatement's serial one.
+__device__ inline float obj_geo_query(const Nav2DObjState& o, const GeoBox* boxes, int K, int M, float px, float py, float x, float y,
+                                      float Di, int lane) {
+    float v = INFINITY;
+    if (Di < INFINITY && geo_visible(boxes, K + M, px, py, x, y)) v = dist(px, py, x, y) + Di;
+    if (lane < M && o.cat[lane] == o.target) {
+        const float cx = o.obj[lane][0], cy = o.obj[lane][1];
+        if (geo_visible_but(boxes, K + M, K + lane, px, py, cx, cy)) v = fminf(v, dist(px, py, cx, cy));
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off));
+    return v;
+}
+
+// The field of one env per 64-thread workgroup (one wavefront), selected like nav2d_geo_build_kernel's.  Lane i owns node i.  The
+// weights are one symmetric 64 x 64 matrix in LDS (16 KiB), each of the 2016 node pairs tested once -- geo_blocked and dist are
+// bitwise symmetric in their two points -- and written to both places: a lane that computed its own row of 63 would run twice the
+// visibility tests, and they are what the kernel's time is.  The pairs go round the lanes in 32 rounds: rows a and 62 - a hold 64
+// pairs together, row 31 alone 32.  A sweep is 64 add / min per lane on its column of the matrix (row j of the array is one dword
+// per lane: no bank conflict) and D (a broadcast read), the two copies of D as in nav2d_geo_build_kernel, then a wave vote.
+__global__ void __launch_bounds__(64)
+nav2d_obj_geo_build_kernel(char* __restrict__ states, size_t state_stride, ObjGeoField* __restrict__ geo, const uint8_t* __restrict__ mask,
+                           int only_ended, int K, int M) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    if (mask && !mask[n]) return;
+    Nav2DObjState& o = *reinterpret_cast<Nav2DObjState*>(states + (size_t)n * state_stride);
+    Nav2DState& s = o.base;
+    if (only_ended && !s.ended) return;
+    __shared__ float node_x[OBJ_GEO_NODES], node_y[OBJ_GEO_NODES];
+    __shared__ int node_ok[OBJ_GEO_NODES];
+    __shared__ GeoBox boxes[OBJ_GEO_BOXES];
+    __shared__ float W[OBJ_GEO_NODES * OBJ_GEO_NODES];
+    __shared__ float D[2][OBJ_GEO_NODES];
+    float x, y;
+    const bool ok = obj_geo_node(o, lane, K, M, x, y) && is_free_obj(x, y, o, K, M);
+    node_x[lane] = x; node_y[lane] = y; node_ok[lane] = ok ? 1 : 0;
+    W[lane * OBJ_GEO_NODES + lane] = INFINITY;
+    obj_geo_fill_boxes(boxes, o, K, M, lane);
+    __syncthreads();
+    const int B = K + M;
+    for (int p = lane; p < OBJ_GEO_NODES * (OBJ_GEO_NODES - 1) / 2; p += 64) {
+        const int a = p >> 6, c = p & 63;
+        const int i = c < 63 - a ? a : 62 - a;
+        const int j = c < 63 - a ? a + 1 + c : i + 1 + (c - (63 - a));
+        float w = INFINITY;
+        if (node_ok[i] && node_ok[j] && geo_visible(boxes, B, node_x[i], node_y[i], node_x[j], node_y[j]))
+            w = dist(node_x[i], node_y[i], node_x[j], node_y[j]);
+        W[i * OBJ_GEO_NODES + j] = w;
+        W[j * OBJ_GEO_NODES + i] = w;
+    }
+    // the last hop: the nearest of the target centres the node sees, each through its own square
+    float d = INFINITY;
+    if (ok) {
+        for (int t = 0; t < M; ++t) {
+            if (o.cat[t] != o.target) continue;
+            const float cx = o.obj[t][0], cy = o.obj[t][1];
+            if (geo_visible_but(boxes, B, K + t, x, y, cx, cy)) d = fminf(d, dist(x, y, cx, cy));
+        }
+    }
+    D[0][lane] = d;
+    __syncthreads();
+    int cur = 0, sweeps = 0;
+    while (sweeps < 4 * B) {  // uniform over the wave: K and M are arguments, the exit a vote
+        sweeps += 1;
+        float m = INFINITY;
+        for (int j = 0; j < OBJ_GEO_NODES; ++j) m = fminf(m, W[j * OBJ_GEO_NODES + lane] + D[cur][j]);
+        const float before = D[cur][lane];
+        const float after = fminf(before, m);
+        D[cur ^ 1][lane] = after;
+        const bool changed = __ballot(after != before) != 0;
+        __syncthreads();
+        cur ^= 1;
+        if (!changed) break;
+    }
+    const float Di = D[cur][lane];
+    geo[n].D[lane] = Di;
+    const float v = obj_geo_query(o, boxes, K, M, s.px, s.py, x, y, Di, lane);  // g0 = geo(current position)
+    __syncthreads();  // every lane has read the state before lane 0 writes to it
+    if (lane == 0) {
+        const bool reachable = v < INFINITY;
+        geo[n].reachable = reachable ? 1 : 0;
+        geo[n].sweeps = sweeps;
+        geo[n].lost_steps = 0;
+        for (int z = 0; z < 5; ++z) geo[n].zero[z] = 0;
+        if (reachable) s.d_start = s.d_prev = v;
+    }
+}
+
+// end_step for the geodesic object step, which has its distance already: a function of its own beside end_step's instantiations,
+// whose arguments stay as they are (see the comment above end_step).  Then the next world's objects, as nav2d_obj_step_kernel.
+__device__ inline void obj_geo_end_step(Nav2DObjState& o, float d, bool stop, float* __restrict__ reward, uint8_t* __restrict__ not_done,
+                                        float* __restrict__ sums, uint32_t seed, uint32_t env, int n, int N, int K, int nh, int max_steps,
+                                        int M, int C) {
+    Nav2DState& s = o.base;
+    const bool success = stop && (d < OBJ_SUCCESS);
+    reward[n] = (-0.01f + (s.d_prev - d)) + (success ? 2.5f : 0.0f);
+    s.d_prev = d;
+    s.steps += 1;
+    const bool done = stop || (s.steps >= max_steps);
+    not_done[n] = done ? 0 : 1;
+    s.ended = done ? 1 : 0;
+    if (done) {
+        s.last[0] = success ? 1.0f : 0.0f;
+        s.last[1] = success ? __fdiv_rn(s.d_start, fmaxf(s.d_start, s.path)) : 0.0f;
+        s.last[2] = d;
+        s.last[3] = (float)s.collisions;
+        if (sums)
+            for (int m = 0; m < 4; ++m) sums[(size_t)m * N + n] = sums[(size_t)m * N + n] + s.last[m];
+        s.episode += 1;
+        begin_episode<false>(s, seed, env, K, nh);
+        place_objects(o, seed, env, K, M, C);
+    }
+}
+
+// The geodesic form of the object step: one wavefront (a 64-thread workgroup) per env.  Every lane works out the move from the same
+// loads, so the new position is uniform and lane 0 alone writes it; the query of that position takes one node per lane plus the
+// targets and a wave minimum; lane 0 then does what nav2d_obj_step_kernel does after its move, with that distance.  The field of an
+// episode that begins here is built by the launch of nav2d_obj_geo_build_kernel that follows (only_ended).
+__global__ void __launch_bounds__(64)
+nav2d_obj_geo_step_kernel(Nav2DObjState* __restrict__ states, ObjGeoField* __restrict__ geo, const float* __restrict__ dirs,
+                          const float* __restrict__ ctab, const int64_t* __restrict__ actions, const uint8_t* __restrict__ mask,
+                          int64_t* __restrict__ objectgoal, float* __restrict__ gps, float* __restrict__ compass,
+                          float* __restrict__ reward, uint8_t* __restrict__ not_done, float* __restrict__ sums, uint32_t seed,
+                          uint32_t env_offset, int N, int K, int nh, int max_steps, int M, int C, int advance) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    if (mask && !mask[n]) return;
+    Nav2DObjState& o = states[n];
+    Nav2DState& s = o.base;
+    ObjGeoField& g = geo[n];
+    const uint32_t env = env_offset + (uint32_t)n;
+    if (!advance) {
+        if (lane == 0) {
+            first_episode<false>(s, seed, env, K, nh);
+            place_objects(o, seed, env, K, M, C);
+        }
+    } else {
+        __shared__ GeoBox boxes[OBJ_GEO_BOXES];
+        const int64_t a = actions[n];
+        float px = s.px, py = s.py;
+        bool moved = false;
+        if (a == 1) {
+            const float nx = px + FORWARD * dirs[2 * s.heading], ny = py + FORWARD * dirs[2 * s.heading + 1];
+            if (is_free_obj(nx, ny, o, K, M)) { px = nx; py = ny; moved = true; }
+        }
+        const bool reachable = g.reachable != 0;  // of the env, so uniform over the workgroup
+        float d = INFINITY;
+        if (reachable) {
+            obj_geo_fill_boxes(boxes, o, K, M, lane);
+            __syncthreads();
+            float x, y;
+            const float Di = obj_geo_node(o, lane, K, M, x, y) ? g.D[lane] : INFINITY;
+            d = obj_geo_query(o, boxes, K, M, px, py, x, y, Di, lane);
+        }
+        __syncthreads();  // every lane has read the state and the field before lane 0 writes to them
+        if (lane == 0) {
+            if (a == 1) {
+                if (moved) { s.px = px; s.py = py; s.path = s.path + FORWARD; }
+                else s.collisions += 1;
+            } else if (a == 2) {
+                s.heading = (s.heading + 1) % nh;
+            } else if (a == 3) {
+                s.heading = (s.heading + nh - 1) % nh;
+            }
+            const float straight = nearest_target(o, M);  // (gx, gy) stay the Euclidean-nearest centre
+            if (!reachable) d = straight;
+            else if (!(d < INFINITY)) { d = s.d_prev; g.lost_steps += 1; }
+            obj_geo_end_step(o, d, a == 0, reward, not_done, sums, seed, env, n, N, K, nh, max_steps, M, C);
+        }
+    }
+    if (lane == 0) {
+        if (objectgoal) objectgoal[n] = (int64_t)o.target;
+        if (gps) {
+            const float c = dirs[2 * o.h0], sn = dirs[2 * o.h0 + 1];
+            const float dx = s.px - o.sx, dy = s.py - o.sy;
+            gps[2 * n + 0] = dx * c + dy * sn;
+            gps[2 * n + 1] = c * dy - sn * dx;
+        }
+        if (compass) compass[n] = ctab[(s.heading - o.h0 + nh) % nh];
+    }
+}
+
 // ---- rendering ---------------------------------------------------------------------------------------------------------------
 // Entry / exit of the ray p + t d through [lo, hi] on one axis.
 __device__ inline void slab(float lo, float hi, float p, float d, float inv, float& tmin, float& tmax) {
@@ -903,6 +1134,53 @@ extern "C" int hab_nav2d_obj_step(void* state, const float* dirs, const float* r
     nav2d_obj_step_kernel<<<cdiv(N, 64), 64, 0, stream>>>((Nav2DObjState*)state, dirs, compass_table, actions, mask, objectgoal, gps,
                                                           compass, reward, not_done, measure_sums, seed, env_offset, N, num_obstacles,
                                                           num_headings, max_episode_steps, num_objects, num_categories, advance);
+    HAB_LAUNCH_CHECK();
+    return launch_render<true>(a, num_objects);
+}
+
+extern "C" int hab_nav2d_obj_geo_bytes(void) { return (int)sizeof(ObjGeoField); }
+
+static int check_obj_geo_args(const void* state, size_t state_stride_bytes, const void* geo, int N, int num_obstacles) {
+    const int rc = check_geo_args(state, state_stride_bytes, geo, N, num_obstacles);
+    if (rc != HAB_OK) return rc;
+    return state_stride_bytes < sizeof(Nav2DObjState) ? HAB_ERR_ARG : HAB_OK;
+}
+
+extern "C" int hab_nav2d_obj_geo_build(void* state, size_t state_stride_bytes, void* geo, const uint8_t* mask, int only_ended, int N,
+                                       int num_obstacles, int num_objects, hipStream_t stream) {
+    const int rc = check_obj_geo_args(state, state_stride_bytes, geo, N, num_obstacles);
+    if (rc != HAB_OK) return rc;
+    if (num_objects < 1 || num_objects > MAX_M) return HAB_ERR_ARG;
+    nav2d_obj_geo_build_kernel<<<N, 64, 0, stream>>>((char*)state, state_stride_bytes, (ObjGeoField*)geo, mask, only_ended, num_obstacles,
+                                                     num_objects);
+    HAB_LAUNCH_CHECK();
+    return HAB_OK;
+}
+
+// hab_nav2d_obj_step with the field: the step (one wavefront per env), the fields of the episodes that began (at a reset, of every
+// env the mask selects), then the render.
+extern "C" int hab_nav2d_obj_step_geo(void* state, void* geo, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                                      const int64_t* actions, const uint8_t* mask, uint8_t* rgb, float* depth, int32_t* semantic,
+                                      int64_t* objectgoal, float* gps, float* compass, const float* compass_table, float* reward,
+                                      uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
+                                      int num_obstacles, int num_headings, int max_episode_steps, int num_objects, int num_categories,
+                                      int num_actions, int advance, hipStream_t stream) {
+    const StepArgs a{state, geo, dirs, ray, col_cos, tanv, actions, mask, rgb, depth, nullptr, semantic, reward, not_done,
+                     measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream};
+    int rc = check_step_args(a, false);
+    if (rc != HAB_OK) return rc;
+    rc = check_obj_geo_args(state, sizeof(Nav2DObjState), geo, N, num_obstacles);
+    if (rc != HAB_OK) return rc;
+    if (semantic && ((uintptr_t)semantic & 3)) return HAB_ERR_ARG;
+    if (compass && !compass_table) return HAB_ERR_ARG;
+    if (num_objects < 1 || num_objects > MAX_M || num_categories < 1 || num_categories > HAB_NAV2D_MAX_CATEGORIES) return HAB_ERR_ARG;
+    if (num_actions != 4 && num_actions != 6) return HAB_ERR_ARG;
+    nav2d_obj_geo_step_kernel<<<N, 64, 0, stream>>>((Nav2DObjState*)state, (ObjGeoField*)geo, dirs, compass_table, actions, mask, objectgoal,
+                                                    gps, compass, reward, not_done, measure_sums, seed, env_offset, N, num_obstacles,
+                                                    num_headings, max_episode_steps, num_objects, num_categories, advance);
+    HAB_LAUNCH_CHECK();
+    nav2d_obj_geo_build_kernel<<<N, 64, 0, stream>>>((char*)state, sizeof(Nav2DObjState), (ObjGeoField*)geo, mask, advance ? 1 : 0,
+                                                     num_obstacles, num_objects);
     HAB_LAUNCH_CHECK();
     return launch_render<true>(a, num_objects);
 }

@@ -330,6 +330,7 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
     _sensor_set = "nav2d"
     _renders_without_rgb_depth = False
     _state_bytes = "hab_nav2d_state_bytes"
+    _geo_bytes = "hab_nav2d_geo_bytes"  # the size of a field record of the geodesic mode
     num_actions = 4
     # what a subclass with another step changes: the name in the refusals, the library's entries (Euclidean, geodesic), what
     # `actions` has to be (with _actions_shaped), and the two hooks _sensor_rows and _task_parameters
@@ -360,7 +361,7 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
         self.measure_sums = torch.zeros(len(NAV2D_MEASURES), num_envs, device=dev)
         self._geo = None
         if self.distance == "geodesic":
-            self._geo = torch.zeros(num_envs, _lib.lib().hab_nav2d_geo_bytes() // 4, dtype=torch.int32, device=dev)
+            self._geo = torch.zeros(num_envs, getattr(_lib.lib(), self._geo_bytes)() // 4, dtype=torch.int32, device=dev)
         self._actions_host = np.zeros(num_envs, dtype=np.int64)
         self._infos: List[dict] = [{} for _ in range(num_envs)]
         self.number_of_episodes = [1 << 30] * num_envs  # episodes are generated, never repeated
@@ -590,20 +591,46 @@ class Nav2DObjVectorEnv(Nav2DVectorEnv):
       cylinders as geometry (a fixed colour per category) and no goal marker; semantic int32 (H, W, 1): floor 0, ceiling 1, walls 2,
       rectangles 3, an object 4 + category.  The observation-space ranges are the hashed ObjectNav task's, so the same policy is built.
       `semantic` is always rendered, also without rgb and depth.  `step_into_obs` writes any of rgb, depth, semantic, objectgoal, gps,
-      compass, whichever rows `obs` holds; `actions` is int64 (N,) / (N, 1) as for Nav2D-v0."""
+      compass, whichever rows `obs` holds; `actions` is int64 (N,) / (N, 1) as for Nav2D-v0.
+
+    Distance (`distance`, from `habitat.synthetic.distance_to_goal`).  "euclidean", the default, is all of the above.  "geodesic"
+      changes the d of the reward, the success test (STOP and d < 1.0), distance_to_goal and d_start / the SPL numerator -- nothing
+      else: world, objects, target, physics, sensors and render stay -- to the shortest path to the nearest instance of the target
+      category, habitat's ObjectNav definition.  It is Nav2D-v0's geodesic mode (see Nav2DVectorEnv, Distance: boxes, the
+      separating-axis test, E = 2^-10, one float32 rounding per operation) with a field that has several targets.
+      tests/nav2d_obj_geo_reference.py restates it; `nav2d_obj_geo_build_kernel` and `nav2d_obj_geo_step_kernel` match it bit for bit.
+      * Obstacles of the graph.  The K rectangles grown by the agent radius, with Nav2D-v0's expressions, and for object m the
+        axis-aligned square [ox - 0.4, ox + 0.4] x [oy - 0.4, oy + 0.4], the bounding square of its keep-out disc: up to 16 boxes.
+        The visibility boxes are these shrunk by E.  The square is a deliberate over-approximation of the disc: every path of the
+        boxed world is a path of the real one, up to E at the four tangent points, and the graph stays one of boxes.
+      * Nodes.  64: node 4k + j is corner j of rectangle box k, node 32 + 4m + j corner j of object m's square, in the corner order
+        (X0, Y0), (X1, Y0), (X0, Y1), (X1, Y1).  A node is valid iff it is free (arena, rectangles, discs).
+      * Targets.  The centres of all objects of the target category.  The square of object t does not block a segment that ends at
+        centre t; only that box is left out for that segment, all others block it as usual.
+      * Field.  D[i] = +inf for invalid nodes, else the least rounded path sum from node i to any target centre: the last hop is
+        the min over the target centres the node sees, then Jacobi sweeps D <- min(D, min_j fl(w[i][j] + D[j])) until one changes
+        nothing, at most 4 (K + M).
+      * geo(p) = the least of d(p, c_t) over the target centres p sees (own box t ignored) and fl(d(p, node_i) + D[i]) over the
+        nodes with finite D that p sees; +inf if p sees none of these.  A position in the sliver between a disc and its square
+        sees nothing through that box: a lost step by Nav2D-v0's rule, unless it is the target's own sliver, where the centre is seen.
+      * Episode.  As Nav2D-v0: the field is built at the beginning and g0 = geo(start).  g0 finite: d_start = d_prev = g0 and every
+        step's d is geo(p); where that is +inf, d = d_prev and the lost-step counter goes up.  g0 infinite: the episode keeps the
+        Euclidean nearest-centre distance throughout.  The state words (gx, gy) stay the Euclidean-nearest centre in both modes.
+      The field records (`_geo`, (N, 72) int32: 64 D, reachable, sweeps, lost steps, five zeros) exist in this mode only.  The field
+      is built on the device, so in this mode the class itself refuses a device that is no GPU."""
 
     _name = "Nav2DObj"
-    _entries = ("hab_nav2d_obj_step",)  # the mode with a field is refused
+    _entries = ("hab_nav2d_obj_step", "hab_nav2d_obj_step_geo")
     _sensor_set = "objectnav"
     _renders_without_rgb_depth = True
     _state_bytes = "hab_nav2d_obj_state_bytes"
+    _geo_bytes = "hab_nav2d_obj_geo_bytes"
 
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
                  use_depth: bool = True, num_actions: int = 6, device="cuda", num_obstacles: int = 3, turn_angle: int = 10,
                  max_episode_steps: int = 500, num_objects: int = 3, num_categories: int = 4, distance: str = "euclidean"):
-        if nav2d_distance(distance, "Nav2DObj") != "euclidean":
-            raise _lib.HabError("Nav2DObj: distance 'geodesic' is not available for this task: the distance is the one to the nearest "
-                                "object of the target category, which needs a field with several targets")
+        if nav2d_distance(distance, "Nav2DObj") == "geodesic" and torch.device(device).type != "cuda":
+            raise _lib.HabError("Nav2DObj: distance 'geodesic' builds its field on the GPU; no GPU device given")
         if not whole(num_objects) or not 1 <= num_objects <= NAV2D_MAX_OBJECTS:
             raise _lib.HabError(f"Nav2DObj: num_objects {num_objects!r} outside 1..{NAV2D_MAX_OBJECTS}")
         if not whole(num_categories) or not 1 <= num_categories <= NAV2D_MAX_CATEGORIES:
@@ -615,7 +642,7 @@ class Nav2DObjVectorEnv(Nav2DVectorEnv):
             raise _lib.HabError(f"Nav2DObj: the semantic image is always rendered, so the image size {height} x {width} must be positive")
         self.num_objects, self.num_categories, self.num_actions = int(num_objects), int(num_categories), int(num_actions)
         super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
-                         num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps)
+                         num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps, distance=distance)
         self.task = "nav2dobj"
         self.action_spaces = [spaces.Discrete(self.num_actions) for _ in range(num_envs)]
         self.orig_action_spaces = self.action_spaces
@@ -643,8 +670,7 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
     Nav2DVel-v0, its velocity-controlled variant (Nav2DVelVectorEnv), with the further `habitat.synthetic` keys named there; one
     starting with "nav2dobj" selects Nav2DObj-v0 (Nav2DObjVectorEnv: objects, a target category, the ObjectNav sensor set), which
     reads num_objects / num_categories too and takes its image size from the rgb, else the depth, else the semantic sensor.
-    `habitat.synthetic.distance_to_goal` ("euclidean", the default, or "geodesic") is the distance mode of the Nav2D tasks; the
-    object task refuses "geodesic"."""
+    `habitat.synthetic.distance_to_goal` ("euclidean", the default, or "geodesic") is the distance mode of all three Nav2D tasks."""
 
     def __init__(self, use_rgb: bool = True, use_depth: bool = True):
         self.use_rgb, self.use_depth = use_rgb, use_depth

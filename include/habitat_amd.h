@@ -168,6 +168,33 @@ int hab_nav2d_obj_step(void* state /*N,HAB_NAV2D_OBJ_STATE_BYTES*/, const float*
                        uint8_t* not_done /*N*/, float* measure_sums /*4,N*/, uint32_t seed, uint32_t env_offset, int N, int H, int W,
                        int num_obstacles, int num_headings, int max_episode_steps, int num_objects, int num_categories,
                        int num_actions, int advance, hipStream_t stream);
+/* The geodesic distance mode of Nav2DObj-v0 (habitat_amd/common/env_factory.py, Nav2DObjVectorEnv with distance = "geodesic";
+ * bit-identical to tests/nav2d_obj_geo_reference.py).  World, objects, target, physics, sensors and render are Nav2DObj-v0's; the
+ * distance of the reward, the success test, distance_to_goal and SPL is the shortest path to the nearest centre of the target
+ * category round the rectangles grown by the agent radius and the bounding squares of the objects' keep-out discs, over the
+ * visibility graph of the corners of those up to 16 boxes.  `geo` is N field records of HAB_NAV2D_OBJ_GEO_BYTES, 4-byte aligned,
+ * owned by the caller: 64 f32 shortest-path lengths (node 4k + j: corner j of rectangle k's box; node 32 + 4m + j: corner j of
+ * object m's square; +inf where it is no node), then the three words named below; the remaining five are zero.
+ * hab_nav2d_obj_geo_build is hab_nav2d_geo_build for such records: `state` are records with a stride >=
+ * HAB_NAV2D_OBJ_STATE_BYTES (a multiple of 4) that begin with a Nav2DObj-v0 record, num_objects in 1..HAB_NAV2D_MAX_OBJECTS.
+ * hab_nav2d_obj_step_geo is hab_nav2d_obj_step with `geo` after `state`: the step, then the build for the envs whose episode ended
+ * (advance = 0: for every selected env), then the render.  The checks come in the order: hab_nav2d_step's, the field's (geo NULL or
+ * misaligned), hab_nav2d_obj_step's own. */
+#define HAB_NAV2D_OBJ_GEO_BYTES 288
+#define HAB_NAV2D_OBJ_GEO_W_REACHABLE 64
+#define HAB_NAV2D_OBJ_GEO_W_SWEEPS 65   /* relaxation sweeps of the build, the one that changed nothing included */
+#define HAB_NAV2D_OBJ_GEO_W_LOST_STEPS 66
+int hab_nav2d_obj_geo_bytes(void);
+int hab_nav2d_obj_geo_build(void* state, size_t state_stride_bytes, void* geo /*N,HAB_NAV2D_OBJ_GEO_BYTES*/, const uint8_t* mask /*N*/,
+                            int only_ended, int N, int num_obstacles, int num_objects, hipStream_t stream);
+int hab_nav2d_obj_step_geo(void* state /*N,HAB_NAV2D_OBJ_STATE_BYTES*/, void* geo /*N,HAB_NAV2D_OBJ_GEO_BYTES*/, const float* dirs,
+                           const float* ray, const float* col_cos, const float* tanv, const int64_t* actions /*N*/,
+                           const uint8_t* mask /*N*/, uint8_t* rgb /*N,H,W,3*/, float* depth /*N,H,W,1*/,
+                           int32_t* semantic /*N,H,W,1*/, int64_t* objectgoal /*N,1*/, float* gps /*N,2*/, float* compass /*N,1*/,
+                           const float* compass_table /*num_headings*/, float* reward /*N*/, uint8_t* not_done /*N*/,
+                           float* measure_sums /*4,N*/, uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles,
+                           int num_headings, int max_episode_steps, int num_objects, int num_categories, int num_actions,
+                           int advance, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Observation transformers, fused: ResizeShortestEdge followed by CenterCropper
