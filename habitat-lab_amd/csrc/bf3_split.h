@@ -24,4 +24,11 @@ __device__ __forceinline__ void bf3_split2(float x0, float x1, unsigned& w1, uns
     w3 = __builtin_bit_cast(unsigned, __builtin_convertvector(q, bf16x2));
 }
 
+// The alternating sign schedule of the split-bf16 kernels (igemm_bf3.h), on unless HAB_BF3_NOSIGN is set (development: measures
+// its cost).  Read once per process; the launchers run on several inference-worker threads.
+inline int bf3_sign_schedule() {
+    static const int on = !hab_env_flag("HAB_BF3_NOSIGN");
+    return on;
+}
+
 }  // namespace hab

@@ -279,19 +279,18 @@ inline bool conv1x1_gn_stream_covers(int C, int Cout, int H, int W, int KH, int 
     return (long long)Ho * Wo * C <= 65536;
 }
 
-// 1: geometry not covered.
+// HAB_NOT_APPLICABLE: geometry not covered.
 inline int conv1x1_gn_stream(C1gArgs a, hipStream_t stream) {
     if (!a.x || !a.wq || !a.gamma || !a.beta || !a.y || a.B <= 0) return HAB_ERR_ARG;
     if ((a.mean == nullptr) != (a.rstd == nullptr)) return HAB_ERR_ARG;
-    if (!conv1x1_gn_stream_covers(a.C, a.Cout, a.H, a.W, 1, 1, a.stride, 0, a.groups)) return 1;
+    if (!conv1x1_gn_stream_covers(a.C, a.Cout, a.H, a.W, 1, 1, a.stride, 0, a.groups)) return HAB_NOT_APPLICABLE;
     if ((reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.wq) | reinterpret_cast<uintptr_t>(a.y) | reinterpret_cast<uintptr_t>(a.gamma) |
          reinterpret_cast<uintptr_t>(a.beta) | reinterpret_cast<uintptr_t>(a.residual) | reinterpret_cast<uintptr_t>(a.raw)) & 15)
-        return 1;
+        return HAB_NOT_APPLICABLE;
     a.Ho = (a.H - 1) / a.stride + 1; a.Wo = (a.W - 1) / a.stride + 1; a.HoWo = a.Ho * a.Wo;
     a.KS = a.C / 16; a.gs = a.Cout / a.groups; a.nslab = a.Cout / 32;
-    static const int sign_schedule = !hab_env_flag("HAB_BF3_NOSIGN");
-    a.sign_schedule = sign_schedule;
-    if ((long long)a.B * a.nslab > 0x7fffffffLL) return 1;
+    a.sign_schedule = bf3_sign_schedule();
+    if ((long long)a.B * a.nslab > 0x7fffffffLL) return HAB_NOT_APPLICABLE;
     const int grid = a.B * a.nslab;
     const int mt = a.HoWo <= 256 ? 1 : (a.HoWo <= 512 ? 2 : 4);
     const int ch = a.C >= 128 ? 128 : a.C;

@@ -199,22 +199,21 @@ inline bool conv2_dgrad_strip_covers(const ConvDesc& d) {
     return d.KH == 4 && d.KW == 4 && d.stride == 2 && d.pad == 0 && d.C == 32 && d.Cout == 64 && d.H >= 4 && d.W >= 4 && d.H <= 63 && d.W <= 63;
 }
 
-// 1: shape not covered.
+// HAB_NOT_APPLICABLE: shape not covered.
 inline int conv2_dgrad_strip(const ConvDesc& d, const float* dy, const float* wd, const float* mask, const float* add, float* dx,
                              hipStream_t stream) {
-    if (!conv2_dgrad_strip_covers(d)) return 1;
-    if (add || d.B < 16 || !dy || !wd || !dx) return 1;
-    if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(wd) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(mask)) & 15) return 1;
+    if (!conv2_dgrad_strip_covers(d)) return HAB_NOT_APPLICABLE;
+    if (add || d.B < 16 || !dy || !wd || !dx) return HAB_NOT_APPLICABLE;
+    if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(wd) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(mask)) & 15) return HAB_NOT_APPLICABLE;
     constexpr int R2 = 2;
     using Cfg = C2dCfg<R2>;
     C2dArgs a;
     a.dy = dy; a.wd = wd; a.mask = mask; a.dx = dx; a.B = d.B;
     a.H = d.H; a.W = d.W; a.Ho = (d.H - 4) / 2 + 1; a.Wo = (d.W - 4) / 2 + 1;
     a.strips = ((d.H + 1) / 2 + R2 - 1) / R2;  // cell rows = ceil(H / 2)
-    if ((long long)d.B * a.strips > 0x7fffffffLL) return 1;
+    if ((long long)d.B * a.strips > 0x7fffffffLL) return HAB_NOT_APPLICABLE;
     a.items = d.B * a.strips;
-    static const int sign_schedule = !hab_env_flag("HAB_BF3_NOSIGN");
-    a.sign_schedule = sign_schedule;
+    a.sign_schedule = bf3_sign_schedule();
     // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
     static const hipError_t attr_err = [] {
         const hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_dgrad_strip_kernel<R2, false>),

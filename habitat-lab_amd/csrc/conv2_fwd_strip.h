@@ -191,23 +191,22 @@ inline bool conv2_fwd_strip_covers(const ConvGeom& g) {
     return g.KH == 4 && g.KW == 4 && g.stride == 2 && g.pad == 0 && g.C == 32 && g.Cout == 64 && g.H >= 4 && g.W >= 4 && g.W <= 63;
 }
 
-// 1: shape not covered.
+// HAB_NOT_APPLICABLE: shape not covered.
 inline int conv2_fwd_strip(const ConvFwdProb& p, float* /*ws*/, size_t /*ws_floats*/, hipStream_t stream) {
     const ConvGeom& g = p.g;
-    if (!conv2_fwd_strip_covers(g)) return 1;
-    if ((p.ldy != 0 && p.ldy != 64) || g.B < 16) return 1;
-    if ((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.w) | reinterpret_cast<uintptr_t>(p.y) | reinterpret_cast<uintptr_t>(p.bias)) & 15) return 1;
+    if (!conv2_fwd_strip_covers(g)) return HAB_NOT_APPLICABLE;
+    if ((p.ldy != 0 && p.ldy != 64) || g.B < 16) return HAB_NOT_APPLICABLE;
+    if ((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.w) | reinterpret_cast<uintptr_t>(p.y) | reinterpret_cast<uintptr_t>(p.bias)) & 15) return HAB_NOT_APPLICABLE;
     constexpr int R = 2;
     using Cfg = C2fCfg<R>;
     C2fArgs a;
     a.x = p.x; a.wf = p.w; a.bias = p.bias; a.y = p.y; a.B = g.B;
     a.H = g.H; a.W = g.W; a.Ho = (g.H - 4) / 2 + 1; a.Wo = (g.W - 4) / 2 + 1;
     a.strips = (a.Ho + R - 1) / R;
-    if ((long long)g.B * a.strips > 0x7fffffffLL) return 1;
+    if ((long long)g.B * a.strips > 0x7fffffffLL) return HAB_NOT_APPLICABLE;
     a.items = g.B * a.strips;
     a.relu = p.relu;
-    static const int sign_schedule = !hab_env_flag("HAB_BF3_NOSIGN");
-    a.sign_schedule = sign_schedule;
+    a.sign_schedule = bf3_sign_schedule();
     const bool bench_geom = g.H == 63 && g.W == 63;
     // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
     static const hipError_t attr_err = [] {

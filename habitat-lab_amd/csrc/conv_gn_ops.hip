@@ -22,7 +22,7 @@ int conv_gn_fused(const ConvGnArgs& q, hipStream_t s) {
     a.B = q.B; a.H = q.H; a.W = q.W; a.C = q.C; a.Cout = q.Cout; a.KH = q.KH; a.KW = q.KW; a.stride = q.stride; a.pad = q.pad;
     a.groups = q.groups; a.relu = q.relu; a.eps = q.eps;
     const int rc = conv_gn_slab(a, s);
-    if (rc != 1 || q.KH != 1 || q.KW != 1 || q.pad != 0) return rc;
+    if (rc != HAB_NOT_APPLICABLE || q.KH != 1 || q.KW != 1 || q.pad != 0) return rc;
     // 1x1 convolutions whose frames do not fit LDS (the bottleneck net's 32 x 32-pixel layers): activations streamed from memory
     C1gArgs b{};
     b.x = q.x; b.wq = q.w_planes; b.gamma = q.gamma; b.beta = q.beta; b.residual = q.residual; b.y = q.y;
@@ -52,12 +52,12 @@ extern "C" int hab_stem_split_weights(const float* w_fwd, uint16_t* planes, hipS
 extern "C" int hab_stem_conv_wgrad(const float* x, const float* dy, float* dw_oihw, int B, int H, int W, int creal, float* ws, size_t ws_floats,
                                    const float* norm, hipStream_t stream) {
     const int rc = stem_conv_wgrad(x, dy, dw_oihw, B, H, W, creal, ws, ws_floats, stream, norm);
-    return rc == 1 ? HAB_ERR_UNSUPPORTED : rc;
+    return rc == HAB_NOT_APPLICABLE ? HAB_ERR_UNSUPPORTED : rc;
 }
 extern "C" int hab_stem_conv_fwd(const float* x, const uint16_t* w_planes, float* y, int B, int H, int W, const float* norm, float* gn_part,
                                  int gn_groups, hipStream_t stream) {
     const int rc = stem_conv_forward(x, w_planes, y, B, H, W, stream, norm, gn_part, gn_groups);
-    return rc == 1 ? HAB_ERR_UNSUPPORTED : rc;
+    return rc == HAB_NOT_APPLICABLE ? HAB_ERR_UNSUPPORTED : rc;
 }
 
 extern "C" int hab_split_weight_planes(const float* w_fwd, int Cout, int K, uint16_t* planes, hipStream_t stream) {
@@ -73,5 +73,5 @@ extern "C" int hab_conv_gn_fwd(const float* x, const uint16_t* w_planes, const f
     q.B = B; q.H = H; q.W = W; q.C = C; q.Cout = Cout; q.KH = KH; q.KW = KW; q.stride = stride; q.pad = pad; q.groups = groups;
     q.relu = relu; q.eps = eps;
     const int rc = conv_gn_fused(q, stream);
-    return rc == 1 ? HAB_ERR_UNSUPPORTED : rc;
+    return rc == HAB_NOT_APPLICABLE ? HAB_ERR_UNSUPPORTED : rc;
 }

@@ -414,7 +414,7 @@ inline int cgs_launch(CgsArgs& a, hipStream_t stream) {
     a.nslab = a.Cout / Cfg::Nt;
     a.sub = (a.KH == 1 && a.KW == 1) ? 1 : 0;
     const size_t lds = cgs_lds<MT, NT, WM, WK>(a, &a.region0_bytes, &a.prow);
-    if (lds == 0) return 1;
+    if (lds == 0) return HAB_NOT_APPLICABLE;
     auto kern = conv_gn_slab_kernel<MT, NT, WM, WK, D>;
     // set once per process and instantiation (thread-safe static initialisation: engines of several inference workers call this concurrently)
     static const hipError_t attr_err =
@@ -430,8 +430,8 @@ inline int cgs_prepare(CgsArgs& a) {
     a.Ho = (a.H + 2 * a.pad - a.KH) / a.stride + 1;
     a.Wo = (a.W + 2 * a.pad - a.KW) / a.stride + 1;
     a.HoWo = a.Ho * a.Wo;
-    if (a.Ho <= 0 || a.Wo <= 0 || !conv_gn_slab_shape(a.C, a.Cout, a.HoWo, a.groups)) return 1;
-    if (a.KH == 1 && a.KW == 1 && a.pad != 0) return 1;
+    if (a.Ho <= 0 || a.Wo <= 0 || !conv_gn_slab_shape(a.C, a.Cout, a.HoWo, a.groups)) return HAB_NOT_APPLICABLE;
+    if (a.KH == 1 && a.KW == 1 && a.pad != 0) return HAB_NOT_APPLICABLE;
     a.K = a.KH * a.KW * a.C;
     a.KS = a.K / 16;
     a.gs = a.Cout / a.groups;
@@ -452,7 +452,7 @@ inline bool conv_gn_slab_covers(int C, int Cout, int H, int W, int KH, int KW, i
     return cgs_lds<2, 1, 4, 2>(a, &r0, &pr) != 0;
 }
 
-// 1: geometry not covered (the caller runs the unfused path).
+// HAB_NOT_APPLICABLE: geometry not covered (the caller runs the unfused path).
 inline int conv_gn_slab(CgsArgs a, hipStream_t stream) {
     if (!a.x || !a.wq || !a.gamma || !a.beta || !a.y || a.B <= 0) return HAB_ERR_ARG;
     if ((a.mean == nullptr) != (a.rstd == nullptr)) return HAB_ERR_ARG;
@@ -460,9 +460,8 @@ inline int conv_gn_slab(CgsArgs a, hipStream_t stream) {
     if (rc != HAB_OK) return rc;
     if ((reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.wq) | reinterpret_cast<uintptr_t>(a.y) | reinterpret_cast<uintptr_t>(a.gamma) |
          reinterpret_cast<uintptr_t>(a.beta) | reinterpret_cast<uintptr_t>(a.residual) | reinterpret_cast<uintptr_t>(a.raw)) & 15)
-        return 1;
-    static const int sign_schedule = !hab_env_flag("HAB_BF3_NOSIGN");
-    a.sign_schedule = sign_schedule;
+        return HAB_NOT_APPLICABLE;
+    a.sign_schedule = bf3_sign_schedule();
     static const int ablate = hab_env_int("HAB_CGS_ABLATE", 0);
     a.ablate = ablate;
     if (a.gs > 64) return cgs_launch<1, 4, 1, 8, 2>(a, stream);

@@ -344,12 +344,12 @@ inline int conv_patch_bf3_launch(const P& p, PatchGeom gq, float* ws, size_t ws_
     gq.PW = gq.Wo + 2;
     gq.PP = (Cfg::TH + 2) * gq.PW;
     gq.dPW = FastDiv(gq.PW);
-    if (gq.PP > Cfg::MAX_PP) return 1;
+    if (gq.PP > Cfg::MAX_PP) return HAB_NOT_APPLICABLE;
     const int B = p.M / (gq.Ho * gq.Wo);
     gq.nt_m = B * gq.tiles_per_img;
     gq.nt_n = cdiv(p.N, Cfg::BN);
     const int ntiles = gq.nt_m * gq.nt_n;
-    static const int sign_schedule = !hab_env_flag("HAB_BF3_NOSIGN");
+    const int sign_schedule = bf3_sign_schedule();
     constexpr int wgs_per_cu = 2;  // measured (round 2): two persistent workgroups per CU
     const int occ = (int)(160 * 1024 / Cfg::LDS_BYTES) < wgs_per_cu ? (int)(160 * 1024 / Cfg::LDS_BYTES) : wgs_per_cu;
     int grid = 256 * (occ > 0 ? occ : 1);
@@ -390,17 +390,17 @@ inline int conv_patch_bf3_launch(const P& p, PatchGeom gq, float* ws, size_t ws_
     return HAB_OK;
 }
 
-// Picks a configuration for the output width / channel count; returns 1 when the shape is not covered (caller falls back).
+// Picks a configuration for the output width / channel count; returns HAB_NOT_APPLICABLE when the shape is not covered (caller falls back).
 template <class P>
 inline int conv_patch_bf3_dispatch(const P& p, const PatchGeom& gq, float* ws, size_t ws_floats, hipStream_t stream) {
-    if (gq.KH != 3 || gq.KW != 3 || gq.Ci % CPB_CC != 0 || (p.N & 31) || gq.Wo > 32 || gq.Wo < 5 || p.M % (gq.Ho * gq.Wo) != 0) return 1;
+    if (gq.KH != 3 || gq.KW != 3 || gq.Ci % CPB_CC != 0 || (p.N & 31) || gq.Wo > 32 || gq.Wo < 5 || p.M % (gq.Ho * gq.Wo) != 0) return HAB_NOT_APPLICABLE;
     // Measured (tools/bench_layers.py, 1024 frames): the patch form wins where the im2col form is bound by the A split, i.e. N = 32
     // (ResNet layer1 32x32: 92 -> 135 TFLOP/s-eq forward, 88 -> 136 data gradient; SimpleCNN conv3 forward 91 -> 119); at N >= 64
     // (layer2 / layer3, conv3's data gradient) it ties or loses against igemm_bf3's larger N tiles, so those stay there.
-    if (p.N != 32) return 1;
+    if (p.N != 32) return HAB_NOT_APPLICABLE;
     if (gq.Wo > 16) return conv_patch_bf3_launch<P, 32, 4, 1, 1, 3>(p, gq, ws, ws_floats, stream);
     if (gq.Wo > 8) return conv_patch_bf3_launch<P, 16, 4, 1, 1, 3>(p, gq, ws, ws_floats, stream);
-    return 1;
+    return HAB_NOT_APPLICABLE;
 }
 
 }  // namespace hab

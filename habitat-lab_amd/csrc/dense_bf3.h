@@ -382,8 +382,7 @@ inline int dense_bf3_launch(DenseArgs g, hipStream_t stream) {
     auto kern = dense_bf3_kernel<A_IC, B_IC>;
     static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, DN_LDS_BYTES);
     if (attr_err != hipSuccess) return (int)attr_err;
-    static const int sign_schedule = !hab_env_flag("HAB_BF3_NOSIGN");
-    g.sign_schedule = sign_schedule;
+    g.sign_schedule = bf3_sign_schedule();
     static const int skew = hab_env_int("HAB_DENSE_SKEW", 1);
     g.skew = skew;
     static const int ablate = hab_env_int("HAB_DENSE_ABLATE", 0);

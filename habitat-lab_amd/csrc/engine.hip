@@ -233,7 +233,7 @@ extern "C" int hab_policy_repack(hab_policy* e, hipStream_t stream) {
     HAB_TRY(repack_conv(e->p(e->i_c1w), e->PK + e->pk_c1f, nullptr, 32, e->Cin, 8, 8, e->Cin, stream));
     if (e->pk_c1img >= 0) {  // (was one launch in front of EVERY conv1 call: 12 -> 11 launches per rollout step)
         const int rc = obs_conv_weight_image(e->PK + e->pk_c1f, 32, 8, 8, e->Cin, e->PK + e->pk_c1img, stream);
-        if (rc != HAB_OK) return rc == 1 ? HAB_ERR_UNSUPPORTED : rc;
+        if (rc != HAB_OK) return rc == HAB_NOT_APPLICABLE ? HAB_ERR_UNSUPPORTED : rc;
     }
     HAB_TRY(repack_conv(e->p(e->i_c2w), e->PK + e->pk_c2f, e->PK + e->pk_c2d, 64, 32, 4, 4, 32, stream));
     HAB_TRY(repack_conv(e->p(e->i_c3w), e->PK + e->pk_c3f, e->PK + e->pk_c3d, 32, 64, 3, 3, 64, stream));
@@ -568,7 +568,7 @@ static int rnn_packed_forward(hab_policy* e, const int* rows, const float* hidde
         Probe pr(e, HAB_PROBE_RNN_FWD, stream);
         const int rc = rnn_seq_wave_forward(e->d.rnn_type, H, L, lps, wks, layer_x(e, 0), layer_ld(e, 0), hin, cin, pk, W + e->w_ws,
                                             e->ws_floats, stream);
-        return rc == 1 ? HAB_ERR_UNSUPPORTED : rc;
+        return rc == HAB_NOT_APPLICABLE ? HAB_ERR_UNSUPPORTED : rc;
     }
     for (int l = 0; l < L; ++l) {
         Probe pr(e, HAB_PROBE_RNN_FWD, stream);
@@ -731,7 +731,7 @@ static int rnn_packed_backward(hab_policy* e, const hab_pack_info* pack, hipStre
         const int rc = rnn_seq_wave_backward(e->d.rnn_type, H, L, lps, wiht, wks, x0, e->rnn_ld, layer_dout(e, L - 1), blind0 ? nullptr : layer_dx(e, 0),
                                              e->rnn_ld, nofc ? nullptr : x0, e->rnn_ld, nofc ? 0 : H, pk, W + e->w_scratch, W + e->w_ws, e->ws_floats,
                                              stream);
-        return rc == 1 ? HAB_ERR_UNSUPPORTED : rc;
+        return rc == HAB_NOT_APPLICABLE ? HAB_ERR_UNSUPPORTED : rc;
     }
     for (int l = L - 1; l >= 0; --l) {
         Probe pr(e, HAB_PROBE_RNN_BWD, stream);

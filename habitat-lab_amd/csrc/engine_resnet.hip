@@ -439,7 +439,7 @@ static int conv_gn_forward(hab_policy* e, const RnConv& c, const float* in, cons
         q.B = B; q.H = cd.H; q.W = cd.W; q.C = cd.C; q.Cout = cd.Cout; q.KH = cd.KH; q.KW = cd.KW; q.stride = cd.stride; q.pad = cd.pad;
         q.groups = c.groups; q.relu = relu; q.eps = 1e-5f;
         const int rc = conv_gn_fused(q, s);
-        if (rc != 1) return rc;
+        if (rc != HAB_NOT_APPLICABLE) return rc;
     }
     HAB_TRY(conv_fwd(cd, in, e->PK + c.pk_f, nullptr, raw, 0, W + e->w_ws, e->ws_floats, s));
     return groupnorm_forward(g, s);
@@ -615,11 +615,11 @@ static int stem_conv(hab_policy* e, int B, int f0, hipStream_t s, bool want_part
     const int stat_chunks = (cd.Ho() + STEM_STAT_ROWS - 1) / STEM_STAT_ROWS;
     want_part = want_part && (st.groups == 8 || st.groups == 16 || st.groups == 32) && (size_t)B * stat_chunks * st.groups * 2 <= e->ws_floats;
     const int rc = st.pk_p >= 0 ? stem_conv_forward(x0, reinterpret_cast<const unsigned short*>(e->PK + st.pk_p), raw, B, cd.H, cd.W, s,
-                                                    r->x0_raw ? W + r->w_stats + 32 : nullptr, want_part ? W + e->w_ws : nullptr, st.groups) : 1;
+                                                    r->x0_raw ? W + r->w_stats + 32 : nullptr, want_part ? W + e->w_ws : nullptr, st.groups) : HAB_NOT_APPLICABLE;
     if (have_part) *have_part = want_part && rc == 0;
-    if (rc != 0 && rc != 1) return rc;
-    if (rc == 1 && r->x0_raw) return HAB_ERR_UNSUPPORTED;  // (stem_takes_raw was decided on the same coverage predicates)
-    if (rc == 1) HAB_TRY(conv_fwd(cd, x0, e->PK + st.pk_f, nullptr, raw, 0, W + e->w_ws, e->ws_floats, s));
+    if (rc != HAB_OK && rc != HAB_NOT_APPLICABLE) return rc;
+    if (rc == HAB_NOT_APPLICABLE && r->x0_raw) return HAB_ERR_UNSUPPORTED;  // (stem_takes_raw was decided on the same coverage predicates)
+    if (rc == HAB_NOT_APPLICABLE) HAB_TRY(conv_fwd(cd, x0, e->PK + st.pk_f, nullptr, raw, 0, W + e->w_ws, e->ws_floats, s));
     return HAB_OK;
 }
 
@@ -645,8 +645,8 @@ static int resnet_layers_forward(hab_policy* e, int Btot, int f0, int B, hipStre
         gf.mean = gf.rstd = nullptr;
         HAB_TRY(stem_conv(e, B, f0, s, fusable, &have_part));
         const int rc = groupnorm_relu_maxpool_forward(gf, sH, sW, pool, nullptr, s, have_part ? gn_part : nullptr, STEM_STAT_ROWS);
-        if (rc != 0 && rc != 1) return rc;
-        if (rc == 1) {  // small frames: the register-resident GroupNorm, then the pool
+        if (rc != HAB_OK && rc != HAB_NOT_APPLICABLE) return rc;
+        if (rc == HAB_NOT_APPLICABLE) {  // small frames: the register-resident GroupNorm, then the pool
             HAB_TRY(groupnorm_forward(g, s));
             HAB_TRY(maxpool_forward(g.y, pool, pool_idx, B, sH, sW, g.C, s));
         }
@@ -884,13 +884,13 @@ int resnet_encoder_backward(hab_policy* e, const hab_obs* obs, const uint8_t* ma
     }
     ConvDesc c0 = r->stem.cd;
     c0.B = B;
-    int rcw = 1;
-    if (r->cpad == 4 && c0.Cout == 32)  // strip-resident form (stem_wgrad_strip.h); 1: geometry not covered
+    int rcw = HAB_NOT_APPLICABLE;
+    if (r->cpad == 4 && c0.Cout == 32)  // strip-resident form (stem_wgrad_strip.h); HAB_NOT_APPLICABLE: geometry not covered
         rcw = stem_conv_wgrad(W + r->w_x0, d_raw0, e->g(r->stem.i_w), B, c0.H, c0.W, r->creal, ws, e->ws_floats, s,
                               r->x0_raw ? W + r->w_stats + 32 : nullptr);
-    if (rcw != 0 && rcw != 1) return rcw;
-    if (rcw == 1 && r->x0_raw) return HAB_ERR_UNSUPPORTED;
-    if (rcw == 1) HAB_TRY(conv_wgrad(c0, W + r->w_x0, d_raw0, e->g(r->stem.i_w), nullptr, ws, e->ws_floats, s));
+    if (rcw != HAB_OK && rcw != HAB_NOT_APPLICABLE) return rcw;
+    if (rcw == HAB_NOT_APPLICABLE && r->x0_raw) return HAB_ERR_UNSUPPORTED;
+    if (rcw == HAB_NOT_APPLICABLE) HAB_TRY(conv_wgrad(c0, W + r->w_x0, d_raw0, e->g(r->stem.i_w), nullptr, ws, e->ws_floats, s));
     return HAB_OK;
 }
 

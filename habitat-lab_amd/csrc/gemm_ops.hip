@@ -24,52 +24,75 @@
 
 namespace hab {
 
-// Tile choice by output width N (= Cout / out-features) and height M: tall-skinny tiles because the policy's
-// layers have N in 32..512 and M in 1e2..1e7 (SURVEY.md H3).  Weight-gradient problems have small M x N and a
-// huge reduction: the 96-row tile (3 waves) avoids padding M = 288 / 576 / 1152 (3x3 taps x 32..128 channels).
-static bool no_dma() { static const bool v = hab_env_flag("HAB_NO_DMA"); return v; }
-static bool no_merged_dgrad() { static const bool v = hab_env_flag("HAB_NO_MERGED_DGRAD"); return v; }
-static bool no_patch() { static const bool v = hab_env_flag("HAB_NO_PATCH"); return v; }
-// split-bf16 matrix-pipe path (igemm_bf3.h) for the r-contiguous x r-contiguous contractions
-// bit 0: r-contiguous x r-contiguous problems, bit 1: observation-ingest convolution (obs_conv_bf3.h), bit 2: problems with an
-// i/j-contiguous operand (weight gradients, Linear data gradient), bit 3: prefer it over the fp32 patch / DMA weight-gradient kernels,
-// bit 4: input-patch-resident stride-1 3x3 convolutions (conv_patch_bf3.h), bit 5: producer / consumer waves where they won
-// (igemm_bf3_ws.h: long-K 128 x 128 forward-form tiles; obs_conv_bf3_ws.h: the observation-ingest convolution), bit 6: the
-// observation-ingest convolution with the input patch resident in LDS (obs_conv_patch.h), bit 7: strip-resident 3x3 weight gradients
-// (wgrad3x3_bf3.h), bit 8 / 9: SimpleCNN conv2 strip kernels, bit 10: the plain dense GEMM kernel for large Linear layers (dense_bf3.h), bit 11 (tests): that kernel for every shape it applies to,
-// bit 12 (tests): the time-major recurrence as one launch per step instead of the persistent kernels (rnn_persist.h)
+// The mask of hab_set_matrix_path (env HAB_BF3): which contractions run on the split-bf16 matrix-pipe kernels and in which form.
+// ops.h names the bits (MatrixPath), include/habitat_amd.h describes them.
 static std::atomic<int> g_bf3_mode{-1};  // engines of several inference-worker threads dispatch concurrently
-static int bf3_mode() {
+int matrix_path_bits() {
     int m = g_bf3_mode.load(std::memory_order_relaxed);
     if (m < 0) {
-        static const int from_env = hab_env_int("HAB_BF3", 2047);
+        static const int from_env = hab_env_int("HAB_BF3", MP_DEFAULT);
         int expected = -1;
         g_bf3_mode.compare_exchange_strong(expected, from_env, std::memory_order_relaxed);
         m = g_bf3_mode.load(std::memory_order_relaxed);
     }
     return m;
 }
-int matrix_path_bits() { return bf3_mode(); }
 extern "C" int hab_set_matrix_path(int mode) {
-    const int prev = bf3_mode();
+    const int prev = matrix_path_bits();
     if (mode >= 0) g_bf3_mode.store(mode, std::memory_order_relaxed);
     return prev;
 }
 
+// Tile choice by output width N (= Cout / out-features) and height M: tall-skinny tiles because the policy's
+// layers have N in 32..512 and M in 1e2..1e7 (SURVEY.md H3).  Weight-gradient problems have small M x N and a
+// huge reduction: the 96-row tile (3 waves) avoids padding M = 288 / 576 / 1152 (3x3 taps x 32..128 channels).
+template <int TM_, int TN_, int WM_, int WN_>
+struct Tile {  // TM x TN MFMA blocks of 32 x 32 per wave, WM x WN waves
+    static constexpr int TM = TM_, TN = TN_, WM = WM_, WN = WN_;
+};
+using Tile128x128 = Tile<2, 2, 2, 2>;
+// tiles of `rows` rows pad M less than tiles of `other` rows do (or not at all)
+static bool rows_fit(int M, int rows, int other) { return M % rows == 0 || cdiv(M, rows) * rows < cdiv(M, other) * other; }
+// The width classes of every tile family (split-bf16, LDS-DMA, fp32, merged data gradient): launch(Tile<...>{}) for the class of N;
+// WG (weight-gradient problems) adds the 96-row tiles.  A family instantiates its kernel for the tiles named here under its WG and
+// for those it names itself, no others.
+template <bool WG, class F>
+static int by_width(int M, int N, F launch) {
+    if (N <= 32) {
+        if constexpr (WG) {
+            if (rows_fit(M, 96, 256)) return launch(Tile<1, 1, 3, 1>{});
+        }
+        return launch(Tile<2, 1, 4, 1>{});
+    }
+    if (N <= 64) {
+        if constexpr (WG) {
+            if (rows_fit(M, 96, 128)) return launch(Tile<1, 2, 3, 1>{});
+        }
+        return launch(Tile<1, 2, 4, 1>{});
+    }
+    return launch(Tile128x128{});
+}
 
-// Producer / consumer waves (igemm_bf3_ws.h, matrix-path bit 5, on by default).  Measured on the MI355X against igemm_bf3_kernel, same
+// Producer / consumer waves (igemm_bf3_ws.h, MP_WS, on by default).  Measured on the MI355X against igemm_bf3_kernel, same
 // arithmetic and bit-identical results (profiles/r03_ws_vs_base_layers.txt): the 128 x 128 forward-form tiles with a long reduction gain
 // (3x3 256->256 at 4x4: 128 -> 163 TFLOP/s-eq forward and data gradient, fc 25088->512 forward 132 -> 150), every other shape loses
 // (32- / 64-column tiles -10..-45 %, i/j-contiguous operands -30 %, K = 256 merged data gradient -18 %: the longer prologue and the
 // halved MFMA wave count are not paid back).  It is therefore selected only where it won.
-template <class P, int TM, int TN, int WM, int WN>
+template <class P, class T>
 static int bf3_launch(const P& p, float* ws, size_t ws_floats, int target_blocks, hipStream_t stream) {
-    constexpr bool WS_SHAPE = P::A_RC && P::B_RC && TM == 2 && TN == 2 && WM == 2 && WN == 2;
-    if constexpr (WS_SHAPE) {
+    if constexpr (P::A_RC && P::B_RC && std::is_same_v<T, Tile128x128>) {
         constexpr int ws_min_k = 2048;
-        if ((bf3_mode() & 32) && p.K >= ws_min_k) return igemm_bf3_ws_launch<P, TM, TN, WM, WN, 4>(p, ws, ws_floats, target_blocks, stream);
+        if (matrix_path_on(MP_WS) && p.K >= ws_min_k) return igemm_bf3_ws_launch<P, T::TM, T::TN, T::WM, T::WN, 4>(p, ws, ws_floats, target_blocks, stream);
     }
-    return igemm_bf3_launch<P, TM, TN, WM, WN>(p, ws, ws_floats, target_blocks, stream);
+    return igemm_bf3_launch<P, T::TM, T::TN, T::WM, T::WN>(p, ws, ws_floats, target_blocks, stream);
+}
+// LDS-DMA staged variant (igemm_dma.h).  DB_WIDE: the 128 x 128 tile double-buffers its LDS stage.
+template <bool DB_WIDE, class P>
+static int dma_launch(const P& p, float* ws, size_t ws_floats, int target_blocks, hipStream_t stream) {
+    return by_width<false>(p.M, p.N, [&](auto t) {
+        using T = decltype(t);
+        return igemm_dma_launch<P, T::TM, T::TN, T::WM, T::WN, DB_WIDE && std::is_same_v<T, Tile128x128>>(p, ws, ws_floats, target_blocks, stream);
+    });
 }
 
 template <class P>
@@ -79,79 +102,51 @@ static int run_igemm(const P& p, float* ws, size_t ws_floats, hipStream_t stream
     // (measured: target 1024 -> 256 is +4 % on C2, +6 % on C3, all of it in the 64-frame rollout forward passes).  Weight
     // gradients (tiny M*N, K in the millions) keep the deeper split.
     if (P::A_RC || P::B_RC) target_blocks = 256;
+    constexpr bool RC = P::A_RC && P::B_RC;                                 // both operands r-contiguous
+    constexpr bool IJ = !RC && AKv<P>::value == 4;                          // an i/j-contiguous operand: register-transposed staging (igemm_bf3.h)
     constexpr bool WG = !P::A_RC && !P::B_RC && AKv<P>::value == 4;  // weight-gradient form
-    if constexpr (P::A_RC && P::B_RC) {
-        if ((bf3_mode() & 1) && p.M > 64) {
-            if (p.N <= 32) return bf3_launch<P, 2, 1, 4, 1>(p, ws, ws_floats, target_blocks, stream);
-            if (p.N <= 64) {
+    if constexpr (RC || IJ) {
+        if (matrix_path_on(RC ? MP_RC : MP_IJ) && p.M > 64) {
+            if constexpr (RC) {
                 // 256 x 64 tiles halve the weight traffic per output row: +12 % on the 3x3 64 -> 64 convolutions of ResNet layer2
                 // (0.089 -> 0.079 ms at 512 frames, forward and data gradient), nothing on SimpleCNN conv2 (K = 512: 0.308 vs 0.312 ms)
-                if (p.M >= 256 * 512 && p.K >= 576) return bf3_launch<P, 2, 2, 4, 1>(p, ws, ws_floats, target_blocks, stream);
-                return bf3_launch<P, 1, 2, 4, 1>(p, ws, ws_floats, target_blocks, stream);
+                if (p.N > 32 && p.N <= 64 && p.M >= 256 * 512 && p.K >= 576) return bf3_launch<P, Tile<2, 2, 4, 1>>(p, ws, ws_floats, target_blocks, stream);
             }
-            return bf3_launch<P, 2, 2, 2, 2>(p, ws, ws_floats, target_blocks, stream);
-        }
-    } else if constexpr (AKv<P>::value == 4) {  // an i/j-contiguous operand: register-transposed staging (igemm_bf3.h)
-        if ((bf3_mode() & 4) && p.M > 64) {
-            if (p.N <= 32) {
-                if constexpr (WG) {
-                    if (p.M % 96 == 0 || cdiv(p.M, 96) * 96 < cdiv(p.M, 256) * 256)
-                        return bf3_launch<P, 1, 1, 3, 1>(p, ws, ws_floats, target_blocks, stream);
-                }
-                return bf3_launch<P, 2, 1, 4, 1>(p, ws, ws_floats, target_blocks, stream);
-            }
-            if (p.N <= 64) {
-                if constexpr (WG) {
-                    if (p.M % 96 == 0 || cdiv(p.M, 96) * 96 < cdiv(p.M, 128) * 128)
-                        return bf3_launch<P, 1, 2, 3, 1>(p, ws, ws_floats, target_blocks, stream);
-                }
-                return bf3_launch<P, 1, 2, 4, 1>(p, ws, ws_floats, target_blocks, stream);
-            }
-            return bf3_launch<P, 2, 2, 2, 2>(p, ws, ws_floats, target_blocks, stream);
+            return by_width<WG>(p.M, p.N, [&](auto t) { return bf3_launch<P, decltype(t)>(p, ws, ws_floats, target_blocks, stream); });
         }
     }
     if constexpr (std::is_same_v<P, ConvFwdProb> || std::is_same_v<P, ConvDgradProb>) {
-        if (p.dma_ok() && p.M > 64 && !no_dma()) {  // LDS-DMA staged variant (igemm_dma.h)
-            if (p.N <= 32) return igemm_dma_launch<P, 2, 1, 4, 1, false>(p, ws, ws_floats, target_blocks, stream);
-            if (p.N <= 64) return igemm_dma_launch<P, 1, 2, 4, 1, false>(p, ws, ws_floats, target_blocks, stream);
-            if (p.N <= 128) return igemm_dma_launch<P, 2, 2, 2, 2, true>(p, ws, ws_floats, target_blocks, stream);
-        }
+        if (p.dma_ok() && p.M > 64 && p.N <= 128) return dma_launch<true>(p, ws, ws_floats, target_blocks, stream);
     }
-    if (p.N <= 32) {
-        if (p.M <= 64) return igemm_launch<P, 1, 1, 2, 1>(p, ws, ws_floats, target_blocks, stream);
-        if constexpr (WG) {
-            if (p.M % 96 == 0 || cdiv(p.M, 96) * 96 < cdiv(p.M, 256) * 256)
-                return igemm_launch<P, 1, 1, 3, 1>(p, ws, ws_floats, target_blocks, stream);
-        }
-        return igemm_launch<P, 2, 1, 4, 1>(p, ws, ws_floats, target_blocks, stream);
-    } else if (p.N <= 64) {
-        if (p.M <= 64) return igemm_launch<P, 1, 1, 2, 2>(p, ws, ws_floats, target_blocks, stream);
-        if constexpr (WG) {
-            if (p.M % 96 == 0 || cdiv(p.M, 96) * 96 < cdiv(p.M, 128) * 128)
-                return igemm_launch<P, 1, 2, 3, 1>(p, ws, ws_floats, target_blocks, stream);
-        }
-        return igemm_launch<P, 1, 2, 4, 1>(p, ws, ws_floats, target_blocks, stream);
-    } else {
-        if (p.M <= 64) return igemm_launch<P, 1, 2, 2, 2>(p, ws, ws_floats, target_blocks, stream);
-        return igemm_launch<P, 2, 2, 2, 2>(p, ws, ws_floats, target_blocks, stream);
+    if (p.M <= 64) {
+        if (p.N <= 32) return igemm_launch<P, 1, 1, 2, 1>(p, ws, ws_floats, target_blocks, stream);
+        if (p.N <= 64) return igemm_launch<P, 1, 1, 2, 2>(p, ws, ws_floats, target_blocks, stream);
+        return igemm_launch<P, 1, 2, 2, 2>(p, ws, ws_floats, target_blocks, stream);
     }
+    return by_width<WG>(p.M, p.N, [&](auto t) {
+        using T = decltype(t);
+        return igemm_launch<P, T::TM, T::TN, T::WM, T::WN>(p, ws, ws_floats, target_blocks, stream);
+    });
+}
+
+// Stride-1 3x3 convolutions with the input patch resident in LDS (conv_patch_bf3.h, MP_PATCH3X3): `in` is x for the forward and dY,
+// with the taps flipped, for the data gradient; off is the input offset of tap 0 relative to the output pixel.
+static bool patch3x3_wanted(const ConvDesc& d, int M) { return matrix_path_on(MP_PATCH3X3) && d.stride == 1 && d.KH == 3 && d.KW == 3 && M > 64; }
+static PatchGeom patch3x3_geom(const float* in, int Hi, int Wi, int Ci, int Ho, int Wo, int off, int flip) {
+    PatchGeom gq{};
+    gq.in = in; gq.Hi = Hi; gq.Wi = Wi; gq.Ci = Ci; gq.Ho = Ho; gq.Wo = Wo; gq.KH = 3; gq.KW = 3;
+    gq.off_h = off; gq.off_w = off; gq.flip = flip;
+    return gq;
 }
 
 int conv_fwd(const ConvDesc& d, const float* x, const float* wf, const float* bias, float* y, int relu, float* ws,
              size_t ws_floats, hipStream_t stream) {
     ConvFwdProb p;
     HAB_TRY(build(p, d, x, wf, bias, y, relu));
-    if ((bf3_mode() & 256) && (bf3_mode() & 1)) {  // SimpleCNN conv2: input strip in LDS, filter slices in registers (conv2_fwd_strip.h)
-        const int rc = conv2_fwd_strip(p, ws, ws_floats, stream);
-        if (rc != 1) return rc;
-    }
-    if ((bf3_mode() & 16) && d.stride == 1 && d.KH == 3 && d.KW == 3 && p.M > 64) {  // input patch resident in LDS (conv_patch_bf3.h)
-        PatchGeom gq{};
-        gq.in = x; gq.Hi = d.H; gq.Wi = d.W; gq.Ci = d.C; gq.Ho = p.g.Ho; gq.Wo = p.g.Wo; gq.KH = 3; gq.KW = 3;
-        gq.off_h = -d.pad; gq.off_w = -d.pad; gq.flip = 0;
-        const int rc = conv_patch_bf3_dispatch(p, gq, ws, ws_floats, stream);
-        if (rc != 1) return rc;
-    }
+    if (matrix_path_on(MP_CONV2_FWD | MP_RC))  // SimpleCNN conv2: input strip in LDS, filter slices in registers (conv2_fwd_strip.h)
+        HAB_TRY_FORM(conv2_fwd_strip(p, ws, ws_floats, stream));
+    if (patch3x3_wanted(d, p.M))
+        HAB_TRY_FORM(conv_patch_bf3_dispatch(p, patch3x3_geom(x, d.H, d.W, d.C, p.g.Ho, p.g.Wo, -d.pad, 0), ws, ws_floats, stream));
     return run_igemm(p, ws, ws_floats, stream);
 }
 int64_t obs_conv_weight_image_floats() { return ((int64_t)OCP_W_ELEMS + 1) / 2 + 4; }
@@ -162,18 +157,12 @@ int obs_conv_fwd(const ConvDesc& d, const ObsView& obs, const float* wf, const f
                  size_t ws_floats, hipStream_t stream, const void* wimg) {
     ObsConvFwdProb p;
     HAB_TRY(build(p, d, obs, wf, bias, y, relu));
-    if ((bf3_mode() & 64) && (bf3_mode() & 2) && p.quad) {  // observation patch resident in LDS (obs_conv_patch.h): 8x8 / 4 RGB-D -> 32 only
-        const int rc = obs_conv_patch_launch(p, ws, ws_floats, stream, reinterpret_cast<const unsigned short*>(wimg));
-        if (rc != 1) return rc;
-    }
-    if ((bf3_mode() & 32) && (bf3_mode() & 2) && p.quad && p.M > 64) {  // producer / consumer waves (obs_conv_bf3_ws.h): 133 -> 148-152 TFLOP/s-eq at 1024 frames
-        const int rc = obs_conv_bf3_ws_launch(p, ws, ws_floats, stream);
-        if (rc != 1) return rc;
-    }
-    if ((bf3_mode() & 2) && p.quad && p.M > 64) {  // uint8 x split-bf16 weights on the matrix pipe (obs_conv_bf3.h)
-        const int rc = obs_conv_bf3_launch<2>(p, ws, ws_floats, stream);
-        if (rc != 1) return rc;
-    }
+    if (matrix_path_on(MP_OBS_PATCH | MP_OBS) && p.quad)  // observation patch resident in LDS (obs_conv_patch.h): 8x8 / 4 RGB-D -> 32 only
+        HAB_TRY_FORM(obs_conv_patch_launch(p, ws, ws_floats, stream, reinterpret_cast<const unsigned short*>(wimg)));
+    if (matrix_path_on(MP_WS | MP_OBS) && p.quad && p.M > 64)  // producer / consumer waves (obs_conv_bf3_ws.h): 133 -> 148-152 TFLOP/s-eq at 1024 frames
+        HAB_TRY_FORM(obs_conv_bf3_ws_launch(p, ws, ws_floats, stream));
+    if (matrix_path_on(MP_OBS) && p.quad && p.M > 64)  // uint8 x split-bf16 weights on the matrix pipe (obs_conv_bf3.h)
+        HAB_TRY_FORM(obs_conv_bf3_launch<2>(p, ws, ws_floats, stream));
     return run_igemm(p, ws, ws_floats, stream);
 }
 // dX pixels whose class has no taps (possible only when stride > kernel size) receive no contribution:
@@ -186,11 +175,9 @@ __global__ void dgrad_empty_class_kernel(ConvDgradProb p) {
 
 int conv_dgrad(const ConvDesc& d, const float* dy, const float* wd, const float* mask, const float* add, float* dx,
                float* ws, size_t ws_floats, hipStream_t stream) {
-    if ((bf3_mode() & 512) && (bf3_mode() & 1)) {  // SimpleCNN conv2: dY strip in LDS, filter slices in registers (conv2_dgrad_strip.h)
-        const int rc = conv2_dgrad_strip(d, dy, wd, mask, add, dx, stream);
-        if (rc != 1) return rc;
-    }
-    if (d.stride > 1 && !no_dma() && !no_merged_dgrad()) {
+    if (matrix_path_on(MP_CONV2_DGRAD | MP_RC))  // SimpleCNN conv2: dY strip in LDS, filter slices in registers (conv2_dgrad_strip.h)
+        HAB_TRY_FORM(conv2_dgrad_strip(d, dy, wd, mask, add, dx, stream));
+    if (d.stride > 1) {
         // kernel size a multiple of the stride: the stride classes share their dY gather -> one contraction with N = s*s*Cin
         ConvDgradMergedProb q;
         HAB_TRY(check_conv(d));
@@ -198,18 +185,11 @@ int conv_dgrad(const ConvDesc& d, const float* dy, const float* wd, const float*
         if (ConvDgradMergedProb::applicable(q.g)) {
             q.dy = dy; q.w = wd; q.mask = mask; q.add = add; q.dx = dx;
             q.finish();
-            if ((bf3_mode() & 1) && q.M > 64) {  // split-bf16 matrix path, register-staged (igemm_bf3.h)
-                if (q.N <= 32) return bf3_launch<ConvDgradMergedProb, 2, 1, 4, 1>(q, ws, ws_floats, 256, stream);
-                if (q.N <= 64) return bf3_launch<ConvDgradMergedProb, 1, 2, 4, 1>(q, ws, ws_floats, 256, stream);
-                return bf3_launch<ConvDgradMergedProb, 2, 2, 2, 2>(q, ws, ws_floats, 256, stream);
-            }
-            if (q.dma_ok()) {
-                if (q.N <= 32) return igemm_dma_launch<ConvDgradMergedProb, 2, 1, 4, 1, false>(q, ws, ws_floats, 1024, stream);
-                if (q.N <= 64) return igemm_dma_launch<ConvDgradMergedProb, 1, 2, 4, 1, false>(q, ws, ws_floats, 1024, stream);
-                // single LDS buffer: K is short (KH/s * KW/s taps), 4 resident workgroups overlap each other's prologue / epilogue
-                // (measured 79 vs 68 TFLOP/s double-buffered on SimpleCNN conv2 with the ReLU-mask epilogue)
-                return igemm_dma_launch<ConvDgradMergedProb, 2, 2, 2, 2, false>(q, ws, ws_floats, 1024, stream);
-            }
+            if (matrix_path_on(MP_RC) && q.M > 64)  // split-bf16 matrix path, register-staged (igemm_bf3.h)
+                return by_width<false>(q.M, q.N, [&](auto t) { return bf3_launch<ConvDgradMergedProb, decltype(t)>(q, ws, ws_floats, 256, stream); });
+            // single LDS buffer at every width: K is short (KH/s * KW/s taps), 4 resident workgroups overlap each other's prologue / epilogue
+            // (measured 79 vs 68 TFLOP/s double-buffered on SimpleCNN conv2 with the ReLU-mask epilogue)
+            if (q.dma_ok()) return dma_launch<false>(q, ws, ws_floats, 1024, stream);
         }
     }
     for (int ph = 0; ph < d.stride; ++ph)
@@ -217,13 +197,10 @@ int conv_dgrad(const ConvDesc& d, const float* dy, const float* wd, const float*
             ConvDgradProb p;
             HAB_TRY(build(p, d, dy, wd, mask, add, dx, ph, pw));
             if (p.Hc <= 0 || p.Wc <= 0) continue;
-            if ((bf3_mode() & 16) && d.stride == 1 && d.KH == 3 && d.KW == 3 && p.M > 64 && p.K > 0) {  // conv_patch_bf3.h, taps flipped
-                PatchGeom gq{};
-                gq.in = dy; gq.Hi = p.g.Ho; gq.Wi = p.g.Wo; gq.Ci = d.Cout; gq.Ho = d.H; gq.Wo = d.W; gq.KH = 3; gq.KW = 3;
-                gq.off_h = d.pad - 2; gq.off_w = d.pad - 2; gq.flip = 1;
-                const int rc = conv_patch_bf3_dispatch(p, gq, ws, ws_floats, stream);
+            if (patch3x3_wanted(d, p.M) && p.K > 0) {
+                const int rc = conv_patch_bf3_dispatch(p, patch3x3_geom(dy, p.g.Ho, p.g.Wo, d.Cout, d.H, d.W, d.pad - 2, 1), ws, ws_floats, stream);
                 if (rc == HAB_OK) continue;
-                if (rc != 1) return rc;
+                if (rc != HAB_NOT_APPLICABLE) return rc;
             }
             if (p.K <= 0) {
                 p.M = d.B * p.Hc * p.Wc;
@@ -239,24 +216,23 @@ int conv_wgrad(const ConvDesc& d, const float* x, const float* dy, float* dw_oih
                hipStream_t stream) {
     ConvWgradProb p;
     HAB_TRY(build(p, d, x, dy, dw_oihw, dbias));
-    if (ws && (bf3_mode() & 8) && (bf3_mode() & 128) && wgrad3x3_bf3_shape(p)) {  // strip-resident, transpose reads (wgrad3x3_bf3.h)
-        const int rc = wgrad3x3_bf3(p, ws, ws_floats, stream);
-        if (rc != 1) return rc;
-    }
-    if (ws && wgrad3x3_patch_ok(p) && !no_patch() && !(bf3_mode() & 8)) {  // 3x3/1/1 with W in {16, 32}: patch-resident kernel
+    if (ws && matrix_path_on(MP_WGRAD_STRIP | MP_IJ_WGRAD) && wgrad3x3_bf3_shape(p))  // strip-resident, transpose reads (wgrad3x3_bf3.h)
+        HAB_TRY_FORM(wgrad3x3_bf3(p, ws, ws_floats, stream));
+    if (ws && !matrix_path_on(MP_IJ_WGRAD)) {
+        // the fp32 patch / LDS-DMA kernels never see dY in registers: they take the problem without `colsum`, the bias gradient is a
+        // separate column sum
         ConvWgradProb q = p;
         q.colsum = nullptr;
-        if (dbias) HAB_TRY(colsum(dy, p.N, p.K, p.N, dbias, 0, ws, ws_floats, stream));
-        return wgrad3x3_patch(q, ws, ws_floats, stream);
-    }
-    // LDS-DMA staged variant (igemm_dma_wgrad.h): measured faster only for unpadded convolutions with Cout <= 32 (SimpleCNN conv3:
-    // 51 -> 64 TFLOP/s); with padding the per-pixel scalar decode + border tests cost more than the VGPR staging they replace.
-    if (ws && d.pad == 0 && p.N <= 32 && !no_dma() && !(bf3_mode() & 8)) {
-        ConvWgradProb q = p;
-        q.colsum = nullptr;  // the DMA path never sees dY in registers: the bias gradient is a separate column sum
-        if (wgrad_dma_ok(q)) {
-            if (dbias) HAB_TRY(colsum(dy, p.N, p.K, p.N, dbias, 0, ws, ws_floats, stream));
-            if ((q.M % 288 == 0) || (cdiv(q.M, 288) * 288 < cdiv(q.M, 256) * 256)) return igemm_dma_wgrad_launch<3, 3, 1>(q, ws, ws_floats, 1024, stream);
+        auto bias_grad = [&] { return dbias ? colsum(dy, p.N, p.K, p.N, dbias, 0, ws, ws_floats, stream) : HAB_OK; };
+        if (wgrad3x3_patch_ok(p)) {  // 3x3/1/1 with W in {16, 32}: patch-resident kernel
+            HAB_TRY(bias_grad());
+            return wgrad3x3_patch(q, ws, ws_floats, stream);
+        }
+        // LDS-DMA staged variant (igemm_dma_wgrad.h): measured faster only for unpadded convolutions with Cout <= 32 (SimpleCNN conv3:
+        // 51 -> 64 TFLOP/s); with padding the per-pixel scalar decode + border tests cost more than the VGPR staging they replace.
+        if (d.pad == 0 && p.N <= 32 && wgrad_dma_ok(q)) {
+            HAB_TRY(bias_grad());
+            if (rows_fit(q.M, 288, 256)) return igemm_dma_wgrad_launch<3, 3, 1>(q, ws, ws_floats, 1024, stream);
             return igemm_dma_wgrad_launch<2, 4, 1>(q, ws, ws_floats, 1024, stream);
         }
     }
@@ -266,60 +242,54 @@ int obs_conv_wgrad(const ConvDesc& d, const ObsView& obs, const float* dy, float
                    size_t ws_floats, hipStream_t stream) {
     ObsConvWgradProb p;
     HAB_TRY(build(p, d, obs, dy, dw_oihw, dbias));
-    if ((bf3_mode() & 2) && p.quad && p.K > 4096) {  // uint8 x split-bf16 dY on the matrix pipe (obs_wgrad_bf3.h)
-        const int rc = obs_wgrad_bf3_launch(p, ws, ws_floats, stream);
-        if (rc != 1) return rc;
-    }
+    if (matrix_path_on(MP_OBS) && p.quad && p.K > 4096)  // uint8 x split-bf16 dY on the matrix pipe (obs_wgrad_bf3.h)
+        HAB_TRY_FORM(obs_wgrad_bf3_launch(p, ws, ws_floats, stream));
     return run_igemm(p, ws, ws_floats, stream);
 }
-// Large dense layers on dense_bf3.h (matrix-path bit 10).  Returns 1 when the kernel does not apply.
-static bool dense_on() { return (bf3_mode() & 1024) && (bf3_mode() & 1); }
-static bool dense_worth(long long M, long long N, long long K) {
-    if (bf3_mode() & 2048) return true;  // matrix-path bit 11 (tests): every applicable shape
+
+// Large Linear layers on the plain dense GEMM kernel (dense_bf3.h, MP_DENSE with MP_RC).
+static bool dense_wanted(long long M, long long N, long long K) {
+    if (!matrix_path_on(MP_DENSE | MP_RC)) return false;
+    if (matrix_path_on(MP_DENSE_ALL)) return true;  // (tests) every applicable shape
     // the shapes it was built and measured for: >= ~10 GFLOP contractions (SimpleCNN's visual fc and its gradients); smaller layers keep
     // the igemm tiles (their launch is shorter than this kernel's 256 x 128 x K prologue / epilogue)
     static const long long min_flop = (long long)hab_env_int("HAB_DENSE_MIN_MFLOP", 4000) * 1000000LL;
     return 2 * M * N * K >= min_flop;
 }
+// g: the operands and epilogue of C[M][N] = A B^T; p: the same layer as an igemm problem, whose reduction pass sums the split-K slabs.
+// HAB_NOT_APPLICABLE: the caller runs the igemm tiles.
+template <int A_IC, int B_IC, class P>
+static int dense_try(DenseArgs g, const P& p, float* ws, size_t ws_floats, hipStream_t stream) {
+    if (!dense_wanted(g.M, g.N, g.K) || !dense_bf3_ok(g, A_IC, B_IC)) return HAB_NOT_APPLICABLE;
+    g.partial = ws;
+    g.nsplit = ws ? dense_bf3_splits(g, ws_floats) : 1;
+    HAB_TRY((dense_bf3_launch<A_IC, B_IC>(g, stream)));
+    if (g.nsplit > 1) {
+        igemm_splitk_reduce<P>(p, ws, g.nsplit, stream);
+        HAB_LAUNCH_CHECK();
+    }
+    return HAB_OK;
+}
 int linear_fwd(const float* x, int ldx, const float* w, int ldw, const float* bias, float* y, int ldy, int M, int N, int K,
                int relu, int accumulate, float* ws, size_t ws_floats, hipStream_t stream) {
     LinearFwdProb p;
     HAB_TRY(build(p, x, ldx, w, ldw, bias, y, ldy, M, N, K, relu, accumulate));
-    if (dense_on() && dense_worth(M, N, K)) {
-        DenseArgs g{};
-        g.M = M; g.N = N; g.K = K; g.a = x; g.lda = ldx; g.b = w; g.ldb = ldw; g.c = y; g.ldc = ldy; g.bias = bias; g.relu = relu;
-        g.accumulate = accumulate; g.partial = ws;
-        g.a_bytes = ((long long)(M - 1) * ldx + K) * 4; g.b_bytes = ((long long)(N - 1) * ldw + K) * 4;
-        if (dense_bf3_ok(g, false, false)) {
-            g.nsplit = ws ? dense_bf3_splits(g, ws_floats) : 1;
-            HAB_TRY((dense_bf3_launch<0, 0>(g, stream)));
-            if (g.nsplit > 1) {
-                igemm_splitk_reduce<LinearFwdProb>(p, ws, g.nsplit, stream);
-                HAB_LAUNCH_CHECK();
-            }
-            return HAB_OK;
-        }
-    }
+    DenseArgs g{};
+    g.M = M; g.N = N; g.K = K; g.a = x; g.lda = ldx; g.b = w; g.ldb = ldw; g.c = y; g.ldc = ldy; g.bias = bias; g.relu = relu;
+    g.accumulate = accumulate;
+    g.a_bytes = ((long long)(M - 1) * ldx + K) * 4; g.b_bytes = ((long long)(N - 1) * ldw + K) * 4;
+    HAB_TRY_FORM((dense_try<0, 0>(g, p, ws, ws_floats, stream)));
     return run_igemm(p, ws, ws_floats, stream);
 }
 int linear_dgrad(const float* dy, int lddy, const float* w, int ldw, const float* mask, int ldmask, int mask_cols, float* dx,
                  int lddx, int M, int Nin, int Kout, int accumulate, float* ws, size_t ws_floats, hipStream_t stream) {
     LinearDgradProb p;
     HAB_TRY(build(p, dy, lddy, w, ldw, mask, ldmask, mask_cols, dx, lddx, M, Nin, Kout, accumulate));
-    if (dense_on() && !mask && dense_worth(M, Nin, Kout)) {  // dX[M][Nin] = dY[M][Kout] W[Kout][Nin]: W is the k-strided operand
+    if (!mask) {  // dX[M][Nin] = dY[M][Kout] W[Kout][Nin]: W is the k-strided operand
         DenseArgs g{};
         g.M = M; g.N = Nin; g.K = Kout; g.a = dy; g.lda = lddy; g.b = w; g.ldb = ldw; g.c = dx; g.ldc = lddx; g.accumulate = accumulate;
-        g.partial = ws;
         g.a_bytes = ((long long)(M - 1) * lddy + Kout) * 4; g.b_bytes = ((long long)(Kout - 1) * ldw + Nin) * 4;
-        if (dense_bf3_ok(g, false, true)) {
-            g.nsplit = ws ? dense_bf3_splits(g, ws_floats) : 1;
-            HAB_TRY((dense_bf3_launch<0, 1>(g, stream)));
-            if (g.nsplit > 1) {
-                igemm_splitk_reduce<LinearDgradProb>(p, ws, g.nsplit, stream);
-                HAB_LAUNCH_CHECK();
-            }
-            return HAB_OK;
-        }
+        HAB_TRY_FORM((dense_try<0, 1>(g, p, ws, ws_floats, stream)));
     }
     return run_igemm(p, ws, ws_floats, stream);
 }
@@ -327,21 +297,13 @@ int linear_wgrad(const float* dy, int lddy, const float* x, int ldx, float* dw, 
                  int perm_c, int perm_hw, int accumulate, float* ws, size_t ws_floats, hipStream_t stream) {
     LinearWgradProb p;
     HAB_TRY(build(p, dy, lddy, x, ldx, dw, lddw, Mrows, Nout, Kin, perm_c, perm_hw, accumulate));
-    if (dense_on() && dense_worth(Nout, Kin, Mrows)) {  // dW[Nout][Kin] = dY^T X: both operands are indexed by the frame = k-strided
-        DenseArgs g{};
-        g.M = Nout; g.N = Kin; g.K = Mrows; g.a = dy; g.lda = lddy; g.b = x; g.ldb = ldx; g.c = dw; g.ldc = lddw; g.accumulate = accumulate;
-        g.perm_c = perm_c; g.perm_hw = perm_hw; g.partial = ws;
-        g.a_bytes = ((long long)(Mrows - 1) * lddy + Nout) * 4; g.b_bytes = ((long long)(Mrows - 1) * ldx + Kin) * 4;
-        if (dense_bf3_ok(g, true, true)) {
-            g.nsplit = ws ? dense_bf3_splits(g, ws_floats) : 1;
-            HAB_TRY((dense_bf3_launch<1, 1>(g, stream)));
-            if (g.nsplit > 1) {  // (the reduction pass applies the flatten permutation and `accumulate`: LinearWgradProb::store)
-                igemm_splitk_reduce<LinearWgradProb>(p, ws, g.nsplit, stream);
-                HAB_LAUNCH_CHECK();
-            }
-            return HAB_OK;
-        }
-    }
+    // dW[Nout][Kin] = dY^T X: both operands are indexed by the frame = k-strided (the reduction pass applies the flatten permutation and
+    // `accumulate`: LinearWgradProb::store)
+    DenseArgs g{};
+    g.M = Nout; g.N = Kin; g.K = Mrows; g.a = dy; g.lda = lddy; g.b = x; g.ldb = ldx; g.c = dw; g.ldc = lddw; g.accumulate = accumulate;
+    g.perm_c = perm_c; g.perm_hw = perm_hw;
+    g.a_bytes = ((long long)(Mrows - 1) * lddy + Nout) * 4; g.b_bytes = ((long long)(Mrows - 1) * ldx + Kin) * 4;
+    HAB_TRY_FORM((dense_try<1, 1>(g, p, ws, ws_floats, stream)));
     return run_igemm(p, ws, ws_floats, stream);
 }
 

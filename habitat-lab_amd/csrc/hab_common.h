@@ -7,6 +7,9 @@
 #define HAB_OK 0
 #define HAB_ERR_ARG -1
 #define HAB_ERR_UNSUPPORTED -2
+// Internal: "this kernel form does not apply to the problem, try the next one".  Returned by the launch functions of the kernel
+// headers to their callers inside the library; it never crosses the C ABI (the entry points map it to HAB_ERR_UNSUPPORTED).
+#define HAB_NOT_APPLICABLE 1
 
 #define HAB_LAUNCH_CHECK()                                  \
     do {                                                    \
@@ -20,6 +23,13 @@
         if (r__ != 0) return r__;                           \
     } while (0)
 
+// Try one kernel form: return its result unless the form does not apply to this problem.
+#define HAB_TRY_FORM(expr)                                  \
+    do {                                                    \
+        int r__ = (int)(expr);                              \
+        if (r__ != HAB_NOT_APPLICABLE) return r__;          \
+    } while (0)
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -27,7 +37,7 @@ namespace hab {
 
 constexpr int WAVE = 64;
 
-// Development switches (HAB_NO_DMA, HAB_GN_STREAM, ...) select the older variant of a kernel for A/B measurements.  They are read
+// Development switches (HAB_GN_STREAM, HAB_BF3_NOSIGN, ...) select the older variant of a kernel for A/B measurements.  They are read
 // once per process: `static const bool off = hab_env_flag("HAB_...");` at the point of use.
 inline bool hab_env_flag(const char* name) { return getenv(name) != nullptr; }
 inline int hab_env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }

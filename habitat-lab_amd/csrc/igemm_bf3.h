@@ -443,7 +443,7 @@ inline int igemm_bf3_launch(const P& p, float* ws, size_t ws_floats, int target_
     if (attr_err != hipSuccess) return (int)attr_err;
     const int ntiles = cdiv(p.M, Cfg::BM) * cdiv(p.N, Cfg::BN);
     const int grid = pl.splits >= 16 ? ntiles * ((pl.splits + 7) / 8 * 8) : ntiles * pl.splits;
-    static const int sign_schedule = !hab_env_flag("HAB_BF3_NOSIGN");  // development: measure the cost of the sign schedule
+    const int sign_schedule = bf3_sign_schedule();
     static const int ablate = hab_env_int("HAB_BF3_ABLATE", 0);
     kern<<<grid, Cfg::NT, Cfg::LDS_BYTES, stream>>>(p, pl.k_per_split, ws, sign_schedule, pl.splits, ablate);
     HAB_LAUNCH_CHECK();

@@ -238,14 +238,14 @@ __global__ void __launch_bounds__(256) obs_conv_bf3_kernel(const ObsConvFwdProb 
     }
 }
 
-// returns HAB_OK, an error, or 1 when the problem / workspace does not fit this path (caller falls back to the generic kernels)
+// returns HAB_OK, an error, or HAB_NOT_APPLICABLE when the problem / workspace does not fit this path (caller falls back to the generic kernels)
 template <int TM>
 inline int obs_conv_bf3_launch(const ObsConvFwdProb& p, float* ws, size_t ws_floats, hipStream_t stream) {
     using Cfg = ObsBf3Cfg<TM>;
-    if (!p.quad || (p.K & 63) || p.M <= 0 || p.N <= 0) return 1;
+    if (!p.quad || (p.K & 63) || p.M <= 0 || p.N <= 0) return HAB_NOT_APPLICABLE;
     const int KT = p.K >> 6, NP = cdiv(p.N, 32) * 32;
     const size_t plane_bytes = (size_t)2 * 3 * KT * NP * OBF_BK * 2;  // +w and -w sets
-    if (!ws || ws_floats * 4 < plane_bytes || (reinterpret_cast<uintptr_t>(ws) & 15)) return 1;
+    if (!ws || ws_floats * 4 < plane_bytes || (reinterpret_cast<uintptr_t>(ws) & 15)) return HAB_NOT_APPLICABLE;
     unsigned short* planes = reinterpret_cast<unsigned short*>(ws);
     obs_conv_bf3_split_weights<<<cdiv(2 * NP * p.K, 256), 256, 0, stream>>>(p.w, p.N, p.K, NP, planes);
     HAB_LAUNCH_CHECK();

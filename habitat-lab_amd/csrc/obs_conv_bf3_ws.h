@@ -268,13 +268,13 @@ __global__ void __launch_bounds__(512) obs_conv_bf3_ws_kernel(const ObsConvFwdPr
     }
 }
 
-// returns HAB_OK, an error, or 1 when the problem / workspace does not fit this path (caller falls back to obs_conv_bf3_launch)
+// returns HAB_OK, an error, or HAB_NOT_APPLICABLE when the problem / workspace does not fit this path (caller falls back to obs_conv_bf3_launch)
 inline int obs_conv_bf3_ws_launch(const ObsConvFwdProb& p, float* ws, size_t ws_floats, hipStream_t stream) {
     using Cfg = ObsWsCfg;
-    if (!p.quad || p.K != 64 * Cfg::KT || p.M <= 0 || p.N <= 0 || p.N > 32 || (p.N & 3) || p.g.Ho * p.g.Wo < Cfg::BM) return 1;
+    if (!p.quad || p.K != 64 * Cfg::KT || p.M <= 0 || p.N <= 0 || p.N > 32 || (p.N & 3) || p.g.Ho * p.g.Wo < Cfg::BM) return HAB_NOT_APPLICABLE;
     const int NPAD = 32;
     const size_t plane_bytes = (size_t)2 * 3 * Cfg::KT * NPAD * OBF_BK * 2;  // +w and -w sets
-    if (!ws || ws_floats * 4 < plane_bytes || (reinterpret_cast<uintptr_t>(ws) & 15)) return 1;
+    if (!ws || ws_floats * 4 < plane_bytes || (reinterpret_cast<uintptr_t>(ws) & 15)) return HAB_NOT_APPLICABLE;
     unsigned short* planes = reinterpret_cast<unsigned short*>(ws);
     obs_conv_bf3_split_weights<<<cdiv(2 * NPAD * p.K, 256), 256, 0, stream>>>(p.w, p.N, p.K, NPAD, planes);
     HAB_LAUNCH_CHECK();

@@ -328,34 +328,34 @@ __global__ void __launch_bounds__(512) obs_conv_patch_kernel(const ObsConvFwdPro
 }
 
 // The weight image alone (packed forward weights [N][8][8][4] -> img, OCP_W_ELEMS bf16): what a caller that keeps the weights fixed over
-// many calls builds once.  1: this filter shape has no image.
+// many calls builds once.  HAB_NOT_APPLICABLE: this filter shape has no image.
 inline int obs_conv_patch_weight_image(const float* w_packed, int N, int KH, int KW, int C, unsigned short* img, hipStream_t stream) {
-    if (KH != 8 || KW != 8 || C != 4 || N > 32 || (N & 3) || !w_packed || !img || (reinterpret_cast<uintptr_t>(img) & 15)) return 1;
+    if (KH != 8 || KW != 8 || C != 4 || N > 32 || (N & 3) || !w_packed || !img || (reinterpret_cast<uintptr_t>(img) & 15)) return HAB_NOT_APPLICABLE;
     obs_patch_split_weights<<<32, 256, 0, stream>>>(w_packed, N, img);
     HAB_LAUNCH_CHECK();
     return HAB_OK;
 }
 
-// returns HAB_OK, an error, or 1 when the problem does not fit this path (caller falls back to the im2col kernels)
+// returns HAB_OK, an error, or HAB_NOT_APPLICABLE when the problem does not fit this path (caller falls back to the im2col kernels)
 // wimg_cached: the weight image of p.w built earlier by obs_conv_patch_weight_image (the engine keeps one per optimiser step) or null
 // (built here into the workspace, one more launch per call)
 inline int obs_conv_patch_launch(const ObsConvFwdProb& p, float* ws, size_t ws_floats, hipStream_t stream, const unsigned short* wimg_cached = nullptr) {
     const ConvGeom& g = p.g;
     if (!p.quad || g.KH != 8 || g.KW != 8 || g.stride != 4 || g.pad != 0 || p.N > 32 || (p.N & 3) || p.K != 256 || g.W > 256 || (g.W & 3) || g.Wo > 64 ||
         g.Wo < 1 || p.M <= 0)
-        return 1;
-    if (!wimg_cached && (!ws || ws_floats * 4 < (size_t)OCP_W_ELEMS * 2 || (reinterpret_cast<uintptr_t>(ws) & 15))) return 1;
-    if (reinterpret_cast<uintptr_t>(wimg_cached) & 15) return 1;
+        return HAB_NOT_APPLICABLE;
+    if (!wimg_cached && (!ws || ws_floats * 4 < (size_t)OCP_W_ELEMS * 2 || (reinterpret_cast<uintptr_t>(ws) & 15))) return HAB_NOT_APPLICABLE;
+    if (reinterpret_cast<uintptr_t>(wimg_cached) & 15) return HAB_NOT_APPLICABLE;
     ObsPatchGeom gq;
     gq.W = g.W; gq.H = g.H; gq.Ho = g.Ho; gq.Wo = g.Wo;
     gq.tiles_per_img = cdiv(g.Ho, OCP_TH);
     gq.ntiles = g.B * gq.tiles_per_img;
     gq.units = OCP_R * (g.W >> 2);
-    if (cdiv(gq.units, 256) > 5) return 1;
+    if (cdiv(gq.units, 256) > 5) return HAB_NOT_APPLICABLE;
     // the idle lane (wo = 63) of the last filter rows reads up to 64 bytes past P0 / P1 / P2 of its group's patch: inside the padding
     gq.patch_elems = OCP_R * g.W * 6 + 64;
     const size_t lds = ((size_t)2 * 32 * OCP_KP + 32 * OCP_DP + 64 + (size_t)2 * gq.patch_elems) * 2;
-    if (lds > 160 * 1024) return 1;
+    if (lds > 160 * 1024) return HAB_NOT_APPLICABLE;
     const unsigned short* wimg = wimg_cached;
     if (!wimg) {
         unsigned short* built = reinterpret_cast<unsigned short*>(ws);
@@ -367,7 +367,7 @@ inline int obs_conv_patch_launch(const ObsConvFwdProb& p, float* ws, size_t ws_f
     // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
     static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (attr_err != hipSuccess) return (int)attr_err;
-    static const int sign_schedule = !hab_env_flag("HAB_BF3_NOSIGN");
+    const int sign_schedule = bf3_sign_schedule();
     static const int ablate = hab_env_int("HAB_OCP_ABLATE", 0);
     const int pairs = (gq.ntiles + 1) / 2;
     const int grid = pairs < 256 ? (pairs + 7) / 8 * 8 : 256;

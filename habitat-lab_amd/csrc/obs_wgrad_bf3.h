@@ -200,10 +200,10 @@ __global__ void __launch_bounds__(256, 2) obs_wgrad_bf3_kernel(const ObsConvWgra
     }
 }
 
-// returns HAB_OK, an error, or 1 when the problem / workspace does not fit this path (caller falls back to the generic kernels)
+// returns HAB_OK, an error, or HAB_NOT_APPLICABLE when the problem / workspace does not fit this path (caller falls back to the generic kernels)
 inline int obs_wgrad_bf3_launch(const ObsConvWgradProb& p, float* ws, size_t ws_floats, hipStream_t stream) {
     const ConvGeom& g = p.g;
-    if (!p.quad || g.KH * g.KW != 64 || p.M != 256 || p.N > 32 || (p.N & 3) || g.pad != 0 || !ws) return 1;
+    if (!p.quad || g.KH * g.KW != 64 || p.M != 256 || p.N > 32 || (p.N & 3) || g.pad != 0 || !ws) return HAB_NOT_APPLICABLE;
     ObsWgradGeom gg;
     gg.WB = cdiv(g.Wo, OWG_BK);
     gg.tiles = g.B * g.Ho * gg.WB;
@@ -213,7 +213,7 @@ inline int obs_wgrad_bf3_launch(const ObsConvWgradProb& p, float* ws, size_t ws_
     int wgs = gg.tiles < wgs_env ? gg.tiles : wgs_env;
     const int MP = p.M + (p.colsum ? 1 : 0);
     while (wgs > 1 && (size_t)wgs * MP * p.N > ws_floats) wgs >>= 1;
-    if ((size_t)wgs * MP * p.N > ws_floats) return 1;
+    if ((size_t)wgs * MP * p.N > ws_floats) return HAB_NOT_APPLICABLE;
     gg.tiles_per_wg = cdiv(gg.tiles, wgs);
     wgs = cdiv(gg.tiles, gg.tiles_per_wg);
     // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)

@@ -19,7 +19,7 @@ int conv_fwd(const ConvDesc& d, const float* x, const float* wf, const float* bi
 int obs_conv_fwd(const ConvDesc& d, const ObsView& obs, const float* wf, const float* bias, float* y, int relu, float* ws,
                  size_t ws_floats, hipStream_t stream, const void* wimg = nullptr);
 int64_t obs_conv_weight_image_floats();
-int obs_conv_weight_image(const float* wf, int Cout, int KH, int KW, int C, void* img, hipStream_t stream);  // 1: no image for this filter
+int obs_conv_weight_image(const float* wf, int Cout, int KH, int KW, int C, void* img, hipStream_t stream);  // HAB_NOT_APPLICABLE: no image for this filter
 int conv_dgrad(const ConvDesc& d, const float* dy, const float* wd, const float* mask, const float* add, float* dx,
                float* ws, size_t ws_floats, hipStream_t stream);
 int conv_wgrad(const ConvDesc& d, const float* x, const float* dy, float* dw_oihw, float* dbias, float* ws, size_t ws_floats,
@@ -77,7 +77,7 @@ int rnn_frag_init(const float* h0, const int* env_rows, int env_stride, const ui
 int rnn_seq_layer_forward(int rnn_type, int H, const RnnLayerParams& lp, const RnnWork& wk, const float* x, int ldx,
                           const float* hinit, const float* cinit, const PackInfo& pk, float* ws, size_t ws_floats,
                           hipStream_t stream);
-// the L layers as a wavefront (one launch per packed step for all layers): 1 = form not applicable
+// the L layers as a wavefront (one launch per packed step for all layers): HAB_NOT_APPLICABLE where the form does not apply
 int rnn_seq_wave_forward(int rnn_type, int H, int L, const RnnLayerParams* lp, const RnnWork* wk, const float* x, int ldx,
                          const float* const* hinit, const float* const* cinit, const PackInfo& pk, float* ws, size_t ws_floats,
                          hipStream_t stream);
@@ -91,7 +91,26 @@ int rnn_seq_layer_backward(int rnn_type, int H, const RnnLayerParams& lp, const 
                            const float* dout, float* dx, int lddx, const float* dx_mask, int ldmask, int mask_cols,
                            const PackInfo& pk, float* scratch /* 3*F*H floats */, float* ws, size_t ws_floats,
                            hipStream_t stream);
-int matrix_path_bits();  // the current mask of hab_set_matrix_path (gemm_ops.hip)
+// The bits of hab_set_matrix_path's mask (env HAB_BF3): names for the table in include/habitat_amd.h, which describes each bit.
+// The values are ABI.  A bit marked "with" acts only together with the bit it names; the site that tests it asks for both.
+enum MatrixPath : int {
+    MP_RC = 1 << 0,            // r-contiguous x r-contiguous problems on the split-bf16 path (igemm_bf3.h)
+    MP_OBS = 1 << 1,           // observation-ingest convolution, forward and weight gradient (obs_conv_bf3.h, obs_wgrad_bf3.h)
+    MP_IJ = 1 << 2,            // problems with an i/j-contiguous operand: register-transposed staging
+    MP_IJ_WGRAD = 1 << 3,      // prefer MP_IJ's kernel over the fp32 patch / LDS-DMA weight-gradient kernels
+    MP_PATCH3X3 = 1 << 4,      // stride-1 3x3 convolutions with the input patch resident in LDS (conv_patch_bf3.h)
+    MP_WS = 1 << 5,            // producer / consumer waves where they won (igemm_bf3_ws.h; with MP_OBS: obs_conv_bf3_ws.h)
+    MP_OBS_PATCH = 1 << 6,     // with MP_OBS: observation patch resident in LDS (obs_conv_patch.h)
+    MP_WGRAD_STRIP = 1 << 7,   // with MP_IJ_WGRAD: strip-resident weight gradients (wgrad3x3_bf3.h)
+    MP_CONV2_FWD = 1 << 8,     // with MP_RC: SimpleCNN conv2 forward strip kernel (conv2_fwd_strip.h)
+    MP_CONV2_DGRAD = 1 << 9,   // with MP_RC: SimpleCNN conv2 data-gradient strip kernel (conv2_dgrad_strip.h)
+    MP_DENSE = 1 << 10,        // with MP_RC: large Linear layers on the plain dense GEMM kernel (dense_bf3.h)
+    MP_DENSE_ALL = 1 << 11,    // (tests) MP_DENSE's kernel for every shape it applies to
+    MP_RNN_STEPWISE = 1 << 12, // (tests) time-major recurrence as one launch per step instead of the persistent kernels (rnn_persist.h)
+    MP_DEFAULT = 2047,         // bits 0-10
+};
+int matrix_path_bits();  // the current mask (gemm_ops.hip)
+inline bool matrix_path_on(int bits) { return (matrix_path_bits() & bits) == bits; }  // all of `bits` are set
 // time-major form (regular T x n minibatch), chunkable in time: see rnn.hip
 int rnn_tm_prepare(const uint8_t* masks, const int* rows, int B, uint8_t* frame_mask, int* iota, hipStream_t stream);
 int rnn_tm_layer_forward(int rnn_type, int H, const RnnLayerParams& lp, const RnnWork& wk, const float* x, int ldx, const float* hinit,

@@ -192,15 +192,15 @@ struct ConvGnArgs {
 };
 int conv_gn_fused_ok(int C, int Cout, int H, int W, int KH, int KW, int stride, int pad, int groups);
 int weight_planes(const float* w, int Cout, int K, unsigned short* planes, hipStream_t s);  // fragment-ordered bf16 planes of the exact split
-int conv_gn_fused(const ConvGnArgs& a, hipStream_t s);  // 1: geometry not covered
+int conv_gn_fused(const ConvGnArgs& a, hipStream_t s);  // HAB_NOT_APPLICABLE: geometry not covered
 // stem convolution 7x7 / 2 / 3, 4 -> 32 channels with the input strip resident in LDS (stem_conv_strip.h)
 constexpr int STEM_PLANE_FLOATS = 3 * 14 * 1024 / 4;  // fragment-ordered bf16 planes of the filter, in floats of the packed arena
 int stem_conv_ok(int H, int W, int C, int Cout, int KH, int KW, int stride, int pad);
 int stem_weight_planes(const float* wf, unsigned short* planes, hipStream_t s);
 int stem_conv_forward(const float* x, const unsigned short* planes, float* y, int B, int H, int W, hipStream_t s, const float* norm = nullptr,
                       float* gn_part = nullptr, int gn_groups = 0);  // gn_part: [B][ceil(Ho / STEM_STAT_ROWS)][groups][2] partial statistics
-constexpr int STEM_STAT_ROWS = 8;  // 1: not covered
-// its weight gradient, both operands resident in LDS, transpose reads (stem_wgrad_strip.h); ws >= 256 * 7 * 1024 floats; 1: not covered
+constexpr int STEM_STAT_ROWS = 8;  // HAB_NOT_APPLICABLE: not covered
+// its weight gradient, both operands resident in LDS, transpose reads (stem_wgrad_strip.h); ws >= 256 * 7 * 1024 floats; HAB_NOT_APPLICABLE: not covered
 int stem_conv_wgrad(const float* x, const float* dy, float* dw_oihw, int B, int H, int W, int creal, float* ws, size_t ws_floats, hipStream_t s,
                     const float* norm = nullptr);
 int stem_wgrad_ok(int H, int W, int C, int Cout, int KH, int KW, int stride, int pad);

@@ -1248,7 +1248,7 @@ int groupnorm_relu_maxpool_forward(const GnArgs& a, int H, int W, float* pool, u
     if ((a.mean == nullptr) != (a.rstd == nullptr)) return HAB_ERR_ARG;
     HAB_TRY(gn_check(a.B, a.C, a.groups));
     int nt, nv, nchunks;
-    if (gn_reg_cfg(a.HW, a.C, nt, nv)) return 1;
+    if (gn_reg_cfg(a.HW, a.C, nt, nv)) return HAB_NOT_APPLICABLE;
     const float* part = a.scratch;
     int chunk4 = GNC_NT * GNC_NV_F;
     if (ext_part) {
@@ -1257,7 +1257,7 @@ int groupnorm_relu_maxpool_forward(const GnArgs& a, int H, int W, float* pool, u
         chunk4 = ext_rows * W * (a.C / 4);
         nchunks = cdiv(H, ext_rows);
     } else {
-        if (!a.scratch || !gn_chunk_cfg(a.B, a.HW, a.C, (size_t)a.groups * 2, a.scratch_floats, GNC_NT * GNC_NV_F, nchunks)) return 1;
+        if (!a.scratch || !gn_chunk_cfg(a.B, a.HW, a.C, (size_t)a.groups * 2, a.scratch_floats, GNC_NT * GNC_NV_F, nchunks)) return HAB_NOT_APPLICABLE;
         const size_t lds1 = (size_t)(GNC_NT * 4 + a.C + a.groups) * sizeof(float);
         gn_chunk_stats_kernel<GNC_NT, GNC_NV_F><<<a.B * nchunks, GNC_NT, lds1, s>>>(a, nchunks, a.scratch);
         HAB_LAUNCH_CHECK();

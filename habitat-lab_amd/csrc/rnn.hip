@@ -279,14 +279,14 @@ int rnn_seq_layer_forward(int rnn_type, int H, const RnnLayerParams& lp, const R
 // Layer 0 reads its input projection from the one large contraction over all frames, as in rnn_seq_layer_forward; a layer above cannot
 // (its input is finished step by step), so its projection runs inside the step kernel (the rollout's fused form) on the rows the layer
 // below wrote in the previous launch.  Saves for BPTT as in the layer-by-layer form; wk[l].gi of the upper layers is not written.
-// Returns 1 when the form does not apply (the caller runs layer by layer).
+// Returns HAB_NOT_APPLICABLE when the form does not apply (the caller runs layer by layer).
 int rnn_seq_wave_forward(int rnn_type, int H, int L, const RnnLayerParams* lp, const RnnWork* wk, const float* x, int ldx,
                          const float* const* hinit, const float* const* cinit, const PackInfo& pk, float* ws, size_t ws_floats,
                          hipStream_t stream) {
     const int G = rnn_type == RNN_GRU ? 3 : 4;
-    if (L < 2 || L > RNN_MAX_WAVE_LAYERS || (H % 64) || pk.max_len < 1) return 1;
+    if (L < 2 || L > RNN_MAX_WAVE_LAYERS || (H % 64) || pk.max_len < 1) return HAB_NOT_APPLICABLE;
     for (int l = 1; l < L; ++l)
-        if (!lp[l].w_ih_pad || lp[l].w_ih_ld != H || (reinterpret_cast<uintptr_t>(lp[l].w_ih_pad) & 15)) return 1;
+        if (!lp[l].w_ih_pad || lp[l].w_ih_ld != H || (reinterpret_cast<uintptr_t>(lp[l].w_ih_pad) & 15)) return HAB_NOT_APPLICABLE;
     HAB_TRY(linear_fwd(x, ldx, lp[0].w_ih, lp[0].in_dim, lp[0].b_ih, wk[0].gi, G * H, pk.P, G * H, lp[0].in_dim, 0, 0, ws, ws_floats, stream));
     const bool wide = H % 128 == 0;
     for (int w = 0; w < pk.max_len + L - 1; ++w) {
@@ -549,14 +549,14 @@ int rnn_seq_layer_backward(int rnn_type, int H, const RnnLayerParams& lp, const 
 // the gradient wrt its output inside its step kernel from the layer above's dgi of the same step (BwdStepArgs::up_dgi) -- the data
 // gradient contraction of the upper layers is gone.  Then the parameter gradients of every layer and layer 0's data gradient as in
 // rnn_seq_layer_backward.  w_ih_t[l]: W_ih of layer l transposed, [H][G * H] (l >= 1).  scratch: L * 2 * F * H floats.
-// Returns 1 when the form does not apply.
+// Returns HAB_NOT_APPLICABLE when the form does not apply.
 int rnn_seq_wave_backward(int rnn_type, int H, int L, const RnnLayerParams* lp, const float* const* w_ih_t, const RnnWork* wk, const float* x0,
                           int ldx0, const float* dout, float* dx0, int lddx0, const float* dx_mask, int ldmask, int mask_cols,
                           const PackInfo& pk, float* scratch, float* ws, size_t ws_floats, hipStream_t stream) {
     const int G = rnn_type == RNN_GRU ? 3 : 4;
-    if (L < 2 || L > RNN_MAX_WAVE_LAYERS || (H % 64) || pk.max_len < 1) return 1;
+    if (L < 2 || L > RNN_MAX_WAVE_LAYERS || (H % 64) || pk.max_len < 1) return HAB_NOT_APPLICABLE;
     for (int l = 1; l < L; ++l)
-        if (!w_ih_t[l] || lp[l].in_dim != H || (reinterpret_cast<uintptr_t>(w_ih_t[l]) & 15)) return 1;
+        if (!w_ih_t[l] || lp[l].in_dim != H || (reinterpret_cast<uintptr_t>(w_ih_t[l]) & 15)) return HAB_NOT_APPLICABLE;
     const int K = G * H;
     const bool wide = K % 128 == 0;
     for (int w = 0; w < pk.max_len + L - 1; ++w) {
@@ -638,7 +638,7 @@ int rnn_tm_prepare(const uint8_t* masks, const int* rows, int B, uint8_t* frame_
 static bool tm_persist_ok(int rnn_type, int H, int n, int T, const float* ws, size_t ws_floats) {
     static const bool on = hab_env_int("HAB_RNN_PERSIST", 1) != 0;
     const int G = rnn_type == RNN_GRU ? 3 : 4;
-    if (!on || (matrix_path_bits() & 4096) || !ws || ws_floats < 64) return false;
+    if (!on || matrix_path_on(MP_RNN_STEPWISE) || !ws || ws_floats < 64) return false;
     if (H != 128 && H != 256 && H != 512) return false;
     if (cdiv(n, 16) > RNNP_MAX_ROW_TILES) return false;
     if ((size_t)T * n * G * H * 4 >= ((size_t)1 << 31)) return false;

@@ -258,21 +258,20 @@ inline bool stem_conv_strip_covers(int H, int W, int C, int Cout, int KH, int KW
     return STEM_W_BYTES + (size_t)3 * STEM_ROWS * PW * 8 + STEM_STAT_FLOATS * sizeof(float) <= 160 * 1024;
 }
 
-// 1: geometry not covered.
+// HAB_NOT_APPLICABLE: geometry not covered.
 // part / groups: GroupNorm partial statistics of the output per (frame, strip of 8 rows, group), see the kernel; groups in {8, 16, 32}
 inline int stem_conv_strip(const float* x, const unsigned short* wq, float* y, int B, int H, int W, hipStream_t stream,
                            const float* norm = nullptr, float* part = nullptr, int groups = 0) {
     if (!x || !wq || !y || B <= 0 || (reinterpret_cast<uintptr_t>(norm) & 15)) return HAB_ERR_ARG;
     if (part && groups != 8 && groups != 16 && groups != 32) return HAB_ERR_ARG;
-    if (!stem_conv_strip_covers(H, W, 4, 32, 7, 7, 2, 3)) return 1;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wq) | reinterpret_cast<uintptr_t>(y)) & 15) return 1;
+    if (!stem_conv_strip_covers(H, W, 4, 32, 7, 7, 2, 3)) return HAB_NOT_APPLICABLE;
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wq) | reinterpret_cast<uintptr_t>(y)) & 15) return HAB_NOT_APPLICABLE;
     StemArgs a;
     a.x = x; a.wq = wq; a.y = y; a.B = B; a.H = H; a.W = W; a.norm = norm; a.part = part;
     a.Ho = (H + 6 - 7) / 2 + 1; a.Wo = (W + 6 - 7) / 2 + 1;
     a.PW = (2 * a.Wo + 6 + 1) & ~1;
     a.strips = (a.Ho + STEM_TH - 1) / STEM_TH;
-    static const int sign_schedule = !hab_env_flag("HAB_BF3_NOSIGN");
-    a.sign_schedule = sign_schedule;
+    a.sign_schedule = bf3_sign_schedule();
     const size_t lds = STEM_W_BYTES + (size_t)3 * STEM_ROWS * a.PW * 8 + STEM_STAT_FLOATS * sizeof(float);
     static const hipError_t attr_err = [] {
         hipError_t e = hipSuccess;
@@ -285,7 +284,7 @@ inline int stem_conv_strip(const float* x, const unsigned short* wq, float* y, i
         return e;
     }();
     if (attr_err != hipSuccess) return (int)attr_err;
-    if ((long long)B * a.strips > 0x7fffffffLL) return 1;
+    if ((long long)B * a.strips > 0x7fffffffLL) return HAB_NOT_APPLICABLE;
     const int cpg = part ? 32 / groups : 0;
     if (cpg == 0) stem_conv_strip_kernel<0><<<B * a.strips, 512, lds, stream>>>(a);
     else if (cpg == 1) stem_conv_strip_kernel<1><<<B * a.strips, 512, lds, stream>>>(a);

@@ -208,24 +208,23 @@ inline bool stem_wgrad_strip_covers(int H, int W, int C, int Cout, int KH, int K
     return (size_t)3 * SWG_XROWS * PW * 8 + (size_t)3 * SWG_TH * Wo * 64 <= 160 * 1024;
 }
 
-// 1: geometry not covered (or the scratch is too small).  ws: >= 256 * 7 * 1024 floats.
+// HAB_NOT_APPLICABLE: geometry not covered (or the scratch is too small).  ws: >= 256 * 7 * 1024 floats.
 inline int stem_wgrad_strip(const float* x, const float* dy, float* dw_oihw, int B, int H, int W, int creal, float* ws, size_t ws_floats,
                             hipStream_t stream, const float* norm = nullptr) {
     if (!x || !dy || !dw_oihw || B <= 0 || creal < 1 || creal > 4 || (reinterpret_cast<uintptr_t>(norm) & 15)) return HAB_ERR_ARG;
-    if (!stem_wgrad_strip_covers(H, W, 4, 32, 7, 7, 2, 3) || !ws) return 1;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(ws)) & 15) return 1;
+    if (!stem_wgrad_strip_covers(H, W, 4, 32, 7, 7, 2, 3) || !ws) return HAB_NOT_APPLICABLE;
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(ws)) & 15) return HAB_NOT_APPLICABLE;
     StemWgArgs a;
     a.x = x; a.dy = dy; a.slabs = ws; a.B = B; a.H = H; a.W = W; a.norm = norm;
     a.Ho = (H + 6 - 7) / 2 + 1; a.Wo = (W + 6 - 7) / 2 + 1;
     a.PW = (2 * a.Wo + 6 + 1) & ~1;
     a.strips = (a.Ho + SWG_TH - 1) / SWG_TH;
-    if ((long long)B * a.strips > 0x7fffffffLL) return 1;
+    if ((long long)B * a.strips > 0x7fffffffLL) return HAB_NOT_APPLICABLE;
     a.items = B * a.strips;
-    static const int sign_schedule = !hab_env_flag("HAB_BF3_NOSIGN");
-    a.sign_schedule = sign_schedule;
+    a.sign_schedule = bf3_sign_schedule();
     int grid = 256;
     while (grid > 8 && grid > a.items) grid -= 8;
-    if ((size_t)grid * 7 * 1024 > ws_floats) return 1;
+    if ((size_t)grid * 7 * 1024 > ws_floats) return HAB_NOT_APPLICABLE;
     const size_t lds = (size_t)3 * SWG_XROWS * a.PW * 8 + (size_t)3 * SWG_TH * a.Wo * 64;
     static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(stem_wgrad_strip_kernel),
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

@@ -249,8 +249,7 @@ inline int wgrad3x3_bf3_run(const ConvWgradProb& p, float* ws, size_t ws_floats,
     a.x = p.x; a.dy = p.dy; a.partial = ws; a.B = g.B; a.H = g.H; a.Ho = g.Ho;
     a.strips = g.Ho / R;
     a.items = g.B * a.strips;
-    static const int sign_schedule = !hab_env_flag("HAB_BF3_NOSIGN");
-    a.sign_schedule = sign_schedule;
+    a.sign_schedule = bf3_sign_schedule();
     a.colsum = p.colsum != nullptr;
     auto kern = wgrad3x3_bf3_kernel<C32, N32, W, PAD, KHW, S, R, KS, NS>;
     // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
@@ -281,7 +280,7 @@ inline int wgrad3x3_bf3_shape(const ConvWgradProb& p) {
     return 0;
 }
 // p.colsum (bias gradient) is produced by the same pass: dY goes through the workgroups' registers anyway.
-// Returns 1 when the workspace cannot hold the slabs of a chip-filling launch (the caller falls back to the implicit-GEMM form).
+// Returns HAB_NOT_APPLICABLE when the workspace cannot hold the slabs of a chip-filling launch (the caller falls back to the implicit-GEMM form).
 inline int wgrad3x3_bf3(const ConvWgradProb& p, float* ws, size_t ws_floats, hipStream_t stream) {
     if (!ws) return HAB_ERR_ARG;
     // Instances (measured at 2048 frames, kernel + slab reduction; implicit-GEMM weight gradient before):
