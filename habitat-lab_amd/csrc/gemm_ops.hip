@@ -13,6 +13,7 @@
 #include "conv2_fwd_strip.h"
 #include "conv2_dgrad_strip.h"
 #include "obs_wgrad_bf3.h"
+#include "obs_wgrad_strip.h"
 #include "conv_patch_bf3.h"
 #include "wgrad3x3_patch.h"
 #include "prob_build.h"
@@ -238,12 +239,22 @@ int conv_wgrad(const ConvDesc& d, const float* x, const float* dy, float* dw_oih
     }
     return run_igemm(p, ws, ws_floats, stream);
 }
+// The form of conv1's weight gradient for a problem and workspace (HAB_OBS_WGRAD_FORM_*): uint8 x split-bf16 dY on the matrix pipe
+// under MP_OBS for more than 4096 output pixels -- with MP_OBS_PATCH the observation rows resident in LDS (obs_wgrad_strip.h), else or
+// where that form does not cover the geometry the im2col gather (obs_wgrad_bf3.h) -- and the igemm tiles for everything else.
+// obs_conv_wgrad and hab_obs_conv2d_wgrad_form both ask it.
+static int choose_obs_wgrad(const ObsConvWgradProb& p, const float* ws, size_t ws_floats) {
+    if (!(matrix_path_on(MP_OBS) && p.quad && p.K > 4096)) return HAB_OBS_WGRAD_FORM_IGEMM;
+    if (matrix_path_on(MP_OBS_PATCH | MP_OBS) && obs_wgrad_strip_covers(p, ws, ws_floats)) return HAB_OBS_WGRAD_FORM_STRIP;
+    return obs_wgrad_bf3_covers(p, ws, ws_floats) ? HAB_OBS_WGRAD_FORM_IM2COL : HAB_OBS_WGRAD_FORM_IGEMM;
+}
 int obs_conv_wgrad(const ConvDesc& d, const ObsView& obs, const float* dy, float* dw_oihw, float* dbias, float* ws,
                    size_t ws_floats, hipStream_t stream) {
     ObsConvWgradProb p;
     HAB_TRY(build(p, d, obs, dy, dw_oihw, dbias));
-    if (matrix_path_on(MP_OBS) && p.quad && p.K > 4096)  // uint8 x split-bf16 dY on the matrix pipe (obs_wgrad_bf3.h)
-        HAB_TRY_FORM(obs_wgrad_bf3_launch(p, ws, ws_floats, stream));
+    const int form = choose_obs_wgrad(p, ws, ws_floats);
+    if (form == HAB_OBS_WGRAD_FORM_STRIP) HAB_TRY_FORM(obs_wgrad_strip_launch(p, ws, ws_floats, stream));
+    if (form >= HAB_OBS_WGRAD_FORM_IM2COL) HAB_TRY_FORM(obs_wgrad_bf3_launch(p, ws, ws_floats, stream));
     return run_igemm(p, ws, ws_floats, stream);
 }
 
@@ -513,6 +524,16 @@ extern "C" int hab_obs_conv2d_wgrad(const uint8_t* rgb, const float* depth, cons
     if ((!rgb && !depth) || !dy || !dw_oihw) return HAB_ERR_ARG;
     ObsView o = mkobs(rgb, depth, rows, H, W);
     return obs_conv_wgrad(mk(B, H, W, o.C, Cout, KH, KW, stride, pad), o, dy, dw_oihw, dbias, ws, ws_floats, stream);
+}
+extern "C" int hab_obs_conv2d_wgrad_form(const uint8_t* rgb, const float* depth, const int* rows, const float* dy, float* dw_oihw,
+                                         float* dbias, int B, int H, int W, int Cout, int KH, int KW, int stride, int pad, const float* ws,
+                                         size_t ws_floats) {
+    if ((!rgb && !depth) || !dy || !dw_oihw) return HAB_ERR_ARG;
+    ObsView o = mkobs(rgb, depth, rows, H, W);
+    ObsConvWgradProb p;
+    const int r = build(p, mk(B, H, W, o.C, Cout, KH, KW, stride, pad), o, dy, dw_oihw, dbias);
+    if (r != HAB_OK) return r;
+    return choose_obs_wgrad(p, ws, ws_floats);
 }
 extern "C" int hab_linear_fwd(const float* x, int ldx, const float* w, int ldw, const float* bias, float* y, int ldy, int M,
                               int N, int K, int relu, int accumulate, float* ws, size_t ws_floats, hipStream_t stream) {

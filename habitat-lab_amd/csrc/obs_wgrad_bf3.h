@@ -200,11 +200,17 @@ __global__ void __launch_bounds__(256, 2) obs_wgrad_bf3_kernel(const ObsConvWgra
     }
 }
 
-// returns HAB_OK, an error, or HAB_NOT_APPLICABLE when the problem / workspace does not fit this path (caller falls back to the generic kernels)
-inline int obs_wgrad_bf3_launch(const ObsConvWgradProb& p, float* ws, size_t ws_floats, hipStream_t stream) {
+// the problems of this path: quad-gatherable RGB-D, 64 taps, Cout <= 32, no padding, and room for one slab at least in the workspace
+inline bool obs_wgrad_bf3_covers(const ObsConvWgradProb& p, const float* ws, size_t ws_floats) {
     const ConvGeom& g = p.g;
-    if (!p.quad || g.KH * g.KW != 64 || p.M != 256 || p.N > 32 || (p.N & 3) || g.pad != 0 || !ws) return HAB_NOT_APPLICABLE;
-    ObsWgradGeom gg;
+    if (!p.quad || g.KH * g.KW != 64 || p.M != 256 || p.N > 32 || (p.N & 3) || g.pad != 0 || !ws) return false;
+    return (size_t)(p.M + (p.colsum ? 1 : 0)) * p.N <= ws_floats;
+}
+
+// Tiles (img, ho, 64-pixel block of wo) over workgroups, one slab each: as many workgroups, up to 512, as the workspace has slabs for.
+// Returns the number of workgroups.  Shared by the two forms of the kernel (obs_wgrad_strip.h), whose slabs are therefore the same sums.
+inline int obs_wgrad_partition(const ObsConvWgradProb& p, size_t ws_floats, ObsWgradGeom& gg) {
+    const ConvGeom& g = p.g;
     gg.WB = cdiv(g.Wo, OWG_BK);
     gg.tiles = g.B * g.Ho * gg.WB;
     gg.dWB = FastDiv(gg.WB);
@@ -213,21 +219,22 @@ inline int obs_wgrad_bf3_launch(const ObsConvWgradProb& p, float* ws, size_t ws_
     int wgs = gg.tiles < wgs_env ? gg.tiles : wgs_env;
     const int MP = p.M + (p.colsum ? 1 : 0);
     while (wgs > 1 && (size_t)wgs * MP * p.N > ws_floats) wgs >>= 1;
-    if ((size_t)wgs * MP * p.N > ws_floats) return HAB_NOT_APPLICABLE;
     gg.tiles_per_wg = cdiv(gg.tiles, wgs);
-    wgs = cdiv(gg.tiles, gg.tiles_per_wg);
+    return cdiv(gg.tiles, gg.tiles_per_wg);
+}
+
+// returns HAB_OK, an error, or HAB_NOT_APPLICABLE when the problem / workspace does not fit this path (caller falls back to the generic kernels)
+inline int obs_wgrad_bf3_launch(const ObsConvWgradProb& p, float* ws, size_t ws_floats, hipStream_t stream) {
+    if (!obs_wgrad_bf3_covers(p, ws, ws_floats)) return HAB_NOT_APPLICABLE;
+    ObsWgradGeom gg;
+    const int wgs = obs_wgrad_partition(p, ws_floats, gg);
     // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
     static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(obs_wgrad_bf3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)OWG_LDS_BYTES);
     if (attr_err != hipSuccess) return (int)attr_err;
     obs_wgrad_bf3_kernel<<<wgs, 256, OWG_LDS_BYTES, stream>>>(p, gg, ws);
     HAB_LAUNCH_CHECK();
-    if (wgs > 1) {
-        igemm_splitk_reduce<ObsConvWgradProb>(p, ws, wgs, stream);
-        HAB_LAUNCH_CHECK();
-    } else {
-        igemm_splitk_reduce<ObsConvWgradProb>(p, ws, 1, stream);
-        HAB_LAUNCH_CHECK();
-    }
+    igemm_splitk_reduce<ObsConvWgradProb>(p, ws, wgs, stream);
+    HAB_LAUNCH_CHECK();
     return HAB_OK;
 }
 

@@ -100,7 +100,7 @@ enum MatrixPath : int {
     MP_IJ_WGRAD = 1 << 3,      // prefer MP_IJ's kernel over the fp32 patch / LDS-DMA weight-gradient kernels
     MP_PATCH3X3 = 1 << 4,      // stride-1 3x3 convolutions with the input patch resident in LDS (conv_patch_bf3.h)
     MP_WS = 1 << 5,            // producer / consumer waves where they won (igemm_bf3_ws.h; with MP_OBS: obs_conv_bf3_ws.h)
-    MP_OBS_PATCH = 1 << 6,     // with MP_OBS: observation patch resident in LDS (obs_conv_patch.h)
+    MP_OBS_PATCH = 1 << 6,     // with MP_OBS: observations resident in LDS, forward patch (obs_conv_patch.h) and weight-gradient rows (obs_wgrad_strip.h)
     MP_WGRAD_STRIP = 1 << 7,   // with MP_IJ_WGRAD: strip-resident weight gradients (wgrad3x3_bf3.h)
     MP_CONV2_FWD = 1 << 8,     // with MP_RC: SimpleCNN conv2 forward strip kernel (conv2_fwd_strip.h)
     MP_CONV2_DGRAD = 1 << 9,   // with MP_RC: SimpleCNN conv2 data-gradient strip kernel (conv2_dgrad_strip.h)

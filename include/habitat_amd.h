@@ -336,7 +336,8 @@ int hab_sample_actions(const float* probs, const float* exp_noise, int64_t* acti
  *     bit 4  stride-1 3x3 convolutions with N = 32 (fwd + dgrad): input patch resident in LDS (conv_patch_bf3.h)
  *     bit 5  producer / consumer waves where they measured faster (igemm_bf3_ws.h: 128 x 128 forward-form tiles with K >= 2048;
  *            obs_conv_bf3_ws.h: the observation-ingest convolution); bit-identical results
- *     bit 6  the observation-ingest convolution (8x8 / 4, RGB-D -> 32) with the input patch resident in LDS (obs_conv_patch.h)
+ *     bit 6  (with bit 1) the observation-ingest convolution (8x8 / 4, RGB-D -> 32) with its input resident in LDS: the forward's input
+ *            patch (obs_conv_patch.h) and the weight gradient's observation rows (obs_wgrad_strip.h; bitwise the results of bit 1 alone)
  *     bit 7  (with bit 3) weight gradient of the small-channel convolutions -- SimpleCNN conv2 (4x4 / 2) and conv3, ResNet layer1 and
  *            layer2 at 128^2 -- with the strip resident in LDS in pixel-major layout, fragments by LDS transpose reads
  *            (wgrad3x3_bf3.h)
@@ -368,6 +369,16 @@ int hab_conv2d_wgrad(const float* x, const float* dy, float* dw_oihw, float* dbi
 int hab_obs_conv2d_wgrad(const uint8_t* rgb, const float* depth, const int* rows, const float* dy, float* dw_oihw,
                          float* dbias, int B, int H, int W, int Cout, int KH, int KW, int stride, int pad, float* ws,
                          size_t ws_floats, hipStream_t stream);
+/* Which kernel hab_obs_conv2d_wgrad runs for such a call under the current matrix-path mask: 0 the igemm tiles, 1 the im2col gather on
+ * the bf16 matrix pipe (obs_wgrad_bf3.h), 2 the same arithmetic with the observation rows resident in LDS (obs_wgrad_strip.h), or a
+ * negative HAB_ERR_* where the call itself would be refused.  Host only: nothing is launched and no pointer is read (null-ness and
+ * alignment count).  The launcher asks the same function.  For tests and tools. */
+#define HAB_OBS_WGRAD_FORM_IGEMM 0
+#define HAB_OBS_WGRAD_FORM_IM2COL 1
+#define HAB_OBS_WGRAD_FORM_STRIP 2
+int hab_obs_conv2d_wgrad_form(const uint8_t* rgb, const float* depth, const int* rows, const float* dy, float* dw_oihw,
+                              float* dbias, int B, int H, int W, int Cout, int KH, int KW, int stride, int pad, const float* ws,
+                              size_t ws_floats);
 int hab_linear_fwd(const float* x, int ldx, const float* w, int ldw, const float* bias, float* y, int ldy, int M, int N,
                    int K, int relu, int accumulate, float* ws, size_t ws_floats, hipStream_t stream);
 int hab_linear_dgrad(const float* dy, int lddy, const float* w, int ldw, const float* relu_mask, int ldmask, float* dx,
