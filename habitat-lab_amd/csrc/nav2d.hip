@@ -6,7 +6,9 @@
 // a step and the render; their specifications are tests/nav2d_vel_reference.py and tests/nav2d_obj_reference.py.
 // The geodesic distance mode of the first two tasks (nav2d_geo_build_kernel, the GEO forms of the step kernels) is specified by
 // tests/nav2d_geo_reference.py, that of Nav2DObj-v0 (nav2d_obj_geo_build_kernel, nav2d_obj_geo_step_kernel: the distance to the
-// nearest instance of the target category) by tests/nav2d_obj_geo_reference.py.
+// nearest instance of the target category) by tests/nav2d_obj_geo_reference.py.  Nav2DRearr-v0 (one object to pick up and to put down
+// at a goal that only the 1-D sensors tell) shares the world, the placement of Nav2DObj-v0 and the render; its specification is
+// tests/nav2d_rearr_reference.py.
 #include <cstddef>
 #include "hab_common.h"
 #include "../../include/habitat_amd.h"
@@ -74,6 +76,29 @@ static_assert(offsetof(Nav2DObjState, h0) == 4 * HAB_NAV2D_OBJ_W_START_HEADING &
               "Nav2DObjState layout");
 static_assert(offsetof(Nav2DObjState, obj) == 4 * HAB_NAV2D_OBJ_W_OBJECTS && offsetof(Nav2DObjState, cat) == 4 * HAB_NAV2D_OBJ_W_CATEGORIES,
               "Nav2DObjState layout");
+
+// One env of Nav2DRearr-v0: a Nav2D-v0 record (gx, gy = the goal position, d_prev = the potential after the last step, d_start = the
+// episode's first), then the agent's start and the two places of the episode in the order they are drawn (the object's start, the
+// goal), named as place_positions reads them, the object's position (the agent's while it is held), the holding flag and the
+// episode's counters.
+struct Nav2DRearrState {
+    Nav2DState base;
+    float sx, sy;
+    float obj[2][2];            // object start (x, y), goal (x, y)
+    float ox, oy;
+    int32_t holding, held, picks, invalid;
+};
+static_assert(sizeof(Nav2DRearrState) == HAB_NAV2D_REARR_STATE_BYTES && offsetof(Nav2DRearrState, base) == 0, "Nav2DRearrState layout");
+static_assert(offsetof(Nav2DRearrState, sx) == 4 * HAB_NAV2D_REARR_W_START && offsetof(Nav2DRearrState, sy) == 4 * HAB_NAV2D_REARR_W_START + 4,
+              "Nav2DRearrState layout");
+static_assert(offsetof(Nav2DRearrState, obj) == 4 * HAB_NAV2D_REARR_W_OBJ_START &&
+              offsetof(Nav2DRearrState, obj) + 8 == 4 * HAB_NAV2D_REARR_W_GOAL && offsetof(Nav2DRearrState, ox) == 4 * HAB_NAV2D_REARR_W_OBJ,
+              "Nav2DRearrState layout");
+static_assert(offsetof(Nav2DRearrState, oy) == 4 * HAB_NAV2D_REARR_W_OBJ + 4, "Nav2DRearrState layout");
+static_assert(offsetof(Nav2DRearrState, holding) == 4 * HAB_NAV2D_REARR_W_HOLDING && offsetof(Nav2DRearrState, held) == 4 * HAB_NAV2D_REARR_W_HELD,
+              "Nav2DRearrState layout");
+static_assert(offsetof(Nav2DRearrState, picks) == 4 * HAB_NAV2D_REARR_W_PICKS && offsetof(Nav2DRearrState, invalid) == 4 * HAB_NAV2D_REARR_W_INVALID,
+              "Nav2DRearrState layout");
 
 // Correctly rounded square root.  NOT `__fsqrt_rn`: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers define that name as the
 // native (1 ulp) square root; `sqrtf` is the IEEE one under hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt.
@@ -426,8 +451,9 @@ __device__ inline bool is_free_obj(float x, float y, const Nav2DObjState& s, int
         if (dist(x, y, s.obj[j][0], s.obj[j][1]) < OBJ_BLOCK) return false;
     return true;
 }
-// Whether (x, y) can take object j: clear of the start and of the objects before it.
-__device__ inline bool object_fits(float x, float y, const Nav2DObjState& s, int j) {
+// Whether (x, y) can take object j: clear of the start and of the objects before it.  S: a record with the start (sx, sy) and obj.
+template <class S>
+__device__ inline bool object_fits(float x, float y, const S& s, int j) {
     if (!(dist(s.sx, s.sy, x, y) >= OBJ_APART)) return false;
     for (int i = 0; i < j; ++i)
         if (!(dist(s.obj[i][0], s.obj[i][1], x, y) >= OBJ_APART)) return false;
@@ -451,23 +477,25 @@ __device__ inline float nearest_target(Nav2DObjState& s, int M) {
     }
     return best;
 }
-// What Nav2DObj-v0 adds to a world that `begin_episode<false>` has just generated: the start pose the gps / compass sensors refer to,
-// the objects, the target, and the distances.
-__device__ void place_objects(Nav2DObjState& s, uint32_t seed, uint32_t env, int K, int M, int C) {
-    const uint32_t ep = (uint32_t)s.base.episode;
-    s.sx = s.base.px; s.sy = s.base.py; s.h0 = s.base.heading;
-    const uint32_t kp = stream_key(seed, S_OBJ_POS, env, ep), kc = stream_key(seed, S_OBJ_CAT, env, ep);
+// Whether (x, y) lies strictly inside one of the K rectangles grown by the object radius.
+__device__ inline bool in_grown_rect(float x, float y, const Nav2DState& s, int K) {
+    bool in_rect = false;
+    for (int k = 0; k < K; ++k)
+        in_rect = in_rect || (x > s.rect[k][0] - OBJ_R && x < s.rect[k][2] + OBJ_R && y > s.rect[k][1] - OBJ_R && y < s.rect[k][3] + OBJ_R);
+    return in_rect;
+}
+// The positions of M objects in the world of `s.base`, whose start (sx, sy) the record holds.  `kp` is the key of stream 21 of the
+// episode, which gives the 16 candidates of each object; then the ring.  `each(j)` runs once object j has its place.  Nav2DObj-v0's
+// objects, and with M = 2 Nav2DRearr-v0's object start and goal.
+template <class S, class Each>
+__device__ inline void place_positions(S& s, uint32_t kp, int K, int M, Each each) {
     for (int j = 0; j < M; ++j) {
         bool placed = false;
         for (int i = 0; i < CANDIDATES && !placed; ++i) {
             const uint32_t w = (uint32_t)(2 * (CANDIDATES * j + i));
             const float x = LO + 7.8f * u01(mix32(kp ^ w)), y = LO + 7.8f * u01(mix32(kp ^ (w + 1u)));
             if (!(x >= OBJ_LO && x <= OBJ_HI && y >= OBJ_LO && y <= OBJ_HI)) continue;
-            bool in_rect = false;
-            for (int k = 0; k < K; ++k)
-                in_rect = in_rect || (x > s.base.rect[k][0] - OBJ_R && x < s.base.rect[k][2] + OBJ_R && y > s.base.rect[k][1] - OBJ_R &&
-                                      y < s.base.rect[k][3] + OBJ_R);
-            if (in_rect || !object_fits(x, y, s, j)) continue;
+            if (in_grown_rect(x, y, s.base, K) || !object_fits(x, y, s, j)) continue;
             s.obj[j][0] = x; s.obj[j][1] = y;
             placed = true;
         }
@@ -477,8 +505,16 @@ __device__ void place_objects(Nav2DObjState& s, uint32_t seed, uint32_t env, int
             s.obj[j][0] = x; s.obj[j][1] = y;
             placed = object_fits(x, y, s, j);
         }
-        s.cat[j] = (int32_t)(mix32(kc ^ (uint32_t)j) % (uint32_t)C);
+        each(j);
     }
+}
+// What Nav2DObj-v0 adds to a world that `begin_episode<false>` has just generated: the start pose the gps / compass sensors refer to,
+// the objects, the target, and the distances.
+__device__ void place_objects(Nav2DObjState& s, uint32_t seed, uint32_t env, int K, int M, int C) {
+    const uint32_t ep = (uint32_t)s.base.episode;
+    s.sx = s.base.px; s.sy = s.base.py; s.h0 = s.base.heading;
+    const uint32_t kp = stream_key(seed, S_OBJ_POS, env, ep), kc = stream_key(seed, S_OBJ_CAT, env, ep);
+    place_positions(s, kp, K, M, [&](int j) { s.cat[j] = (int32_t)(mix32(kc ^ (uint32_t)j) % (uint32_t)C); });
     for (int j = M; j < MAX_M; ++j) { s.obj[j][0] = 0.0f; s.obj[j][1] = 0.0f; s.cat[j] = -1; }
     s.target = s.cat[mix32(stream_key(seed, S_OBJ_TARGET, env, ep) ^ 0u) % (uint32_t)M];
     s.base.d_start = s.base.d_prev = nearest_target(s, M);
@@ -522,6 +558,115 @@ __global__ void nav2d_obj_step_kernel(Nav2DObjState* __restrict__ states, const 
         gps[2 * n + 1] = c * dy - sn * dx;
     }
     if (compass) compass[n] = ctab[(s.heading - o.h0 + nh) % nh];
+}
+
+// ---- Nav2DRearr-v0 (Nav2DRearrVectorEnv; specification: tests/nav2d_rearr_reference.py) ------------------------------------------------
+constexpr float REARR_REACH = 1.0f, REARR_ARM = 0.5f, REARR_SUCCESS = 0.5f;
+
+// The potential d(p, o) + d(o, g) of the current state; `b` is its second term.  A held object is at p, so the first term is 0.
+__device__ inline float rearr_potential(const Nav2DRearrState& r, float& b) {
+    const Nav2DState& s = r.base;
+    b = dist(r.ox, r.oy, s.gx, s.gy);
+    return dist(s.px, s.py, r.ox, r.oy) + b;
+}
+// What Nav2DRearr-v0 adds to a world that `begin_episode<false>` has just generated: the two places (Nav2DObj-v0's objects 0 and 1 of
+// that world), the object at its start or in the agent's hand, the counters and the first potential.
+__device__ inline void rearr_begin(Nav2DRearrState& r, uint32_t seed, uint32_t env, int K, int start_holding) {
+    Nav2DState& s = r.base;
+    r.sx = s.px; r.sy = s.py;
+    place_positions(r, stream_key(seed, S_OBJ_POS, env, (uint32_t)s.episode), K, 2, [](int) {});
+    s.gx = r.obj[1][0]; s.gy = r.obj[1][1];
+    r.holding = r.held = start_holding ? 1 : 0;
+    r.ox = start_holding ? s.px : r.obj[0][0];
+    r.oy = start_holding ? s.py : r.obj[0][1];
+    r.picks = 0;
+    r.invalid = 0;
+    float b;
+    s.d_start = s.d_prev = rearr_potential(r, b);
+}
+
+// One thread per env, as nav2d_step_kernel.  Then the three vector sensors: the object's start and the goal as (dot, cross) in the
+// heading's frame, written term by term like write_goal's, and the holding flag.
+__global__ void nav2d_rearr_step_kernel(Nav2DRearrState* __restrict__ states, const float* __restrict__ dirs,
+                                        const int64_t* __restrict__ actions, const uint8_t* __restrict__ mask,
+                                        float* __restrict__ obj_start, float* __restrict__ obj_goal, float* __restrict__ is_holding,
+                                        float* __restrict__ reward, uint8_t* __restrict__ not_done, float* __restrict__ sums, uint32_t seed,
+                                        uint32_t env_offset, int N, int K, int nh, int max_steps, int start_holding, int advance) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N || (mask && !mask[n])) return;
+    Nav2DRearrState& r = states[n];
+    Nav2DState& s = r.base;
+    const uint32_t env = env_offset + (uint32_t)n;
+    if (!advance) {
+        first_episode<false>(s, seed, env, K, nh);
+        rearr_begin(r, seed, env, K, start_holding);
+    } else {
+        const int64_t a = actions[n];  // anything outside 0..5 moves nothing (the host-side entry points refuse it)
+        const float c = dirs[2 * s.heading], sn = dirs[2 * s.heading + 1];
+        bool first_pick = false;
+        if (a == 1) {
+            const float nx = s.px + FORWARD * c, ny = s.py + FORWARD * sn;
+            const bool open = is_free(nx, ny, s, K) && (r.holding || !(dist(nx, ny, r.ox, r.oy) < OBJ_BLOCK));
+            if (open) { s.px = nx; s.py = ny; s.path = s.path + FORWARD; }
+            else s.collisions += 1;
+        } else if (a == 2) {
+            s.heading = (s.heading + 1) % nh;
+        } else if (a == 3) {
+            s.heading = (s.heading + nh - 1) % nh;
+        } else if (a == 4) {
+            const float dx = r.ox - s.px, dy = r.oy - s.py;
+            if (!r.holding && dist(s.px, s.py, r.ox, r.oy) < REARR_REACH && dx * c + dy * sn > 0.0f) {
+                first_pick = r.picks == 0;
+                r.holding = r.held = 1;
+                r.picks += 1;
+            } else {
+                r.invalid += 1;
+            }
+        } else if (a == 5) {
+            const float qx = s.px + REARR_ARM * c, qy = s.py + REARR_ARM * sn;
+            if (r.holding && qx >= OBJ_LO && qx <= OBJ_HI && qy >= OBJ_LO && qy <= OBJ_HI && !in_grown_rect(qx, qy, s, K)) {
+                r.ox = qx; r.oy = qy;
+                r.holding = 0;
+            } else {
+                r.invalid += 1;
+            }
+        }
+        if (r.holding) { r.ox = s.px; r.oy = s.py; }
+        // the end of the step: end_step's, with the potential in the distance's place, the pick bonus and this task's measures
+        float b;
+        const float phi = rearr_potential(r, b);
+        const bool stop = a == 0;
+        const bool success = stop && !r.holding && b < REARR_SUCCESS;
+        reward[n] = ((-0.01f + (s.d_prev - phi)) + (first_pick ? 1.0f : 0.0f)) + (success ? 2.5f : 0.0f);
+        s.d_prev = phi;
+        s.steps += 1;
+        const bool done = stop || (s.steps >= max_steps);
+        not_done[n] = done ? 0 : 1;
+        s.ended = done ? 1 : 0;
+        if (done) {
+            s.last[0] = success ? 1.0f : 0.0f;
+            s.last[1] = (float)r.held;
+            s.last[2] = b;
+            s.last[3] = (float)s.collisions;
+            if (sums)
+                for (int m = 0; m < 4; ++m) sums[(size_t)m * N + n] = sums[(size_t)m * N + n] + s.last[m];
+            s.episode += 1;
+            begin_episode<false>(s, seed, env, K, nh);
+            rearr_begin(r, seed, env, K, start_holding);
+        }
+    }
+    const float c = dirs[2 * s.heading], sn = dirs[2 * s.heading + 1];
+    if (obj_start) {
+        const float dx = r.obj[0][0] - s.px, dy = r.obj[0][1] - s.py;
+        obj_start[2 * n + 0] = dx * c + dy * sn;
+        obj_start[2 * n + 1] = c * dy - sn * dx;
+    }
+    if (obj_goal) {
+        const float dx = s.gx - s.px, dy = s.gy - s.py;
+        obj_goal[2 * n + 0] = dx * c + dy * sn;
+        obj_goal[2 * n + 1] = c * dy - sn * dx;
+    }
+    if (is_holding) is_holding[n] = (float)r.holding;
 }
 
 // ---- geodesic distance of Nav2DObj-v0 (distance = "geodesic"; specification: tests/nav2d_obj_geo_reference.py) ---------------------
@@ -834,11 +979,15 @@ __device__ inline void sweep_dwords(T* __restrict__ img, int s_px, int e_px, int
 // depth, its shaded colour, as a RowRec).  Colours are packed integers and stay uint32_t from LDS to the store.  A lane's four pixels
 // are four consecutive columns, so the lanes of a wave read the column arrays at a stride of four dwords; column u sits at
 // u + (u >> 5), which spreads a half wave's 32 reads over the 32 banks.
-// OBJ (Nav2DObj-v0): `states` are Nav2DObjState records; the M cylinders are geometry that depth, rgb and semantic see alike and
-// there is no goal marker; a fifth per-column array holds the semantic id of the column's hit and a third sweep writes `semantic`
+// Render::OBJ (Nav2DObj-v0): `states` are Nav2DObjState records; the M cylinders are geometry that depth, rgb and semantic see alike
+// and there is no goal marker; a fifth per-column array holds the semantic id of the column's hit and a third sweep writes `semantic`
 // like depth.  LDS is (4 or 5) * col_pitch(W) dwords + 16 bytes per tile row: at most 20 * 2116 + 16 * 4 bytes (W = 2048) or
 // 16 * 1024 + 20 * 4 (W = 1), under 64 KiB for every accepted width.
-template <bool OBJ>
+// Render::REARR (Nav2DRearr-v0): `states` are Nav2DRearrState records; the object is one cylinder of category 0's colour, geometry
+// for depth and rgb alike while the env's holding flag is clear and absent while it is set; the goal marker is drawn in rgb as in
+// the GOAL form, nearer than whatever the column hit, the cylinder included.  No semantic image: four column arrays.
+enum class Render { GOAL, OBJ, REARR };
+template <Render MODE>
 __global__ void __launch_bounds__(RENDER_THREADS)
 nav2d_render_kernel(const void* __restrict__ states, const float* __restrict__ ray, const float* __restrict__ col_cos,
                     const float* __restrict__ tanv, const uint8_t* __restrict__ mask, uint8_t* __restrict__ rgb,
@@ -852,9 +1001,14 @@ nav2d_render_kernel(const void* __restrict__ states, const float* __restrict__ r
     float* c_zr = c_dw + P;
     uint32_t* c_cw = reinterpret_cast<uint32_t*>(c_zr + P);
     int32_t* c_sem = reinterpret_cast<int32_t*>(c_cw + P);  // OBJ only
+    constexpr bool OBJ = MODE == Render::OBJ, REARR = MODE == Render::REARR;
     RowRec* row = reinterpret_cast<RowRec*>(lds + P) + (OBJ ? P / 4 : 0);
     const Nav2DObjState* os = OBJ ? static_cast<const Nav2DObjState*>(states) + n : nullptr;
-    const Nav2DState& s = OBJ ? os->base : static_cast<const Nav2DState*>(states)[n];
+    const Nav2DRearrState* rs = REARR ? static_cast<const Nav2DRearrState*>(states) + n : nullptr;
+    const Nav2DState& s = OBJ ? os->base : REARR ? rs->base : static_cast<const Nav2DState*>(states)[n];
+    // the cylinders of this env: Nav2DObj-v0's M objects, Nav2DRearr-v0's object unless it is held
+    const float (*cyl)[2] = OBJ ? os->obj : REARR ? reinterpret_cast<const float (*)[2]>(&rs->ox) : nullptr;
+    const int cyls = OBJ ? M : REARR ? (rs->holding ? 0 : 1) : 0;
     const int v0 = blockIdx.x * rows_per_tile, v1 = min(H, v0 + rows_per_tile);
     const float px = s.px, py = s.py;
     const float* rayh = ray + (size_t)s.heading * W * 2;
@@ -872,10 +1026,10 @@ nav2d_render_kernel(const void* __restrict__ states, const float* __restrict__ r
             const float tn = fmaxf(axn, ayn), tm = fminf(axx, ayx);
             if (tn <= tm && tn > 0.0f && tn < t) { t = tn; hit = 4 + k; }
         }
-        if constexpr (OBJ) {
+        if constexpr (OBJ || REARR) {
             // the cylinders: the goal marker's ray-circle test (nearest intersection, ray direction taken as unit length)
-            for (int j = 0; j < M; ++j) {
-                const float ox = px - os->obj[j][0], oy = py - os->obj[j][1];
+            for (int j = 0; j < cyls; ++j) {
+                const float ox = px - cyl[j][0], oy = py - cyl[j][1];
                 const float b = ox * dx + oy * dy;
                 const float c = (ox * ox + oy * oy) - OBJ_R * OBJ_R;
                 const float disc = b * b - c;
@@ -898,7 +1052,7 @@ nav2d_render_kernel(const void* __restrict__ states, const float* __restrict__ r
         }
         uint32_t base;
         if (marker) base = pack_rgb(255, 32, 32);
-        else if (OBJ && hit >= 4 + MAX_K) base = category_color(os->cat[hit - (4 + MAX_K)]);
+        else if ((OBJ || REARR) && hit >= 4 + MAX_K) base = category_color(OBJ ? os->cat[hit - (4 + MAX_K)] : 0);
         else if (hit >= 4) base = s.color[hit - 4];
         else base = hit == 0 ? pack_rgb(200, 180, 150) : hit == 1 ? pack_rgb(150, 200, 180) : hit == 2 ? pack_rgb(180, 150, 200)
                                                                                                         : pack_rgb(200, 200, 150);
@@ -1009,8 +1163,9 @@ static int check_step_args(const StepArgs& a, bool geo_entry) {
     return geo_entry ? check_geo_args(a.state, sizeof(Nav2DState), a.geo, a.N, a.num_obstacles) : HAB_OK;
 }
 
-// The render, where an image destination is given.  `semantic` and `num_objects` are used by the Nav2DObj-v0 instantiation alone.
-template <bool OBJ>
+// The render, where an image destination is given, in the task's form.  `semantic` and `num_objects` are used by the Nav2DObj-v0
+// instantiation alone.
+template <Render MODE>
 static int launch_render(const StepArgs& a, int num_objects) {
     if (!a.image()) return HAB_OK;
     // a tile is at least ~16 KiB of stores per workgroup, so that the W column hits are a small part of its work
@@ -1020,8 +1175,9 @@ static int launch_render(const StepArgs& a, int num_objects) {
     if (rows > RENDER_MAX_ROWS) rows = RENDER_MAX_ROWS;
     if (rows > a.H) rows = a.H;
     dim3 grid(cdiv(a.H, rows), a.N);
-    const size_t lds = (size_t)(col_pitch(a.W) + rows) * sizeof(uint4) + (OBJ ? (size_t)col_pitch(a.W) * sizeof(int32_t) : 0);
-    nav2d_render_kernel<OBJ><<<grid, RENDER_THREADS, lds, a.stream>>>(a.state, a.ray, a.col_cos, a.tanv, a.mask, a.rgb, a.depth, a.semantic,
+    const size_t lds = (size_t)(col_pitch(a.W) + rows) * sizeof(uint4) +
+                       (MODE == Render::OBJ ? (size_t)col_pitch(a.W) * sizeof(int32_t) : 0);
+    nav2d_render_kernel<MODE><<<grid, RENDER_THREADS, lds, a.stream>>>(a.state, a.ray, a.col_cos, a.tanv, a.mask, a.rgb, a.depth, a.semantic,
                                                                        a.H, a.W, a.num_obstacles, num_objects, rows);
     HAB_LAUNCH_CHECK();
     return HAB_OK;
@@ -1036,7 +1192,7 @@ static int finish_goal_step(const StepArgs& a) {
                                                          a.num_obstacles);
         HAB_LAUNCH_CHECK();
     }
-    return launch_render<false>(a, 0);
+    return launch_render<Render::GOAL>(a, 0);
 }
 
 // Nav2D-v0.  hab_nav2d_step is <false> with geo = NULL, which is what its kernel is given; hab_nav2d_step_geo is <true>.
@@ -1135,7 +1291,26 @@ extern "C" int hab_nav2d_obj_step(void* state, const float* dirs, const float* r
                                                           compass, reward, not_done, measure_sums, seed, env_offset, N, num_obstacles,
                                                           num_headings, max_episode_steps, num_objects, num_categories, advance);
     HAB_LAUNCH_CHECK();
-    return launch_render<true>(a, num_objects);
+    return launch_render<Render::OBJ>(a, num_objects);
+}
+
+extern "C" int hab_nav2d_rearr_state_bytes(void) { return (int)sizeof(Nav2DRearrState); }
+
+extern "C" int hab_nav2d_rearr_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                                    const int64_t* actions, const uint8_t* mask, uint8_t* head_rgb, float* head_depth, float* obj_start,
+                                    float* obj_goal, float* is_holding, float* reward, uint8_t* not_done, float* measure_sums,
+                                    uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings,
+                                    int max_episode_steps, int start_holding, int advance, hipStream_t stream) {
+    const StepArgs a{state, nullptr, dirs, ray, col_cos, tanv, actions, mask, head_rgb, head_depth, nullptr, nullptr, reward, not_done,
+                     measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream};
+    const int rc = check_step_args(a, false);
+    if (rc != HAB_OK) return rc;
+    if (start_holding != 0 && start_holding != 1) return HAB_ERR_ARG;
+    nav2d_rearr_step_kernel<<<cdiv(N, 64), 64, 0, stream>>>((Nav2DRearrState*)state, dirs, actions, mask, obj_start, obj_goal, is_holding,
+                                                            reward, not_done, measure_sums, seed, env_offset, N, num_obstacles,
+                                                            num_headings, max_episode_steps, start_holding, advance);
+    HAB_LAUNCH_CHECK();
+    return launch_render<Render::REARR>(a, 0);
 }
 
 extern "C" int hab_nav2d_obj_geo_bytes(void) { return (int)sizeof(ObjGeoField); }
@@ -1182,5 +1357,5 @@ extern "C" int hab_nav2d_obj_step_geo(void* state, void* geo, const float* dirs,
     nav2d_obj_geo_build_kernel<<<N, 64, 0, stream>>>((char*)state, sizeof(Nav2DObjState), (ObjGeoField*)geo, mask, advance ? 1 : 0,
                                                      num_obstacles, num_objects);
     HAB_LAUNCH_CHECK();
-    return launch_render<true>(a, num_objects);
+    return launch_render<Render::OBJ>(a, num_objects);
 }

@@ -51,12 +51,17 @@ class SyntheticVectorEnv:
         self.use_rgb, self.use_depth, self.task = use_rgb, use_depth, task
         self.device = torch.device(device)
         d = {}
+        rgb_key, depth_key = ("head_rgb", "head_depth") if task == "rearrange" else ("rgb", "depth")
         if use_rgb:
-            d["rgb"] = spaces.Box(0, 255, (height, width, 3), np.uint8)
+            d[rgb_key] = spaces.Box(0, 255, (height, width, 3), np.uint8)
         if use_depth:
-            d["depth"] = spaces.Box(0.0, 1.0, (height, width, 1), np.float32)
+            d[depth_key] = spaces.Box(0.0, 1.0, (height, width, 1), np.float32)
         fmin, fmax = np.finfo(np.float32).min, np.finfo(np.float32).max
-        if task == "objectnav":  # sensor set of the ObjectNav experiments (rgb, depth, semantic + objectgoal, compass, gps)
+        if task == "rearrange":  # sensor set of Nav2DRearr-v0: the head camera and three raw 1-D sensors, no goal sensor
+            d["obj_start_sensor"] = spaces.Box(fmin, fmax, (2,), np.float32)
+            d["obj_goal_sensor"] = spaces.Box(fmin, fmax, (2,), np.float32)
+            d["is_holding"] = spaces.Box(0.0, 1.0, (1,), np.float32)
+        elif task == "objectnav":  # sensor set of the ObjectNav experiments (rgb, depth, semantic + objectgoal, compass, gps)
             d["semantic"] = spaces.Box(0, NUM_SEMANTIC_IDS - 1, (height, width, 1), np.int32)
             d["objectgoal"] = spaces.Box(0, NUM_OBJECT_CATEGORIES - 1, (1,), np.int64)
             d["compass"] = spaces.Box(-np.pi, np.pi, (1,), np.float32)
@@ -74,12 +79,15 @@ class SyntheticVectorEnv:
         self._since = torch.zeros(num_envs, dtype=torch.int64, device=dev)
         self._rgb = torch.zeros(num_envs, height, width, 3, dtype=torch.uint8, device=dev) if use_rgb else None
         self._depth = torch.zeros(num_envs, height, width, 1, device=dev) if use_depth else None
-        self._goal = torch.zeros(num_envs, 2, device=dev) if task != "objectnav" else None
+        self._goal = torch.zeros(num_envs, 2, device=dev) if task not in ("objectnav", "rearrange") else None
         self._obj = {}
         if task == "objectnav":
             self._obj = dict(semantic=torch.zeros(num_envs, height, width, 1, dtype=torch.int32, device=dev),
                              objectgoal=torch.zeros(num_envs, 1, dtype=torch.int64, device=dev),
                              compass=torch.zeros(num_envs, 1, device=dev), gps=torch.zeros(num_envs, 2, device=dev))
+        elif task == "rearrange":
+            self._obj = dict(obj_start_sensor=torch.zeros(num_envs, 2, device=dev), obj_goal_sensor=torch.zeros(num_envs, 2, device=dev),
+                             is_holding=torch.zeros(num_envs, 1, device=dev))
         self._rew = torch.zeros(num_envs, device=dev)
         self._nd = torch.zeros(num_envs, dtype=torch.uint8, device=dev)
         self._pending: set = set()      # envs with an outstanding async_step_at (host path)
@@ -325,7 +333,8 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
 
     consumes_actions = True
     measure_names = NAV2D_MEASURES
-    # what a subclass with another sensor set changes: the observation set SyntheticVectorEnv builds, whether an image is rendered
+    # what a subclass with another sensor set changes: the observation set SyntheticVectorEnv builds ("nav2d": the point-goal set,
+    # "objectnav", "rearrange": head camera + object start / goal / holding), whether an image is rendered
     # without rgb and depth, and the size of a state record
     _sensor_set = "nav2d"
     _renders_without_rgb_depth = False
@@ -662,6 +671,106 @@ class Nav2DObjVectorEnv(Nav2DVectorEnv):
         raise _lib.HabError("Nav2DObj: the task has no pointgoal sensor; use step_into_obs with the ObjectNav sensor rows")
 
 
+NAV2D_REARR_MEASURES = ("success", "did_pick_object", "object_to_goal_distance", "collisions")
+NAV2D_REARR_SENSORS = ("head_rgb", "head_depth", "obj_start_sensor", "obj_goal_sensor", "is_holding")
+
+
+class Nav2DRearrVectorEnv(Nav2DVectorEnv):
+    """Nav2DRearr-v0: a pick-and-place task in Nav2D-v0's world, read through the rearrangement observation set: `head_depth` (and
+    optionally `head_rgb`) for the visual encoder and three raw float32 1-D sensors that PointNavResNetPolicy fuses into its recurrent
+    input.  The goal exists only in those sensors, so the task can be solved only through the fused columns.  Arena, rectangles, start,
+    heading, the box free test, streams 16-20, the 0.25 m forward step and the turn table are Nav2D-v0's (see Nav2DVectorEnv).
+    tests/nav2d_rearr_reference.py restates the task in numpy; `nav2d_rearr_step_kernel` and the rearrangement form of
+    `nav2d_render_kernel` (csrc/nav2d.hip) match it bit for bit on every output -- no angle function runs on the device, every float32
+    operation is one rounding in the written order.
+
+    Parameters (`habitat.synthetic`): start_holding (bool, default false), besides Nav2D-v0's num_obstacles and turn_angle.  The
+      distances are Euclidean; `distance_to_goal: geodesic` is refused.
+    Places.  The object's start o0 and the goal g are the positions Nav2DObj-v0 gives objects 0 and 1 of the same (seed, env, episode)
+      world with num_objects = 2 (see Nav2DObjVectorEnv, Objects: stream 21, 16 candidates, the box [0.5, 7.5]^2, not strictly inside
+      a rectangle grown by 0.3 m, at least 1 m from the start and from the earlier object, the 28-slot ring).  Categories and the target
+      stream are not used.  The goal is a place, not geometry: it never blocks the agent and is never in depth.
+    Object and holding.  An upright cylinder of radius 0.3 m at o, initially o0, and a flag h, initially start_holding.  While h = 1
+      the object travels with the agent: it is no geometry, blocks nothing, is not rendered and o = p.  While h = 0 a position closer
+      than 0.4 m to o is not free (Nav2DObj-v0's keep-out).
+    Actions.  Discrete(6): 0 STOP, 1 MOVE_FORWARD, 2 TURN_LEFT, 3 TURN_RIGHT, 4 PICK, 5 PLACE.  MOVE_FORWARD is Nav2D-v0's with this
+      free test; a refused move counts a collision.  With (c, s) the heading's table row, PICK succeeds iff h = 0, d(p, o) < 1.0 and
+      (ox - px) * c + (oy - py) * s > 0 (the front half-plane); then h = 1.  PLACE succeeds iff h = 1 and q = p + 0.5 * dir (a float32
+      multiply, then a separate add) lies in [0.5, 7.5]^2 and not strictly inside a rectangle grown by 0.3 m; then o = q and h = 0.  A
+      refused PICK or PLACE changes nothing but the record's `invalid` counter.
+    Reward.  a = d(p, o), 0 while holding; b = d(o, g); Phi = a + b;
+      reward = ((-0.01 + (Phi_prev - Phi)) + 1.0 * [this step made the episode's first successful PICK]) + 2.5 * success,
+      success = STOP and h = 0 and b < 0.5.  The episode ends on STOP or at max_episode_steps; on done the next episode's world is
+      generated, its first observation is what the step returns and not_done = 0.
+    Measures.  success; did_pick_object, 1 if h was ever 1 in the episode (so 1 under start_holding); object_to_goal_distance = b at
+      the end; collisions.
+    Sensors, in observation-space order.  head_rgb (H, W, 3) uint8, optional; head_depth (H, W, 1) float32; obj_start_sensor (2,)
+      float32 = (dot, cross) of o0 - p in the heading's frame (dot = dx * c + dy * s, cross = c * dy - s * dx), which refers to the
+      START position as habitat's sensor does and goes stale once the object has been moved -- after a misplaced PLACE the object can
+      be found again only in the image; obj_goal_sensor (2,) the same for g; is_holding (1,) in {0, 1}.  head_depth is Nav2D-v0's depth
+      with the cylinder as geometry while h = 0 (Nav2DObj-v0's ray-circle test); head_rgb is the same with the object in category 0's
+      colour and the goal drawn as Nav2D-v0's red marker cylinder (radius 0.2 m), in rgb only.  There is no pointgoal, gps or compass.
+      Without head_rgb and head_depth nothing is rendered.
+
+    `step_into_obs` writes whichever of the five rows `obs` holds; `actions` is int64 (N,) / (N, 1) as for Nav2D-v0.  The record's
+    words beyond Nav2D-v0's are named in include/habitat_amd.h (HAB_NAV2D_REARR_W_*)."""
+
+    _name = "Nav2DRearr"
+    _entries = ("hab_nav2d_rearr_step",)
+    _sensor_set = "rearrange"
+    _state_bytes = "hab_nav2d_rearr_state_bytes"
+    measure_names = NAV2D_REARR_MEASURES
+    num_actions = 6
+
+    def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = False,
+                 use_depth: bool = True, num_actions: int = 6, device="cuda", num_obstacles: int = 3, turn_angle: int = 10,
+                 max_episode_steps: int = 500, start_holding: bool = False, distance: str = "euclidean"):
+        if nav2d_distance(distance, "Nav2DRearr") != "euclidean":
+            raise _lib.HabError("Nav2DRearr: the task has Euclidean distances only; distance_to_goal 'geodesic' is not defined for it")
+        if not isinstance(start_holding, (bool, np.bool_)):
+            raise _lib.HabError(f"Nav2DRearr: start_holding {start_holding!r} must be true or false")
+        if num_actions != 6:
+            raise _lib.HabError("Nav2DRearr: the action space is Discrete(6) (STOP, MOVE_FORWARD, TURN_LEFT, TURN_RIGHT, PICK, PLACE), "
+                                f"got {num_actions}")
+        if (use_rgb or use_depth) and (int(height) <= 0 or int(width) <= 0):
+            raise _lib.HabError(f"Nav2DRearr: the image size {height} x {width} must be positive")
+        self.start_holding = bool(start_holding)
+        super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
+                         num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps)
+        self.task = "nav2drearr"
+        self.action_spaces = [spaces.Discrete(6) for _ in range(num_envs)]
+        self.orig_action_spaces = self.action_spaces
+
+    def _sensor_rows(self, obs):
+        return tuple(ptr(obs.get(k)) for k in NAV2D_REARR_SENSORS)
+
+    def _task_parameters(self):
+        return (int(self.start_holding),)
+
+    def _own_obs(self):
+        o = {}
+        if self.use_rgb:
+            o["head_rgb"] = self._rgb
+        if self.use_depth:
+            o["head_depth"] = self._depth
+        o.update(self._obj)
+        return o
+
+    def _host_obs(self) -> List[Dict[str, np.ndarray]]:
+        host = {k: v.cpu().numpy() for k, v in self._own_obs().items()}
+        return [{k: v[i] for k, v in host.items()} for i in range(self.num_envs)]
+
+    def step_infos_host(self, ids) -> List[dict]:
+        """The scalar infos of the last step of envs `ids`: this task's four measures where that step ended an episode, else {}."""
+        return [dict(zip(NAV2D_REARR_MEASURES, info.values())) if info else {} for info in super().step_infos_host(ids)]
+
+    def reset_into(self, rgb, depth, goal):
+        raise _lib.HabError("Nav2DRearr: the task has no pointgoal sensor; use reset_into_obs with the rearrangement sensor rows")
+
+    def step_into(self, rgb, depth, goal, reward, not_done, actions=None, mask=None):
+        raise _lib.HabError("Nav2DRearr: the task has no pointgoal sensor; use step_into_obs with the rearrangement sensor rows")
+
+
 class SyntheticVectorEnvFactory(VectorEnvFactory):
     """Default `_target_`: N synthetic PointNav envs sized from habitat.simulator.sensors.*; per-rank env ids are
     offset by rank * num_environments exactly like the reference offsets the seed (ppo_trainer.py:208-211).  A
@@ -670,7 +779,9 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
     Nav2DVel-v0, its velocity-controlled variant (Nav2DVelVectorEnv), with the further `habitat.synthetic` keys named there; one
     starting with "nav2dobj" selects Nav2DObj-v0 (Nav2DObjVectorEnv: objects, a target category, the ObjectNav sensor set), which
     reads num_objects / num_categories too and takes its image size from the rgb, else the depth, else the semantic sensor.
-    `habitat.synthetic.distance_to_goal` ("euclidean", the default, or "geodesic") is the distance mode of all three Nav2D tasks."""
+    `habitat.synthetic.distance_to_goal` ("euclidean", the default, or "geodesic") is the distance mode of these three Nav2D tasks.
+    A type starting with "nav2drearr" selects Nav2DRearr-v0 (Nav2DRearrVectorEnv: pick and place, the rearrangement sensor set), which
+    reads start_holding too, takes its image size from the head_rgb, else the head_depth sensor, and refuses the geodesic mode."""
 
     def __init__(self, use_rgb: bool = True, use_depth: bool = True):
         self.use_rgb, self.use_depth = use_rgb, use_depth
@@ -690,7 +801,12 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
                       device=device, num_obstacles=getattr(syn, "num_obstacles", 3), turn_angle=getattr(syn, "turn_angle", 10),
                       max_episode_steps=getattr(hab.environment, "max_episode_steps", 500), distance=distance)
             make = Nav2DVectorEnv
-            if task_type.startswith("nav2dobj"):
+            if task_type.startswith("nav2drearr"):
+                use_rgb, use_depth = self.use_rgb and "head_rgb" in sens, self.use_depth and "head_depth" in sens
+                ref = sens["head_rgb"] if use_rgb else (sens["head_depth"] if use_depth else dict(height=0, width=0))
+                make = Nav2DRearrVectorEnv
+                kw.update(use_rgb=use_rgb, use_depth=use_depth, start_holding=getattr(syn, "start_holding", False))
+            elif task_type.startswith("nav2dobj"):
                 if not (use_rgb or use_depth):
                     if "semantic" not in sens:
                         raise _lib.HabError("Nav2DObj: no rgb, depth or semantic sensor gives the image size")

@@ -195,6 +195,37 @@ int hab_nav2d_obj_step_geo(void* state /*N,HAB_NAV2D_OBJ_STATE_BYTES*/, void* ge
                            float* measure_sums /*4,N*/, uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles,
                            int num_headings, int max_episode_steps, int num_objects, int num_categories, int num_actions,
                            int advance, hipStream_t stream);
+/* Nav2DRearr-v0: the same arena, rectangles, start, heading and forward step with one object (a cylinder of radius 0.3 m) to pick up
+ * and to put down at a goal position that only the fused 1-D sensors tell (definition: habitat_amd/common/env_factory.py,
+ * Nav2DRearrVectorEnv; bit-identical to tests/nav2d_rearr_reference.py on every output, no angle function runs on the device).
+ * `state` is N records of HAB_NAV2D_REARR_STATE_BYTES whose first HAB_NAV2D_STATE_BYTES are a Nav2D-v0 record: the words named above
+ * keep their meaning, with (GX, GY) the goal position, D_PREV the potential d(p, o) + d(o, g) after the last step and D_START the
+ * episode's first one; LAST_MEASURES are success, did_pick_object, object_to_goal_distance, collisions.  Every argument of
+ * hab_nav2d_step keeps its meaning and its checks; there is no goal sensor.  actions int64: 0 STOP, 1 MOVE_FORWARD, 2 TURN_LEFT,
+ * 3 TURN_RIGHT, 4 PICK, 5 PLACE; anything else moves nothing and costs a step.  head_rgb u8 (N,H,W,3) and head_depth f32 (N,H,W,1),
+ * 4-byte aligned: Nav2D-v0's images with the object as geometry while it is not held, and the goal marker in head_rgb alone;
+ * obj_start f32 (N,2), obj_goal f32 (N,2): (dot, cross) of the object's start position / of the goal position minus the agent's
+ * position in the heading's frame; is_holding f32 (N,1) in {0, 1}.  Every destination may be NULL.  start_holding 0 or 1: whether an
+ * episode begins with the object held; any other value is HAB_ERR_ARG. */
+#define HAB_NAV2D_REARR_STATE_BYTES 272
+/* further words of a Nav2DRearr-v0 record: the agent's start position (x, y), the object's start position (x, y), the goal position
+ * (x, y), the object's position (the agent's while held), whether it is held, whether it was ever held in this episode, the
+ * successful PICKs and the refused PICKs / PLACEs of this episode */
+#define HAB_NAV2D_REARR_W_START 56
+#define HAB_NAV2D_REARR_W_OBJ_START 58
+#define HAB_NAV2D_REARR_W_GOAL 60
+#define HAB_NAV2D_REARR_W_OBJ 62
+#define HAB_NAV2D_REARR_W_HOLDING 64
+#define HAB_NAV2D_REARR_W_HELD 65
+#define HAB_NAV2D_REARR_W_PICKS 66
+#define HAB_NAV2D_REARR_W_INVALID 67
+int hab_nav2d_rearr_state_bytes(void);
+int hab_nav2d_rearr_step(void* state /*N,HAB_NAV2D_REARR_STATE_BYTES*/, const float* dirs, const float* ray, const float* col_cos,
+                         const float* tanv, const int64_t* actions /*N*/, const uint8_t* mask /*N*/, uint8_t* head_rgb /*N,H,W,3*/,
+                         float* head_depth /*N,H,W,1*/, float* obj_start /*N,2*/, float* obj_goal /*N,2*/, float* is_holding /*N,1*/,
+                         float* reward /*N*/, uint8_t* not_done /*N*/, float* measure_sums /*4,N*/, uint32_t seed, uint32_t env_offset,
+                         int N, int H, int W, int num_obstacles, int num_headings, int max_episode_steps, int start_holding,
+                         int advance, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Observation transformers, fused: ResizeShortestEdge followed by CenterCropper
