@@ -199,19 +199,25 @@ inline bool conv2_dgrad_strip_covers(const ConvDesc& d) {
     return d.KH == 4 && d.KW == 4 && d.stride == 2 && d.pad == 0 && d.C == 32 && d.Cout == 64 && d.H >= 4 && d.W >= 4 && d.H <= 63 && d.W <= 63;
 }
 
-// HAB_NOT_APPLICABLE: shape not covered.
+constexpr int C2D_CELL_ROWS = 2;  // cell rows per strip
+// the form serves this call (host only: the dispatch rule and the launcher both ask it)
+inline bool conv2_dgrad_strip_serves(const ConvDesc& d, const float* dy, const float* wd, const float* mask, const float* add, const float* dx) {
+    if (!conv2_dgrad_strip_covers(d)) return false;
+    if (add || d.B < 16 || !dy || !wd || !dx) return false;
+    if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(wd) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(mask)) & 15) return false;
+    return (long long)d.B * cdiv((d.H + 1) / 2, C2D_CELL_ROWS) <= 0x7fffffffLL;
+}
+
+// HAB_NOT_APPLICABLE: call not served.
 inline int conv2_dgrad_strip(const ConvDesc& d, const float* dy, const float* wd, const float* mask, const float* add, float* dx,
                              hipStream_t stream) {
-    if (!conv2_dgrad_strip_covers(d)) return HAB_NOT_APPLICABLE;
-    if (add || d.B < 16 || !dy || !wd || !dx) return HAB_NOT_APPLICABLE;
-    if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(wd) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(mask)) & 15) return HAB_NOT_APPLICABLE;
-    constexpr int R2 = 2;
+    if (!conv2_dgrad_strip_serves(d, dy, wd, mask, add, dx)) return HAB_NOT_APPLICABLE;
+    constexpr int R2 = C2D_CELL_ROWS;
     using Cfg = C2dCfg<R2>;
     C2dArgs a;
     a.dy = dy; a.wd = wd; a.mask = mask; a.dx = dx; a.B = d.B;
     a.H = d.H; a.W = d.W; a.Ho = (d.H - 4) / 2 + 1; a.Wo = (d.W - 4) / 2 + 1;
-    a.strips = ((d.H + 1) / 2 + R2 - 1) / R2;  // cell rows = ceil(H / 2)
-    if ((long long)d.B * a.strips > 0x7fffffffLL) return HAB_NOT_APPLICABLE;
+    a.strips = cdiv((d.H + 1) / 2, R2);  // cell rows = ceil(H / 2)
     a.items = d.B * a.strips;
     a.sign_schedule = bf3_sign_schedule();
     // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)

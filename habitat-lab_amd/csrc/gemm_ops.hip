@@ -12,6 +12,7 @@
 #include "wgrad3x3_bf3.h"
 #include "conv2_fwd_strip.h"
 #include "conv2_dgrad_strip.h"
+#include "conv3_dgrad_strip.h"
 #include "obs_wgrad_bf3.h"
 #include "obs_wgrad_strip.h"
 #include "conv_patch_bf3.h"
@@ -174,10 +175,21 @@ __global__ void dgrad_empty_class_kernel(ConvDgradProb p) {
         p.store((int)(e / p.N), (int)(e % p.N), 0.f);
 }
 
+// The form of a convolution's data gradient (HAB_CONV_DGRAD_FORM_*): under MP_CONV2_DGRAD with MP_RC SimpleCNN's conv2 and conv3 on their
+// strip kernels (dY strip in LDS, filter slices in registers: conv2_dgrad_strip.h, conv3_dgrad_strip.h) where those serve the call, the
+// general kernels (patch-resident 3x3, merged stride classes, igemm tiles) for everything else.  conv_dgrad and hab_conv2d_dgrad_form
+// both ask it.
+static int choose_conv_dgrad(const ConvDesc& d, const float* dy, const float* wd, const float* mask, const float* add, const float* dx) {
+    if (!matrix_path_on(MP_CONV2_DGRAD | MP_RC)) return HAB_CONV_DGRAD_FORM_GENERAL;
+    if (conv2_dgrad_strip_serves(d, dy, wd, mask, add, dx)) return HAB_CONV_DGRAD_FORM_CONV2_STRIP;
+    if (conv3_dgrad_strip_serves(d, dy, wd, mask, add, dx)) return HAB_CONV_DGRAD_FORM_CONV3_STRIP;
+    return HAB_CONV_DGRAD_FORM_GENERAL;
+}
 int conv_dgrad(const ConvDesc& d, const float* dy, const float* wd, const float* mask, const float* add, float* dx,
                float* ws, size_t ws_floats, hipStream_t stream) {
-    if (matrix_path_on(MP_CONV2_DGRAD | MP_RC))  // SimpleCNN conv2: dY strip in LDS, filter slices in registers (conv2_dgrad_strip.h)
-        HAB_TRY_FORM(conv2_dgrad_strip(d, dy, wd, mask, add, dx, stream));
+    const int form = choose_conv_dgrad(d, dy, wd, mask, add, dx);
+    if (form == HAB_CONV_DGRAD_FORM_CONV2_STRIP) HAB_TRY_FORM(conv2_dgrad_strip(d, dy, wd, mask, add, dx, stream));
+    if (form == HAB_CONV_DGRAD_FORM_CONV3_STRIP) HAB_TRY_FORM(conv3_dgrad_strip(d, dy, wd, mask, add, dx, stream));
     if (d.stride > 1) {
         // kernel size a multiple of the stride: the stride classes share their dY gather -> one contraction with N = s*s*Cin
         ConvDgradMergedProb q;
@@ -512,6 +524,16 @@ extern "C" int hab_conv2d_dgrad(const float* dy, const float* w_dgrad, const flo
                                 size_t ws_floats, hipStream_t stream) {
     if (!dy || !w_dgrad || !dx) return HAB_ERR_ARG;
     return conv_dgrad(mk(B, H, W, C, Cout, KH, KW, stride, pad), dy, w_dgrad, relu_mask, add, dx, ws, ws_floats, stream);
+}
+extern "C" int hab_conv2d_dgrad_form(const float* dy, const float* w_dgrad, const float* relu_mask, const float* add, float* dx,
+                                     int B, int H, int W, int C, int Cout, int KH, int KW, int stride, int pad, const float* ws,
+                                     size_t ws_floats) {
+    (void)ws; (void)ws_floats;  // no form depends on the workspace
+    if (!dy || !w_dgrad || !dx) return HAB_ERR_ARG;
+    const ConvDesc d = mk(B, H, W, C, Cout, KH, KW, stride, pad);
+    const int r = check_conv(d);
+    if (r != HAB_OK) return r;
+    return choose_conv_dgrad(d, dy, w_dgrad, relu_mask, add, dx);
 }
 extern "C" int hab_conv2d_wgrad(const float* x, const float* dy, float* dw_oihw, float* dbias, int B, int H, int W, int C, int Cout,
                                 int KH, int KW, int stride, int pad, float* ws, size_t ws_floats, hipStream_t stream) {

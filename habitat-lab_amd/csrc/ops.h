@@ -103,7 +103,7 @@ enum MatrixPath : int {
     MP_OBS_PATCH = 1 << 6,     // with MP_OBS: observations resident in LDS, forward patch (obs_conv_patch.h) and weight-gradient rows (obs_wgrad_strip.h)
     MP_WGRAD_STRIP = 1 << 7,   // with MP_IJ_WGRAD: strip-resident weight gradients (wgrad3x3_bf3.h)
     MP_CONV2_FWD = 1 << 8,     // with MP_RC: SimpleCNN conv2 forward strip kernel (conv2_fwd_strip.h)
-    MP_CONV2_DGRAD = 1 << 9,   // with MP_RC: SimpleCNN conv2 data-gradient strip kernel (conv2_dgrad_strip.h)
+    MP_CONV2_DGRAD = 1 << 9,   // with MP_RC: SimpleCNN data-gradient strip kernels (conv2, conv3) (conv2_dgrad_strip.h, conv3_dgrad_strip.h)
     MP_DENSE = 1 << 10,        // with MP_RC: large Linear layers on the plain dense GEMM kernel (dense_bf3.h)
     MP_DENSE_ALL = 1 << 11,    // (tests) MP_DENSE's kernel for every shape it applies to
     MP_RNN_STEPWISE = 1 << 12, // (tests) time-major recurrence as one launch per step instead of the persistent kernels (rnn_persist.h)

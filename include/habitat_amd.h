@@ -374,8 +374,9 @@ int hab_sample_actions(const float* probs, const float* exp_noise, int64_t* acti
  *            (wgrad3x3_bf3.h)
  *     bit 8  (with bit 0) SimpleCNN conv2's forward (4x4 / 2, 32 -> 64 at 63 x 63, >= 16 frames) with the input strip resident in LDS and
  *            the filter slices resident in the waves' registers (conv2_fwd_strip.h)
- *     bit 9  (with bit 0) SimpleCNN conv2's data gradient on the same scheme: dY strip in LDS, filter slices in registers, the four taps
- *            of a row class folded in LDS, ReLU mask fused (conv2_dgrad_strip.h)
+ *     bit 9  (with bit 0) SimpleCNN data-gradient strip kernels (conv2, conv3) on the same scheme: dY strip in LDS, filter slices in
+ *            registers, the waves' partial tiles folded in LDS, ReLU mask fused (conv2_dgrad_strip.h; conv3_dgrad_strip.h: 3x3 / 1 / no
+ *            padding, 32 -> 64 channels back, width <= 32, >= 16 frames)
  *     bit 10 (with bit 0) large Linear layers (>= 4 GFLOP: SimpleCNN's visual fc forward / data gradient / weight gradient, the ResNet
  *            policies' recurrent input projection) on the plain dense GEMM kernel: 256 x 128 tiles, double-buffered LDS, transpose-read
  *            fragments for k-strided operands, LDS-staged epilogue incl. the flatten permutation (dense_bf3.h)
@@ -410,6 +411,15 @@ int hab_obs_conv2d_wgrad(const uint8_t* rgb, const float* depth, const int* rows
 int hab_obs_conv2d_wgrad_form(const uint8_t* rgb, const float* depth, const int* rows, const float* dy, float* dw_oihw,
                               float* dbias, int B, int H, int W, int Cout, int KH, int KW, int stride, int pad, const float* ws,
                               size_t ws_floats);
+/* The form hab_conv2d_dgrad runs for these arguments under the current matrix-path mask: 0 the general kernels (patch-resident 3x3,
+ * merged stride classes, igemm tiles), 1 SimpleCNN conv2's strip kernel (conv2_dgrad_strip.h), 2 SimpleCNN conv3's strip kernel
+ * (conv3_dgrad_strip.h), or a negative HAB_ERR_* where the call itself would be refused.  Host only: nothing is launched and no
+ * pointer is read (null-ness and alignment count).  The launcher asks the same function.  For tests and tools. */
+#define HAB_CONV_DGRAD_FORM_GENERAL 0
+#define HAB_CONV_DGRAD_FORM_CONV2_STRIP 1
+#define HAB_CONV_DGRAD_FORM_CONV3_STRIP 2
+int hab_conv2d_dgrad_form(const float* dy, const float* w_dgrad, const float* relu_mask, const float* add, float* dx, int B,
+                          int H, int W, int C, int Cout, int KH, int KW, int stride, int pad, const float* ws, size_t ws_floats);
 int hab_linear_fwd(const float* x, int ldx, const float* w, int ldw, const float* bias, float* y, int ldy, int M, int N,
                    int K, int relu, int accumulate, float* ws, size_t ws_floats, hipStream_t stream);
 int hab_linear_dgrad(const float* dy, int lddy, const float* w, int ldw, const float* relu_mask, int ldmask, float* dx,

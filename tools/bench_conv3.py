@@ -48,3 +48,22 @@ for name, H, Cc, Cout, pad in (("conv3 64>32 @30", 30, 64, 32, 0), ("layer1 32>3
             t = timeit(lambda: _lib.check(L.hab_conv2d_dgrad(P(y), P(wd), None, None, P(dx), B, H, H, Cc, Cout, 3, 3, 1, pad, P(ws), ws.numel(), S())))
             line += f" | dgrad {t * 1e3:8.1f} us {fl / t / 1e9:7.1f} TF/s"
         print(line, flush=True)
+
+# conv3's data gradient (dX 30x30x64 <- dY 28x28x32, ReLU mask fused) with and without the strip kernel (matrix-path bit 9)
+FORMS = {0: "general", 1: "conv2 strip", 2: "conv3 strip"}
+prev = L.hab_set_matrix_path(-1)
+for B in (64, 512, 1024):
+    dy = torch.randn(B, 28, 28, 32, device="cuda")
+    wd = torch.randn(64, 3, 3, 32, device="cuda") * 0.05
+    mask = torch.randn(B, 30, 30, 64, device="cuda")
+    dx = torch.empty(B, 30, 30, 64, device="cuda")
+    fl = 2.0 * B * 28 * 28 * 32 * 9 * 64
+    ref = torch.nn.functional.conv_transpose2d(dy.permute(0, 3, 1, 2).double(), wd.permute(3, 0, 1, 2).double()).permute(0, 2, 3, 1) * (mask > 0)
+    for mode in (prev & ~512, prev | 513):
+        L.hab_set_matrix_path(mode)
+        args = (P(dy), P(wd), P(mask), None, P(dx), B, 30, 30, 64, 32, 3, 3, 1, 0, P(ws), ws.numel())
+        form = L.hab_conv2d_dgrad_form(*args)
+        t = timeit(lambda: _lib.check(L.hab_conv2d_dgrad(*args, S())))
+        err = float((dx.double() - ref).abs().max() / ref.abs().max())
+        print(f"conv3 dgrad 32>64 @30 B {B:5d} mask {mode:5d} {FORMS[form]:12s} {t * 1e3:8.1f} us {fl / t / 1e9:7.1f} TF/s  rel err {err:.1e}", flush=True)
+L.hab_set_matrix_path(prev)
