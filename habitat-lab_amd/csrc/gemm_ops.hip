@@ -155,12 +155,21 @@ int64_t obs_conv_weight_image_floats() { return ((int64_t)OCP_W_ELEMS + 1) / 2 +
 int obs_conv_weight_image(const float* wf, int Cout, int KH, int KW, int C, void* img, hipStream_t stream) {
     return obs_conv_patch_weight_image(wf, Cout, KH, KW, C, reinterpret_cast<unsigned short*>(img), stream);
 }
+// Whether conv1's forward runs with the observation patch resident in LDS (obs_conv_patch.h, MP_OBS_PATCH with MP_OBS: 8x8 / 4 RGB-D -> at
+// most 32 channels), and in which form of that kernel (HAB_OBS_FWD_FORM_*): the hoisted one, or under MP_OBS_PATCH_PLAIN the plain one.
+// OTHER: the im2col kernels / igemm tiles below.  obs_conv_fwd and hab_obs_conv2d_fwd_form both ask it.
+static int choose_obs_fwd(const ObsConvFwdProb& p, const float* ws, size_t ws_floats, const void* wimg) {
+    if (!(matrix_path_on(MP_OBS_PATCH | MP_OBS) && obs_conv_patch_covers(p, ws, ws_floats, reinterpret_cast<const unsigned short*>(wimg))))
+        return HAB_OBS_FWD_FORM_OTHER;
+    return matrix_path_on(MP_OBS_PATCH_PLAIN) ? HAB_OBS_FWD_FORM_PATCH_PLAIN : HAB_OBS_FWD_FORM_PATCH;
+}
 int obs_conv_fwd(const ConvDesc& d, const ObsView& obs, const float* wf, const float* bias, float* y, int relu, float* ws,
                  size_t ws_floats, hipStream_t stream, const void* wimg) {
     ObsConvFwdProb p;
     HAB_TRY(build(p, d, obs, wf, bias, y, relu));
-    if (matrix_path_on(MP_OBS_PATCH | MP_OBS) && p.quad)  // observation patch resident in LDS (obs_conv_patch.h): 8x8 / 4 RGB-D -> 32 only
-        HAB_TRY_FORM(obs_conv_patch_launch(p, ws, ws_floats, stream, reinterpret_cast<const unsigned short*>(wimg)));
+    const int form = choose_obs_fwd(p, ws, ws_floats, wimg);
+    if (form != HAB_OBS_FWD_FORM_OTHER)
+        HAB_TRY_FORM(obs_conv_patch_launch(p, ws, ws_floats, stream, reinterpret_cast<const unsigned short*>(wimg), form == HAB_OBS_FWD_FORM_PATCH));
     if (matrix_path_on(MP_WS | MP_OBS) && p.quad && p.M > 64)  // producer / consumer waves (obs_conv_bf3_ws.h): 133 -> 148-152 TFLOP/s-eq at 1024 frames
         HAB_TRY_FORM(obs_conv_bf3_ws_launch(p, ws, ws_floats, stream));
     if (matrix_path_on(MP_OBS) && p.quad && p.M > 64)  // uint8 x split-bf16 weights on the matrix pipe (obs_conv_bf3.h)
@@ -518,6 +527,16 @@ extern "C" int hab_obs_conv2d_fwd(const uint8_t* rgb, const float* depth, const 
     if ((!rgb && !depth) || !w_fwd || !y) return HAB_ERR_ARG;
     ObsView o = mkobs(rgb, depth, rows, H, W);
     return obs_conv_fwd(mk(B, H, W, o.C, Cout, KH, KW, stride, pad), o, w_fwd, bias, y, relu, ws, ws_floats, stream);
+}
+extern "C" int hab_obs_conv2d_fwd_form(const uint8_t* rgb, const float* depth, const int* rows, const float* w_fwd,
+                                       const float* bias, float* y, int B, int H, int W, int Cout, int KH, int KW, int stride,
+                                       int pad, int relu, const float* ws, size_t ws_floats) {
+    if ((!rgb && !depth) || !w_fwd || !y) return HAB_ERR_ARG;
+    ObsView o = mkobs(rgb, depth, rows, H, W);
+    ObsConvFwdProb p;
+    const int r = build(p, mk(B, H, W, o.C, Cout, KH, KW, stride, pad), o, w_fwd, bias, y, relu);
+    if (r != HAB_OK) return r;
+    return choose_obs_fwd(p, ws, ws_floats, nullptr);
 }
 extern "C" int hab_conv2d_dgrad(const float* dy, const float* w_dgrad, const float* relu_mask, const float* add, float* dx,
                                 int B, int H, int W, int C, int Cout, int KH, int KW, int stride, int pad, float* ws,

@@ -382,6 +382,8 @@ int hab_sample_actions(const float* probs, const float* exp_noise, int64_t* acti
  *            fragments for k-strided operands, LDS-staged epilogue incl. the flatten permutation (dense_bf3.h)
  *     bit 11 (tests) bit 10's kernel for every shape it applies to
  *     bit 12 (tests) the time-major recurrence as one launch per step instead of the persistent kernels (rnn_persist.h; bit-identical)
+ *     bit 13 (tests, with bit 6) obs_conv_patch.h's forward kernel in its plain form: load addresses and bounds worked out per tile and
+ *            gather unit, the sign schedule applied to every fragment read (bit-identical; for the bitwise tests and A/B runs)
  *   Default 2047 (bits 0-10), env HAB_BF3 overrides.  hab_set_matrix_path(mode >= 0) sets the mask and returns the previous one;
  *   mode < 0 only queries.  Results are fp32-equivalent on either path (tests/test_gpu_bf3.py: error vs float64 of both).
  * ------------------------------------------------------------------------------------------- */
@@ -392,6 +394,17 @@ int hab_conv2d_fwd(const float* x, const float* w_fwd, const float* bias, float*
 int hab_obs_conv2d_fwd(const uint8_t* rgb, const float* depth, const int* rows, const float* w_fwd, const float* bias,
                        float* y, int B, int H, int W, int Cout, int KH, int KW, int stride, int pad, int relu, float* ws,
                        size_t ws_floats, hipStream_t stream);
+/* Whether hab_obs_conv2d_fwd runs such a call on the patch-resident kernel (obs_conv_patch.h) under the current matrix-path mask, and in
+ * which form of it: 0 another kernel (im2col on the bf16 matrix pipe, igemm tiles), 1 the patch kernel (tile-invariant addressing hoisted,
+ * sign applied at staging), 2 the patch kernel in its plain form (bit 13), or a negative HAB_ERR_* where the call itself would be
+ * refused.  Host only: nothing is launched and no pointer is read (null-ness and alignment count).  The launcher asks the same function.
+ * For tests and tools. */
+#define HAB_OBS_FWD_FORM_OTHER 0
+#define HAB_OBS_FWD_FORM_PATCH 1
+#define HAB_OBS_FWD_FORM_PATCH_PLAIN 2
+int hab_obs_conv2d_fwd_form(const uint8_t* rgb, const float* depth, const int* rows, const float* w_fwd, const float* bias,
+                            float* y, int B, int H, int W, int Cout, int KH, int KW, int stride, int pad, int relu, const float* ws,
+                            size_t ws_floats);
 int hab_conv2d_dgrad(const float* dy, const float* w_dgrad, const float* relu_mask, const float* add, float* dx, int B,
                      int H, int W, int C, int Cout, int KH, int KW, int stride, int pad, float* ws, size_t ws_floats,
                      hipStream_t stream);
