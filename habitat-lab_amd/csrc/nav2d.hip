@@ -8,7 +8,8 @@
 // tests/nav2d_geo_reference.py, that of Nav2DObj-v0 (nav2d_obj_geo_build_kernel, nav2d_obj_geo_step_kernel: the distance to the
 // nearest instance of the target category) by tests/nav2d_obj_geo_reference.py.  Nav2DRearr-v0 (one object to pick up and to put down
 // at a goal that only the 1-D sensors tell) shares the world, the placement of Nav2DObj-v0 and the render; its specification is
-// tests/nav2d_rearr_reference.py.
+// tests/nav2d_rearr_reference.py.  Nav2DRearrVel-v0 is that task under Nav2DVel-v0's velocity control plus a grip component; its
+// specification is tests/nav2d_rearr_vel_reference.py.
 #include <cstddef>
 #include "hab_common.h"
 #include "../../include/habitat_amd.h"
@@ -316,6 +317,31 @@ __global__ void __launch_bounds__(GEO ? 64 : 1024) nav2d_step_kernel(Nav2DState*
 // non-finite one acts as 0; the step length is (c_lin + 1) * 0.125, the turn rint(c_ang * max_turn) heading quanta (left positive),
 // and both below their minima is the stop.  A blocked target counts one collision and, with sliding, the agent takes the x or else
 // the y component of the move alone where that is free.  The heading stays an index into `dirs`: no angle is evaluated here.
+// The three helpers are the velocity control of Nav2DVel-v0 and Nav2DRearrVel-v0 alike.
+__device__ inline float vel_clamp(float a) { return isfinite(a) ? fminf(fmaxf(a, -1.0f), 1.0f) : 0.0f; }
+// Steps 1-4: the step length and the turn of (a_lin, a_ang); returns the stop.
+__device__ inline bool vel_decode(float a_lin, float a_ang, int max_turn, int stop_turn, float min_lin, float& l, int& dh) {
+    const float c_lin = vel_clamp(a_lin), c_ang = vel_clamp(a_ang);
+    l = (c_lin + 1.0f) * 0.125f;
+    dh = (int)rintf(c_ang * (float)max_turn);  // |dh| <= max_turn <= nh / 2
+    return (l < min_lin) && (abs(dh) < stop_turn);
+}
+// Step 5: the turn, then the move of length l under the task's free test `free(x, y)`.
+template <class Free>
+__device__ inline void vel_move(Nav2DState& s, const float* __restrict__ dirs, float l, int dh, int nh, int sliding, Free free) {
+    s.heading = (s.heading + dh + nh) % nh;
+    const float nx = s.px + l * dirs[2 * s.heading], ny = s.py + l * dirs[2 * s.heading + 1];
+    if (free(nx, ny)) {
+        s.px = nx; s.py = ny; s.path = s.path + l;
+    } else {
+        s.collisions += 1;
+        if (sliding) {
+            if (free(nx, s.py)) { s.path = s.path + fabsf(nx - s.px); s.px = nx; }
+            else if (free(s.px, ny)) { s.path = s.path + fabsf(ny - s.py); s.py = ny; }
+        }
+    }
+}
+
 template <bool GEO>
 __global__ void __launch_bounds__(GEO ? 64 : 1024) nav2d_vel_step_kernel(Nav2DState* __restrict__ states, const float* __restrict__ dirs, const float2* __restrict__ actions,
                                       const uint8_t* __restrict__ mask, float* __restrict__ goal, float* __restrict__ reward,
@@ -330,24 +356,10 @@ __global__ void __launch_bounds__(GEO ? 64 : 1024) nav2d_vel_step_kernel(Nav2DSt
         first_episode(s, seed, env, K, nh);
     } else {
         const float2 a = actions[n];
-        const float c_lin = isfinite(a.x) ? fminf(fmaxf(a.x, -1.0f), 1.0f) : 0.0f;
-        const float c_ang = isfinite(a.y) ? fminf(fmaxf(a.y, -1.0f), 1.0f) : 0.0f;
-        const float l = (c_lin + 1.0f) * 0.125f;
-        const int dh = (int)rintf(c_ang * (float)max_turn);  // |dh| <= max_turn <= nh / 2
-        const bool stop = (l < min_lin) && (abs(dh) < stop_turn);
-        if (!stop) {
-            s.heading = (s.heading + dh + nh) % nh;
-            const float nx = s.px + l * dirs[2 * s.heading], ny = s.py + l * dirs[2 * s.heading + 1];
-            if (is_free(nx, ny, s, K)) {
-                s.px = nx; s.py = ny; s.path = s.path + l;
-            } else {
-                s.collisions += 1;
-                if (sliding) {
-                    if (is_free(nx, s.py, s, K)) { s.path = s.path + fabsf(nx - s.px); s.px = nx; }
-                    else if (is_free(s.px, ny, s, K)) { s.path = s.path + fabsf(ny - s.py); s.py = ny; }
-                }
-            }
-        }
+        float l;
+        int dh;
+        const bool stop = vel_decode(a.x, a.y, max_turn, stop_turn, min_lin, l, dh);
+        if (!stop) vel_move(s, dirs, l, dh, nh, sliding, [&](float x, float y) { return is_free(x, y, s, K); });
         end_step<true, GEO>(s, stop, 0.2f, reward, not_done, sums, seed, env, n, N, K, nh, max_steps, GEO ? geo + n : nullptr);
     }
     if (goal) write_goal(s, dirs, goal, n);
@@ -585,8 +597,83 @@ __device__ inline void rearr_begin(Nav2DRearrState& r, uint32_t seed, uint32_t e
     s.d_start = s.d_prev = rearr_potential(r, b);
 }
 
-// One thread per env, as nav2d_step_kernel.  Then the three vector sensors: the object's start and the goal as (dot, cross) in the
-// heading's frame, written term by term like write_goal's, and the holding flag.
+// The task's free test: Nav2D-v0's, and outside the object's keep-out disc unless the object is held.
+__device__ inline bool rearr_is_free(float x, float y, const Nav2DRearrState& r, int K) {
+    return is_free(x, y, r.base, K) && (r.holding || !(dist(x, y, r.ox, r.oy) < OBJ_BLOCK));
+}
+// A PICK attempt with (c, sn) the heading's direction; returns whether it was the episode's first successful one.
+__device__ inline bool rearr_pick(Nav2DRearrState& r, float c, float sn) {
+    const Nav2DState& s = r.base;
+    const float dx = r.ox - s.px, dy = r.oy - s.py;
+    if (!r.holding && dist(s.px, s.py, r.ox, r.oy) < REARR_REACH && dx * c + dy * sn > 0.0f) {
+        const bool first_pick = r.picks == 0;
+        r.holding = r.held = 1;
+        r.picks += 1;
+        return first_pick;
+    }
+    r.invalid += 1;
+    return false;
+}
+// A PLACE attempt with (c, sn) the heading's direction.
+__device__ inline void rearr_place(Nav2DRearrState& r, float c, float sn, int K) {
+    const Nav2DState& s = r.base;
+    const float qx = s.px + REARR_ARM * c, qy = s.py + REARR_ARM * sn;
+    if (r.holding && qx >= OBJ_LO && qx <= OBJ_HI && qy >= OBJ_LO && qy <= OBJ_HI && !in_grown_rect(qx, qy, s, K)) {
+        r.ox = qx; r.oy = qy;
+        r.holding = 0;
+    } else {
+        r.invalid += 1;
+    }
+}
+// The end of the step: a held object travels with the agent; then end_step's, with the potential in the distance's place, the pick
+// bonus and this task's measures.  `stop` is the action's request to end the episode.  Forced inline: left to itself the compiler
+// makes it a call from both kernels, and the discrete kernel would no longer be the code it was.
+__device__ __forceinline__ void rearr_end_step(Nav2DRearrState& r, bool stop, bool first_pick, float* __restrict__ reward, uint8_t* __restrict__ not_done,
+                                      float* __restrict__ sums, uint32_t seed, uint32_t env, int n, int N, int K, int nh, int max_steps,
+                                      int start_holding) {
+    Nav2DState& s = r.base;
+    if (r.holding) { r.ox = s.px; r.oy = s.py; }
+    float b;
+    const float phi = rearr_potential(r, b);
+    const bool success = stop && !r.holding && b < REARR_SUCCESS;
+    reward[n] = ((-0.01f + (s.d_prev - phi)) + (first_pick ? 1.0f : 0.0f)) + (success ? 2.5f : 0.0f);
+    s.d_prev = phi;
+    s.steps += 1;
+    const bool done = stop || (s.steps >= max_steps);
+    not_done[n] = done ? 0 : 1;
+    s.ended = done ? 1 : 0;
+    if (done) {
+        s.last[0] = success ? 1.0f : 0.0f;
+        s.last[1] = (float)r.held;
+        s.last[2] = b;
+        s.last[3] = (float)s.collisions;
+        if (sums)
+            for (int m = 0; m < 4; ++m) sums[(size_t)m * N + n] = sums[(size_t)m * N + n] + s.last[m];
+        s.episode += 1;
+        begin_episode<false>(s, seed, env, K, nh);
+        rearr_begin(r, seed, env, K, start_holding);
+    }
+}
+// The three vector sensors: the object's start and the goal as (dot, cross) in the heading's frame, written term by term like
+// write_goal's, and the holding flag.
+__device__ inline void rearr_write_sensors(const Nav2DRearrState& r, const float* __restrict__ dirs, float* __restrict__ obj_start,
+                                           float* __restrict__ obj_goal, float* __restrict__ is_holding, int n) {
+    const Nav2DState& s = r.base;
+    const float c = dirs[2 * s.heading], sn = dirs[2 * s.heading + 1];
+    if (obj_start) {
+        const float dx = r.obj[0][0] - s.px, dy = r.obj[0][1] - s.py;
+        obj_start[2 * n + 0] = dx * c + dy * sn;
+        obj_start[2 * n + 1] = c * dy - sn * dx;
+    }
+    if (obj_goal) {
+        const float dx = s.gx - s.px, dy = s.gy - s.py;
+        obj_goal[2 * n + 0] = dx * c + dy * sn;
+        obj_goal[2 * n + 1] = c * dy - sn * dx;
+    }
+    if (is_holding) is_holding[n] = (float)r.holding;
+}
+
+// One thread per env, as nav2d_step_kernel.  Then the three vector sensors.
 __global__ void nav2d_rearr_step_kernel(Nav2DRearrState* __restrict__ states, const float* __restrict__ dirs,
                                         const int64_t* __restrict__ actions, const uint8_t* __restrict__ mask,
                                         float* __restrict__ obj_start, float* __restrict__ obj_goal, float* __restrict__ is_holding,
@@ -606,67 +693,84 @@ __global__ void nav2d_rearr_step_kernel(Nav2DRearrState* __restrict__ states, co
         bool first_pick = false;
         if (a == 1) {
             const float nx = s.px + FORWARD * c, ny = s.py + FORWARD * sn;
-            const bool open = is_free(nx, ny, s, K) && (r.holding || !(dist(nx, ny, r.ox, r.oy) < OBJ_BLOCK));
-            if (open) { s.px = nx; s.py = ny; s.path = s.path + FORWARD; }
+            if (rearr_is_free(nx, ny, r, K)) { s.px = nx; s.py = ny; s.path = s.path + FORWARD; }
             else s.collisions += 1;
         } else if (a == 2) {
             s.heading = (s.heading + 1) % nh;
         } else if (a == 3) {
             s.heading = (s.heading + nh - 1) % nh;
         } else if (a == 4) {
-            const float dx = r.ox - s.px, dy = r.oy - s.py;
-            if (!r.holding && dist(s.px, s.py, r.ox, r.oy) < REARR_REACH && dx * c + dy * sn > 0.0f) {
-                first_pick = r.picks == 0;
-                r.holding = r.held = 1;
-                r.picks += 1;
-            } else {
-                r.invalid += 1;
-            }
+            first_pick = rearr_pick(r, c, sn);
         } else if (a == 5) {
-            const float qx = s.px + REARR_ARM * c, qy = s.py + REARR_ARM * sn;
-            if (r.holding && qx >= OBJ_LO && qx <= OBJ_HI && qy >= OBJ_LO && qy <= OBJ_HI && !in_grown_rect(qx, qy, s, K)) {
-                r.ox = qx; r.oy = qy;
-                r.holding = 0;
-            } else {
-                r.invalid += 1;
-            }
+            rearr_place(r, c, sn, K);
         }
-        if (r.holding) { r.ox = s.px; r.oy = s.py; }
-        // the end of the step: end_step's, with the potential in the distance's place, the pick bonus and this task's measures
-        float b;
-        const float phi = rearr_potential(r, b);
-        const bool stop = a == 0;
-        const bool success = stop && !r.holding && b < REARR_SUCCESS;
-        reward[n] = ((-0.01f + (s.d_prev - phi)) + (first_pick ? 1.0f : 0.0f)) + (success ? 2.5f : 0.0f);
-        s.d_prev = phi;
-        s.steps += 1;
-        const bool done = stop || (s.steps >= max_steps);
-        not_done[n] = done ? 0 : 1;
-        s.ended = done ? 1 : 0;
-        if (done) {
-            s.last[0] = success ? 1.0f : 0.0f;
-            s.last[1] = (float)r.held;
-            s.last[2] = b;
-            s.last[3] = (float)s.collisions;
-            if (sums)
-                for (int m = 0; m < 4; ++m) sums[(size_t)m * N + n] = sums[(size_t)m * N + n] + s.last[m];
-            s.episode += 1;
-            begin_episode<false>(s, seed, env, K, nh);
-            rearr_begin(r, seed, env, K, start_holding);
+        rearr_end_step(r, a == 0, first_pick, reward, not_done, sums, seed, env, n, N, K, nh, max_steps, start_holding);
+    }
+    rearr_write_sensors(r, dirs, obj_start, obj_goal, is_holding, n);
+}
+
+// Nav2DRearrVel-v0 (Nav2DRearrVelVectorEnv; specification: tests/nav2d_rearr_vel_reference.py): Nav2DRearr-v0's record, world, places,
+// reward, measures and sensors under Nav2DVel-v0's velocity control plus a grip component.  The action (a_lin, a_ang, a_grip) is one
+// 12-byte row of an (N, 3) float32 tensor, read as three scalars: a row is 4-byte aligned and no more.  The motion is vel_decode /
+// vel_move with this task's free test; then, on every step, the grip with the new position and heading: c_grip > 0 with empty hands
+// is a PICK attempt, c_grip < 0 while holding a PLACE attempt, every other combination nothing; then Nav2DRearr-v0's end of the step
+// with the velocity stop in STOP's place.
+// A step of this task tests up to three positions, and is_free reads the rectangles through the state pointer, a memory latency per
+// rectangle and test for the one wave that the 64 envs of a workgroup are.  So the K inflated boxes -- is_free's expressions -- are
+// computed once into registers, the loops over k unrolled over MAX_K with the uniform k < K as a guard as in geo_query, and a test is
+// straight-line compares.  The booleans are is_free's.
+struct FreeBoxes { float x0[MAX_K], y0[MAX_K], x1[MAX_K], y1[MAX_K]; };
+__device__ inline void load_free_boxes(FreeBoxes& b, const Nav2DState& s, int K) {
+#pragma unroll
+    for (int k = 0; k < MAX_K; ++k) {
+        if (k < K) {
+            b.x0[k] = s.rect[k][0] - RADIUS; b.y0[k] = s.rect[k][1] - RADIUS; b.x1[k] = s.rect[k][2] + RADIUS; b.y1[k] = s.rect[k][3] + RADIUS;
         }
     }
-    const float c = dirs[2 * s.heading], sn = dirs[2 * s.heading + 1];
-    if (obj_start) {
-        const float dx = r.obj[0][0] - s.px, dy = r.obj[0][1] - s.py;
-        obj_start[2 * n + 0] = dx * c + dy * sn;
-        obj_start[2 * n + 1] = c * dy - sn * dx;
+}
+__device__ inline bool is_free_boxes(float x, float y, const FreeBoxes& b, int K) {
+    bool free = x >= LO && x <= HI && y >= LO && y <= HI;
+#pragma unroll
+    for (int k = 0; k < MAX_K; ++k)
+        if (k < K) free &= !((x > b.x0[k]) & (x < b.x1[k]) & (y > b.y0[k]) & (y < b.y1[k]));
+    return free;
+}
+
+__global__ void __launch_bounds__(64)
+nav2d_rearr_vel_step_kernel(Nav2DRearrState* __restrict__ states, const float* __restrict__ dirs, const float* __restrict__ actions,
+                            const uint8_t* __restrict__ mask, float* __restrict__ obj_start, float* __restrict__ obj_goal,
+                            float* __restrict__ is_holding, float* __restrict__ reward, uint8_t* __restrict__ not_done,
+                            float* __restrict__ sums, uint32_t seed, uint32_t env_offset, int N, int K, int nh, int max_steps,
+                            int start_holding, int max_turn, int stop_turn, float min_lin, int sliding, int advance) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N || (mask && !mask[n])) return;
+    Nav2DRearrState& r = states[n];
+    Nav2DState& s = r.base;
+    const uint32_t env = env_offset + (uint32_t)n;
+    if (!advance) {
+        first_episode<false>(s, seed, env, K, nh);
+        rearr_begin(r, seed, env, K, start_holding);
+    } else {
+        const float a_lin = actions[3 * (size_t)n], a_ang = actions[3 * (size_t)n + 1], c_grip = vel_clamp(actions[3 * (size_t)n + 2]);
+        float l;
+        int dh;
+        const bool stop = vel_decode(a_lin, a_ang, max_turn, stop_turn, min_lin, l, dh);
+        if (!stop) {
+            FreeBoxes boxes;
+            load_free_boxes(boxes, s, K);
+            const bool holding = r.holding;
+            const float ox = r.ox, oy = r.oy;  // neither moves during the move: a held object follows at the end of the step
+            vel_move(s, dirs, l, dh, nh, sliding, [&](float x, float y) {  // rearr_is_free, on the registers
+                return is_free_boxes(x, y, boxes, K) && (holding || !(dist(x, y, ox, oy) < OBJ_BLOCK));
+            });
+        }
+        const float c = dirs[2 * s.heading], sn = dirs[2 * s.heading + 1];
+        bool first_pick = false;
+        if (c_grip > 0.0f && !r.holding) first_pick = rearr_pick(r, c, sn);
+        else if (c_grip < 0.0f && r.holding) rearr_place(r, c, sn, K);
+        rearr_end_step(r, stop, first_pick, reward, not_done, sums, seed, env, n, N, K, nh, max_steps, start_holding);
     }
-    if (obj_goal) {
-        const float dx = s.gx - s.px, dy = s.gy - s.py;
-        obj_goal[2 * n + 0] = dx * c + dy * sn;
-        obj_goal[2 * n + 1] = c * dy - sn * dx;
-    }
-    if (is_holding) is_holding[n] = (float)r.holding;
+    rearr_write_sensors(r, dirs, obj_start, obj_goal, is_holding, n);
 }
 
 // ---- geodesic distance of Nav2DObj-v0 (distance = "geodesic"; specification: tests/nav2d_obj_geo_reference.py) ---------------------
@@ -1309,6 +1413,28 @@ extern "C" int hab_nav2d_rearr_step(void* state, const float* dirs, const float*
     nav2d_rearr_step_kernel<<<cdiv(N, 64), 64, 0, stream>>>((Nav2DRearrState*)state, dirs, actions, mask, obj_start, obj_goal, is_holding,
                                                             reward, not_done, measure_sums, seed, env_offset, N, num_obstacles,
                                                             num_headings, max_episode_steps, start_holding, advance);
+    HAB_LAUNCH_CHECK();
+    return launch_render<Render::REARR>(a, 0);
+}
+
+extern "C" int hab_nav2d_rearr_vel_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                                        const float* actions, const uint8_t* mask, uint8_t* head_rgb, float* head_depth, float* obj_start,
+                                        float* obj_goal, float* is_holding, float* reward, uint8_t* not_done, float* measure_sums,
+                                        uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings,
+                                        int max_episode_steps, int start_holding, int max_turn_steps, int stop_turn_steps,
+                                        float min_abs_lin_speed, int allow_sliding, int advance, hipStream_t stream) {
+    const StepArgs a{state, nullptr, dirs, ray, col_cos, tanv, actions, mask, head_rgb, head_depth, nullptr, nullptr, reward, not_done,
+                     measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream};
+    const int rc = check_step_args(a, false);
+    if (rc != HAB_OK) return rc;
+    if (start_holding != 0 && start_holding != 1) return HAB_ERR_ARG;
+    if ((uintptr_t)actions & 3) return HAB_ERR_ARG;  // a row of three floats is read as three scalars
+    if (max_turn_steps < 1 || max_turn_steps > num_headings / 2 || stop_turn_steps < 1 || stop_turn_steps > max_turn_steps)
+        return HAB_ERR_ARG;
+    nav2d_rearr_vel_step_kernel<<<cdiv(N, 64), 64, 0, stream>>>((Nav2DRearrState*)state, dirs, actions, mask, obj_start, obj_goal,
+                                                                is_holding, reward, not_done, measure_sums, seed, env_offset, N,
+                                                                num_obstacles, num_headings, max_episode_steps, start_holding,
+                                                                max_turn_steps, stop_turn_steps, min_abs_lin_speed, allow_sliding, advance);
     HAB_LAUNCH_CHECK();
     return launch_render<Render::REARR>(a, 0);
 }

@@ -474,19 +474,19 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
         raise _lib.HabError("Nav2D: episodes are generated and never repeat, so no env is ever paused")
 
 
-def nav2d_vel_parameters(turn_angle, max_turn_angle, min_abs_lin_speed, min_abs_ang_speed):
-    """Checks the `habitat.synthetic` keys of Nav2DVel-v0 and returns (num_headings, M, S): the largest turn of one step and the
-    smallest turn that is not a stop, both in heading quanta."""
+def nav2d_vel_parameters(turn_angle, max_turn_angle, min_abs_lin_speed, min_abs_ang_speed, who: str = "Nav2DVel"):
+    """Checks the `habitat.synthetic` keys of Nav2DVel-v0 (and of `who`, a task with the same motion) and returns (num_headings, M, S):
+    the largest turn of one step and the smallest turn that is not a stop, both in heading quanta."""
     nh = nav2d_num_headings(turn_angle)
     if not whole(max_turn_angle) or max_turn_angle <= 0 or max_turn_angle % turn_angle != 0 or max_turn_angle > 180:
-        raise _lib.HabError(f"Nav2DVel: max_turn_angle {max_turn_angle!r} must be a positive multiple of turn_angle {turn_angle} "
+        raise _lib.HabError(f"{who}: max_turn_angle {max_turn_angle!r} must be a positive multiple of turn_angle {turn_angle} "
                             "(whole degrees), at most 180")
     if not whole(min_abs_ang_speed) or min_abs_ang_speed <= 0 or min_abs_ang_speed % turn_angle != 0 or min_abs_ang_speed > max_turn_angle:
-        raise _lib.HabError(f"Nav2DVel: min_abs_ang_speed {min_abs_ang_speed!r} must be a positive multiple of turn_angle {turn_angle} "
+        raise _lib.HabError(f"{who}: min_abs_ang_speed {min_abs_ang_speed!r} must be a positive multiple of turn_angle {turn_angle} "
                             f"(whole degrees), at most max_turn_angle {max_turn_angle}")
     if (isinstance(min_abs_lin_speed, bool) or not isinstance(min_abs_lin_speed, (int, float, np.integer, np.floating))
             or not 0.0 < float(min_abs_lin_speed) <= 0.25):
-        raise _lib.HabError(f"Nav2DVel: min_abs_lin_speed {min_abs_lin_speed!r} must be a length in (0, 0.25] metres")
+        raise _lib.HabError(f"{who}: min_abs_lin_speed {min_abs_lin_speed!r} must be a length in (0, 0.25] metres")
     return nh, int(max_turn_angle) // int(turn_angle), int(min_abs_ang_speed) // int(turn_angle)
 
 
@@ -771,6 +771,98 @@ class Nav2DRearrVectorEnv(Nav2DVectorEnv):
         raise _lib.HabError("Nav2DRearr: the task has no pointgoal sensor; use step_into_obs with the rearrangement sensor rows")
 
 
+class Nav2DRearrVelVectorEnv(Nav2DRearrVectorEnv):
+    """Nav2DRearrVel-v0: pick and place under velocity and grip control, the source on which the Gaussian head, the previous-action
+    embedding, float action storage and the fused sensor columns run together.  The task is Nav2DRearr-v0 word for word (see
+    Nav2DRearrVectorEnv) except the action and the physics of one step.  What stays the same: world, places, object, holding flag,
+    `start_holding`, keep-out 0.4 m, reach 1.0 m, arm 0.5 m, potential Phi = d(p, o) + d(o, g), pick bonus, success radius 0.5 m, the
+    four measures, the five sensors, rendering, the state record, streams, Euclidean distances only.
+    tests/nav2d_rearr_vel_reference.py restates the task in numpy; `nav2d_rearr_vel_step_kernel` (csrc/nav2d.hip) matches it bit for
+    bit on every output.  No angle function runs on the device; the heading stays an index into the host tables.
+
+    Parameters (`habitat.synthetic`): Nav2DVel-v0's motion parameters (see Nav2DVelVectorEnv): turn_angle (default 1 here as there),
+      max_turn_angle, min_abs_lin_speed, min_abs_ang_speed, allow_sliding, checked by `nav2d_vel_parameters`, giving M and S; and
+      Nav2DRearr-v0's start_holding and num_obstacles.
+    Action space: Box(-1, 1, (3,), float32), a = (a_lin, a_ang, a_grip).
+    One step (every written float32 operation is one rounding, no fused multiply-add), in this order:
+      1. per component c = min(max(a, -1), 1), and c = 0 for a non-finite a: Nav2DVel-v0's step 1, on three components;
+      2. l = (c_lin + 1) * 0.125; dh = (int) rint(c_ang * M); stop = (l < min_abs_lin_speed) and (|dh| < S): Nav2DVel-v0's steps 2-4,
+         bit for bit;
+      3. if not stop: h = (h + dh) mod num_headings and, with (c, s) = dirs[h], the target is (px + l * c, py + l * s).  A position is
+         free iff Nav2D-v0's box test holds and (holding or not d(pos, o) < 0.4): Nav2DRearr-v0's MOVE_FORWARD test.  A free target
+         is taken and path grows by l.  A blocked target counts one collision; with sliding (nx, py) is then tried, else (px, ny),
+         exactly as Nav2DVel-v0's step 5 with this free test and its path increments.  On stop nothing moves;
+      4. grip, evaluated on every step (stop or not), after step 3, with the new position and the new heading's (c, s):
+         c_grip > 0 and holding = 0 is a PICK attempt under Nav2DRearr-v0's rule: it needs d(p, o) < 1.0 and
+         (ox - px) * c + (oy - py) * s > 0; on success holding = held = 1, picks += 1 and first_pick = (picks was 0); on refusal
+         invalid += 1.  c_grip < 0 and holding = 1 is a PLACE attempt under Nav2DRearr-v0's rule: it needs q = p + 0.5 * dir inside
+         [0.5, 7.5]^2 and not strictly inside a grown rectangle; on success o = q and holding = 0; on refusal invalid += 1.  Every
+         other combination -- c_grip == 0, c_grip > 0 while holding, c_grip < 0 with empty hands -- changes nothing and counts
+         nothing.  While holding, o = p;
+      5. end of step: Nav2DRearr-v0's, with `stop` in STOP's place: reward = ((-0.01 + (Phi_prev - Phi)) + 1.0 * first_pick) +
+         2.5 * success; success = stop and holding = 0 and b < 0.5, so "release and stand still" in one step can succeed;
+         done = stop or steps >= max_episode_steps; measures, sums, the next episode's world on done and the three vector sensors
+         are as there.
+
+    `step_into_obs(obs, reward, not_done, actions=...)` takes the (N, 3) float32 rows the policy stored; the env clamps, so the stored
+    action stays unclipped.  `async_step_at(i, a)` takes a length-3 array (or {"action": array})."""
+
+    _name = "Nav2DRearrVel"
+    _entries = ("hab_nav2d_rearr_vel_step",)
+    _action_dtype, _action_text = torch.float32, "float32 device tensor of shape (N, 3)"
+    num_actions = 1
+
+    def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = False,
+                 use_depth: bool = True, num_actions: int = 1, device="cuda", num_obstacles: int = 3, turn_angle: int = 1,
+                 max_episode_steps: int = 500, start_holding: bool = False, max_turn_angle: int = 10, min_abs_lin_speed: float = 0.025,
+                 min_abs_ang_speed: int = 5, allow_sliding: bool = True, distance: str = "euclidean"):
+        if nav2d_distance(distance, "Nav2DRearrVel") != "euclidean":
+            raise _lib.HabError("Nav2DRearrVel: the task has Euclidean distances only; distance_to_goal 'geodesic' is not defined for it")
+        _, self.max_turn_steps, self.stop_turn_steps = nav2d_vel_parameters(turn_angle, max_turn_angle, min_abs_lin_speed,
+                                                                            min_abs_ang_speed, "Nav2DRearrVel")
+        if not isinstance(allow_sliding, (bool, np.bool_)):
+            raise _lib.HabError(f"Nav2DRearrVel: allow_sliding {allow_sliding!r} must be true or false")
+        if not isinstance(start_holding, (bool, np.bool_)):
+            raise _lib.HabError(f"Nav2DRearrVel: start_holding {start_holding!r} must be true or false")
+        if num_actions != 1:
+            raise _lib.HabError(f"Nav2DRearrVel: the task has the one action velocity_control (with its grip component), got {num_actions} actions")
+        if (use_rgb or use_depth) and (int(height) <= 0 or int(width) <= 0):
+            raise _lib.HabError(f"Nav2DRearrVel: the image size {height} x {width} must be positive")
+        self.max_turn_angle, self.min_abs_ang_speed = int(max_turn_angle), int(min_abs_ang_speed)
+        self.min_abs_lin_speed, self.allow_sliding = float(min_abs_lin_speed), bool(allow_sliding)
+        super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
+                         num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps,
+                         start_holding=start_holding)
+        self.task = "nav2drearrvel"
+        self.action_spaces = [spaces.Box(-1.0, 1.0, (3,), np.float32) for _ in range(num_envs)]
+        self.orig_action_spaces = self.action_spaces
+        self._actions_host = np.zeros((num_envs, 3), dtype=np.float32)
+
+    def _actions_shaped(self, actions) -> bool:
+        return tuple(actions.shape) == (self.num_envs, 3)
+
+    def _task_parameters(self):
+        return (int(self.start_holding), self.max_turn_steps, self.stop_turn_steps, self.min_abs_lin_speed, int(self.allow_sliding))
+
+    def async_step_at(self, index_env: int, action) -> None:
+        if isinstance(action, dict):
+            action = action["action"]
+        try:
+            a = np.asarray(action, dtype=np.float32)
+        except (TypeError, ValueError):
+            a = None
+        if a is None or a.shape != (3,):
+            raise _lib.HabError(f"Nav2DRearrVel: env {index_env}: action {action!r} is not a length-3 array (a_lin, a_ang, a_grip)")
+        SyntheticVectorEnv.async_step_at(self, index_env, action)
+        self._actions_host[int(index_env)] = a
+
+    def reset_into(self, rgb, depth, goal):
+        raise _lib.HabError("Nav2DRearrVel: the task has no pointgoal sensor; use reset_into_obs with the rearrangement sensor rows")
+
+    def step_into(self, rgb, depth, goal, reward, not_done, actions=None, mask=None):
+        raise _lib.HabError("Nav2DRearrVel: the task has no pointgoal sensor; use step_into_obs with the rearrangement sensor rows")
+
+
 class SyntheticVectorEnvFactory(VectorEnvFactory):
     """Default `_target_`: N synthetic PointNav envs sized from habitat.simulator.sensors.*; per-rank env ids are
     offset by rank * num_environments exactly like the reference offsets the seed (ppo_trainer.py:208-211).  A
@@ -781,7 +873,10 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
     reads num_objects / num_categories too and takes its image size from the rgb, else the depth, else the semantic sensor.
     `habitat.synthetic.distance_to_goal` ("euclidean", the default, or "geodesic") is the distance mode of these three Nav2D tasks.
     A type starting with "nav2drearr" selects Nav2DRearr-v0 (Nav2DRearrVectorEnv: pick and place, the rearrangement sensor set), which
-    reads start_holding too, takes its image size from the head_rgb, else the head_depth sensor, and refuses the geodesic mode."""
+    reads start_holding too, takes its image size from the head_rgb, else the head_depth sensor, and refuses the geodesic mode.  A type
+    starting with "nav2drearrvel" -- tested before "nav2drearr", which keeps its meaning for everything else -- selects
+    Nav2DRearrVel-v0 (Nav2DRearrVelVectorEnv: that task under velocity and grip control), which reads Nav2DVel-v0's keys and
+    start_holding and takes its image size like Nav2DRearr-v0."""
 
     def __init__(self, use_rgb: bool = True, use_depth: bool = True):
         self.use_rgb, self.use_depth = use_rgb, use_depth
@@ -806,6 +901,11 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
                 ref = sens["head_rgb"] if use_rgb else (sens["head_depth"] if use_depth else dict(height=0, width=0))
                 make = Nav2DRearrVectorEnv
                 kw.update(use_rgb=use_rgb, use_depth=use_depth, start_holding=getattr(syn, "start_holding", False))
+                if task_type.startswith("nav2drearrvel"):
+                    make = Nav2DRearrVelVectorEnv
+                    kw.update(turn_angle=getattr(syn, "turn_angle", 1), max_turn_angle=getattr(syn, "max_turn_angle", 10),
+                              min_abs_lin_speed=getattr(syn, "min_abs_lin_speed", 0.025),
+                              min_abs_ang_speed=getattr(syn, "min_abs_ang_speed", 5), allow_sliding=getattr(syn, "allow_sliding", True))
             elif task_type.startswith("nav2dobj"):
                 if not (use_rgb or use_depth):
                     if "semantic" not in sens:

@@ -226,6 +226,23 @@ int hab_nav2d_rearr_step(void* state /*N,HAB_NAV2D_REARR_STATE_BYTES*/, const fl
                          float* reward /*N*/, uint8_t* not_done /*N*/, float* measure_sums /*4,N*/, uint32_t seed, uint32_t env_offset,
                          int N, int H, int W, int num_obstacles, int num_headings, int max_episode_steps, int start_holding,
                          int advance, hipStream_t stream);
+/* Nav2DRearrVel-v0: Nav2DRearr-v0 under Nav2DVel-v0's velocity control plus one grip component (definition:
+ * habitat_amd/common/env_factory.py, Nav2DRearrVelVectorEnv; bit-identical to tests/nav2d_rearr_vel_reference.py on every output).
+ * The record is Nav2DRearr-v0's (hab_nav2d_rearr_state_bytes) and every argument of hab_nav2d_rearr_step keeps its meaning and its
+ * checks, except: actions f32 (N,3), rows (a_lin, a_ang, a_grip), 4-byte aligned and no more -- a row is read as three scalars, a
+ * pointer that is not 4-byte aligned is HAB_ERR_ARG.  Each component is clamped to [-1, 1], a non-finite one acts as 0.  a_lin and
+ * a_ang move the agent as hab_nav2d_vel_step's do, with this task's free test; the four arguments after start_holding are that
+ * entry's, with its checks.  Then, on every step, the grip at the new position and heading: c_grip > 0 with empty hands is a PICK
+ * attempt, c_grip < 0 while holding a PLACE attempt, both under Nav2DRearr-v0's rules (a refusal counts in INVALID); every other
+ * combination does and counts nothing.  The episode ends on the velocity stop, which takes STOP's place in the success test, or at
+ * max_episode_steps. */
+int hab_nav2d_rearr_vel_step(void* state /*N,HAB_NAV2D_REARR_STATE_BYTES*/, const float* dirs, const float* ray, const float* col_cos,
+                             const float* tanv, const float* actions /*N,3*/, const uint8_t* mask /*N*/, uint8_t* head_rgb /*N,H,W,3*/,
+                             float* head_depth /*N,H,W,1*/, float* obj_start /*N,2*/, float* obj_goal /*N,2*/, float* is_holding /*N,1*/,
+                             float* reward /*N*/, uint8_t* not_done /*N*/, float* measure_sums /*4,N*/, uint32_t seed,
+                             uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings, int max_episode_steps,
+                             int start_holding, int max_turn_steps, int stop_turn_steps, float min_abs_lin_speed, int allow_sliding,
+                             int advance, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Observation transformers, fused: ResizeShortestEdge followed by CenterCropper
