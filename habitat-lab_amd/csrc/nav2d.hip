@@ -9,7 +9,9 @@
 // nearest instance of the target category) by tests/nav2d_obj_geo_reference.py.  Nav2DRearr-v0 (one object to pick up and to put down
 // at a goal that only the 1-D sensors tell) shares the world, the placement of Nav2DObj-v0 and the render; its specification is
 // tests/nav2d_rearr_reference.py.  Nav2DRearrVel-v0 is that task under Nav2DVel-v0's velocity control plus a grip component; its
-// specification is tests/nav2d_rearr_vel_reference.py.
+// specification is tests/nav2d_rearr_vel_reference.py.  The geodesic distance mode of these two (nav2d_rearr_geo_build_kernel,
+// nav2d_rearr_geo_step_kernel: two fields per env, one of which moves with the object) is specified by
+// tests/nav2d_rearr_geo_reference.py.
 #include <cstddef>
 #include "hab_common.h"
 #include "../../include/habitat_amd.h"
@@ -105,7 +107,9 @@ static_assert(offsetof(Nav2DRearrState, picks) == 4 * HAB_NAV2D_REARR_W_PICKS &&
 // native (1 ulp) square root; `sqrtf` is the IEEE one under hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt.
 __device__ inline float sqrt_rn(float x) { return __builtin_sqrtf(x); }
 
-__device__ inline bool is_free(float x, float y, const Nav2DState& s, int K) {
+// S: a record with the rectangles, a Nav2DState or the geodesic rearrangement step's RearrLane::Base.
+template <class S>
+__device__ inline bool is_free(float x, float y, const S& s, int K) {
     if (!(x >= LO && x <= HI && y >= LO && y <= HI)) return false;
     for (int k = 0; k < K; ++k)
         if (x > s.rect[k][0] - RADIUS && x < s.rect[k][2] + RADIUS && y > s.rect[k][1] - RADIUS && y < s.rect[k][3] + RADIUS)
@@ -327,8 +331,8 @@ __device__ inline bool vel_decode(float a_lin, float a_ang, int max_turn, int st
     return (l < min_lin) && (abs(dh) < stop_turn);
 }
 // Step 5: the turn, then the move of length l under the task's free test `free(x, y)`.
-template <class Free>
-__device__ inline void vel_move(Nav2DState& s, const float* __restrict__ dirs, float l, int dh, int nh, int sliding, Free free) {
+template <class S, class Free>
+__device__ inline void vel_move(S& s, const float* __restrict__ dirs, float l, int dh, int nh, int sliding, Free free) {
     s.heading = (s.heading + dh + nh) % nh;
     const float nx = s.px + l * dirs[2 * s.heading], ny = s.py + l * dirs[2 * s.heading + 1];
     if (free(nx, ny)) {
@@ -490,7 +494,8 @@ __device__ inline float nearest_target(Nav2DObjState& s, int M) {
     return best;
 }
 // Whether (x, y) lies strictly inside one of the K rectangles grown by the object radius.
-__device__ inline bool in_grown_rect(float x, float y, const Nav2DState& s, int K) {
+template <class S>
+__device__ inline bool in_grown_rect(float x, float y, const S& s, int K) {
     bool in_rect = false;
     for (int k = 0; k < K; ++k)
         in_rect = in_rect || (x > s.rect[k][0] - OBJ_R && x < s.rect[k][2] + OBJ_R && y > s.rect[k][1] - OBJ_R && y < s.rect[k][3] + OBJ_R);
@@ -597,13 +602,16 @@ __device__ inline void rearr_begin(Nav2DRearrState& r, uint32_t seed, uint32_t e
     s.d_start = s.d_prev = rearr_potential(r, b);
 }
 
-// The task's free test: Nav2D-v0's, and outside the object's keep-out disc unless the object is held.
-__device__ inline bool rearr_is_free(float x, float y, const Nav2DRearrState& r, int K) {
+// The task's free test: Nav2D-v0's, and outside the object's keep-out disc unless the object is held.  R, here and in rearr_pick and
+// rearr_place: a Nav2DRearrState, or the geodesic step's RearrLane.
+template <class R>
+__device__ inline bool rearr_is_free(float x, float y, const R& r, int K) {
     return is_free(x, y, r.base, K) && (r.holding || !(dist(x, y, r.ox, r.oy) < OBJ_BLOCK));
 }
 // A PICK attempt with (c, sn) the heading's direction; returns whether it was the episode's first successful one.
-__device__ inline bool rearr_pick(Nav2DRearrState& r, float c, float sn) {
-    const Nav2DState& s = r.base;
+template <class R>
+__device__ inline bool rearr_pick(R& r, float c, float sn) {
+    const auto& s = r.base;
     const float dx = r.ox - s.px, dy = r.oy - s.py;
     if (!r.holding && dist(s.px, s.py, r.ox, r.oy) < REARR_REACH && dx * c + dy * sn > 0.0f) {
         const bool first_pick = r.picks == 0;
@@ -615,8 +623,9 @@ __device__ inline bool rearr_pick(Nav2DRearrState& r, float c, float sn) {
     return false;
 }
 // A PLACE attempt with (c, sn) the heading's direction.
-__device__ inline void rearr_place(Nav2DRearrState& r, float c, float sn, int K) {
-    const Nav2DState& s = r.base;
+template <class R>
+__device__ inline void rearr_place(R& r, float c, float sn, int K) {
+    const auto& s = r.base;
     const float qx = s.px + REARR_ARM * c, qy = s.py + REARR_ARM * sn;
     if (r.holding && qx >= OBJ_LO && qx <= OBJ_HI && qy >= OBJ_LO && qy <= OBJ_HI && !in_grown_rect(qx, qy, s, K)) {
         r.ox = qx; r.oy = qy;
@@ -1003,6 +1012,305 @@ nav2d_obj_geo_step_kernel(Nav2DObjState* __restrict__ states, ObjGeoField* __res
     }
 }
 
+// ---- geodesic distances of Nav2DRearr-v0 and Nav2DRearrVel-v0 (distance = "geodesic"; specification: --------------------------------
+// tests/nav2d_rearr_geo_reference.py) ------------------------------------------------------------------------------------------------
+// The two terms of the potential along shortest paths over Nav2D-v0's graph (the object is no obstacle of it): a = geo_o(p), 0 while
+// the object is held, and b = geo_g(o), evaluated when the object comes to rest and kept while it rests, geo_g(p) while it is held.
+// The record of one env's running episode (HAB_NAV2D_REARR_GEO_BYTES): the field DG towards the goal, the field DO towards the place
+// where the object rests (+inf while it has not rested in the episode), the two terms after the last step and the counters.
+struct RearrGeoField {
+    float DG[GEO_NODES], DO[GEO_NODES];
+    float a, b;
+    int32_t reachable, sweeps_goal, sweeps_obj, lost_steps, rebuilds, zero;
+};
+static_assert(sizeof(RearrGeoField) == HAB_NAV2D_REARR_GEO_BYTES, "RearrGeoField layout");
+static_assert(offsetof(RearrGeoField, DG) == 4 * HAB_NAV2D_REARR_GEO_W_DG && offsetof(RearrGeoField, DO) == 4 * HAB_NAV2D_REARR_GEO_W_DO,
+              "RearrGeoField layout");
+static_assert(offsetof(RearrGeoField, a) == 4 * HAB_NAV2D_REARR_GEO_W_A && offsetof(RearrGeoField, b) == 4 * HAB_NAV2D_REARR_GEO_W_B,
+              "RearrGeoField layout");
+static_assert(offsetof(RearrGeoField, reachable) == 4 * HAB_NAV2D_REARR_GEO_W_REACHABLE &&
+              offsetof(RearrGeoField, sweeps_goal) == 4 * HAB_NAV2D_REARR_GEO_W_SWEEPS_GOAL &&
+              offsetof(RearrGeoField, sweeps_obj) == 4 * HAB_NAV2D_REARR_GEO_W_SWEEPS_OBJ, "RearrGeoField layout");
+static_assert(offsetof(RearrGeoField, lost_steps) == 4 * HAB_NAV2D_REARR_GEO_W_LOST_STEPS &&
+              offsetof(RearrGeoField, rebuilds) == 4 * HAB_NAV2D_REARR_GEO_W_REBUILDS, "RearrGeoField layout");
+
+// What one wavefront keeps in LDS of one env's graph: nav2d_geo_build_kernel's arrays.  The nodes and boxes serve the queries; the
+// weights and the two copies of D a build.
+struct GeoGraph {
+    float node_x[GEO_NODES], node_y[GEO_NODES];
+    int node_ok[GEO_NODES];
+    GeoBox boxes[MAX_K];
+    float W[GEO_NODES * GEO_NODES];
+    float D[2][GEO_NODES];
+};
+// The nodes (lane l < 32: node l), the diagonal of the weights and the K visibility boxes (lanes 32 ..); the caller puts the barrier
+// after it.
+__device__ inline void geo_graph_nodes(GeoGraph& G, const Nav2DState& s, int K, int lane) {
+    if (lane < GEO_NODES) {
+        float x = 0.0f, y = 0.0f;
+        bool ok = false;
+        if (lane < 4 * K) {
+            geo_corner(s, lane >> 2, lane & 3, x, y);
+            ok = is_free(x, y, s, K);
+        }
+        G.node_x[lane] = x; G.node_y[lane] = y; G.node_ok[lane] = ok ? 1 : 0;
+        G.W[lane * GEO_NODES + lane] = INFINITY;
+    } else if (lane - GEO_NODES < K) {
+        G.boxes[lane - GEO_NODES] = geo_box(s, lane - GEO_NODES);
+    }
+}
+// The symmetric weights, the 496 pairs round the lanes as in nav2d_geo_build_kernel; needs the nodes, and a barrier after it.
+__device__ inline void geo_graph_weights(GeoGraph& G, int K, int lane) {
+    for (int p = lane; p < GEO_NODES * (GEO_NODES - 1) / 2; p += 64) {
+        const int a = p >> 5, c = p & 31;
+        const int i = c < 31 - a ? a : 30 - a;
+        const int j = c < 31 - a ? a + 1 + c : i + 1 + (c - (31 - a));
+        float w = INFINITY;
+        if (G.node_ok[i] && G.node_ok[j] && geo_visible(G.boxes, K, G.node_x[i], G.node_y[i], G.node_x[j], G.node_y[j]))
+            w = dist(G.node_x[i], G.node_y[i], G.node_x[j], G.node_y[j]);
+        G.W[i * GEO_NODES + j] = w;
+        G.W[j * GEO_NODES + i] = w;
+    }
+}
+// One field by one wavefront, towards the target (tx, ty), over a graph whose nodes and weights are in LDS behind a barrier: the last
+// hops, then nav2d_geo_build_kernel's sweeps (lane l owns half l & 1 of row l >> 1, the wave votes on the end).  Returns the sweeps;
+// `Dl` is D[lane] on the lanes below 32 and +inf on the others.  Uniform over the wave; ends behind a barrier, so that another field
+// may follow.
+__device__ inline int geo_field_towards(GeoGraph& G, int K, float tx, float ty, int lane, float& Dl) {
+    if (lane < GEO_NODES) {
+        float d = INFINITY;
+        if (G.node_ok[lane] && geo_visible(G.boxes, K, G.node_x[lane], G.node_y[lane], tx, ty)) d = dist(G.node_x[lane], G.node_y[lane], tx, ty);
+        G.D[0][lane] = d;
+    }
+    __syncthreads();
+    const int row = lane >> 1, half = lane & 1;
+    float w[GEO_NODES / 2];
+#pragma unroll
+    for (int t = 0; t < GEO_NODES / 2; ++t) w[t] = G.W[(half * (GEO_NODES / 2) + t) * GEO_NODES + row];
+    int cur = 0, sweeps = 0;
+    while (sweeps < 4 * K) {
+        sweeps += 1;
+        float m = INFINITY;
+#pragma unroll
+        for (int t = 0; t < GEO_NODES / 2; ++t) m = fminf(m, w[t] + G.D[cur][half * (GEO_NODES / 2) + t]);
+        m = fminf(m, __shfl_xor(m, 1));
+        const float before = G.D[cur][row];
+        const float after = fminf(before, m);
+        if (half == 0) G.D[cur ^ 1][row] = after;
+        const bool changed = __ballot(after != before) != 0;
+        __syncthreads();
+        cur ^= 1;
+        if (!changed) break;
+    }
+    Dl = lane < GEO_NODES ? G.D[cur][lane] : INFINITY;
+    __syncthreads();
+    return sweeps;
+}
+// geo_T(x) by one wavefront: node l with its field value Dl on lane l < 32, the direct hop to the target T on lane 32, then the
+// minimum over the wave, which is exact and so the restatement's serial one.  Needs the nodes and boxes in LDS.
+__device__ inline float geo_query_wave(const GeoGraph& G, int K, float x, float y, float tx, float ty, float Dl, int lane) {
+    float v = INFINITY;
+    if (lane < GEO_NODES) {
+        if (Dl < INFINITY && geo_visible(G.boxes, K, x, y, G.node_x[lane], G.node_y[lane])) v = dist(x, y, G.node_x[lane], G.node_y[lane]) + Dl;
+    } else if (lane == GEO_NODES) {
+        if (geo_visible(G.boxes, K, x, y, tx, ty)) v = dist(x, y, tx, ty);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+    return v;
+}
+
+// What the beginning of an episode needs, one env per 64-thread workgroup (one wavefront), selected like nav2d_geo_build_kernel's.
+// `state` is a record that rearr_begin has just filled: the object is at its start, or at the agent's position under start_holding.
+// Nodes, boxes and weights are computed once and serve both fields.  DG, then b0 = geo_g(o); without start_holding DO towards o and
+// a0 = geo_o(p), with it DO = +inf, no sweeps and a0 = 0.  Both terms finite: reachable, and d_start = d_prev = a0 + b0.
+__global__ void __launch_bounds__(64)
+nav2d_rearr_geo_build_kernel(char* __restrict__ states, size_t state_stride, RearrGeoField* __restrict__ geo, const uint8_t* __restrict__ mask,
+                             int only_ended, int K, int start_holding) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    if (mask && !mask[n]) return;
+    Nav2DRearrState& r = *reinterpret_cast<Nav2DRearrState*>(states + (size_t)n * state_stride);
+    Nav2DState& s = r.base;
+    if (only_ended && !s.ended) return;
+    __shared__ GeoGraph G;
+    geo_graph_nodes(G, s, K, lane);
+    __syncthreads();
+    geo_graph_weights(G, K, lane);
+    const float px = s.px, py = s.py, gx = s.gx, gy = s.gy, ox = r.ox, oy = r.oy;
+    __syncthreads();
+    float Dg, Do = INFINITY;
+    const int sweeps_goal = geo_field_towards(G, K, gx, gy, lane, Dg);
+    const float b0 = geo_query_wave(G, K, ox, oy, gx, gy, Dg, lane);
+    int sweeps_obj = 0;
+    float a0 = 0.0f;
+    if (!start_holding) {
+        sweeps_obj = geo_field_towards(G, K, ox, oy, lane, Do);
+        a0 = geo_query_wave(G, K, px, py, ox, oy, Do, lane);
+    }
+    RearrGeoField& g = geo[n];
+    if (lane < GEO_NODES) { g.DG[lane] = Dg; g.DO[lane] = Do; }
+    __syncthreads();  // every lane has read the state before lane 0 writes to it
+    if (lane == 0) {
+        const bool reachable = (a0 < INFINITY) && (b0 < INFINITY);
+        g.a = a0; g.b = b0;
+        g.reachable = reachable ? 1 : 0;
+        g.sweeps_goal = sweeps_goal;
+        g.sweeps_obj = sweeps_obj;
+        g.lost_steps = 0;
+        g.rebuilds = 0;
+        g.zero = 0;
+        if (reachable) s.d_start = s.d_prev = a0 + b0;
+    }
+}
+
+// rearr_end_step for the geodesic step, which has its potential and its second term already: a function of its own, so that
+// rearr_end_step and the two Euclidean kernels stay the code they are (see the comment there).
+__device__ inline void rearr_geo_end_step(Nav2DRearrState& r, float phi, float b, bool stop, bool first_pick, float* __restrict__ reward,
+                                          uint8_t* __restrict__ not_done, float* __restrict__ sums, uint32_t seed, uint32_t env, int n, int N,
+                                          int K, int nh, int max_steps, int start_holding) {
+    Nav2DState& s = r.base;
+    const bool success = stop && !r.holding && b < REARR_SUCCESS;
+    reward[n] = ((-0.01f + (s.d_prev - phi)) + (first_pick ? 1.0f : 0.0f)) + (success ? 2.5f : 0.0f);
+    s.d_prev = phi;
+    s.steps += 1;
+    const bool done = stop || (s.steps >= max_steps);
+    not_done[n] = done ? 0 : 1;
+    s.ended = done ? 1 : 0;
+    if (done) {
+        s.last[0] = success ? 1.0f : 0.0f;
+        s.last[1] = (float)r.held;
+        s.last[2] = b;
+        s.last[3] = (float)s.collisions;
+        if (sums)
+            for (int m = 0; m < 4; ++m) sums[(size_t)m * N + n] = sums[(size_t)m * N + n] + s.last[m];
+        s.episode += 1;
+        begin_episode<false>(s, seed, env, K, nh);
+        rearr_begin(r, seed, env, K, start_holding);
+    }
+}
+
+// What a step changes of a record before its end, as a lane's own copy in registers, with the rectangles, which it does not change,
+// behind a pointer to the record: the members the motion, PICK and PLACE helpers read and write.  A copy of the whole record would be
+// indexed by k and live in scratch memory.
+struct RearrLane {
+    struct Base {
+        float px, py, path;
+        int32_t heading, collisions;
+        const float (*rect)[4];
+    } base;
+    float ox, oy;
+    int32_t holding, held, picks, invalid;
+};
+
+// The geodesic form of both rearrangement steps: one wavefront (a 64-thread workgroup) per env, as nav2d_obj_geo_step_kernel.  Every
+// lane takes its own copy of the record's changing words and derives the move, the PICK or the PLACE on it through the helpers of the
+// Euclidean kernels, from the same loads, so the outcome is uniform over the wave; lane 0 alone writes it back.  In a reachable episode the
+// nodes and boxes go to LDS and the terms are queries of one node per lane; a successful PLACE first builds DO towards the new
+// resting place, the weights included.  Lane 0 then applies the lost-step rule and does the end of the step.  The fields of an
+// episode that begins here are built by the launch of nav2d_rearr_geo_build_kernel that follows (only_ended).
+// VEL: `actions` are Nav2DRearrVel-v0's (N, 3) float rows and the four motion parameters are used; else int64 actions.
+template <bool VEL>
+__global__ void __launch_bounds__(64)
+nav2d_rearr_geo_step_kernel(Nav2DRearrState* __restrict__ states, RearrGeoField* __restrict__ geo, const float* __restrict__ dirs,
+                            const void* __restrict__ actions, const uint8_t* __restrict__ mask, float* __restrict__ obj_start,
+                            float* __restrict__ obj_goal, float* __restrict__ is_holding, float* __restrict__ reward,
+                            uint8_t* __restrict__ not_done, float* __restrict__ sums, uint32_t seed, uint32_t env_offset, int N, int K,
+                            int nh, int max_steps, int start_holding, int max_turn, int stop_turn, float min_lin, int sliding, int advance) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    if (mask && !mask[n]) return;
+    Nav2DRearrState& rec = states[n];
+    RearrGeoField& g = geo[n];
+    const uint32_t env = env_offset + (uint32_t)n;
+    if (!advance) {
+        if (lane == 0) {
+            first_episode<false>(rec.base, seed, env, K, nh);
+            rearr_begin(rec, seed, env, K, start_holding);
+        }
+    } else {
+        __shared__ GeoGraph G;
+        RearrLane r{{rec.base.px, rec.base.py, rec.base.path, rec.base.heading, rec.base.collisions, rec.base.rect},
+                    rec.ox, rec.oy, rec.holding, rec.held, rec.picks, rec.invalid};  // this lane's copy
+        RearrLane::Base& s = r.base;
+        const float gx = rec.base.gx, gy = rec.base.gy;
+        const bool was_holding = r.holding != 0;
+        bool stop, first_pick = false;
+        if constexpr (VEL) {
+            const float* act = static_cast<const float*>(actions) + 3 * (size_t)n;
+            const float a_lin = act[0], a_ang = act[1], c_grip = vel_clamp(act[2]);
+            float l;
+            int dh;
+            stop = vel_decode(a_lin, a_ang, max_turn, stop_turn, min_lin, l, dh);
+            if (!stop) vel_move(s, dirs, l, dh, nh, sliding, [&](float x, float y) { return rearr_is_free(x, y, r, K); });
+            const float c = dirs[2 * s.heading], sn = dirs[2 * s.heading + 1];
+            if (c_grip > 0.0f && !r.holding) first_pick = rearr_pick(r, c, sn);
+            else if (c_grip < 0.0f && r.holding) rearr_place(r, c, sn, K);
+        } else {
+            const int64_t a = static_cast<const int64_t*>(actions)[n];
+            const float c = dirs[2 * s.heading], sn = dirs[2 * s.heading + 1];
+            if (a == 1) {
+                const float nx = s.px + FORWARD * c, ny = s.py + FORWARD * sn;
+                if (rearr_is_free(nx, ny, r, K)) { s.px = nx; s.py = ny; s.path = s.path + FORWARD; }
+                else s.collisions += 1;
+            } else if (a == 2) {
+                s.heading = (s.heading + 1) % nh;
+            } else if (a == 3) {
+                s.heading = (s.heading + nh - 1) % nh;
+            } else if (a == 4) {
+                first_pick = rearr_pick(r, c, sn);
+            } else if (a == 5) {
+                rearr_place(r, c, sn, K);
+            }
+            stop = a == 0;
+        }
+        if (r.holding) { r.ox = s.px; r.oy = s.py; }
+        const bool placed = was_holding && !r.holding;  // the object came to rest in this step
+        const bool reachable = g.reachable != 0;        // of the env, so uniform over the workgroup
+        float ta = g.a, tb = g.b;                       // the terms after the previous step
+        float na = 0.0f, nb = tb, Do = INFINITY;
+        int sweeps_obj = 0;
+        if (reachable) {
+            geo_graph_nodes(G, rec.base, K, lane);
+            __syncthreads();
+            const float Dg = lane < GEO_NODES ? g.DG[lane] : INFINITY;
+            if (placed) {
+                geo_graph_weights(G, K, lane);
+                __syncthreads();
+                sweeps_obj = geo_field_towards(G, K, r.ox, r.oy, lane, Do);
+                nb = geo_query_wave(G, K, r.ox, r.oy, gx, gy, Dg, lane);
+                na = geo_query_wave(G, K, s.px, s.py, r.ox, r.oy, Do, lane);
+            } else if (r.holding) {
+                nb = geo_query_wave(G, K, s.px, s.py, gx, gy, Dg, lane);
+            } else {
+                Do = lane < GEO_NODES ? g.DO[lane] : INFINITY;
+                na = geo_query_wave(G, K, s.px, s.py, r.ox, r.oy, Do, lane);
+            }
+        }
+        __syncthreads();  // every lane has read the record and the field before lane 0 writes to them
+        if (reachable && placed && lane < GEO_NODES) g.DO[lane] = Do;
+        if (lane == 0) {
+            Nav2DState& t = rec.base;
+            t.px = s.px; t.py = s.py; t.path = s.path; t.heading = s.heading; t.collisions = s.collisions;
+            rec.ox = r.ox; rec.oy = r.oy;
+            rec.holding = r.holding; rec.held = r.held; rec.picks = r.picks; rec.invalid = r.invalid;
+            float phi, b;
+            if (reachable) {
+                const bool lost = !(na < INFINITY) || !(nb < INFINITY);
+                if (na < INFINITY) ta = na;
+                if (nb < INFINITY) tb = nb;
+                g.a = ta; g.b = tb;
+                if (lost) g.lost_steps += 1;
+                if (placed) { g.sweeps_obj = sweeps_obj; g.rebuilds += 1; }
+                phi = ta + tb;
+                b = tb;
+            } else {
+                phi = rearr_potential(rec, b);  // of the record as just written
+            }
+            rearr_geo_end_step(rec, phi, b, stop, first_pick, reward, not_done, sums, seed, env, n, N, K, nh, max_steps, start_holding);
+        }
+    }
+    if (lane == 0) rearr_write_sensors(rec, dirs, obj_start, obj_goal, is_holding, n);
+}
+
 // ---- rendering ---------------------------------------------------------------------------------------------------------------
 // Entry / exit of the ray p + t d through [lo, hi] on one axis.
 __device__ inline void slab(float lo, float hi, float p, float d, float inv, float& tmin, float& tmax) {
@@ -1255,8 +1563,9 @@ static int check_geo_args(const void* state, size_t state_stride_bytes, const vo
     return HAB_OK;
 }
 
-// The argument checks the step entries share, then, for a `_geo` entry, those of the field.
-static int check_step_args(const StepArgs& a, bool geo_entry) {
+// The argument checks the step entries share, then, for a `_geo` entry, those of the field; `state_stride` is the size of the task's
+// state record.
+static int check_step_args(const StepArgs& a, bool geo_entry, size_t state_stride = sizeof(Nav2DState)) {
     if (!a.state || !a.dirs || a.N <= 0 || a.num_headings <= 0 || a.max_episode_steps <= 0) return HAB_ERR_ARG;
     if (a.num_obstacles < 0 || a.num_obstacles > MAX_K) return HAB_ERR_ARG;
     if (a.advance && (!a.actions || !a.reward || !a.not_done)) return HAB_ERR_ARG;
@@ -1264,7 +1573,7 @@ static int check_step_args(const StepArgs& a, bool geo_entry) {
     if (a.image() && (a.W > HAB_NAV2D_MAX_WIDTH || (long long)a.H * a.W > (1ll << 24))) return HAB_ERR_UNSUPPORTED;
     if (a.image() && a.N > 65535) return HAB_ERR_UNSUPPORTED;  // the render's grid.y is the env
     if (a.depth && ((uintptr_t)a.depth & 3)) return HAB_ERR_ARG;
-    return geo_entry ? check_geo_args(a.state, sizeof(Nav2DState), a.geo, a.N, a.num_obstacles) : HAB_OK;
+    return geo_entry ? check_geo_args(a.state, state_stride, a.geo, a.N, a.num_obstacles) : HAB_OK;
 }
 
 // The render, where an image destination is given, in the task's form.  `semantic` and `num_objects` are used by the Nav2DObj-v0
@@ -1484,4 +1793,69 @@ extern "C" int hab_nav2d_obj_step_geo(void* state, void* geo, const float* dirs,
                                                      num_obstacles, num_objects);
     HAB_LAUNCH_CHECK();
     return launch_render<Render::OBJ>(a, num_objects);
+}
+
+extern "C" int hab_nav2d_rearr_geo_bytes(void) { return (int)sizeof(RearrGeoField); }
+
+extern "C" int hab_nav2d_rearr_geo_build(void* state, size_t state_stride_bytes, void* geo, const uint8_t* mask, int only_ended, int N,
+                                         int num_obstacles, int start_holding, hipStream_t stream) {
+    const int rc = check_geo_args(state, state_stride_bytes, geo, N, num_obstacles);
+    if (rc != HAB_OK) return rc;
+    if (state_stride_bytes < sizeof(Nav2DRearrState)) return HAB_ERR_ARG;
+    if (start_holding != 0 && start_holding != 1) return HAB_ERR_ARG;
+    nav2d_rearr_geo_build_kernel<<<N, 64, 0, stream>>>((char*)state, state_stride_bytes, (RearrGeoField*)geo, mask, only_ended,
+                                                       num_obstacles, start_holding);
+    HAB_LAUNCH_CHECK();
+    return HAB_OK;
+}
+
+// Both rearrangement steps with the fields: the step (one wavefront per env), the fields of the episodes that began (at a reset, of
+// every env the mask selects), then the render.  The four motion parameters are Nav2DRearrVel-v0's and unused without VEL.
+template <bool VEL>
+static int rearr_step_geo(const StepArgs& a, float* obj_start, float* obj_goal, float* is_holding, int start_holding, int max_turn_steps,
+                          int stop_turn_steps, float min_abs_lin_speed, int allow_sliding) {
+    const int rc = check_step_args(a, true, sizeof(Nav2DRearrState));
+    if (rc != HAB_OK) return rc;
+    if (start_holding != 0 && start_holding != 1) return HAB_ERR_ARG;
+    if (VEL) {
+        if ((uintptr_t)a.actions & 3) return HAB_ERR_ARG;  // a row of three floats is read as three scalars
+        if (max_turn_steps < 1 || max_turn_steps > a.num_headings / 2 || stop_turn_steps < 1 || stop_turn_steps > max_turn_steps)
+            return HAB_ERR_ARG;
+    }
+    nav2d_rearr_geo_step_kernel<VEL><<<a.N, 64, 0, a.stream>>>((Nav2DRearrState*)a.state, (RearrGeoField*)a.geo, a.dirs, a.actions, a.mask,
+                                                               obj_start, obj_goal, is_holding, a.reward, a.not_done, a.measure_sums,
+                                                               a.seed, a.env_offset, a.N, a.num_obstacles, a.num_headings,
+                                                               a.max_episode_steps, start_holding, max_turn_steps, stop_turn_steps,
+                                                               min_abs_lin_speed, allow_sliding, a.advance);
+    HAB_LAUNCH_CHECK();
+    nav2d_rearr_geo_build_kernel<<<a.N, 64, 0, a.stream>>>((char*)a.state, sizeof(Nav2DRearrState), (RearrGeoField*)a.geo, a.mask,
+                                                           a.advance ? 1 : 0, a.num_obstacles, start_holding);
+    HAB_LAUNCH_CHECK();
+    return launch_render<Render::REARR>(a, 0);
+}
+
+extern "C" int hab_nav2d_rearr_step_geo(void* state, void* geo, const float* dirs, const float* ray, const float* col_cos,
+                                        const float* tanv, const int64_t* actions, const uint8_t* mask, uint8_t* head_rgb,
+                                        float* head_depth, float* obj_start, float* obj_goal, float* is_holding, float* reward,
+                                        uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
+                                        int num_obstacles, int num_headings, int max_episode_steps, int start_holding, int advance,
+                                        hipStream_t stream) {
+    return rearr_step_geo<false>({state, geo, dirs, ray, col_cos, tanv, actions, mask, head_rgb, head_depth, nullptr, nullptr, reward,
+                                  not_done, measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps,
+                                  advance, stream},
+                                 obj_start, obj_goal, is_holding, start_holding, 0, 0, 0.0f, 0);
+}
+
+extern "C" int hab_nav2d_rearr_vel_step_geo(void* state, void* geo, const float* dirs, const float* ray, const float* col_cos,
+                                            const float* tanv, const float* actions, const uint8_t* mask, uint8_t* head_rgb,
+                                            float* head_depth, float* obj_start, float* obj_goal, float* is_holding, float* reward,
+                                            uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H,
+                                            int W, int num_obstacles, int num_headings, int max_episode_steps, int start_holding,
+                                            int max_turn_steps, int stop_turn_steps, float min_abs_lin_speed, int allow_sliding,
+                                            int advance, hipStream_t stream) {
+    return rearr_step_geo<true>({state, geo, dirs, ray, col_cos, tanv, actions, mask, head_rgb, head_depth, nullptr, nullptr, reward,
+                                 not_done, measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps,
+                                 advance, stream},
+                                obj_start, obj_goal, is_holding, start_holding, max_turn_steps, stop_turn_steps, min_abs_lin_speed,
+                                allow_sliding);
 }

@@ -341,10 +341,12 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
     _state_bytes = "hab_nav2d_state_bytes"
     _geo_bytes = "hab_nav2d_geo_bytes"  # the size of a field record of the geodesic mode
     num_actions = 4
-    # what a subclass with another step changes: the name in the refusals, the library's entries (Euclidean, geodesic), what
+    # what a subclass with another step changes: the name in the refusals, the library's entries (Euclidean, geodesic; a subclass
+    # whose _entries names the Euclidean one alone names the geodesic one in _geo_entry), what
     # `actions` has to be (with _actions_shaped), and the two hooks _sensor_rows and _task_parameters
     _name = "Nav2D"
     _entries = ("hab_nav2d_step", "hab_nav2d_step_geo")
+    _geo_entry = None
     _action_dtype, _action_text = torch.int64, "int64 device tensor of shape (N,) or (N, 1)"
 
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
@@ -375,7 +377,7 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
         self._infos: List[dict] = [{} for _ in range(num_envs)]
         self.number_of_episodes = [1 << 30] * num_envs  # episodes are generated, never repeated
         # the step entry and the arguments that no call changes, before and after the ones _launch is given
-        self._entry = self._entries[0] if self._geo is None else self._entries[1]
+        self._entry = self._entries[0] if self._geo is None else (self._geo_entry or self._entries[1])
         self._step = getattr(_lib.lib(), self._entry)
         field = () if self._geo is None else (ptr(self._geo),)
         self._head = (ptr(self._state), *field, *map(ptr, self._tables))
@@ -684,8 +686,8 @@ class Nav2DRearrVectorEnv(Nav2DVectorEnv):
     `nav2d_render_kernel` (csrc/nav2d.hip) match it bit for bit on every output -- no angle function runs on the device, every float32
     operation is one rounding in the written order.
 
-    Parameters (`habitat.synthetic`): start_holding (bool, default false), besides Nav2D-v0's num_obstacles and turn_angle.  The
-      distances are Euclidean; `distance_to_goal: geodesic` is refused.
+    Parameters (`habitat.synthetic`): start_holding (bool, default false), besides Nav2D-v0's num_obstacles and turn_angle, and
+      distance_to_goal (see Distance below; "euclidean", the default, is what the following paragraphs describe).
     Places.  The object's start o0 and the goal g are the positions Nav2DObj-v0 gives objects 0 and 1 of the same (seed, env, episode)
       world with num_objects = 2 (see Nav2DObjVectorEnv, Objects: stream 21, 16 candidates, the box [0.5, 7.5]^2, not strictly inside
       a rectangle grown by 0.3 m, at least 1 m from the start and from the earlier object, the 28-slot ring).  Categories and the target
@@ -712,11 +714,45 @@ class Nav2DRearrVectorEnv(Nav2DVectorEnv):
       colour and the goal drawn as Nav2D-v0's red marker cylinder (radius 0.2 m), in rgb only.  There is no pointgoal, gps or compass.
       Without head_rgb and head_depth nothing is rendered.
 
+    Distance (`distance`, from `habitat.synthetic.distance_to_goal`).  "geodesic" changes the d inside Phi, the success test b < 0.5,
+      object_to_goal_distance and d_prev / d_start -- nothing else: world, places, physics, the PICK and PLACE rules, sensors, render and
+      the state record stay -- to shortest paths round the obstacles, as habitat defines its rearrangement navigation rewards.
+      tests/nav2d_rearr_geo_reference.py restates it; `nav2d_rearr_geo_build_kernel` and `nav2d_rearr_geo_step_kernel` match it bit for
+      bit.  Every float32 operation is one rounding in the written order.
+      * Graph.  Nav2D-v0's, word for word (see Nav2DVectorEnv, Distance): the K rectangles grown by the agent radius, visibility
+        boxes shrunk by E = 2^-10, the separating-axis test, the 4K corner nodes; a node is valid iff it is free by Nav2D-v0's box
+        test.  The object is never an obstacle of the graph and never invalidates a node: leg b is walked carrying the object, which
+        is then no geometry; leg a ends at the object, so its own keep-out is left out, as Nav2DObj-v0 leaves out the target's own
+        square; and there is no second object.  So a path of leg a may pass within 0.4 m of o -- where the agent is already within
+        the 1.0 m reach.  o0, g and every placed q lie outside the rectangles grown by 0.3 m, so all segment ends are ordinary
+        points of the graph.
+      * Two fields per env.  DG[32] towards the goal g, built when an episode begins.  DO[32] towards the object's resting place,
+        built whenever the object comes to rest: at the beginning of an episode without start_holding (target o0) and at every
+        successful PLACE (target q).  While the object has not rested in the episode, DO is +inf in all words and sweeps_obj = 0.
+        Both are Nav2D-v0's field: last hops, then Jacobi sweeps until one changes nothing, at most 4K.
+      * geo_T(x) is Nav2D-v0's geo from the point x with the target T and its field.
+      * Terms after the physics of a step.  Holding: a = 0, b = geo_g(p).  Not holding: a = geo_o(p), and b is the value evaluated
+        when the object came to rest, kept while it rests: geo_g(o0) from the episode's beginning, geo_g(q) from a PLACE.  A PLACE
+        step is, in order: o = q, holding = 0, build DO towards q, b = geo_g(q), a = geo_q(p).  A PICK step: a = 0, b = geo_g(p).
+        Phi = a + b.
+      * Lost steps.  A term that comes out +inf keeps the value it had after the previous step, and the step counts once in
+        lost_steps.  The previous a and b are kept in the field record.
+      * Episode.  At its beginning the fields are built and a0 = geo_o0(start), b0 = geo_g(o0); under start_holding a0 = 0 and
+        b0 = geo_g(start).  Both finite: reachable = 1 and d_start = d_prev = a0 + b0.  Otherwise reachable = 0 and the episode keeps
+        the Euclidean Phi, b and success test throughout (Nav2D-v0's rule for a walled-off goal); no field is rebuilt in such an
+        episode, and the record keeps a0 and b0 as they came out.
+      * At K = 0 there are no nodes, every geo is the direct distance and all outputs are bitwise those of the Euclidean mode.
+      The field records (`_geo`, (N, 72) int32: 32 DG, 32 DO, a, b, reachable, sweeps_goal, sweeps_obj, lost_steps, rebuilds -- the
+      successful PLACEs that rebuilt DO -- and one zero; HAB_NAV2D_REARR_GEO_W_*) exist in this mode only.  The fields are built on
+      the device, so in this mode the class itself refuses a device that is no GPU.
+
     `step_into_obs` writes whichever of the five rows `obs` holds; `actions` is int64 (N,) / (N, 1) as for Nav2D-v0.  The record's
     words beyond Nav2D-v0's are named in include/habitat_amd.h (HAB_NAV2D_REARR_W_*)."""
 
     _name = "Nav2DRearr"
     _entries = ("hab_nav2d_rearr_step",)
+    _geo_entry = "hab_nav2d_rearr_step_geo"
+    _geo_bytes = "hab_nav2d_rearr_geo_bytes"
     _sensor_set = "rearrange"
     _state_bytes = "hab_nav2d_rearr_state_bytes"
     measure_names = NAV2D_REARR_MEASURES
@@ -725,8 +761,7 @@ class Nav2DRearrVectorEnv(Nav2DVectorEnv):
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = False,
                  use_depth: bool = True, num_actions: int = 6, device="cuda", num_obstacles: int = 3, turn_angle: int = 10,
                  max_episode_steps: int = 500, start_holding: bool = False, distance: str = "euclidean"):
-        if nav2d_distance(distance, "Nav2DRearr") != "euclidean":
-            raise _lib.HabError("Nav2DRearr: the task has Euclidean distances only; distance_to_goal 'geodesic' is not defined for it")
+        self._check_distance(distance, device)
         if not isinstance(start_holding, (bool, np.bool_)):
             raise _lib.HabError(f"Nav2DRearr: start_holding {start_holding!r} must be true or false")
         if num_actions != 6:
@@ -736,10 +771,17 @@ class Nav2DRearrVectorEnv(Nav2DVectorEnv):
             raise _lib.HabError(f"Nav2DRearr: the image size {height} x {width} must be positive")
         self.start_holding = bool(start_holding)
         super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
-                         num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps)
+                         num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps, distance=distance)
         self.task = "nav2drearr"
         self.action_spaces = [spaces.Discrete(6) for _ in range(num_envs)]
         self.orig_action_spaces = self.action_spaces
+
+    @classmethod
+    def _check_distance(cls, distance, device):
+        """The geodesic mode builds its fields on the device: refused where that is no GPU, before the device is touched."""
+        if nav2d_distance(distance, cls._name) == "geodesic" and torch.device(device).type != "cuda":
+            raise _lib.HabError(f"{cls._name}: distance 'geodesic' builds its fields on the GPU; without a GPU device the task has "
+                                "Euclidean distances only")
 
     def _sensor_rows(self, obs):
         return tuple(ptr(obs.get(k)) for k in NAV2D_REARR_SENSORS)
@@ -776,7 +818,9 @@ class Nav2DRearrVelVectorEnv(Nav2DRearrVectorEnv):
     embedding, float action storage and the fused sensor columns run together.  The task is Nav2DRearr-v0 word for word (see
     Nav2DRearrVectorEnv) except the action and the physics of one step.  What stays the same: world, places, object, holding flag,
     `start_holding`, keep-out 0.4 m, reach 1.0 m, arm 0.5 m, potential Phi = d(p, o) + d(o, g), pick bonus, success radius 0.5 m, the
-    four measures, the five sensors, rendering, the state record, streams, Euclidean distances only.
+    four measures, the five sensors, rendering, the state record, streams, and the two distance modes: `distance="geodesic"` is
+    Nav2DRearr-v0's geodesic mode, word for word (see Nav2DRearrVectorEnv, Distance), with `stop` in STOP's place;
+    tests/nav2d_rearr_geo_reference.py restates it for this task too.
     tests/nav2d_rearr_vel_reference.py restates the task in numpy; `nav2d_rearr_vel_step_kernel` (csrc/nav2d.hip) matches it bit for
     bit on every output.  No angle function runs on the device; the heading stays an index into the host tables.
 
@@ -809,6 +853,7 @@ class Nav2DRearrVelVectorEnv(Nav2DRearrVectorEnv):
 
     _name = "Nav2DRearrVel"
     _entries = ("hab_nav2d_rearr_vel_step",)
+    _geo_entry = "hab_nav2d_rearr_vel_step_geo"
     _action_dtype, _action_text = torch.float32, "float32 device tensor of shape (N, 3)"
     num_actions = 1
 
@@ -816,8 +861,6 @@ class Nav2DRearrVelVectorEnv(Nav2DRearrVectorEnv):
                  use_depth: bool = True, num_actions: int = 1, device="cuda", num_obstacles: int = 3, turn_angle: int = 1,
                  max_episode_steps: int = 500, start_holding: bool = False, max_turn_angle: int = 10, min_abs_lin_speed: float = 0.025,
                  min_abs_ang_speed: int = 5, allow_sliding: bool = True, distance: str = "euclidean"):
-        if nav2d_distance(distance, "Nav2DRearrVel") != "euclidean":
-            raise _lib.HabError("Nav2DRearrVel: the task has Euclidean distances only; distance_to_goal 'geodesic' is not defined for it")
         _, self.max_turn_steps, self.stop_turn_steps = nav2d_vel_parameters(turn_angle, max_turn_angle, min_abs_lin_speed,
                                                                             min_abs_ang_speed, "Nav2DRearrVel")
         if not isinstance(allow_sliding, (bool, np.bool_)):
@@ -832,7 +875,7 @@ class Nav2DRearrVelVectorEnv(Nav2DRearrVectorEnv):
         self.min_abs_lin_speed, self.allow_sliding = float(min_abs_lin_speed), bool(allow_sliding)
         super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
                          num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps,
-                         start_holding=start_holding)
+                         start_holding=start_holding, distance=distance)
         self.task = "nav2drearrvel"
         self.action_spaces = [spaces.Box(-1.0, 1.0, (3,), np.float32) for _ in range(num_envs)]
         self.orig_action_spaces = self.action_spaces
@@ -871,9 +914,10 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
     Nav2DVel-v0, its velocity-controlled variant (Nav2DVelVectorEnv), with the further `habitat.synthetic` keys named there; one
     starting with "nav2dobj" selects Nav2DObj-v0 (Nav2DObjVectorEnv: objects, a target category, the ObjectNav sensor set), which
     reads num_objects / num_categories too and takes its image size from the rgb, else the depth, else the semantic sensor.
-    `habitat.synthetic.distance_to_goal` ("euclidean", the default, or "geodesic") is the distance mode of these three Nav2D tasks.
+    `habitat.synthetic.distance_to_goal` ("euclidean", the default, or "geodesic") is the distance mode of every Nav2D task.
     A type starting with "nav2drearr" selects Nav2DRearr-v0 (Nav2DRearrVectorEnv: pick and place, the rearrangement sensor set), which
-    reads start_holding too, takes its image size from the head_rgb, else the head_depth sensor, and refuses the geodesic mode.  A type
+    reads start_holding too and takes its image size from the head_rgb, else the head_depth sensor; in the geodesic mode both terms
+    of its potential are shortest paths.  A type
     starting with "nav2drearrvel" -- tested before "nav2drearr", which keeps its meaning for everything else -- selects
     Nav2DRearrVel-v0 (Nav2DRearrVelVectorEnv: that task under velocity and grip control), which reads Nav2DVel-v0's keys and
     start_holding and takes its image size like Nav2DRearr-v0."""

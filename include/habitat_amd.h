@@ -243,6 +243,48 @@ int hab_nav2d_rearr_vel_step(void* state /*N,HAB_NAV2D_REARR_STATE_BYTES*/, cons
                              uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings, int max_episode_steps,
                              int start_holding, int max_turn_steps, int stop_turn_steps, float min_abs_lin_speed, int allow_sliding,
                              int advance, hipStream_t stream);
+/* The geodesic distance mode of Nav2DRearr-v0 and Nav2DRearrVel-v0 (habitat_amd/common/env_factory.py, Nav2DRearrVectorEnv with
+ * distance = "geodesic"; bit-identical to tests/nav2d_rearr_geo_reference.py).  World, places, physics, the PICK and PLACE rules,
+ * sensors and render are the tasks'; the two terms of the potential Phi = a + b, the success test b < 0.5 and
+ * object_to_goal_distance are shortest paths round the rectangles grown by the agent radius, over Nav2D-v0's visibility graph (the
+ * object is no obstacle of it).  `geo` is N field records of HAB_NAV2D_REARR_GEO_BYTES, 4-byte aligned, owned by the caller: 32 f32
+ * shortest-path lengths DG towards the goal, 32 DO towards the place where the object rests (+inf in every word while it has not
+ * rested in the episode), then the words named below; the last one is zero.
+ * hab_nav2d_rearr_geo_build is hab_nav2d_geo_build for such records: `state` are records with a stride >=
+ * HAB_NAV2D_REARR_STATE_BYTES (a multiple of 4) that begin with a Nav2DRearr-v0 record at the beginning of an episode; it builds DG,
+ * and DO unless start_holding, the two terms, REACHABLE, and where that is 1 D_START = D_PREV = a + b.  start_holding is 0 or 1.
+ * hab_nav2d_rearr_step_geo / hab_nav2d_rearr_vel_step_geo are hab_nav2d_rearr_step / hab_nav2d_rearr_vel_step with `geo` after
+ * `state`: the step (a successful PLACE rebuilds DO inside it), then the build for the envs whose episode ended (advance = 0: for
+ * every selected env), then the render.  The checks are those entries', then the field's (geo NULL or misaligned). */
+#define HAB_NAV2D_REARR_GEO_BYTES          288
+#define HAB_NAV2D_REARR_GEO_W_DG           0    /* 32 words */
+#define HAB_NAV2D_REARR_GEO_W_DO           32   /* 32 words */
+#define HAB_NAV2D_REARR_GEO_W_A            64   /* f32: the term a after the last step */
+#define HAB_NAV2D_REARR_GEO_W_B            65   /* f32: the term b after the last step */
+#define HAB_NAV2D_REARR_GEO_W_REACHABLE    66
+#define HAB_NAV2D_REARR_GEO_W_SWEEPS_GOAL  67   /* relaxation sweeps of DG's build, the one that changed nothing included */
+#define HAB_NAV2D_REARR_GEO_W_SWEEPS_OBJ   68   /* the same of DO's last build; 0 while the object has not rested */
+#define HAB_NAV2D_REARR_GEO_W_LOST_STEPS   69
+#define HAB_NAV2D_REARR_GEO_W_REBUILDS     70   /* successful PLACEs of the episode that rebuilt DO */
+int hab_nav2d_rearr_geo_bytes(void);
+int hab_nav2d_rearr_geo_build(void* state, size_t state_stride_bytes, void* geo /*N,HAB_NAV2D_REARR_GEO_BYTES*/,
+                              const uint8_t* mask /*N*/, int only_ended, int N, int num_obstacles, int start_holding,
+                              hipStream_t stream);
+int hab_nav2d_rearr_step_geo(void* state /*N,HAB_NAV2D_REARR_STATE_BYTES*/, void* geo /*N,HAB_NAV2D_REARR_GEO_BYTES*/,
+                             const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                             const int64_t* actions /*N*/, const uint8_t* mask /*N*/, uint8_t* head_rgb /*N,H,W,3*/,
+                             float* head_depth /*N,H,W,1*/, float* obj_start /*N,2*/, float* obj_goal /*N,2*/,
+                             float* is_holding /*N,1*/, float* reward /*N*/, uint8_t* not_done /*N*/, float* measure_sums /*4,N*/,
+                             uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings,
+                             int max_episode_steps, int start_holding, int advance, hipStream_t stream);
+int hab_nav2d_rearr_vel_step_geo(void* state /*N,HAB_NAV2D_REARR_STATE_BYTES*/, void* geo /*N,HAB_NAV2D_REARR_GEO_BYTES*/,
+                                 const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                                 const float* actions /*N,3*/, const uint8_t* mask /*N*/, uint8_t* head_rgb /*N,H,W,3*/,
+                                 float* head_depth /*N,H,W,1*/, float* obj_start /*N,2*/, float* obj_goal /*N,2*/,
+                                 float* is_holding /*N,1*/, float* reward /*N*/, uint8_t* not_done /*N*/, float* measure_sums /*4,N*/,
+                                 uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings,
+                                 int max_episode_steps, int start_holding, int max_turn_steps, int stop_turn_steps,
+                                 float min_abs_lin_speed, int allow_sliding, int advance, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Observation transformers, fused: ResizeShortestEdge followed by CenterCropper

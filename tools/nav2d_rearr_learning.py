@@ -46,7 +46,7 @@ def z_of(per_update):
                 distance_last=last[:, 2].mean(), z=z)
 
 
-def learning_run(folder, seed=100, updates=100, lr=5.0e-4, max_steps=48, size=64, every=0):
+def learning_run(folder, seed=100, updates=100, lr=5.0e-4, max_steps=48, size=64, every=0, obstacles=0, distance="euclidean"):
     from habitat_amd.common.baseline_registry import baseline_registry
     from habitat_amd.config.default import get_config
     import habitat_amd.rl.ppo.ppo_trainer  # noqa: F401
@@ -54,7 +54,8 @@ def learning_run(folder, seed=100, updates=100, lr=5.0e-4, max_steps=48, size=64
           "habitat_baselines.total_num_steps=-1", "habitat_baselines.num_checkpoints=-1", "habitat_baselines.checkpoint_interval=1000000",
           "habitat_baselines.rl.ppo.hidden_size=128", f"habitat_baselines.checkpoint_folder={folder}", "habitat_baselines.log_interval=100000",
           f"habitat_baselines.tensorboard_dir={folder}/tb", "habitat_baselines.rl.preemption.save_resume_state_interval=1000000000",
-          "habitat_baselines.trainer_name=ppo", f"habitat.environment.max_episode_steps={max_steps}", "habitat.synthetic.num_obstacles=0",
+          "habitat_baselines.trainer_name=ppo", f"habitat.environment.max_episode_steps={max_steps}",
+          f"habitat.synthetic.num_obstacles={obstacles}", f"habitat.synthetic.distance_to_goal={distance}",
           "habitat.synthetic.turn_angle=30", "habitat.synthetic.start_holding=True", f"habitat.seed={seed}",
           f"habitat_baselines.rl.ppo.lr={lr}", "habitat_baselines.rl.ppo.ppo_epoch=4", "habitat_baselines.rl.ppo.num_mini_batch=2",
           "habitat_baselines.rl.ppo.clip_param=0.2", "habitat_baselines.rl.ddppo.num_recurrent_layers=1",
@@ -95,7 +96,8 @@ def learning_run(folder, seed=100, updates=100, lr=5.0e-4, max_steps=48, size=64
                   f"{r['success_first']:.3f} -> {r['success_last']:.3f}  distance {r['distance_first']:.3f} -> {r['distance_last']:.3f}  "
                   f"z {r['z']:.2f}", flush=True)
     trainer.envs.close()
-    return dict(seed=seed, updates=updates, lr=lr, max_episode_steps=max_steps, size=size, seconds=time.time() - t0, **z_of(per_update))
+    return dict(seed=seed, updates=updates, lr=lr, max_episode_steps=max_steps, size=size, num_obstacles=obstacles, distance=distance,
+                seconds=time.time() - t0, **z_of(per_update))
 
 
 def criterion(r):
