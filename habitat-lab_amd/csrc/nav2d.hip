@@ -11,7 +11,8 @@
 // tests/nav2d_rearr_reference.py.  Nav2DRearrVel-v0 is that task under Nav2DVel-v0's velocity control plus a grip component; its
 // specification is tests/nav2d_rearr_vel_reference.py.  The geodesic distance mode of these two (nav2d_rearr_geo_build_kernel,
 // nav2d_rearr_geo_step_kernel: two fields per env, one of which moves with the object) is specified by
-// tests/nav2d_rearr_geo_reference.py.
+// tests/nav2d_rearr_geo_reference.py.  Nav2DSocial-v0 (a person who walks the graph's shortest paths, to be found and followed under
+// velocity control; nav2d_social_step_kernel, nav2d_social_build_kernel) is specified by tests/nav2d_social_reference.py.
 #include <cstddef>
 #include "hab_common.h"
 #include "../../include/habitat_amd.h"
@@ -1311,6 +1312,245 @@ nav2d_rearr_geo_step_kernel(Nav2DRearrState* __restrict__ states, RearrGeoField*
     if (lane == 0) rearr_write_sensors(rec, dirs, obj_start, obj_goal, is_holding, n);
 }
 
+// ---- Nav2DSocial-v0 (Nav2DSocialVectorEnv; specification: tests/nav2d_social_reference.py) ------------------------------------------
+// A person walks about Nav2D-v0's world, from waypoint to waypoint along the shortest paths of Nav2D-v0's graph, and the agent has to
+// find and then to follow them under Nav2DVel-v0's velocity control.  The graph is planned with here: the person's hop is the
+// arg-min of the wave query, and the field towards a new waypoint is built inside the step that reaches the old one.
+constexpr uint32_t S_WAYPOINT = 24u;
+constexpr float SOCIAL_NEAR = 1.0f, SOCIAL_FAR = 2.0f;
+
+// One env of Nav2DSocial-v0: a Nav2D-v0 record ((gx, gy) zero, d_prev = d(p, h) after the last step, d_start = the episode's first),
+// then the agent's start, the person's position h (named as place_positions reads it), the waypoint and its index in the episode,
+// the found flag, the episode's counters and the field DW towards the waypoint.
+struct Nav2DSocialState {
+    Nav2DState base;
+    float sx, sy;
+    float obj[1][2];            // the person (x, y)
+    float wx, wy;
+    int32_t wp_index, found, following_steps, first_encounter;
+    int32_t arrivals, person_waits, person_lost, sweeps, rebuilds, zero;
+    float DW[GEO_NODES];
+};
+static_assert(sizeof(Nav2DSocialState) == HAB_NAV2D_SOCIAL_STATE_BYTES && offsetof(Nav2DSocialState, base) == 0, "Nav2DSocialState layout");
+static_assert(offsetof(Nav2DSocialState, sx) == 4 * HAB_NAV2D_SOCIAL_W_START && offsetof(Nav2DSocialState, sy) == 4 * HAB_NAV2D_SOCIAL_W_START + 4,
+              "Nav2DSocialState layout");
+static_assert(offsetof(Nav2DSocialState, obj) == 4 * HAB_NAV2D_SOCIAL_W_PERSON && offsetof(Nav2DSocialState, wx) == 4 * HAB_NAV2D_SOCIAL_W_WAYPOINT &&
+              offsetof(Nav2DSocialState, wy) == 4 * HAB_NAV2D_SOCIAL_W_WAYPOINT + 4, "Nav2DSocialState layout");
+static_assert(offsetof(Nav2DSocialState, wp_index) == 4 * HAB_NAV2D_SOCIAL_W_WAYPOINT_INDEX && offsetof(Nav2DSocialState, found) == 4 * HAB_NAV2D_SOCIAL_W_FOUND,
+              "Nav2DSocialState layout");
+static_assert(offsetof(Nav2DSocialState, following_steps) == 4 * HAB_NAV2D_SOCIAL_W_FOLLOWING_STEPS &&
+              offsetof(Nav2DSocialState, first_encounter) == 4 * HAB_NAV2D_SOCIAL_W_FIRST_ENCOUNTER, "Nav2DSocialState layout");
+static_assert(offsetof(Nav2DSocialState, arrivals) == 4 * HAB_NAV2D_SOCIAL_W_ARRIVALS && offsetof(Nav2DSocialState, person_waits) == 4 * HAB_NAV2D_SOCIAL_W_PERSON_WAITS &&
+              offsetof(Nav2DSocialState, person_lost) == 4 * HAB_NAV2D_SOCIAL_W_PERSON_LOST, "Nav2DSocialState layout");
+static_assert(offsetof(Nav2DSocialState, sweeps) == 4 * HAB_NAV2D_SOCIAL_W_SWEEPS && offsetof(Nav2DSocialState, rebuilds) == 4 * HAB_NAV2D_SOCIAL_W_REBUILDS &&
+              offsetof(Nav2DSocialState, DW) == 4 * HAB_NAV2D_SOCIAL_W_DW, "Nav2DSocialState layout");
+
+// Waypoint j of the episode whose key of stream 24 is `kw`, for a person at (hx, hy): the first of its 16 candidates, else the first
+// ring slot, inside [0.5, 7.5]^2, not strictly inside a rectangle grown by 0.3 m and at least 1 m from the person.  An open disc of
+// radius 1 holds at most three ring slots, so one always fits.  S: a record with the rectangles.
+template <class S>
+__device__ inline void social_waypoint(const S& s, uint32_t kw, int K, int j, float hx, float hy, float& wx, float& wy) {
+    auto fits = [&](float x, float y) {
+        return x >= OBJ_LO && x <= OBJ_HI && y >= OBJ_LO && y <= OBJ_HI && !in_grown_rect(x, y, s, K) && dist(hx, hy, x, y) >= OBJ_APART;
+    };
+    for (int i = 0; i < CANDIDATES; ++i) {
+        const uint32_t w = 2u * ((uint32_t)CANDIDATES * (uint32_t)j + (uint32_t)i);
+        wx = LO + 7.8f * u01(mix32(kw ^ w)); wy = LO + 7.8f * u01(mix32(kw ^ (w + 1u)));
+        if (fits(wx, wy)) return;
+    }
+    for (int q = 0; q < RING_SLOTS; ++q) {
+        ring_slot(q, wx, wy);
+        if (fits(wx, wy)) return;
+    }
+}
+// What Nav2DSocial-v0 adds to a world that `begin_episode<false>` has just generated: the person where Nav2DObj-v0 puts object 0 of
+// that world with one object, waypoint 0, the counters and the first distance.  The field is built by nav2d_social_build_kernel.
+__device__ inline void social_begin(Nav2DSocialState& r, uint32_t seed, uint32_t env, int K) {
+    Nav2DState& s = r.base;
+    const uint32_t ep = (uint32_t)s.episode;
+    r.sx = s.px; r.sy = s.py;
+    place_positions(r, stream_key(seed, S_OBJ_POS, env, ep), K, 1, [](int) {});
+    s.gx = 0.0f; s.gy = 0.0f;
+    r.wp_index = 0;
+    social_waypoint(s, stream_key(seed, S_WAYPOINT, env, ep), K, 0, r.obj[0][0], r.obj[0][1], r.wx, r.wy);
+    r.found = r.following_steps = r.first_encounter = 0;
+    r.arrivals = r.person_waits = r.person_lost = r.sweeps = r.rebuilds = r.zero = 0;
+    s.d_start = s.d_prev = dist(s.px, s.py, r.obj[0][0], r.obj[0][1]);
+}
+// (dot, cross) of h - p in the heading's frame, written term by term like write_goal's, and whether the agent sees the person: inside
+// the camera's 90 degree field of view and visible over the graph's boxes.  By one thread, the boxes through the record.
+__device__ inline bool social_sees(const Nav2DSocialState& r, const float* __restrict__ dirs, int K, float& dot, float& cross) {
+    const Nav2DState& s = r.base;
+    const float c = dirs[2 * s.heading], sn = dirs[2 * s.heading + 1];
+    const float hx = r.obj[0][0], hy = r.obj[0][1];
+    const float dx = hx - s.px, dy = hy - s.py;
+    dot = dx * c + dy * sn;
+    cross = c * dy - sn * dx;
+    if (!(dot > 0.0f && fabsf(cross) <= dot)) return false;
+    for (int k = 0; k < K; ++k)
+        if (geo_blocked(geo_box(s, k), s.px, s.py, hx, hy)) return false;
+    return true;
+}
+
+// The field towards the waypoint of an episode that has just begun, one env per 64-thread workgroup (one wavefront), selected like
+// nav2d_geo_build_kernel's.  `states` are records that social_begin has just filled.
+__global__ void __launch_bounds__(64)
+nav2d_social_build_kernel(Nav2DSocialState* __restrict__ states, const uint8_t* __restrict__ mask, int only_ended, int K) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    if (mask && !mask[n]) return;
+    Nav2DSocialState& r = states[n];
+    if (only_ended && !r.base.ended) return;
+    __shared__ GeoGraph G;
+    geo_graph_nodes(G, r.base, K, lane);
+    __syncthreads();
+    geo_graph_weights(G, K, lane);
+    const float wx = r.wx, wy = r.wy;
+    __syncthreads();
+    float Dl;
+    const int sweeps = geo_field_towards(G, K, wx, wy, lane, Dl);
+    if (lane < GEO_NODES) r.DW[lane] = Dl;
+    if (lane == 0) r.sweeps = sweeps;
+}
+
+// What the agent's move changes of a record, as a lane's own copy: the members vel_move reads and writes.
+struct SocialLane {
+    float px, py, path;
+    int32_t heading, collisions;
+};
+
+// One step of one env by one wavefront (a 64-thread workgroup), as nav2d_rearr_geo_step_kernel.  Every lane takes its own copy of the
+// record's changing words -- before lane 0 writes any -- and derives the agent's move on it, from the same loads, so the outcome is
+// uniform over the wave.  The person's hop is the arg-min form of geo_query_wave: node l with DW[l] on lane l < 32, the waypoint on
+// lane 32, and a reduction over (value, rank) with rank 0 for the waypoint and l + 1 for node l, so that among equal values the
+// waypoint wins, then the lowest node; the order is total, so every lane ends with the same pair.  A node at distance exactly 0 is
+// no candidate.  A waypoint reached or given up draws the next one and builds its field here, the weights included; a step that
+// builds nothing needs nodes and boxes alone.  Lane 0 then writes the record back and does the end of the step.  The field of an
+// episode that begins here is built by the launch of nav2d_social_build_kernel that follows (only_ended).
+__global__ void __launch_bounds__(64)
+nav2d_social_step_kernel(Nav2DSocialState* __restrict__ states, const float* __restrict__ dirs, const float* __restrict__ actions,
+                         const uint8_t* __restrict__ mask, float* __restrict__ person_sensor, float* __restrict__ person_visible,
+                         float* __restrict__ reward, uint8_t* __restrict__ not_done, float* __restrict__ sums, uint32_t seed,
+                         uint32_t env_offset, int N, int K, int nh, int max_steps, int max_turn, int stop_turn, float min_lin, int sliding,
+                         float speed, int always_visible, int advance) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    if (mask && !mask[n]) return;
+    Nav2DSocialState& rec = states[n];
+    const uint32_t env = env_offset + (uint32_t)n;
+    if (!advance) {
+        if (lane == 0) {
+            first_episode<false>(rec.base, seed, env, K, nh);
+            social_begin(rec, seed, env, K);
+        }
+    } else {
+        __shared__ GeoGraph G;
+        SocialLane s{rec.base.px, rec.base.py, rec.base.path, rec.base.heading, rec.base.collisions};  // this lane's copy
+        float hx = rec.obj[0][0], hy = rec.obj[0][1], wx = rec.wx, wy = rec.wy;
+        int wp = rec.wp_index;
+        float Dl = lane < GEO_NODES ? rec.DW[lane] : INFINITY;
+        const uint32_t kw = stream_key(seed, S_WAYPOINT, env, (uint32_t)rec.base.episode);
+        // 1. the agent, against the person's old position
+        const float a_lin = actions[2 * (size_t)n], a_ang = actions[2 * (size_t)n + 1];
+        float l;
+        int dh;
+        const bool stop = vel_decode(a_lin, a_ang, max_turn, stop_turn, min_lin, l, dh);
+        if (!stop)
+            vel_move(s, dirs, l, dh, nh, sliding,
+                     [&](float x, float y) { return is_free(x, y, rec.base, K) && !(dist(x, y, hx, hy) < OBJ_BLOCK); });
+        // 2. the person, against the agent's new position
+        geo_graph_nodes(G, rec.base, K, lane);
+        __syncthreads();
+        float v = INFINITY;
+        int rank = lane == GEO_NODES ? 0 : lane + 1;
+        if (lane < GEO_NODES) {
+            if (Dl < INFINITY && geo_visible(G.boxes, K, hx, hy, G.node_x[lane], G.node_y[lane])) {
+                const float di = dist(hx, hy, G.node_x[lane], G.node_y[lane]);
+                if (di != 0.0f) v = di + Dl;
+            }
+        } else if (lane == GEO_NODES) {
+            if (geo_visible(G.boxes, K, hx, hy, wx, wy)) v = dist(hx, hy, wx, wy);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(v, o);
+            const int orank = __shfl_xor(rank, o);
+            if (ov < v || (ov == v && orank < rank)) { v = ov; rank = orank; }
+        }
+        const bool lost = !(v < INFINITY);
+        bool waits = false, arrived = false;
+        if (!lost) {
+            const int node = rank > 0 ? rank - 1 : 0;  // in 0..31: the minimum is finite, so its rank is at most 32
+            const float tx = rank == 0 ? wx : G.node_x[node], ty = rank == 0 ? wy : G.node_y[node];
+            const float L = dist(hx, hy, tx, ty);
+            float qx = tx, qy = ty;
+            if (!(L <= speed)) {
+                const float f = __fdiv_rn(speed, L);
+                qx = hx + f * (tx - hx); qy = hy + f * (ty - hy);
+            }
+            if (dist(qx, qy, s.px, s.py) < OBJ_BLOCK) {
+                waits = true;
+            } else {
+                hx = qx; hy = qy;
+                arrived = hx == wx && hy == wy;
+            }
+        }
+        const bool rebuild = lost || arrived;  // uniform over the wave, like everything above
+        int sweeps = 0;
+        if (rebuild) {
+            wp += 1;
+            social_waypoint(rec.base, kw, K, wp, hx, hy, wx, wy);
+            geo_graph_weights(G, K, lane);
+            __syncthreads();
+            sweeps = geo_field_towards(G, K, wx, wy, lane, Dl);
+        }
+        __syncthreads();  // every lane has read the record before a lane writes to it
+        if (rebuild && lane < GEO_NODES) rec.DW[lane] = Dl;
+        if (lane == 0) {
+            Nav2DState& t = rec.base;
+            t.px = s.px; t.py = s.py; t.path = s.path; t.heading = s.heading; t.collisions = s.collisions;
+            rec.obj[0][0] = hx; rec.obj[0][1] = hy;
+            rec.wx = wx; rec.wy = wy; rec.wp_index = wp;
+            if (arrived) rec.arrivals += 1;
+            if (waits) rec.person_waits += 1;
+            if (lost) rec.person_lost += 1;
+            if (rebuild) { rec.sweeps = sweeps; rec.rebuilds += 1; }
+            // 3. - 5. the terms, the reward, the end of the episode
+            float dot, cross;
+            const bool sees = social_sees(rec, dirs, K, dot, cross);
+            const float d = dist(t.px, t.py, hx, hy);
+            const bool following = d >= SOCIAL_NEAR && d <= SOCIAL_FAR && sees;
+            const bool was_found = rec.found != 0, sets = following && !was_found;
+            reward[n] = ((-0.01f + (t.d_prev - d) * (was_found ? 0.0f : 1.0f)) + (sets ? 2.5f : 0.0f)) + (following ? 0.1f : 0.0f);
+            t.d_prev = d;
+            t.steps += 1;
+            if (sets) { rec.found = 1; rec.first_encounter = t.steps; }
+            if (following) rec.following_steps += 1;
+            const bool done = t.steps >= max_steps;
+            not_done[n] = done ? 0 : 1;
+            t.ended = done ? 1 : 0;
+            if (done) {
+                t.last[0] = (float)rec.found;
+                t.last[1] = __fdiv_rn((float)rec.following_steps, (float)t.steps);
+                t.last[2] = (float)(rec.found ? rec.first_encounter : t.steps);
+                t.last[3] = (float)t.collisions;
+                if (sums)
+                    for (int m = 0; m < 4; ++m) sums[(size_t)m * N + n] = sums[(size_t)m * N + n] + t.last[m];
+                t.episode += 1;
+                begin_episode<false>(t, seed, env, K, nh);
+                social_begin(rec, seed, env, K);
+            }
+        }
+    }
+    if (lane == 0 && (person_sensor || person_visible)) {
+        float dot, cross;
+        const bool shown = social_sees(rec, dirs, K, dot, cross) || always_visible;
+        if (person_sensor) {
+            person_sensor[2 * (size_t)n + 0] = shown ? dot : 0.0f;
+            person_sensor[2 * (size_t)n + 1] = shown ? cross : 0.0f;
+        }
+        if (person_visible) person_visible[n] = shown ? 1.0f : 0.0f;
+    }
+}
+
 // ---- rendering ---------------------------------------------------------------------------------------------------------------
 // Entry / exit of the ray p + t d through [lo, hi] on one axis.
 __device__ inline void slab(float lo, float hi, float p, float d, float inv, float& tmin, float& tmax) {
@@ -1398,7 +1638,9 @@ __device__ inline void sweep_dwords(T* __restrict__ img, int s_px, int e_px, int
 // Render::REARR (Nav2DRearr-v0): `states` are Nav2DRearrState records; the object is one cylinder of category 0's colour, geometry
 // for depth and rgb alike while the env's holding flag is clear and absent while it is set; the goal marker is drawn in rgb as in
 // the GOAL form, nearer than whatever the column hit, the cylinder included.  No semantic image: four column arrays.
-enum class Render { GOAL, OBJ, REARR };
+// Render::SOCIAL (Nav2DSocial-v0): `states` are Nav2DSocialState records; the person is one cylinder of category 0's colour, geometry
+// for depth and rgb alike, and there is no goal marker: nothing is drawn in rgb only.  No semantic image: four column arrays.
+enum class Render { GOAL, OBJ, REARR, SOCIAL };
 template <Render MODE>
 __global__ void __launch_bounds__(RENDER_THREADS)
 nav2d_render_kernel(const void* __restrict__ states, const float* __restrict__ ray, const float* __restrict__ col_cos,
@@ -1413,14 +1655,15 @@ nav2d_render_kernel(const void* __restrict__ states, const float* __restrict__ r
     float* c_zr = c_dw + P;
     uint32_t* c_cw = reinterpret_cast<uint32_t*>(c_zr + P);
     int32_t* c_sem = reinterpret_cast<int32_t*>(c_cw + P);  // OBJ only
-    constexpr bool OBJ = MODE == Render::OBJ, REARR = MODE == Render::REARR;
+    constexpr bool OBJ = MODE == Render::OBJ, REARR = MODE == Render::REARR, SOCIAL = MODE == Render::SOCIAL;
     RowRec* row = reinterpret_cast<RowRec*>(lds + P) + (OBJ ? P / 4 : 0);
     const Nav2DObjState* os = OBJ ? static_cast<const Nav2DObjState*>(states) + n : nullptr;
     const Nav2DRearrState* rs = REARR ? static_cast<const Nav2DRearrState*>(states) + n : nullptr;
-    const Nav2DState& s = OBJ ? os->base : REARR ? rs->base : static_cast<const Nav2DState*>(states)[n];
-    // the cylinders of this env: Nav2DObj-v0's M objects, Nav2DRearr-v0's object unless it is held
-    const float (*cyl)[2] = OBJ ? os->obj : REARR ? reinterpret_cast<const float (*)[2]>(&rs->ox) : nullptr;
-    const int cyls = OBJ ? M : REARR ? (rs->holding ? 0 : 1) : 0;
+    const Nav2DSocialState* ss = SOCIAL ? static_cast<const Nav2DSocialState*>(states) + n : nullptr;
+    const Nav2DState& s = OBJ ? os->base : REARR ? rs->base : SOCIAL ? ss->base : static_cast<const Nav2DState*>(states)[n];
+    // the cylinders of this env: Nav2DObj-v0's M objects, Nav2DRearr-v0's object unless it is held, Nav2DSocial-v0's person
+    const float (*cyl)[2] = OBJ ? os->obj : REARR ? reinterpret_cast<const float (*)[2]>(&rs->ox) : SOCIAL ? ss->obj : nullptr;
+    const int cyls = OBJ ? M : REARR ? (rs->holding ? 0 : 1) : SOCIAL ? 1 : 0;
     const int v0 = blockIdx.x * rows_per_tile, v1 = min(H, v0 + rows_per_tile);
     const float px = s.px, py = s.py;
     const float* rayh = ray + (size_t)s.heading * W * 2;
@@ -1438,7 +1681,7 @@ nav2d_render_kernel(const void* __restrict__ states, const float* __restrict__ r
             const float tn = fmaxf(axn, ayn), tm = fminf(axx, ayx);
             if (tn <= tm && tn > 0.0f && tn < t) { t = tn; hit = 4 + k; }
         }
-        if constexpr (OBJ || REARR) {
+        if constexpr (OBJ || REARR || SOCIAL) {
             // the cylinders: the goal marker's ray-circle test (nearest intersection, ray direction taken as unit length)
             for (int j = 0; j < cyls; ++j) {
                 const float ox = px - cyl[j][0], oy = py - cyl[j][1];
@@ -1453,7 +1696,7 @@ nav2d_render_kernel(const void* __restrict__ states, const float* __restrict__ r
         const float z_wall = t * cf;
         float z_rgb = z_wall;
         bool marker = false;
-        if constexpr (!OBJ) {
+        if constexpr (!OBJ && !SOCIAL) {
             const float ox = px - s.gx, oy = py - s.gy;
             const float b = ox * dx + oy * dy;
             const float c = (ox * ox + oy * oy) - 0.2f * 0.2f;
@@ -1464,7 +1707,7 @@ nav2d_render_kernel(const void* __restrict__ states, const float* __restrict__ r
         }
         uint32_t base;
         if (marker) base = pack_rgb(255, 32, 32);
-        else if ((OBJ || REARR) && hit >= 4 + MAX_K) base = category_color(OBJ ? os->cat[hit - (4 + MAX_K)] : 0);
+        else if ((OBJ || REARR || SOCIAL) && hit >= 4 + MAX_K) base = category_color(OBJ ? os->cat[hit - (4 + MAX_K)] : 0);
         else if (hit >= 4) base = s.color[hit - 4];
         else base = hit == 0 ? pack_rgb(200, 180, 150) : hit == 1 ? pack_rgb(150, 200, 180) : hit == 2 ? pack_rgb(180, 150, 200)
                                                                                                         : pack_rgb(200, 200, 150);
@@ -1858,4 +2101,33 @@ extern "C" int hab_nav2d_rearr_vel_step_geo(void* state, void* geo, const float*
                                  advance, stream},
                                 obj_start, obj_goal, is_holding, start_holding, max_turn_steps, stop_turn_steps, min_abs_lin_speed,
                                 allow_sliding);
+}
+
+extern "C" int hab_nav2d_social_state_bytes(void) { return (int)sizeof(Nav2DSocialState); }
+
+// Nav2DSocial-v0: the step (one wavefront per env), the fields of the episodes that began (at a reset, of every env the mask selects),
+// then the render.
+extern "C" int hab_nav2d_social_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                                     const float* actions, const uint8_t* mask, uint8_t* head_rgb, float* head_depth, float* person_sensor,
+                                     float* person_visible, float* reward, uint8_t* not_done, float* measure_sums, uint32_t seed,
+                                     uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings, int max_episode_steps,
+                                     int max_turn_steps, int stop_turn_steps, float min_abs_lin_speed, int allow_sliding, float person_speed,
+                                     int person_always_visible, int advance, hipStream_t stream) {
+    const StepArgs a{state, nullptr, dirs, ray, col_cos, tanv, actions, mask, head_rgb, head_depth, nullptr, nullptr, reward, not_done,
+                     measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream};
+    const int rc = check_step_args(a, false);
+    if (rc != HAB_OK) return rc;
+    if (((uintptr_t)state & 3) || ((uintptr_t)actions & 3)) return HAB_ERR_ARG;  // a row of two floats is read as two scalars
+    if (max_turn_steps < 1 || max_turn_steps > num_headings / 2 || stop_turn_steps < 1 || stop_turn_steps > max_turn_steps)
+        return HAB_ERR_ARG;
+    if (!(person_speed > 0.0f && person_speed <= 0.25f)) return HAB_ERR_ARG;
+    if (person_always_visible != 0 && person_always_visible != 1) return HAB_ERR_ARG;
+    nav2d_social_step_kernel<<<N, 64, 0, stream>>>((Nav2DSocialState*)state, dirs, actions, mask, person_sensor, person_visible, reward,
+                                                   not_done, measure_sums, seed, env_offset, N, num_obstacles, num_headings,
+                                                   max_episode_steps, max_turn_steps, stop_turn_steps, min_abs_lin_speed, allow_sliding,
+                                                   person_speed, person_always_visible, advance);
+    HAB_LAUNCH_CHECK();
+    nav2d_social_build_kernel<<<N, 64, 0, stream>>>((Nav2DSocialState*)state, mask, advance ? 1 : 0, num_obstacles);
+    HAB_LAUNCH_CHECK();
+    return launch_render<Render::SOCIAL>(a, 0);
 }

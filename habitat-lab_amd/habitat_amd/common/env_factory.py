@@ -51,7 +51,7 @@ class SyntheticVectorEnv:
         self.use_rgb, self.use_depth, self.task = use_rgb, use_depth, task
         self.device = torch.device(device)
         d = {}
-        rgb_key, depth_key = ("head_rgb", "head_depth") if task == "rearrange" else ("rgb", "depth")
+        rgb_key, depth_key = ("head_rgb", "head_depth") if task in ("rearrange", "social") else ("rgb", "depth")
         if use_rgb:
             d[rgb_key] = spaces.Box(0, 255, (height, width, 3), np.uint8)
         if use_depth:
@@ -61,6 +61,9 @@ class SyntheticVectorEnv:
             d["obj_start_sensor"] = spaces.Box(fmin, fmax, (2,), np.float32)
             d["obj_goal_sensor"] = spaces.Box(fmin, fmax, (2,), np.float32)
             d["is_holding"] = spaces.Box(0.0, 1.0, (1,), np.float32)
+        elif task == "social":  # sensor set of Nav2DSocial-v0: the head camera and two raw 1-D sensors, no goal sensor
+            d["person_sensor"] = spaces.Box(fmin, fmax, (2,), np.float32)
+            d["person_visible"] = spaces.Box(0.0, 1.0, (1,), np.float32)
         elif task == "objectnav":  # sensor set of the ObjectNav experiments (rgb, depth, semantic + objectgoal, compass, gps)
             d["semantic"] = spaces.Box(0, NUM_SEMANTIC_IDS - 1, (height, width, 1), np.int32)
             d["objectgoal"] = spaces.Box(0, NUM_OBJECT_CATEGORIES - 1, (1,), np.int64)
@@ -79,7 +82,7 @@ class SyntheticVectorEnv:
         self._since = torch.zeros(num_envs, dtype=torch.int64, device=dev)
         self._rgb = torch.zeros(num_envs, height, width, 3, dtype=torch.uint8, device=dev) if use_rgb else None
         self._depth = torch.zeros(num_envs, height, width, 1, device=dev) if use_depth else None
-        self._goal = torch.zeros(num_envs, 2, device=dev) if task not in ("objectnav", "rearrange") else None
+        self._goal = torch.zeros(num_envs, 2, device=dev) if task not in ("objectnav", "rearrange", "social") else None
         self._obj = {}
         if task == "objectnav":
             self._obj = dict(semantic=torch.zeros(num_envs, height, width, 1, dtype=torch.int32, device=dev),
@@ -88,6 +91,8 @@ class SyntheticVectorEnv:
         elif task == "rearrange":
             self._obj = dict(obj_start_sensor=torch.zeros(num_envs, 2, device=dev), obj_goal_sensor=torch.zeros(num_envs, 2, device=dev),
                              is_holding=torch.zeros(num_envs, 1, device=dev))
+        elif task == "social":
+            self._obj = dict(person_sensor=torch.zeros(num_envs, 2, device=dev), person_visible=torch.zeros(num_envs, 1, device=dev))
         self._rew = torch.zeros(num_envs, device=dev)
         self._nd = torch.zeros(num_envs, dtype=torch.uint8, device=dev)
         self._pending: set = set()      # envs with an outstanding async_step_at (host path)
@@ -334,7 +339,8 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
     consumes_actions = True
     measure_names = NAV2D_MEASURES
     # what a subclass with another sensor set changes: the observation set SyntheticVectorEnv builds ("nav2d": the point-goal set,
-    # "objectnav", "rearrange": head camera + object start / goal / holding), whether an image is rendered
+    # "objectnav", "rearrange": head camera + object start / goal / holding, "social": head camera + person sensor / visible),
+    # whether an image is rendered
     # without rgb and depth, and the size of a state record
     _sensor_set = "nav2d"
     _renders_without_rgb_depth = False
@@ -906,6 +912,167 @@ class Nav2DRearrVelVectorEnv(Nav2DRearrVectorEnv):
         raise _lib.HabError("Nav2DRearrVel: the task has no pointgoal sensor; use step_into_obs with the rearrangement sensor rows")
 
 
+NAV2D_SOCIAL_MEASURES = ("has_found_person", "following_rate", "first_encounter_steps", "collisions")
+NAV2D_SOCIAL_SENSORS = ("head_rgb", "head_depth", "person_sensor", "person_visible")
+
+
+class Nav2DSocialVectorEnv(Nav2DVectorEnv):
+    """Nav2DSocial-v0: find a person who walks about Nav2D-v0's world, then stay near and facing them.  It is the one source whose
+    world changes on its own, whose reward is no potential, whose fused sensor is absent for most of an episode and whose episodes
+    end at the step limit alone.  Read through `head_depth` (and optionally `head_rgb`) and two raw float32 1-D sensors that
+    PointNavResNetPolicy fuses into its recurrent input, under Nav2DVel-v0's velocity control.  A measurement source, not a simulator.
+    tests/nav2d_social_reference.py restates the task in numpy; `nav2d_social_step_kernel`, `nav2d_social_build_kernel` and the
+    social form of `nav2d_render_kernel` (csrc/nav2d.hip) match it bit for bit on every output -- no angle function runs on the
+    device, every float32 operation is one rounding in the written order, division and square root are correctly rounded.
+
+    World.  Nav2D-v0's, unchanged (see Nav2DVectorEnv): the arena, K = num_obstacles rectangles, start, heading table, streams
+      16-20 and the 0.1 m box free test.  There is no goal; the record's (gx, gy) are zero.
+    Person.  An upright cylinder of radius 0.3 m at h.  Initially h is the position Nav2DObj-v0 gives object 0 of the same
+      (seed, env, episode) world with num_objects = 1 (see Nav2DObjVectorEnv, Objects: stream 21, 16 candidates, the box
+      [0.5, 7.5]^2, not strictly inside a rectangle grown by 0.3 m, at least 1 m from the start, the 28-slot ring).  A position
+      closer than 0.4 m to h is not free for the agent (the keep-out of the rearrangement object); a refused move counts a collision.
+      The person walks as a POINT on Nav2D-v0's visibility graph (see Nav2DVectorEnv, Distance: boxes grown by the agent's 0.1 m,
+      visibility boxes shrunk by E = 2^-10, the separating-axis test, the 4K corner nodes valid iff free), so the rendered cylinder
+      may overlap a rectangle's corner by up to 0.2 m; depth is the minimum over hits either way.
+    Waypoints.  Waypoint j = 0, 1, ... of an episode comes from stream 24, keyed by (seed, 24, env, episode): candidate i = 0..15 is
+      (0.1 + 7.8 u_2(16j+i), 0.1 + 7.8 u_2(16j+i)+1), and the waypoint is the first candidate that lies in [0.5, 7.5]^2, is not
+      strictly inside a rectangle grown by 0.3 m and is at least 1 m (float32 d >= 1) from the person's current position; failing
+      all 16, the first of Nav2DObj-v0's 28 ring slots that passes the same three tests (an open disc of radius 1 holds at most three
+      slots, so one does).  The field DW[32] towards the waypoint is Nav2D-v0's field (last hops, then Jacobi sweeps until one
+      changes nothing, at most 4K), built when an episode begins and again inside the step whenever the waypoint changes.  It is
+      stored per env in the record; graph weights are computed only when a field is built.
+    Parameters (`habitat.synthetic`): Nav2DVel-v0's turn_angle (default 1), max_turn_angle (10), min_abs_lin_speed (0.025),
+      min_abs_ang_speed (5), allow_sliding (true), checked by `nav2d_vel_parameters`; person_speed v in (0, 0.25] metres per step
+      (default 0.125); person_always_visible (bool, default false); num_obstacles.
+    Action space: Box(-1, 1, (2,), float32), a = (a_lin, a_ang).
+    One step, in this order:
+      1. The agent moves against the person's OLD position: Nav2DVel-v0's steps 1-5 (`vel_clamp`, `vel_decode`, `vel_move`) with
+         this task's free test.  The velocity stop is standing still; it never ends the episode.
+      2. The person moves against the agent's NEW position.  Candidate i < 32 is node c_i with the value fl(d(h, c_i) + DW[i]) where
+         DW[i] is finite, h sees c_i and d(h, c_i) is not exactly 0 (a person standing on node i would otherwise tie with its own
+         zero-length hop at the field's fixed point and never leave).  Candidate 32 is the waypoint w with the value d(h, w) where h
+         sees it.  The least value wins; ties go to the waypoint, then to the lowest node index.  No candidate: the person stays,
+         waypoint j + 1 is drawn, its field built and person_lost goes up.  Otherwise, with t the chosen hop's end, L = d(h, t):
+         h' = t exactly if L <= v, else h' = h + (v / L) * (t - h) (one division, then a multiply and an add per component); what is
+         left of the step is dropped.  If d(h', p) < 0.4 the person stays and person_waits goes up.  Otherwise h = h', and if h
+         equals the waypoint in both coordinates, waypoint j + 1 is drawn (from the new h), DW rebuilt in this same step and
+         arrivals goes up.
+      3. Terms.  d = float32 Euclidean d(p, h); (dot, cross) = h - p in the heading's frame (dot = dx * c + dy * s,
+         cross = c * dy - s * dx); facing = dot > 0 and |cross| <= dot, the camera's 90 degree field of view; sees = facing and the
+         graph's visible(p, h); following = 1.0 <= d <= 2.0 and sees; found is sticky, set by the first step that is following.
+      4. reward = ((-0.01 + (d_prev - d) * [found was 0 before this step]) + 2.5 * [this step set found]) + 0.1 * following, in
+         float32 in this order; d_prev = d after every step.
+      5. The step count goes up; the episode ends when it reaches habitat.environment.max_episode_steps, and only then.  On done the
+         next episode's world, person, waypoint 0 and field are generated, its first observation is what the step returns and
+         not_done = 0.
+      After every step d(p, h) >= 0.4.
+    Measures.  has_found_person; following_rate = following steps / episode steps (one float32 division); first_encounter_steps =
+      the step count (from 1) of the step that set found, or the episode's step count if none did; collisions.
+    Sensors, in observation-space order.  head_rgb (H, W, 3) uint8, optional; head_depth (H, W, 1) float32; person_sensor (2,)
+      float32 = (dot, cross) while sees, else (0, 0); person_visible (1,) float32 = sees.  With person_always_visible both are given
+      as if the person were seen on every step: person_sensor = (dot, cross) and person_visible = 1; the reward still uses sees.
+      That mode makes the task solvable blind and is for the learning test.  head_depth is Nav2D-v0's depth with the person's
+      cylinder as geometry (Nav2DObj-v0's ray-circle test); head_rgb is the same with the person in category 0's colour.  Nothing is
+      drawn in rgb only.  Without head_rgb and head_depth nothing is rendered.
+    Distance.  Euclidean d only: `distance="geodesic"` is refused, because the target moves every step and would need a field per
+      step.  The fields are built on the device, so the class itself refuses a device that is no GPU.
+
+    `step_into_obs` writes whichever of the four rows `obs` holds; `actions` are the (N, 2) float32 rows the policy stored (the env
+    clamps).  The record's words beyond Nav2D-v0's are named in include/habitat_amd.h (HAB_NAV2D_SOCIAL_W_*): the start, the person,
+    the waypoint and its index j, found, the following steps, the step that set found, arrivals, person_waits, person_lost, the sweeps
+    of the last build, the builds inside steps of the episode (`rebuilds`), one zero and DW."""
+
+    _name = "Nav2DSocial"
+    _entries = ("hab_nav2d_social_step",)
+    _sensor_set = "social"
+    _state_bytes = "hab_nav2d_social_state_bytes"
+    _action_dtype, _action_text = torch.float32, "float32 device tensor of shape (N, 2)"
+    measure_names = NAV2D_SOCIAL_MEASURES
+    num_actions = 1
+
+    def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = False,
+                 use_depth: bool = True, num_actions: int = 1, device="cuda", num_obstacles: int = 3, turn_angle: int = 1,
+                 max_episode_steps: int = 500, max_turn_angle: int = 10, min_abs_lin_speed: float = 0.025, min_abs_ang_speed: int = 5,
+                 allow_sliding: bool = True, person_speed: float = 0.125, person_always_visible: bool = False,
+                 distance: str = "euclidean"):
+        if nav2d_distance(distance, "Nav2DSocial") == "geodesic":
+            raise _lib.HabError("Nav2DSocial: distance 'geodesic' is refused: the target moves every step, so it would need a field "
+                                "per step; the task has the Euclidean distance only")
+        _, self.max_turn_steps, self.stop_turn_steps = nav2d_vel_parameters(turn_angle, max_turn_angle, min_abs_lin_speed,
+                                                                            min_abs_ang_speed, "Nav2DSocial")
+        if not isinstance(allow_sliding, (bool, np.bool_)):
+            raise _lib.HabError(f"Nav2DSocial: allow_sliding {allow_sliding!r} must be true or false")
+        if not isinstance(person_always_visible, (bool, np.bool_)):
+            raise _lib.HabError(f"Nav2DSocial: person_always_visible {person_always_visible!r} must be true or false")
+        if (isinstance(person_speed, bool) or not isinstance(person_speed, (int, float, np.integer, np.floating))
+                or not 0.0 < float(np.float32(person_speed)) <= 0.25):
+            raise _lib.HabError(f"Nav2DSocial: person_speed {person_speed!r} must be a length in (0, 0.25] metres")
+        if num_actions != 1:
+            raise _lib.HabError(f"Nav2DSocial: the task has the one action velocity_control, got {num_actions} actions")
+        if (use_rgb or use_depth) and (int(height) <= 0 or int(width) <= 0):
+            raise _lib.HabError(f"Nav2DSocial: the image size {height} x {width} must be positive")
+        self.max_turn_angle, self.min_abs_ang_speed = int(max_turn_angle), int(min_abs_ang_speed)
+        self.min_abs_lin_speed, self.allow_sliding = float(min_abs_lin_speed), bool(allow_sliding)
+        self.person_speed, self.person_always_visible = float(person_speed), bool(person_always_visible)
+        try:
+            super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
+                             num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps)
+        except _lib.HabError as err:
+            # Nav2D-v0's own parameter refusals come first and stand; the one that is left where the spaces exist is the device's
+            if torch.device(device).type != "cuda" and hasattr(self, "observation_spaces"):
+                raise _lib.HabError("Nav2DSocial: the person's fields are built on the GPU; no GPU device given") from err
+            raise
+        self.task = "nav2dsocial"
+        self.action_spaces = [spaces.Box(-1.0, 1.0, (2,), np.float32) for _ in range(num_envs)]
+        self.orig_action_spaces = self.action_spaces
+        self._actions_host = np.zeros((num_envs, 2), dtype=np.float32)
+
+    def _actions_shaped(self, actions) -> bool:
+        return tuple(actions.shape) == (self.num_envs, 2)
+
+    def _sensor_rows(self, obs):
+        return tuple(ptr(obs.get(k)) for k in NAV2D_SOCIAL_SENSORS)
+
+    def _task_parameters(self):
+        return (self.max_turn_steps, self.stop_turn_steps, self.min_abs_lin_speed, int(self.allow_sliding), self.person_speed,
+                int(self.person_always_visible))
+
+    def _own_obs(self):
+        o = {}
+        if self.use_rgb:
+            o["head_rgb"] = self._rgb
+        if self.use_depth:
+            o["head_depth"] = self._depth
+        o.update(self._obj)
+        return o
+
+    def _host_obs(self) -> List[Dict[str, np.ndarray]]:
+        host = {k: v.cpu().numpy() for k, v in self._own_obs().items()}
+        return [{k: v[i] for k, v in host.items()} for i in range(self.num_envs)]
+
+    def async_step_at(self, index_env: int, action) -> None:
+        if isinstance(action, dict):
+            action = action["action"]
+        try:
+            a = np.asarray(action, dtype=np.float32)
+        except (TypeError, ValueError):
+            a = None
+        if a is None or a.shape != (2,):
+            raise _lib.HabError(f"Nav2DSocial: env {index_env}: action {action!r} is not a length-2 array (a_lin, a_ang)")
+        SyntheticVectorEnv.async_step_at(self, index_env, action)
+        self._actions_host[int(index_env)] = a
+
+    def step_infos_host(self, ids) -> List[dict]:
+        """The scalar infos of the last step of envs `ids`: this task's four measures where that step ended an episode, else {}."""
+        return [dict(zip(NAV2D_SOCIAL_MEASURES, info.values())) if info else {} for info in super().step_infos_host(ids)]
+
+    def reset_into(self, rgb, depth, goal):
+        raise _lib.HabError("Nav2DSocial: the task has no pointgoal sensor; use reset_into_obs with the task's sensor rows")
+
+    def step_into(self, rgb, depth, goal, reward, not_done, actions=None, mask=None):
+        raise _lib.HabError("Nav2DSocial: the task has no pointgoal sensor; use step_into_obs with the task's sensor rows")
+
+
 class SyntheticVectorEnvFactory(VectorEnvFactory):
     """Default `_target_`: N synthetic PointNav envs sized from habitat.simulator.sensors.*; per-rank env ids are
     offset by rank * num_environments exactly like the reference offsets the seed (ppo_trainer.py:208-211).  A
@@ -920,7 +1087,9 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
     of its potential are shortest paths.  A type
     starting with "nav2drearrvel" -- tested before "nav2drearr", which keeps its meaning for everything else -- selects
     Nav2DRearrVel-v0 (Nav2DRearrVelVectorEnv: that task under velocity and grip control), which reads Nav2DVel-v0's keys and
-    start_holding and takes its image size like Nav2DRearr-v0."""
+    start_holding and takes its image size like Nav2DRearr-v0.  A type starting with "nav2dsocial" -- tested before "nav2d" -- selects
+    Nav2DSocial-v0 (Nav2DSocialVectorEnv: find and follow a walking person), which reads Nav2DVel-v0's keys, person_speed and
+    person_always_visible, takes its image size like Nav2DRearr-v0 and has the Euclidean distance mode only."""
 
     def __init__(self, use_rgb: bool = True, use_depth: bool = True):
         self.use_rgb, self.use_depth = use_rgb, use_depth
@@ -940,7 +1109,16 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
                       device=device, num_obstacles=getattr(syn, "num_obstacles", 3), turn_angle=getattr(syn, "turn_angle", 10),
                       max_episode_steps=getattr(hab.environment, "max_episode_steps", 500), distance=distance)
             make = Nav2DVectorEnv
-            if task_type.startswith("nav2drearr"):
+            if task_type.startswith("nav2dsocial"):
+                use_rgb, use_depth = self.use_rgb and "head_rgb" in sens, self.use_depth and "head_depth" in sens
+                ref = sens["head_rgb"] if use_rgb else (sens["head_depth"] if use_depth else dict(height=0, width=0))
+                make = Nav2DSocialVectorEnv
+                kw.update(use_rgb=use_rgb, use_depth=use_depth, turn_angle=getattr(syn, "turn_angle", 1),
+                          max_turn_angle=getattr(syn, "max_turn_angle", 10), min_abs_lin_speed=getattr(syn, "min_abs_lin_speed", 0.025),
+                          min_abs_ang_speed=getattr(syn, "min_abs_ang_speed", 5), allow_sliding=getattr(syn, "allow_sliding", True),
+                          person_speed=getattr(syn, "person_speed", 0.125),
+                          person_always_visible=getattr(syn, "person_always_visible", False))
+            elif task_type.startswith("nav2drearr"):
                 use_rgb, use_depth = self.use_rgb and "head_rgb" in sens, self.use_depth and "head_depth" in sens
                 ref = sens["head_rgb"] if use_rgb else (sens["head_depth"] if use_depth else dict(height=0, width=0))
                 make = Nav2DRearrVectorEnv

@@ -823,10 +823,12 @@ class PointNavResNetPolicy(NetPolicy):
         hb = config.habitat_baselines
         ppo, dd = hb.rl.ppo, hb.rl.ddppo
         n_envs = int(hb.num_environments)
+        policy_config = hb.rl.policy[kwargs.get("agent_name") or "main_agent"]
+        fuse_keys = getattr(policy_config, "fuse_keys", None)  # absent: every sensor of the observation space (resolve_sensors)
         return cls(observation_space=observation_space, action_space=action_space, hidden_size=ppo.hidden_size,
                    rnn_type=dd.rnn_type, num_recurrent_layers=dd.num_recurrent_layers, backbone=dd.backbone,
                    normalize_visual_inputs="rgb" in observation_space.spaces,
                    force_blind_policy=getattr(hb, "force_blind_policy", False),
-                   policy_config=hb.rl.policy[kwargs.get("agent_name") or "main_agent"],
+                   policy_config=policy_config, fuse_keys=None if fuse_keys is None else list(fuse_keys),
                    aux_loss_config=getattr(hb.rl, "auxiliary_losses", None),
                    max_frames=int(ppo.num_steps) * max(1, -(-n_envs // int(ppo.num_mini_batch))), max_envs=n_envs)

@@ -74,7 +74,7 @@ def batch_obs(observations, device):
 @baseline_registry.register_trainer(name="ddppo")
 @baseline_registry.register_trainer(name="ppo")
 class PPOTrainer(BaseRLTrainer):
-    supported_tasks = ["Nav-v0", "ObjectNav-v1", "Nav2D-v0", "Nav2DObj-v0", "Nav2DRearr-v0", "Nav2DRearrVel-v0"]
+    supported_tasks = ["Nav-v0", "ObjectNav-v1", "Nav2D-v0", "Nav2DObj-v0", "Nav2DRearr-v0", "Nav2DRearrVel-v0", "Nav2DSocial-v0"]
     SHORT_ROLLOUT_THRESHOLD: float = 0.25
 
     def __init__(self, config=None):

@@ -285,6 +285,48 @@ int hab_nav2d_rearr_vel_step_geo(void* state /*N,HAB_NAV2D_REARR_STATE_BYTES*/, 
                                  uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings,
                                  int max_episode_steps, int start_holding, int max_turn_steps, int stop_turn_steps,
                                  float min_abs_lin_speed, int allow_sliding, int advance, hipStream_t stream);
+/* Nav2DSocial-v0: find and follow a person who walks about Nav2D-v0's world along the shortest paths of its visibility graph
+ * (definition: habitat_amd/common/env_factory.py, Nav2DSocialVectorEnv; bit-identical to tests/nav2d_social_reference.py on every
+ * output, no angle function runs on the device).  `state` is N records of HAB_NAV2D_SOCIAL_STATE_BYTES whose first
+ * HAB_NAV2D_STATE_BYTES are a Nav2D-v0 record: the words named above keep their meaning, with (GX, GY) zero, D_PREV the distance
+ * d(p, h) to the person after the last step and D_START the episode's first one; LAST_MEASURES are has_found_person,
+ * following_rate, first_encounter_steps, collisions.  Every argument of hab_nav2d_vel_step keeps its meaning and its checks, except:
+ * there is no goal sensor, and actions f32 (N,2) need be 4-byte aligned only (a row is read as two scalars; a pointer that is not is
+ * HAB_ERR_ARG).  The velocity stop is standing still and ends nothing: an episode ends at max_episode_steps alone.  head_rgb u8
+ * (N,H,W,3) and head_depth f32 (N,H,W,1), 4-byte aligned: Nav2D-v0's images with the person's cylinder as geometry and no goal
+ * marker; person_sensor f32 (N,2): (dot, cross) of the person's position minus the agent's in the heading's frame while the agent
+ * sees the person, else (0, 0); person_visible f32 (N,1) in {0, 1}.  Every destination may be NULL.  person_speed: the person's step
+ * in metres, in (0, 0.25], else HAB_ERR_ARG.  person_always_visible 0 or 1 (else HAB_ERR_ARG): 1 gives both vector sensors on every
+ * step whether the person is seen or not; the reward is the same in both.  The entry runs the step (one wavefront per env; a
+ * waypoint that changes rebuilds the field inside it), then the build of the fields of the envs whose episode ended (advance = 0:
+ * of every selected env), then the render. */
+#define HAB_NAV2D_SOCIAL_STATE_BYTES 416
+/* further words of a Nav2DSocial-v0 record: the agent's start position (x, y), the person's position (x, y), the waypoint the person
+ * walks to (x, y) and its index in the episode, whether the person was found, the following steps, the step that set FOUND (0 while
+ * it is clear), the waypoints reached, the steps the person waited for the agent, the waypoints given up as unreachable, the sweeps
+ * of the field's last build (the one that changed nothing included), the builds inside steps of this episode, one zero, and the 32
+ * f32 shortest-path lengths DW from the nodes of Nav2D-v0's graph to the waypoint (+inf: no node, or no path) */
+#define HAB_NAV2D_SOCIAL_W_START 56
+#define HAB_NAV2D_SOCIAL_W_PERSON 58
+#define HAB_NAV2D_SOCIAL_W_WAYPOINT 60
+#define HAB_NAV2D_SOCIAL_W_WAYPOINT_INDEX 62
+#define HAB_NAV2D_SOCIAL_W_FOUND 63
+#define HAB_NAV2D_SOCIAL_W_FOLLOWING_STEPS 64
+#define HAB_NAV2D_SOCIAL_W_FIRST_ENCOUNTER 65
+#define HAB_NAV2D_SOCIAL_W_ARRIVALS 66
+#define HAB_NAV2D_SOCIAL_W_PERSON_WAITS 67
+#define HAB_NAV2D_SOCIAL_W_PERSON_LOST 68
+#define HAB_NAV2D_SOCIAL_W_SWEEPS 69
+#define HAB_NAV2D_SOCIAL_W_REBUILDS 70
+#define HAB_NAV2D_SOCIAL_W_DW 72
+int hab_nav2d_social_state_bytes(void);
+int hab_nav2d_social_step(void* state /*N,HAB_NAV2D_SOCIAL_STATE_BYTES*/, const float* dirs, const float* ray, const float* col_cos,
+                          const float* tanv, const float* actions /*N,2*/, const uint8_t* mask /*N*/, uint8_t* head_rgb /*N,H,W,3*/,
+                          float* head_depth /*N,H,W,1*/, float* person_sensor /*N,2*/, float* person_visible /*N,1*/,
+                          float* reward /*N*/, uint8_t* not_done /*N*/, float* measure_sums /*4,N*/, uint32_t seed,
+                          uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings, int max_episode_steps,
+                          int max_turn_steps, int stop_turn_steps, float min_abs_lin_speed, int allow_sliding, float person_speed,
+                          int person_always_visible, int advance, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Observation transformers, fused: ResizeShortestEdge followed by CenterCropper
