@@ -466,13 +466,13 @@ extern "C" int hab_ppo_loss_ver(const float* values, const float* logp, const fl
                                 float clip_param, float value_loss_coef, float entropy_coef, int use_clipped_value_loss,
                                 const float* is_coeffs, const uint8_t* is_stale, const int64_t* policy_version,
                                 int64_t current_policy_version, const float* log_alpha, float entropy_threshold, float* d_value,
-                                float* d_logp, float* d_entropy, float* out20, hipStream_t stream) {
+                                float* d_logp, float* d_entropy, float* out24, hipStream_t stream) {
     if (B <= 0 || !values || !logp || !entropy || !old_logp || !adv || !old_values || !returns || !d_value || !d_logp ||
-        !d_entropy || !out20)
+        !d_entropy || !out24)
         return HAB_ERR_ARG;
     ppo_loss_kernel<<<1, 1024, 0, stream>>>(values, logp, entropy, old_logp, adv, old_values, returns, rows, B, clip_param,
                                             value_loss_coef, entropy_coef, use_clipped_value_loss, d_value, d_logp,
-                                            d_entropy, out20, is_coeffs, is_stale, policy_version, (long long)current_policy_version,
+                                            d_entropy, out24, is_coeffs, is_stale, policy_version, (long long)current_policy_version,
                                             log_alpha, entropy_threshold);
     HAB_LAUNCH_CHECK();
     return HAB_OK;

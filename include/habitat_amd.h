@@ -406,16 +406,18 @@ int hab_ppo_loss(const float* values, const float* logp, const float* entropy, c
 
 /* The same with VER's importance weights and learner statistics (rl/ppo/ppo.py:226-231,262-263,285-299): every per-frame loss term
  * is multiplied by min(is_coeffs, 1) before the batch mean.  is_coeffs / is_stale / policy_version are storage buffers gathered
- * through rows (each nullable).  out20 = out12 + {[12] reserved (grad norm), ver_is_coeffs min/mean/max, fraction_stale,
- * policy_version_difference min/mean/max}.
+ * through rows (each nullable).  out24: 24 floats = out12 + {[12] reserved (grad norm), [13..15] ver_is_coeffs min/mean/max,
+ * [16] fraction_stale, [17..19] policy_version_difference min/mean/max, [20] [21] see log_alpha, [22] [23] reserved}.  [13..19] are written
+ * when at least one of the three is given (the statistics of one that is not: +inf / 0 / -inf, fraction 0), [20] [21] when log_alpha is;
+ * reserved and unwritten entries are left alone.
  * log_alpha (nullable, device scalar): adaptive entropy penalty (LagrangeInequalityCoefficient, utils/common.py:749-806; ppo.py:85-96,
  * 236-239): the entropy coefficient is exp(*log_alpha) instead of entropy_coef, the total loss carries alpha * (threshold - [ent]) -
- * [alpha] * ent, and out[20] = d loss / d log_alpha, out[21] = alpha (out must then hold 24 floats). */
+ * [alpha] * ent, and out24[20] = d loss / d log_alpha, out24[21] = alpha. */
 int hab_ppo_loss_ver(const float* values, const float* logp, const float* entropy, const float* old_logp, const float* adv,
                      const float* old_values, const float* returns, const int* rows, int B, float clip_param, float value_loss_coef,
                      float entropy_coef, int use_clipped_value_loss, const float* is_coeffs, const uint8_t* is_stale,
                      const int64_t* policy_version, int64_t current_policy_version, const float* log_alpha, float entropy_threshold,
-                     float* d_value, float* d_logp, float* d_entropy, float* out20, hipStream_t stream);
+                     float* d_value, float* d_logp, float* d_entropy, float* out24, hipStream_t stream);
 /* Adam step (torch.optim.Adam arithmetic, gradient first multiplied by grad_scale) + projection into [log_alpha_min, log_alpha_max] of
  * the adaptive entropy coefficient (rl/ppo/ppo.py:112-137,373-375). */
 int hab_lagrange_adam_step(float* log_alpha, float* exp_avg, float* exp_avg_sq, const float* grad, float grad_scale, float lr, float beta1,
@@ -436,7 +438,8 @@ int hab_ver_is_coeffs(const int64_t* environment_ids, int n, int num_envs, int n
 
 /* nn.utils.clip_grad_norm_ + optim.Adam(foreach).step (rl/ppo/ppo.py:347-371,112-137,257) over the
  * flat parameter arena.  grads are first multiplied by grad_scale (1/world_size after a sum
- * all-reduce).  scratch_partials: >= 1024 doubles.  step counts from 1.  All pointers 16-B aligned. */
+ * all-reduce).  scratch_partials: scratch_len >= 1 doubles, of which the first min(scratch_len, 1024) are used (fewer partials only
+ * mean fewer blocks in the norm pass).  max_grad_norm <= 0: no clipping.  step counts from 1.  The four float arrays 16-B aligned. */
 int hab_clip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n,
                        double* scratch_partials, int scratch_len, float grad_scale, float max_grad_norm, float lr,
                        float beta1, float beta2, float eps, int step, float* grad_norm_out, hipStream_t stream);
