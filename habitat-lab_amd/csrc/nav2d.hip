@@ -165,7 +165,9 @@ __device__ inline bool geo_visible(const GeoBox* boxes, int K, float ax, float a
 // visibility boxes are computed once into registers: the loops over k are unrolled over MAX_K with the uniform k < K as a guard, so
 // every index is static, and a visibility test is straight-line arithmetic over the boxes with no load and no branch in it: the
 // 64 envs of a workgroup are one wave, so a test that reads a box through the state pointer costs a memory latency each time.
-__device__ inline float geo_query(const Nav2DState& s, const GeoField& g, int K) {
+// p = (px, py) is the point the distance is taken from: the agent's position for the step kernels, a candidate's target for the
+// follower.
+__device__ inline float geo_query(const Nav2DState& s, const GeoField& g, int K, float px, float py) {
     float X0[MAX_K], Y0[MAX_K], X1[MAX_K], Y1[MAX_K];
     GeoBox box[MAX_K];
 #pragma unroll
@@ -175,7 +177,6 @@ __device__ inline float geo_query(const Nav2DState& s, const GeoField& g, int K)
             box[k] = geo_box(s, k);
         }
     }
-    const float px = s.px, py = s.py;
     auto sees = [&](float x, float y) {
         bool blocked = false;
 #pragma unroll
@@ -256,7 +257,7 @@ __device__ inline void end_step(Nav2DState& s, bool stop, float success_dist, fl
     float d = dist(s.px, s.py, s.gx, s.gy);
     if constexpr (GEO) {
         if (geo->reachable) {
-            d = geo_query(s, *geo, K);
+            d = geo_query(s, *geo, K, s.px, s.py);
             if (!(d < INFINITY)) { d = s.d_prev; geo->lost_steps += 1; }
         }
     }
@@ -458,6 +459,84 @@ nav2d_geo_build_kernel(char* __restrict__ states, size_t state_stride, GeoField*
         geo[n].lost_steps = 0;
         for (int z = 0; z < 5; ++z) geo[n].zero[z] = 0;
         if (reachable) s.d_start = s.d_prev = v;
+    }
+}
+
+// ---- the shortest-path follower of Nav2D-v0 and Nav2DVel-v0 (specification: tests/nav2d_follow_reference.py) -----------------------
+// What turns the rule's answer into the task's action.  `go` is status GO, `delta` the signed number of heading quanta to the winner.
+struct FollowDiscrete {
+    using Action = int64_t;
+    __device__ Action operator()(bool go, int delta) const { return !go ? 0 : delta == 0 ? 1 : delta > 0 ? 2 : 3; }
+};
+struct FollowVelocity {
+    using Action = float2;
+    int max_turn;
+    __device__ Action operator()(bool go, int delta) const {
+        if (!go) return make_float2(-1.0f, 0.0f);
+        if (abs(delta) <= max_turn) return make_float2(1.0f, __fdiv_rn((float)delta, (float)max_turn));  // decodes to l = 0.25, dh = delta
+        return make_float2(-1.0f, delta > 0 ? 1.0f : -1.0f);                                             // a turn in place of max_turn
+    }
+};
+
+// One env per 64-thread workgroup (one wavefront), selected by `mask` (NULL: all); lane = candidate heading, the lanes stride over
+// the nh headings by 64.  State and field are read only, through pointers that are uniform over the wave.  A lane's candidate is the
+// target p' of a forward at its heading; where p' is free it runs the straight-line query of the step kernels at p'.  A valid
+// candidate (v finite and below D_PREV) has the 64-bit key v's bits << 32 | |delta| << 1 | (delta < 0): v is not negative, so the
+// bit patterns order like the floats, and the least key is the lowest value, then the fewest turns, then left.  One wave-wide
+// minimum; lane 0 writes the action, next_d and status.
+template <class Writer>
+__global__ void __launch_bounds__(64)
+nav2d_follow_kernel(const char* __restrict__ states, size_t state_stride, const GeoField* __restrict__ geo, const float* __restrict__ dirs,
+                    const uint8_t* __restrict__ mask, typename Writer::Action* __restrict__ actions, float* __restrict__ next_d,
+                    int32_t* __restrict__ status, int K, int nh, Writer writer) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    if (mask && !mask[n]) return;
+    const Nav2DState& s = *reinterpret_cast<const Nav2DState*>(states + (size_t)n * state_stride);
+    const GeoField& g = geo[n];
+    const float d_prev = s.d_prev;
+    int st, delta = 0;
+    float nd = INFINITY;
+    if (!g.reachable) {
+        st = HAB_NAV2D_FOLLOW_UNREACHABLE;
+    } else if (d_prev < 0.2f) {
+        st = HAB_NAV2D_FOLLOW_ARRIVED;
+        nd = d_prev;
+    } else {
+        const float px = s.px, py = s.py;
+        const int heading = s.heading;
+        constexpr unsigned long long NONE = ~0ull;
+        unsigned long long key = NONE;
+        for (int h0 = 0; h0 < nh; h0 += 64) {  // uniform over the wave
+            const int h = h0 + lane;
+            if (h >= nh) continue;
+            const float nx = px + FORWARD * dirs[2 * h], ny = py + FORWARD * dirs[2 * h + 1];
+            if (!is_free(nx, ny, s, K)) continue;
+            const float v = geo_query(s, g, K, nx, ny);
+            if (!(v < INFINITY && v < d_prev)) continue;
+            int d = (h - heading) % nh;
+            if (d < 0) d += nh;
+            if (2 * d > nh) d -= nh;  // the half turn stays positive: left
+            const unsigned long long k = ((unsigned long long)__float_as_uint(v) << 32) | ((unsigned long long)abs(d) << 1) | (d < 0 ? 1ull : 0ull);
+            key = k < key ? k : key;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long other = __shfl_xor(key, o);
+            key = other < key ? other : key;
+        }
+        if (key == NONE) {
+            st = HAB_NAV2D_FOLLOW_STUCK;
+        } else {
+            st = HAB_NAV2D_FOLLOW_GO;
+            nd = __uint_as_float((uint32_t)(key >> 32));
+            const int turns = (int)((uint32_t)key >> 1);
+            delta = (key & 1ull) ? -turns : turns;
+        }
+    }
+    if (lane == 0) {
+        actions[n] = writer(st == HAB_NAV2D_FOLLOW_GO, delta);
+        if (next_d) next_d[n] = nd;
+        if (status) status[n] = st;
     }
 }
 
@@ -1927,6 +2006,37 @@ extern "C" int hab_nav2d_vel_step_geo(void* state, void* geo, const float* dirs,
     return vel_step<true>({state, geo, dirs, ray, col_cos, tanv, actions, mask, rgb, depth, goal, nullptr, reward, not_done, measure_sums,
                            seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream},
                           max_turn_steps, stop_turn_steps, min_abs_lin_speed, allow_sliding);
+}
+
+// The shortest-path follower: the checks of the field entries, then those of its own arguments; an action row is read and written
+// as one word of its size.
+template <class Writer>
+static int follow(const void* state, size_t state_stride_bytes, const void* geo, const float* dirs, const uint8_t* mask,
+                  typename Writer::Action* actions, float* next_d, int32_t* status, int N, int num_obstacles, int num_headings,
+                  hipStream_t stream, Writer writer) {
+    const int rc = check_geo_args(state, state_stride_bytes, geo, N, num_obstacles);
+    if (rc != HAB_OK) return rc;
+    if (!dirs || ((uintptr_t)dirs & 3) || !actions || ((uintptr_t)actions & (sizeof(typename Writer::Action) - 1))) return HAB_ERR_ARG;
+    if (((uintptr_t)next_d & 3) || ((uintptr_t)status & 3) || num_headings <= 0) return HAB_ERR_ARG;
+    nav2d_follow_kernel<Writer><<<N, 64, 0, stream>>>((const char*)state, state_stride_bytes, (const GeoField*)geo, dirs, mask, actions,
+                                                      next_d, status, num_obstacles, num_headings, writer);
+    HAB_LAUNCH_CHECK();
+    return HAB_OK;
+}
+
+extern "C" int hab_nav2d_follow(const void* state, size_t state_stride_bytes, const void* geo, const float* dirs, const uint8_t* mask,
+                                int64_t* actions, float* next_d, int32_t* status, int N, int num_obstacles, int num_headings,
+                                hipStream_t stream) {
+    return follow(state, state_stride_bytes, geo, dirs, mask, actions, next_d, status, N, num_obstacles, num_headings, stream,
+                  FollowDiscrete{});
+}
+
+extern "C" int hab_nav2d_vel_follow(const void* state, size_t state_stride_bytes, const void* geo, const float* dirs,
+                                    const uint8_t* mask, float* actions, float* next_d, int32_t* status, int N, int num_obstacles,
+                                    int num_headings, int max_turn_steps, hipStream_t stream) {
+    if (num_headings <= 0 || max_turn_steps < 1 || max_turn_steps > num_headings / 2) return HAB_ERR_ARG;
+    return follow(state, state_stride_bytes, geo, dirs, mask, (float2*)actions, next_d, status, N, num_obstacles, num_headings, stream,
+                  FollowVelocity{max_turn_steps});
 }
 
 extern "C" int hab_nav2d_obj_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,

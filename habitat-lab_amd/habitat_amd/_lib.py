@@ -72,6 +72,8 @@ SIGNATURES = {
     "hab_nav2d_geo_build": (c_int, [vp, c_size_t, vp, vp, c_int, c_int, c_int, vp]),
     "hab_nav2d_step_geo": (c_int, [vp] * 14 + [c_uint32, c_uint32] + [c_int] * 7 + [vp]),
     "hab_nav2d_vel_step_geo": (c_int, [vp] * 14 + [c_uint32, c_uint32] + [c_int] * 8 + [c_float, c_int, c_int, vp]),
+    "hab_nav2d_follow": (c_int, [vp, c_size_t] + [vp] * 6 + [c_int] * 3 + [vp]),
+    "hab_nav2d_vel_follow": (c_int, [vp, c_size_t] + [vp] * 6 + [c_int] * 4 + [vp]),
     "hab_nav2d_obj_state_bytes": (c_int, []),
     "hab_nav2d_obj_step": (c_int, [vp] * 17 + [c_uint32, c_uint32] + [c_int] * 10 + [vp]),
     "hab_nav2d_obj_geo_bytes": (c_int, []),

@@ -354,6 +354,10 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
     _entries = ("hab_nav2d_step", "hab_nav2d_step_geo")
     _geo_entry = None
     _action_dtype, _action_text = torch.int64, "int64 device tensor of shape (N,) or (N, 1)"
+    # the library's shortest-path follower of the task (`follower_actions`), None where the task has none, and the shape of its
+    # actions after the env count
+    _follow_entry = "hab_nav2d_follow"
+    _follow_shape = ()
 
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
                  use_depth: bool = True, num_actions: int = 4, device="cuda", num_obstacles: int = 3, turn_angle: int = 10,
@@ -418,6 +422,43 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
         if actions is None:
             raise _lib.HabError(f"{self._name}: step_into_obs needs the actions of the step")
         self._launch(obs, reward, not_done, actions, mask, 1)
+
+    # ---- the shortest-path follower -------------------------------------------------------------
+    def _follow_parameters(self):
+        """The follower entry's arguments between num_headings and the stream."""
+        return ()
+
+    def follower_actions(self, out=None, mask=None, next_d=None, status=None):
+        """The actions of the shortest-path follower (habitat's ShortestPathFollower.get_next_action for every env at once): a greedy
+        step down the geodesic distance, computed on the device from the env's own records, in the dtype and shape `step_into_obs`
+        takes.  tests/nav2d_follow_reference.py states the rule; the kernel matches it bit for bit.  In short: STOP where the episode
+        is unreachable, where D_PREV < 0.2 (the success test of the stop then holds) and where no forward of 0.25 m at any heading
+        lowers the distance (STUCK); else the heading whose forward leads to the lowest distance, then the fewest turns, then left:
+        forward if the agent faces it, else a turn towards it.
+        `out` receives the actions (allocated if None) and is returned; `mask` (uint8 (N,)) selects envs, the outputs of the others
+        stay untouched; `next_d` (float32 (N,)) receives the distance the env will report after the step of a GO (D_PREV where
+        ARRIVED, +inf otherwise), `status` (int32 (N,)) the code 0 GO, 1 ARRIVED, 2 UNREACHABLE, 3 STUCK.  Only Nav2D-v0 and
+        Nav2DVel-v0 in the geodesic distance mode have a follower."""
+        if self._follow_entry is None:
+            raise _lib.HabError(f"{self._name}: the task has no shortest-path follower (Nav2D-v0 and Nav2DVel-v0 have one)")
+        if self.distance != "geodesic":
+            raise _lib.HabError(f"{self._name}: the shortest-path follower needs `distance_to_goal: geodesic`, the env has "
+                                f"{self.distance!r}")
+        N, dev = self.num_envs, self._state.device
+        if out is None:
+            out = torch.zeros((N, *self._follow_shape), dtype=self._action_dtype, device=dev)
+        wanted = ((out, self._action_dtype, self._actions_shaped, "out"), (mask, torch.uint8, None, "mask"),
+                  (next_d, torch.float32, None, "next_d"), (status, torch.int32, None, "status"))
+        for t, dtype, shaped, what in wanted:
+            if t is None:
+                continue
+            ok = shaped(t) if shaped else tuple(t.shape) == (N,)
+            if not (ok and t.dtype == dtype and t.is_contiguous() and t.device == dev):
+                raise _lib.HabError(f"{self._name}: follower_actions: `{what}` must be a contiguous {dtype} tensor for {N} envs on {dev}")
+        check(getattr(_lib.lib(), self._follow_entry)(ptr(self._state), self._state.shape[1] * 4, ptr(self._geo), ptr(self._tables[0]),
+                                                      ptr(mask), ptr(out), ptr(next_d), ptr(status), N, self.num_obstacles,
+                                                      self.num_headings, *self._follow_parameters(), stream_ptr()), self._follow_entry)
+        return out
 
     def reset_into(self, rgb, depth, goal):
         self.reset_into_obs({k: v for k, v in (("rgb", rgb), ("depth", depth), (GOAL_UUID, goal)) if v is not None})
@@ -532,6 +573,7 @@ class Nav2DVelVectorEnv(Nav2DVectorEnv):
 
     _name = "Nav2DVel"
     _entries = ("hab_nav2d_vel_step", "hab_nav2d_vel_step_geo")
+    _follow_entry, _follow_shape = "hab_nav2d_vel_follow", (2,)
     _action_dtype, _action_text = torch.float32, "float32 device tensor of shape (N, 2)"
 
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
@@ -558,6 +600,9 @@ class Nav2DVelVectorEnv(Nav2DVectorEnv):
 
     def _task_parameters(self):
         return self.max_turn_steps, self.stop_turn_steps, self.min_abs_lin_speed, int(self.allow_sliding)
+
+    def _follow_parameters(self):
+        return (self.max_turn_steps,)
 
     def async_step_at(self, index_env: int, action) -> None:
         if isinstance(action, dict):
@@ -638,6 +683,7 @@ class Nav2DObjVectorEnv(Nav2DVectorEnv):
 
     _name = "Nav2DObj"
     _entries = ("hab_nav2d_obj_step", "hab_nav2d_obj_step_geo")
+    _follow_entry = None  # no shortest-path follower: see Nav2DVectorEnv.follower_actions
     _sensor_set = "objectnav"
     _renders_without_rgb_depth = True
     _state_bytes = "hab_nav2d_obj_state_bytes"
@@ -757,6 +803,7 @@ class Nav2DRearrVectorEnv(Nav2DVectorEnv):
 
     _name = "Nav2DRearr"
     _entries = ("hab_nav2d_rearr_step",)
+    _follow_entry = None  # no shortest-path follower: see Nav2DVectorEnv.follower_actions
     _geo_entry = "hab_nav2d_rearr_step_geo"
     _geo_bytes = "hab_nav2d_rearr_geo_bytes"
     _sensor_set = "rearrange"
@@ -984,6 +1031,7 @@ class Nav2DSocialVectorEnv(Nav2DVectorEnv):
 
     _name = "Nav2DSocial"
     _entries = ("hab_nav2d_social_step",)
+    _follow_entry = None  # no shortest-path follower: see Nav2DVectorEnv.follower_actions
     _sensor_set = "social"
     _state_bytes = "hab_nav2d_social_state_bytes"
     _action_dtype, _action_text = torch.float32, "float32 device tensor of shape (N, 2)"

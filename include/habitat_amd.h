@@ -138,6 +138,33 @@ int hab_nav2d_vel_step_geo(void* state /*N,HAB_NAV2D_STATE_BYTES*/, void* geo /*
                            uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings, int max_episode_steps,
                            int max_turn_steps, int stop_turn_steps, float min_abs_lin_speed, int allow_sliding, int advance,
                            hipStream_t stream);
+/* The shortest-path follower of Nav2D-v0 and Nav2DVel-v0 in geodesic mode (definition: tests/nav2d_follow_reference.py, bit-identical
+ * to it on every output): the action of a greedy step down the geodesic distance, from the records the entries above keep.  `state`
+ * and `geo` are read and not written: `state` as hab_nav2d_geo_build takes it (any stride >= HAB_NAV2D_STATE_BYTES, a multiple of
+ * 4), `geo` the field records, `dirs` the (num_headings, 2) heading table of the step entries.  Per env that `mask` selects (NULL =
+ * all; the outputs of the others stay untouched): REACHABLE == 0 gives UNREACHABLE; else D_PREV < 0.2 gives ARRIVED; else every
+ * heading h is a candidate with the target p' = p + 0.25 * dirs[h] of a forward, valid iff p' is free and v = geo(p') is finite and
+ * below D_PREV; the winner has the lowest v, then the fewest turns delta from the HEADING word (signed, the half turn counts as
+ * left), then left; no valid candidate gives STUCK.  `status` (NULL: not written) gets the code below, `next_d` (NULL: not written)
+ * the winner's v (GO), D_PREV (ARRIVED) or +inf.  actions: hab_nav2d_follow writes int64 -- 0 STOP unless GO, else 1 MOVE_FORWARD at
+ * delta == 0, 2 TURN_LEFT at delta > 0, 3 TURN_RIGHT -- and hab_nav2d_vel_follow one 8-byte aligned f32 row (a_lin, a_ang): (-1, 0)
+ * unless GO, else (1, delta / max_turn_steps) where |delta| <= max_turn_steps (hab_nav2d_vel_step decodes it to a step of 0.25 m
+ * after a turn of delta), else (-1, +-1), a turn in place towards delta.  A forward it asks for is never refused by the step, and
+ * the step's distance after it is next_d.  Refused: what hab_nav2d_geo_build refuses (state or geo NULL or misaligned, the stride,
+ * N <= 0, num_obstacles outside 0..HAB_NAV2D_MAX_OBSTACLES); dirs or actions NULL or misaligned; next_d or status misaligned;
+ * num_headings <= 0; max_turn_steps outside 1..num_headings / 2. */
+#define HAB_NAV2D_FOLLOW_GO 0
+#define HAB_NAV2D_FOLLOW_ARRIVED 1
+#define HAB_NAV2D_FOLLOW_UNREACHABLE 2
+#define HAB_NAV2D_FOLLOW_STUCK 3
+int hab_nav2d_follow(const void* state, size_t state_stride_bytes, const void* geo /*N,HAB_NAV2D_GEO_BYTES*/,
+                     const float* dirs /*num_headings,2*/, const uint8_t* mask /*N or NULL*/, int64_t* actions /*N*/,
+                     float* next_d /*N or NULL*/, int32_t* status /*N or NULL*/, int N, int num_obstacles, int num_headings,
+                     hipStream_t stream);
+int hab_nav2d_vel_follow(const void* state, size_t state_stride_bytes, const void* geo /*N,HAB_NAV2D_GEO_BYTES*/,
+                         const float* dirs /*num_headings,2*/, const uint8_t* mask /*N or NULL*/, float* actions /*N,2*/,
+                         float* next_d /*N or NULL*/, int32_t* status /*N or NULL*/, int N, int num_obstacles, int num_headings,
+                         int max_turn_steps, hipStream_t stream);
 /* Nav2DObj-v0: the same arena, rectangles, start, heading and forward step with num_objects (1..HAB_NAV2D_MAX_OBJECTS) cylinders of
  * radius 0.3 m, each of one of num_categories (1..HAB_NAV2D_MAX_CATEGORIES) categories; the agent is told a category and has to
  * STOP within 1 m of the nearest centre of it (definition: habitat_amd/common/env_factory.py, Nav2DObjVectorEnv; bit-identical to
