@@ -166,8 +166,9 @@ __device__ inline bool geo_visible(const GeoBox* boxes, int K, float ax, float a
 // every index is static, and a visibility test is straight-line arithmetic over the boxes with no load and no branch in it: the
 // 64 envs of a workgroup are one wave, so a test that reads a box through the state pointer costs a memory latency each time.
 // p = (px, py) is the point the distance is taken from: the agent's position for the step kernels, a candidate's target for the
-// follower.
-__device__ inline float geo_query(const Nav2DState& s, const GeoField& g, int K, float px, float py) {
+// follower.  T = (tx, ty) is the target and D[GEO_NODES] the field towards it: the record's goal and GeoField::D for Nav2D-v0 and
+// Nav2DVel-v0 (the form below), the goal with DG or the object's place with DO for the rearrangement oracle.
+__device__ inline float geo_query(const Nav2DState& s, const float* __restrict__ D, int K, float px, float py, float tx, float ty) {
     float X0[MAX_K], Y0[MAX_K], X1[MAX_K], Y1[MAX_K];
     GeoBox box[MAX_K];
 #pragma unroll
@@ -184,13 +185,13 @@ __device__ inline float geo_query(const Nav2DState& s, const GeoField& g, int K,
             if (k < K) blocked |= geo_blocked(box[k], px, py, x, y);
         return !blocked;
     };
-    float best = sees(s.gx, s.gy) ? dist(px, py, s.gx, s.gy) : INFINITY;
+    float best = sees(tx, ty) ? dist(px, py, tx, ty) : INFINITY;
 #pragma unroll
     for (int k = 0; k < MAX_K; ++k) {
         if (k < K) {
 #pragma unroll 1
             for (int j = 0; j < 4; ++j) {
-                const float Di = g.D[4 * k + j];
+                const float Di = D[4 * k + j];
                 if (!(Di < INFINITY)) continue;
                 const float x = (j & 1) ? X1[k] : X0[k], y = (j & 2) ? Y1[k] : Y0[k];
                 if (sees(x, y)) best = fminf(best, dist(px, py, x, y) + Di);
@@ -198,6 +199,9 @@ __device__ inline float geo_query(const Nav2DState& s, const GeoField& g, int K,
         }
     }
     return best;
+}
+__device__ inline float geo_query(const Nav2DState& s, const GeoField& g, int K, float px, float py) {
+    return geo_query(s, g.D, K, px, py, s.gx, s.gy);
 }
 
 // A new episode's world.  GOAL (Nav2D-v0, Nav2DVel-v0): rectangles, their colours, the start, the goal, the heading, the distances and
@@ -478,6 +482,28 @@ struct FollowVelocity {
     }
 };
 
+// The turns from `heading` to h as a key that orders like (|delta|, delta < 0): delta = (h - heading) mod nh, minus nh where
+// 2 * delta > nh, so the half turn stays positive (left); and the delta of such a key.
+__device__ inline uint32_t turn_key(int h, int heading, int nh) {
+    int d = (h - heading) % nh;
+    if (d < 0) d += nh;
+    if (2 * d > nh) d -= nh;
+    return ((uint32_t)abs(d) << 1) | (d < 0 ? 1u : 0u);
+}
+__device__ inline int turn_key_delta(uint32_t k) {
+    const int turns = (int)(k >> 1);
+    return (k & 1u) ? -turns : turns;
+}
+// The least of the wave's 64-bit keys, on every lane.
+__device__ inline unsigned long long wave_min_key(unsigned long long key) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(key, o);
+        key = other < key ? other : key;
+    }
+    return key;
+}
+
 // One env per 64-thread workgroup (one wavefront), selected by `mask` (NULL: all); lane = candidate heading, the lanes stride over
 // the nh headings by 64.  State and field are read only, through pointers that are uniform over the wave.  A lane's candidate is the
 // target p' of a forward at its heading; where p' is free it runs the straight-line query of the step kernels at p'.  A valid
@@ -513,24 +539,16 @@ nav2d_follow_kernel(const char* __restrict__ states, size_t state_stride, const 
             if (!is_free(nx, ny, s, K)) continue;
             const float v = geo_query(s, g, K, nx, ny);
             if (!(v < INFINITY && v < d_prev)) continue;
-            int d = (h - heading) % nh;
-            if (d < 0) d += nh;
-            if (2 * d > nh) d -= nh;  // the half turn stays positive: left
-            const unsigned long long k = ((unsigned long long)__float_as_uint(v) << 32) | ((unsigned long long)abs(d) << 1) | (d < 0 ? 1ull : 0ull);
+            const unsigned long long k = ((unsigned long long)__float_as_uint(v) << 32) | turn_key(h, heading, nh);
             key = k < key ? k : key;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long other = __shfl_xor(key, o);
-            key = other < key ? other : key;
-        }
+        key = wave_min_key(key);
         if (key == NONE) {
             st = HAB_NAV2D_FOLLOW_STUCK;
         } else {
             st = HAB_NAV2D_FOLLOW_GO;
             nd = __uint_as_float((uint32_t)(key >> 32));
-            const int turns = (int)((uint32_t)key >> 1);
-            delta = (key & 1ull) ? -turns : turns;
+            delta = turn_key_delta((uint32_t)key);
         }
     }
     if (lane == 0) {
@@ -1391,6 +1409,105 @@ nav2d_rearr_geo_step_kernel(Nav2DRearrState* __restrict__ states, RearrGeoField*
     if (lane == 0) rearr_write_sensors(rec, dirs, obj_start, obj_goal, is_holding, n);
 }
 
+// ---- the pick-and-place oracle of Nav2DRearr-v0 in geodesic mode (specification: tests/nav2d_rearr_oracle_reference.py) -------------
+// One env per 64-thread workgroup (one wavefront), selected by `mask` (NULL: all); lane = candidate heading, the lanes stride over
+// the nh headings by 64, as in nav2d_follow_kernel.  State and field are read only, through pointers that are uniform over the wave,
+// and so are `holding` and "in reach": an env runs one of three paths.
+//   * Not holding, in reach: the dot test of rearr_pick per heading; the fewest turns win.
+//   * Not holding, out of reach: the follower's forward search towards o over DO below the term a, with the task's free test.
+//   * Holding: the place search -- q of rearr_place per heading, eligible where the PLACE would be accepted and w = geo_g(q) < 0.5;
+//     the fewest turns win -- and, where no heading is eligible, the forward search towards g over DG below the term b.
+// Both forward searches are one piece of code with a uniform field pointer, target and bound, so a lane runs at most two
+// straight-line queries per pass of the lanes: one of the place search, one of the forward search.  The forward search has the
+// follower's 64-bit key; the two turn-only searches have the turn key in the high word and w's bits (0 for the dot test) in the low
+// word, which the minimum carries along for next_d.  One wave-wide minimum per search; lane 0 writes action, next_d and status.
+__global__ void __launch_bounds__(64)
+nav2d_rearr_oracle_kernel(const char* __restrict__ states, size_t state_stride, const RearrGeoField* __restrict__ geo,
+                          const float* __restrict__ dirs, const uint8_t* __restrict__ mask, int64_t* __restrict__ actions,
+                          float* __restrict__ next_d, int32_t* __restrict__ status, int K, int nh) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    if (mask && !mask[n]) return;
+    const Nav2DRearrState& r = *reinterpret_cast<const Nav2DRearrState*>(states + (size_t)n * state_stride);
+    const Nav2DState& s = r.base;
+    const RearrGeoField& g = geo[n];
+    constexpr unsigned long long NONE = ~0ull;
+    const float px = s.px, py = s.py, ta = g.a, tb = g.b;
+    const int heading = s.heading;
+    const bool holding = r.holding != 0;
+    int st = HAB_NAV2D_ORACLE_STUCK, delta = 0;
+    float nd = INFINITY;
+    const float* D = nullptr;  // the forward search's field: set where the env's path comes to it
+    float tx = 0.0f, ty = 0.0f, bound = 0.0f;
+    if (!g.reachable) {
+        st = HAB_NAV2D_ORACLE_UNREACHABLE;
+    } else if (!holding && tb < REARR_SUCCESS) {
+        st = HAB_NAV2D_ORACLE_ARRIVED;
+        nd = tb;
+    } else if (!holding && dist(px, py, r.ox, r.oy) < REARR_REACH) {
+        const float dx = r.ox - px, dy = r.oy - py;
+        unsigned long long key = NONE;
+        for (int h0 = 0; h0 < nh; h0 += 64) {  // uniform over the wave
+            const int h = h0 + lane;
+            if (h >= nh) continue;
+            if (!(dx * dirs[2 * h] + dy * dirs[2 * h + 1] > 0.0f)) continue;
+            const unsigned long long k = (unsigned long long)turn_key(h, heading, nh) << 32;
+            key = k < key ? k : key;
+        }
+        key = wave_min_key(key);
+        if (key != NONE) {
+            delta = turn_key_delta((uint32_t)(key >> 32));
+            st = delta == 0 ? HAB_NAV2D_ORACLE_PICK : HAB_NAV2D_ORACLE_GO;
+            nd = delta == 0 ? 0.0f : ta;
+        }
+    } else if (!holding) {
+        D = g.DO; tx = r.ox; ty = r.oy; bound = ta;
+    } else {
+        unsigned long long key = NONE;
+        for (int h0 = 0; h0 < nh; h0 += 64) {
+            const int h = h0 + lane;
+            if (h >= nh) continue;
+            const float qx = px + REARR_ARM * dirs[2 * h], qy = py + REARR_ARM * dirs[2 * h + 1];
+            if (!(qx >= OBJ_LO && qx <= OBJ_HI && qy >= OBJ_LO && qy <= OBJ_HI) || in_grown_rect(qx, qy, s, K)) continue;
+            const float w = geo_query(s, g.DG, K, qx, qy, s.gx, s.gy);
+            if (!(w < INFINITY && w < REARR_SUCCESS)) continue;
+            const unsigned long long k = ((unsigned long long)turn_key(h, heading, nh) << 32) | __float_as_uint(w);
+            key = k < key ? k : key;
+        }
+        key = wave_min_key(key);
+        if (key != NONE) {
+            delta = turn_key_delta((uint32_t)(key >> 32));
+            st = delta == 0 ? HAB_NAV2D_ORACLE_PLACE : HAB_NAV2D_ORACLE_GO;
+            nd = delta == 0 ? __uint_as_float((uint32_t)key) : tb;
+        } else {
+            D = g.DG; tx = s.gx; ty = s.gy; bound = tb;
+        }
+    }
+    if (D) {
+        unsigned long long key = NONE;
+        for (int h0 = 0; h0 < nh; h0 += 64) {
+            const int h = h0 + lane;
+            if (h >= nh) continue;
+            const float nx = px + FORWARD * dirs[2 * h], ny = py + FORWARD * dirs[2 * h + 1];
+            if (!rearr_is_free(nx, ny, r, K)) continue;
+            const float v = geo_query(s, D, K, nx, ny, tx, ty);
+            if (!(v < INFINITY && v < bound)) continue;
+            const unsigned long long k = ((unsigned long long)__float_as_uint(v) << 32) | turn_key(h, heading, nh);
+            key = k < key ? k : key;
+        }
+        key = wave_min_key(key);
+        if (key != NONE) {
+            st = HAB_NAV2D_ORACLE_GO;
+            delta = turn_key_delta((uint32_t)key);
+            nd = delta == 0 ? __uint_as_float((uint32_t)(key >> 32)) : bound;  // a turn leaves the leg's term as it is
+        }
+    }
+    if (lane == 0) {
+        actions[n] = st == HAB_NAV2D_ORACLE_GO ? FollowDiscrete{}(true, delta) : st == HAB_NAV2D_ORACLE_PICK ? 4 : st == HAB_NAV2D_ORACLE_PLACE ? 5 : 0;
+        if (next_d) next_d[n] = nd;
+        if (status) status[n] = st;
+    }
+}
+
 // ---- Nav2DSocial-v0 (Nav2DSocialVectorEnv; specification: tests/nav2d_social_reference.py) ------------------------------------------
 // A person walks about Nav2D-v0's world, from waypoint to waypoint along the shortest paths of Nav2D-v0's graph, and the agent has to
 // find and then to follow them under Nav2DVel-v0's velocity control.  The graph is planned with here: the person's hop is the
@@ -2211,6 +2328,22 @@ extern "C" int hab_nav2d_rearr_vel_step_geo(void* state, void* geo, const float*
                                  advance, stream},
                                 obj_start, obj_goal, is_holding, start_holding, max_turn_steps, stop_turn_steps, min_abs_lin_speed,
                                 allow_sliding);
+}
+
+// The pick-and-place oracle: the checks of hab_nav2d_rearr_geo_build for state, stride, field, N and K, then those of its own
+// arguments.
+extern "C" int hab_nav2d_rearr_oracle(const void* state, size_t state_stride_bytes, const void* geo, const float* dirs,
+                                      const uint8_t* mask, int64_t* actions, float* next_d, int32_t* status, int N, int num_obstacles,
+                                      int num_headings, hipStream_t stream) {
+    const int rc = check_geo_args(state, state_stride_bytes, geo, N, num_obstacles);
+    if (rc != HAB_OK) return rc;
+    if (state_stride_bytes < sizeof(Nav2DRearrState)) return HAB_ERR_ARG;
+    if (!dirs || ((uintptr_t)dirs & 3) || !actions || ((uintptr_t)actions & 7)) return HAB_ERR_ARG;
+    if (((uintptr_t)next_d & 3) || ((uintptr_t)status & 3) || num_headings <= 0) return HAB_ERR_ARG;
+    nav2d_rearr_oracle_kernel<<<N, 64, 0, stream>>>((const char*)state, state_stride_bytes, (const RearrGeoField*)geo, dirs, mask, actions,
+                                                    next_d, status, num_obstacles, num_headings);
+    HAB_LAUNCH_CHECK();
+    return HAB_OK;
 }
 
 extern "C" int hab_nav2d_social_state_bytes(void) { return (int)sizeof(Nav2DSocialState); }

@@ -86,6 +86,7 @@ SIGNATURES = {
     "hab_nav2d_rearr_geo_build": (c_int, [vp, c_size_t, vp, vp, c_int, c_int, c_int, c_int, vp]),
     "hab_nav2d_rearr_step_geo": (c_int, [vp] * 16 + [c_uint32, c_uint32] + [c_int] * 8 + [vp]),
     "hab_nav2d_rearr_vel_step_geo": (c_int, [vp] * 16 + [c_uint32, c_uint32] + [c_int] * 9 + [c_float, c_int, c_int, vp]),
+    "hab_nav2d_rearr_oracle": (c_int, [vp, c_size_t] + [vp] * 6 + [c_int] * 3 + [vp]),
     "hab_nav2d_social_state_bytes": (c_int, []),
     "hab_nav2d_social_step": (c_int, [vp] * 14 + [c_uint32, c_uint32] + [c_int] * 8 + [c_float, c_int, c_float, c_int, c_int, vp]),
     "hab_obs_resize_crop": (c_int, [vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp]),

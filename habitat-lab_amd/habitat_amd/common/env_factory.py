@@ -444,9 +444,15 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
         if self.distance != "geodesic":
             raise _lib.HabError(f"{self._name}: the shortest-path follower needs `distance_to_goal: geodesic`, the env has "
                                 f"{self.distance!r}")
+        return self._advised_actions(self._follow_entry, "follower_actions", self._follow_shape, self._follow_parameters(), out, mask,
+                                     next_d, status)
+
+    def _advised_actions(self, entry, method, shape, parameters, out, mask, next_d, status):
+        """What `follower_actions` and `oracle_actions` share: the checks of the four tensors, then the library's `entry` on the env's
+        records.  `shape` is the shape of one env's action, `parameters` the entry's arguments between num_headings and the stream."""
         N, dev = self.num_envs, self._state.device
         if out is None:
-            out = torch.zeros((N, *self._follow_shape), dtype=self._action_dtype, device=dev)
+            out = torch.zeros((N, *shape), dtype=self._action_dtype, device=dev)
         wanted = ((out, self._action_dtype, self._actions_shaped, "out"), (mask, torch.uint8, None, "mask"),
                   (next_d, torch.float32, None, "next_d"), (status, torch.int32, None, "status"))
         for t, dtype, shaped, what in wanted:
@@ -454,10 +460,10 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
                 continue
             ok = shaped(t) if shaped else tuple(t.shape) == (N,)
             if not (ok and t.dtype == dtype and t.is_contiguous() and t.device == dev):
-                raise _lib.HabError(f"{self._name}: follower_actions: `{what}` must be a contiguous {dtype} tensor for {N} envs on {dev}")
-        check(getattr(_lib.lib(), self._follow_entry)(ptr(self._state), self._state.shape[1] * 4, ptr(self._geo), ptr(self._tables[0]),
-                                                      ptr(mask), ptr(out), ptr(next_d), ptr(status), N, self.num_obstacles,
-                                                      self.num_headings, *self._follow_parameters(), stream_ptr()), self._follow_entry)
+                raise _lib.HabError(f"{self._name}: {method}: `{what}` must be a contiguous {dtype} tensor for {N} envs on {dev}")
+        check(getattr(_lib.lib(), entry)(ptr(self._state), self._state.shape[1] * 4, ptr(self._geo), ptr(self._tables[0]), ptr(mask),
+                                         ptr(out), ptr(next_d), ptr(status), N, self.num_obstacles, self.num_headings, *parameters,
+                                         stream_ptr()), entry)
         return out
 
     def reset_into(self, rgb, depth, goal):
@@ -799,11 +805,13 @@ class Nav2DRearrVectorEnv(Nav2DVectorEnv):
       the device, so in this mode the class itself refuses a device that is no GPU.
 
     `step_into_obs` writes whichever of the five rows `obs` holds; `actions` is int64 (N,) / (N, 1) as for Nav2D-v0.  The record's
-    words beyond Nav2D-v0's are named in include/habitat_amd.h (HAB_NAV2D_REARR_W_*)."""
+    words beyond Nav2D-v0's are named in include/habitat_amd.h (HAB_NAV2D_REARR_W_*).  In the geodesic mode `oracle_actions` returns
+    the actions of the pick-and-place oracle (common/rearrange_oracle.py)."""
 
     _name = "Nav2DRearr"
     _entries = ("hab_nav2d_rearr_step",)
     _follow_entry = None  # no shortest-path follower: see Nav2DVectorEnv.follower_actions
+    _oracle_entry = "hab_nav2d_rearr_oracle"  # the library's pick-and-place oracle of the task (`oracle_actions`), None where it has none
     _geo_entry = "hab_nav2d_rearr_step_geo"
     _geo_bytes = "hab_nav2d_rearr_geo_bytes"
     _sensor_set = "rearrange"
@@ -835,6 +843,30 @@ class Nav2DRearrVectorEnv(Nav2DVectorEnv):
         if nav2d_distance(distance, cls._name) == "geodesic" and torch.device(device).type != "cuda":
             raise _lib.HabError(f"{cls._name}: distance 'geodesic' builds its fields on the GPU; without a GPU device the task has "
                                 "Euclidean distances only")
+
+    def oracle_actions(self, out=None, mask=None, next_d=None, status=None):
+        """The actions of the pick-and-place oracle, one per env, computed on the device from the env's own records (which it does
+        not write) in the dtype and shape `step_into_obs` takes: go to the object down the field DO, PICK, carry it down DG, PLACE
+        where it will rest within the success distance, STOP.  tests/nav2d_rearr_oracle_reference.py states the rule;
+        `nav2d_rearr_oracle_kernel` matches it bit for bit.  In short, with "the fewest turns" the least (|delta|, delta < 0) of the
+        signed turns from the heading: STOP where the episode is unreachable and where the object rests with b < 0.5 (ARRIVED: the
+        success test of that stop holds).  Not holding: within the 1.0 m reach the heading that has the object ahead by the PICK
+        rule's dot test and the fewest turns wins, PICK if the agent faces it, else a turn; out of reach a greedy step down geo_o
+        as `follower_actions` takes it, below the term a, with the task's free test.  Holding: every heading whose PLACE would be
+        accepted and leave the object with geo_g(q) < 0.5 is eligible and the fewest turns win, PLACE if the agent faces it, else a
+        turn; where none is eligible a greedy step down geo_g below the term b.  STOP where no forward lowers the leg's term
+        (STUCK, an honest give-up).
+        `out` receives the actions (allocated if None) and is returned; `mask` (uint8 (N,)) selects envs, the outputs of the others
+        stay untouched; `next_d` (float32 (N,)) receives the leg's term as the env will report it after the step (a not holding, b
+        holding; 0 at a PICK, geo_g(q) at a PLACE, b where ARRIVED, +inf where UNREACHABLE or STUCK), `status` (int32 (N,)) the code
+        0 GO, 1 ARRIVED, 2 UNREACHABLE, 3 STUCK, 4 PICK, 5 PLACE.  Only Nav2DRearr-v0 in the geodesic distance mode has the oracle."""
+        if self._oracle_entry is None:
+            raise _lib.HabError(f"{self._name}: the task has no pick-and-place oracle (Nav2DRearr-v0 has one: under velocity and grip "
+                                "control turning to face and then gripping is not one step's choice)")
+        if self.distance != "geodesic":
+            raise _lib.HabError(f"{self._name}: the pick-and-place oracle needs `distance_to_goal: geodesic`, the env has "
+                                f"{self.distance!r}")
+        return self._advised_actions(self._oracle_entry, "oracle_actions", (), (), out, mask, next_d, status)
 
     def _sensor_rows(self, obs):
         return tuple(ptr(obs.get(k)) for k in NAV2D_REARR_SENSORS)
@@ -906,6 +938,7 @@ class Nav2DRearrVelVectorEnv(Nav2DRearrVectorEnv):
 
     _name = "Nav2DRearrVel"
     _entries = ("hab_nav2d_rearr_vel_step",)
+    _oracle_entry = None  # no pick-and-place oracle: see Nav2DRearrVectorEnv.oracle_actions
     _geo_entry = "hab_nav2d_rearr_vel_step_geo"
     _action_dtype, _action_text = torch.float32, "float32 device tensor of shape (N, 3)"
     num_actions = 1

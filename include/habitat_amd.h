@@ -312,6 +312,34 @@ int hab_nav2d_rearr_vel_step_geo(void* state /*N,HAB_NAV2D_REARR_STATE_BYTES*/, 
                                  uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings,
                                  int max_episode_steps, int start_holding, int max_turn_steps, int stop_turn_steps,
                                  float min_abs_lin_speed, int allow_sliding, int advance, hipStream_t stream);
+/* The pick-and-place oracle of Nav2DRearr-v0 in geodesic mode (definition: tests/nav2d_rearr_oracle_reference.py, bit-identical to
+ * it on every output): go to the object down DO, PICK, carry it down DG, PLACE where it will rest within the success distance, STOP.
+ * `state` (stride >= HAB_NAV2D_REARR_STATE_BYTES, a multiple of 4) and `geo` (the field records) are read and not written; `dirs`
+ * is the (num_headings, 2) heading table of the step entries.  Per env that `mask` selects (NULL = all; the outputs of the others
+ * stay untouched), with delta the signed turns from the HEADING word (the half turn counts as left) and "the fewest turns" the least
+ * (|delta|, delta < 0):  REACHABLE == 0 gives UNREACHABLE;  else HOLDING == 0 and B < 0.5 gives ARRIVED;  else HOLDING == 0: within
+ * reach (dist(p, o) < 1.0) the heading with (o - p) . dirs[h] > 0 and the fewest turns wins -- PICK at delta == 0, else GO, a turn;
+ * none gives STUCK -- and out of reach hab_nav2d_follow's forward search runs towards o over DO: p' = p + 0.25 * dirs[h] valid iff
+ * free by the task's test (the object's 0.4 m keep-out included) and v = geo_o(p') finite and below A; the lowest v, then the fewest
+ * turns win; GO;  else (holding) every heading whose PLACE target q = p + 0.5 * dirs[h] the PLACE rule accepts and whose
+ * w = geo_g(q) over DG is finite and < 0.5 is eligible, the fewest turns win -- PLACE at delta == 0, else GO, a turn -- and where
+ * none is eligible the forward search runs towards g over DG below B with Nav2D-v0's free test; no valid candidate gives STUCK.
+ * actions (int64): 0 STOP for ARRIVED, UNREACHABLE and STUCK, 4 PICK, 5 PLACE, a GO is 1 MOVE_FORWARD at delta == 0, 2 TURN_LEFT at
+ * delta > 0, else 3 TURN_RIGHT.  `status` (NULL: not written) gets the code below; `next_d` (NULL: not written) the leg's term as
+ * the step will leave it: the winner's v after a forward, A (not holding) or B (holding) at a turn, 0 at a PICK, the winner's w at a
+ * PLACE, B where ARRIVED, +inf where UNREACHABLE or STUCK.  A forward, PICK or PLACE it asks for is never refused by the step, and
+ * the answer after a PLACE is ARRIVED.  Refused: what hab_nav2d_rearr_geo_build refuses of state, stride, geo, N and num_obstacles;
+ * dirs or actions NULL; dirs not 4-byte, actions not 8-byte aligned; next_d or status misaligned; num_headings <= 0. */
+#define HAB_NAV2D_ORACLE_GO 0
+#define HAB_NAV2D_ORACLE_ARRIVED 1
+#define HAB_NAV2D_ORACLE_UNREACHABLE 2
+#define HAB_NAV2D_ORACLE_STUCK 3
+#define HAB_NAV2D_ORACLE_PICK 4
+#define HAB_NAV2D_ORACLE_PLACE 5
+int hab_nav2d_rearr_oracle(const void* state, size_t state_stride_bytes, const void* geo /*N,HAB_NAV2D_REARR_GEO_BYTES*/,
+                           const float* dirs /*num_headings,2*/, const uint8_t* mask /*N or NULL*/, int64_t* actions /*N*/,
+                           float* next_d /*N or NULL*/, int32_t* status /*N or NULL*/, int N, int num_obstacles, int num_headings,
+                           hipStream_t stream);
 /* Nav2DSocial-v0: find and follow a person who walks about Nav2D-v0's world along the shortest paths of its visibility graph
  * (definition: habitat_amd/common/env_factory.py, Nav2DSocialVectorEnv; bit-identical to tests/nav2d_social_reference.py on every
  * output, no angle function runs on the device).  `state` is N records of HAB_NAV2D_SOCIAL_STATE_BYTES whose first
