@@ -131,6 +131,46 @@ extern "C" int hab_rollout_step_stats(const float* rewards, const uint8_t* not_d
     return HAB_OK;
 }
 
+// DAgger's per-step mix of teacher and learner actions (tests/dagger_reference.py states the rule; this kernel matches it bit for
+// bit).  One thread per env.  The two counters are integers, so the order of the additions cannot show: each wave counts its lanes
+// with a ballot and lane 0 adds the two numbers with ordinary vector atomics.
+__global__ void __launch_bounds__(64) dagger_mix_kernel(int64_t* __restrict__ actions, const int64_t* __restrict__ expert,
+                                                        const int32_t* __restrict__ status, const uint8_t* __restrict__ not_done,
+                                                        const float* __restrict__ u, const uint8_t* __restrict__ mask, float beta,
+                                                        float inflection_coef, int64_t* __restrict__ prev_expert,
+                                                        float* __restrict__ weights, unsigned long long* __restrict__ agree, int N) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool counted = false, agreed = false;
+    if (i < N && (!mask || mask[i])) {
+        const int64_t e = expert[i], a = actions[i];
+        const int32_t s = status[i];
+        const bool gave_up = (s == HAB_NAV2D_ORACLE_UNREACHABLE) || (s == HAB_NAV2D_ORACLE_STUCK);
+        const bool inflection = (not_done[i] == 0) || (prev_expert[i] != e);
+        const float w = gave_up ? 0.0f : (inflection ? inflection_coef : 1.0f);
+        counted = w > 0.0f;
+        agreed = counted && (a == e);        // the policy's own sample against the label, before the mix
+        weights[i] = w;
+        if (u[i] < beta) actions[i] = e;     // strict: beta = 0 never takes the teacher, beta = 1 always (u is in [0, 1))
+        prev_expert[i] = e;
+    }
+    const unsigned long long c = __ballot(counted), g = __ballot(agreed);
+    if ((threadIdx.x & 63) == 0) {
+        if (g) atomicAdd(&agree[0], (unsigned long long)__popcll(g));
+        if (c) atomicAdd(&agree[1], (unsigned long long)__popcll(c));
+    }
+}
+extern "C" int hab_dagger_mix(int64_t* actions, const int64_t* expert, const int32_t* status, const uint8_t* not_done, const float* u,
+                              const uint8_t* mask, float beta, float inflection_coef, int64_t* prev_expert, float* weights,
+                              int64_t* agree, int N, hipStream_t stream) {
+    if (!actions || !expert || !status || !not_done || !u || !prev_expert || !weights || !agree || N <= 0) return HAB_ERR_ARG;
+    if (!(beta >= 0.0f && beta <= 1.0f)) return HAB_ERR_ARG;                          // NaN fails both comparisons
+    if (!(inflection_coef >= 0.0f && inflection_coef <= 3.402823466e+38f)) return HAB_ERR_ARG;  // negative, NaN or +inf
+    dagger_mix_kernel<<<cdiv(N, 64), 64, 0, stream>>>(actions, expert, status, not_done, u, mask, beta, inflection_coef, prev_expert,
+                                                      weights, reinterpret_cast<unsigned long long*>(agree), N);
+    HAB_LAUNCH_CHECK();
+    return HAB_OK;
+}
+
 // ObjectNav sensor set for the current env clock (oracle/synth.py: semantic, objectgoal, compass, gps).
 __global__ void __launch_bounds__(256) synth_semantic_kernel(int32_t* __restrict__ semantic, const int64_t* __restrict__ env_t,
                                                              uint32_t seed, uint32_t env_offset, int words) {
@@ -474,6 +514,92 @@ extern "C" int hab_ppo_loss_ver(const float* values, const float* logp, const fl
                                             value_loss_coef, entropy_coef, use_clipped_value_loss, d_value, d_logp,
                                             d_entropy, out24, is_coeffs, is_stale, policy_version, (long long)current_policy_version,
                                             log_alpha, entropy_threshold);
+    HAB_LAUNCH_CHECK();
+    return HAB_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Weighted behaviour-cloning loss, forward + backward: the sibling of ppo_loss_kernel for the DAgger updater.  values / logp /
+// entropy are the dense [B] outputs of hab_policy_evaluate called with the EXPERT actions; weights and returns are (T+1,N) storage
+// buffers gathered through rows[f] (rows == nullptr -> dense).  With W = sum w and Wd = max(W, 1):
+//  bc = sum w * (-logp) / Wd, value_loss = mean 0.5 (v - ret)^2, ent = mean entropy, total = bc + value_coef * value_loss - entropy_coef * ent
+//  d_logp = -w / Wd, d_value = value_coef * (v - ret) / B, d_entropy = -entropy_coef / B
+//  out[0..3] value_loss, bc, ent, total   out[4..6] value_pred min/mean/max   out[7..9] expert_prob = exp(logp) min/mean/max over the
+//  frames with w > 0 (+inf, 0, -inf where there is none)   out[10] W   out[11] B.
+// Single 1024-thread block and the reduction order of ppo_loss_kernel (thread-serial, six shuffle rounds, 16 partials in order), so
+// the result is deterministic.  d_logp needs W, so it is written by a second pass over the block's own frames after the reduction.
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(1024) bc_loss_kernel(const float* __restrict__ values, const float* __restrict__ logp,
+                                                       const float* __restrict__ entropy, const float* __restrict__ weights,
+                                                       const float* __restrict__ returns, const int* __restrict__ rows, int B,
+                                                       float value_coef, float entropy_coef, float* __restrict__ d_value,
+                                                       float* __restrict__ d_logp, float* __restrict__ d_entropy,
+                                                       float* __restrict__ out) {
+    __shared__ float red[16][7];
+    __shared__ float redmm[16][4];
+    __shared__ float s_Wd;
+    const int tid = threadIdx.x;
+    const float invB = 1.0f / (float)B;
+    const float den = -entropy_coef * invB;
+    float s_vl = 0, s_bc = 0, s_en = 0, s_v = 0, s_w = 0, s_p = 0, s_n = 0;
+    float v_min = INFINITY, v_max = -INFINITY, p_min = INFINITY, p_max = -INFINITY;
+    for (int f = tid; f < B; f += 1024) {
+        const int g = rows ? rows[f] : f;
+        const float v = values[f], lp = logp[f], en = entropy[f];
+        const float w = weights[g], ret = returns[g];
+        const float e = v - ret;
+        d_value[f] = value_coef * e * invB;
+        d_entropy[f] = den;
+        s_vl += 0.5f * (e * e); s_bc += w * (-lp); s_en += en; s_v += v; s_w += w;
+        v_min = fminf(v_min, v); v_max = fmaxf(v_max, v);
+        if (w > 0.0f) {
+            const float p = expf(lp);
+            s_p += p; s_n += 1.0f;
+            p_min = fminf(p_min, p); p_max = fmaxf(p_max, p);
+        }
+    }
+    float sums[7] = {s_vl, s_bc, s_en, s_v, s_w, s_p, s_n};
+#pragma unroll
+    for (int k = 0; k < 7; ++k) sums[k] = wave_sum(sums[k]);
+    v_min = wave_min(v_min); v_max = wave_max(v_max); p_min = wave_min(p_min); p_max = wave_max(p_max);
+    const int wv = tid >> 6;
+    if ((tid & 63) == 0) {
+        for (int k = 0; k < 7; ++k) red[wv][k] = sums[k];
+        redmm[wv][0] = v_min; redmm[wv][1] = v_max; redmm[wv][2] = p_min; redmm[wv][3] = p_max;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float t[7] = {0, 0, 0, 0, 0, 0, 0};
+        float mn_v = INFINITY, mx_v = -INFINITY, mn_p = INFINITY, mx_p = -INFINITY;
+        for (int i = 0; i < 16; ++i) {
+            for (int k = 0; k < 7; ++k) t[k] += red[i][k];
+            mn_v = fminf(mn_v, redmm[i][0]); mx_v = fmaxf(mx_v, redmm[i][1]);
+            mn_p = fminf(mn_p, redmm[i][2]); mx_p = fmaxf(mx_p, redmm[i][3]);
+        }
+        const float Wd = fmaxf(t[4], 1.0f);
+        s_Wd = Wd;
+        const float vl = t[0] * invB, bc = t[1] / Wd, en = t[2] * invB;
+        out[0] = vl; out[1] = bc; out[2] = en;
+        out[3] = (bc + value_coef * vl) - entropy_coef * en;
+        out[4] = mn_v; out[5] = t[3] * invB; out[6] = mx_v;
+        out[7] = mn_p; out[8] = (t[6] > 0.0f) ? t[5] / t[6] : 0.0f; out[9] = mx_p;
+        out[10] = t[4]; out[11] = (float)B;
+    }
+    __syncthreads();
+    const float Wd = s_Wd;
+    for (int f = tid; f < B; f += 1024) {
+        const int g = rows ? rows[f] : f;
+        d_logp[f] = -weights[g] / Wd;
+    }
+}
+
+extern "C" int hab_bc_loss(const float* values, const float* logp, const float* entropy, const float* weights, const float* returns,
+                           const int* rows, int B, float value_loss_coef, float entropy_coef, float* d_value, float* d_logp,
+                           float* d_entropy, float* out12, hipStream_t stream) {
+    if (B <= 0 || !values || !logp || !entropy || !weights || !returns || !d_value || !d_logp || !d_entropy || !out12)
+        return HAB_ERR_ARG;
+    bc_loss_kernel<<<1, 1024, 0, stream>>>(values, logp, entropy, weights, returns, rows, B, value_loss_coef, entropy_coef, d_value,
+                                           d_logp, d_entropy, out12);
     HAB_LAUNCH_CHECK();
     return HAB_OK;
 }

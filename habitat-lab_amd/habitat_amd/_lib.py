@@ -98,6 +98,8 @@ SIGNATURES = {
     "hab_ppo_loss": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_int, c_float, c_float, c_float, c_int, vp, vp, vp, vp, vp]),
     "hab_ppo_loss_ver": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_int, c_float, c_float, c_float, c_int, vp, vp, vp, c_int64, vp, c_float,
                                  vp, vp, vp, vp, vp]),
+    "hab_dagger_mix": (c_int, [vp, vp, vp, vp, vp, vp, c_float, c_float, vp, vp, vp, c_int, vp]),
+    "hab_bc_loss": (c_int, [vp, vp, vp, vp, vp, vp, c_int, c_float, c_float, vp, vp, vp, vp, vp]),
     "hab_lagrange_adam_step": (c_int, [vp, vp, vp, vp, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_float, vp, vp]),
     "hab_ver_compute_returns": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_int, c_double, c_double, vp]),
     "hab_ver_is_coeffs": (c_int, [vp, c_int, c_int, c_int, vp, vp, vp]),

@@ -447,6 +447,19 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
         return self._advised_actions(self._follow_entry, "follower_actions", self._follow_shape, self._follow_parameters(), out, mask,
                                      next_d, status)
 
+    # ---- the teacher (DAgger) -------------------------------------------------------------------
+    _expert_method = "follower_actions"  # which of the task's advisers labels the learner's states; None where the task has none
+
+    def expert_actions(self, out=None, mask=None, next_d=None, status=None):
+        """One discrete teacher action per env for imitation (the DAgger updater): `follower_actions` on Nav2D-v0, `oracle_actions` on
+        Nav2DRearr-v0, with their arguments; `status` holds HAB_NAV2D_ORACLE_* codes, of which the follower's four are the first
+        four.  Every other Nav2D task refuses: the velocity tasks' advice is a float row, Nav2DObj-v0 and Nav2DSocial-v0 have no
+        adviser.  The Euclidean distance mode refuses as the two advisers do."""
+        if self._expert_method is None:
+            raise _lib.HabError(f"{self._name}: the task has no discrete teacher for imitation (Nav2D-v0 has the shortest-path follower, "
+                                "Nav2DRearr-v0 the pick-and-place oracle)")
+        return getattr(self, self._expert_method)(out=out, mask=mask, next_d=next_d, status=status)
+
     def _advised_actions(self, entry, method, shape, parameters, out, mask, next_d, status):
         """What `follower_actions` and `oracle_actions` share: the checks of the four tensors, then the library's `entry` on the env's
         records.  `shape` is the shape of one env's action, `parameters` the entry's arguments between num_headings and the stream."""
@@ -580,6 +593,7 @@ class Nav2DVelVectorEnv(Nav2DVectorEnv):
     _name = "Nav2DVel"
     _entries = ("hab_nav2d_vel_step", "hab_nav2d_vel_step_geo")
     _follow_entry, _follow_shape = "hab_nav2d_vel_follow", (2,)
+    _expert_method = None  # the velocity follower answers a float row: see Nav2DVectorEnv.expert_actions
     _action_dtype, _action_text = torch.float32, "float32 device tensor of shape (N, 2)"
 
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
@@ -688,6 +702,7 @@ class Nav2DObjVectorEnv(Nav2DVectorEnv):
       is built on the device, so in this mode the class itself refuses a device that is no GPU."""
 
     _name = "Nav2DObj"
+    _expert_method = None  # no teacher: see Nav2DVectorEnv.expert_actions
     _entries = ("hab_nav2d_obj_step", "hab_nav2d_obj_step_geo")
     _follow_entry = None  # no shortest-path follower: see Nav2DVectorEnv.follower_actions
     _sensor_set = "objectnav"
@@ -812,6 +827,7 @@ class Nav2DRearrVectorEnv(Nav2DVectorEnv):
     _entries = ("hab_nav2d_rearr_step",)
     _follow_entry = None  # no shortest-path follower: see Nav2DVectorEnv.follower_actions
     _oracle_entry = "hab_nav2d_rearr_oracle"  # the library's pick-and-place oracle of the task (`oracle_actions`), None where it has none
+    _expert_method = "oracle_actions"
     _geo_entry = "hab_nav2d_rearr_step_geo"
     _geo_bytes = "hab_nav2d_rearr_geo_bytes"
     _sensor_set = "rearrange"
@@ -939,6 +955,7 @@ class Nav2DRearrVelVectorEnv(Nav2DRearrVectorEnv):
     _name = "Nav2DRearrVel"
     _entries = ("hab_nav2d_rearr_vel_step",)
     _oracle_entry = None  # no pick-and-place oracle: see Nav2DRearrVectorEnv.oracle_actions
+    _expert_method = None  # no discrete teacher: see Nav2DVectorEnv.expert_actions
     _geo_entry = "hab_nav2d_rearr_vel_step_geo"
     _action_dtype, _action_text = torch.float32, "float32 device tensor of shape (N, 3)"
     num_actions = 1
@@ -1063,6 +1080,7 @@ class Nav2DSocialVectorEnv(Nav2DVectorEnv):
     of the last build, the builds inside steps of the episode (`rebuilds`), one zero and DW."""
 
     _name = "Nav2DSocial"
+    _expert_method = None  # no teacher: see Nav2DVectorEnv.expert_actions
     _entries = ("hab_nav2d_social_step",)
     _follow_entry = None  # no shortest-path follower: see Nav2DVectorEnv.follower_actions
     _sensor_set = "social"

@@ -215,3 +215,23 @@ class RolloutStorage(Storage):
 
     def __setstate__(self, state: Dict[str, Any]):
         self.__dict__.update(state)
+
+
+@baseline_registry.register_storage
+class ImitationRolloutStorage(RolloutStorage):
+    """RolloutStorage with the two rows DAgger adds to a step: `expert_actions` (the teacher's label, shape and dtype of `actions`)
+    and `expert_weights` ((T+1, N, 1) float32, what hab_dagger_mix wrote: 0 where the teacher gave up, the inflection coefficient
+    where an episode starts or the label changes, else 1).  `actions` holds the EXECUTED action (teacher's or learner's), which is what
+    `prev_actions` of the next step repeats; `action_log_probs` stays the log-probability of the policy's own sample and is not used
+    by the DAgger updater.  Discrete action spaces only."""
+
+    def __init__(self, numsteps, num_envs, observation_space, action_space, actor_critic, is_double_buffered: bool = False,
+                 device=None, gae_variant: str = "scan"):
+        _, discrete_actions = get_action_space_info(action_space)
+        if not discrete_actions:
+            raise _lib.HabError("ImitationRolloutStorage: the teacher's labels are discrete actions; a continuous action space is refused")
+        super().__init__(numsteps, num_envs, observation_space, action_space, actor_critic, is_double_buffered=is_double_buffered,
+                         device=device, gae_variant=gae_variant)
+        B = self.buffers
+        dict.__setitem__(B, "expert_actions", torch.zeros_like(B["actions"]))
+        dict.__setitem__(B, "expert_weights", torch.zeros(numsteps + 1, num_envs, 1, dtype=torch.float32, device=self.device))

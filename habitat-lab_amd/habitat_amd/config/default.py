@@ -80,7 +80,11 @@ def _defaults() -> dict:
                 policy=dict(main_agent=policy), ppo=ppo, ddppo=ddppo, auxiliary_losses={},
                 # VERConfig with the reference's defaults (default_structured_configs.py:318-324): two inference workers (worker 0 is
                 # the trainer's own thread), learning between rollouts
-                ver=dict(variable_experience=True, num_inference_workers=2, overlap_rollouts_and_learn=False)),
+                ver=dict(variable_experience=True, num_inference_workers=2, overlap_rollouts_and_learn=False),
+                # DAgger on the PPO trainer (rl/ppo/ppo_trainer.py, Imitation): the env's teacher labels every visited state, the
+                # executed action is the teacher's with probability beta, which falls linearly from beta_start to beta_end over the
+                # first beta_decay_updates updates; inflection_weight_coef weighs the steps where the label changes
+                imitation=dict(enabled=False, beta_start=1.0, beta_end=0.0, beta_decay_updates=100, inflection_weight_coef=1.0)),
     )
     habitat = dict(
         seed=100,  # HL/config/default_structured_configs.py:1918

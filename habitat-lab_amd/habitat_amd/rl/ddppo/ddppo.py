@@ -26,7 +26,7 @@ import torch
 import torch.distributed as distrib
 
 from habitat_amd.common.baseline_registry import baseline_registry
-from habitat_amd.rl.ppo.ppo import PPO
+from habitat_amd.rl.ppo.ppo import PPO, DAgger
 
 
 def _vote(ok: bool, device) -> bool:
@@ -273,3 +273,11 @@ class DecentralizedDistributedMixin:
 @baseline_registry.register_updater
 class DDPPO(DecentralizedDistributedMixin, PPO):
     pass
+
+
+@baseline_registry.register_updater
+class DDDAgger(DecentralizedDistributedMixin, DAgger):
+    """The imitation updater (rl/ppo/ppo.py: DAgger) with DD-PPO's gradient averaging.  Each rank's hab_bc_loss normalises d_logp by
+    its own max(W_rank, 1) and the gradients are then averaged over the ranks, so the BC term is the mean of the ranks' weighted
+    means, not the weighted mean over all ranks' samples; the two differ where the ranks' weight sums differ.  Registered and
+    covered by the registry test; it has not run on more than one GPU."""

@@ -466,3 +466,89 @@ class PPO(nn.Module, Updater):
             self.optimizer.load_state_dict(state["optim_state"])
         if "aux_optim_state" in state and self._aux_optimizer() is not None:
             self._aux_opt.load_state_dict(state["aux_optim_state"])
+
+
+DAGGER_METRIC_KEYS = ["value_loss", "action_loss", "dist_entropy", "_total", "value_pred_min", "value_pred_mean", "value_pred_max",
+                      "expert_prob_min", "expert_prob_mean", "expert_prob_max", "imitation_weight_sum", "_B"]
+
+
+@baseline_registry.register_updater
+class DAgger(PPO):
+    """Imitation of a teacher that lives in the env (DAgger, Ross et al. 2011) on the PPO updater's engine: the rollout
+    (ImitationRolloutStorage) holds, per step, the teacher's label and its weight next to the executed action, and a minibatch is
+
+        evaluate with the EXPERT actions (prev_actions stay the executed ones) -> hab_bc_loss (weighted negative log-likelihood +
+        value loss - entropy bonus, their gradients, metrics) -> engine backward with the expert actions -> clip + Adam
+
+    `ppo_epoch` and `num_mini_batch` keep their meaning; advantages are not needed, the value head is still regressed on the GAE
+    returns.  Clip + Adam, the hooks and the resume state are PPO's.  `action_loss` is the BC loss.  The trainer adds
+    `imitation_agreement` and `imitation_beta` to the metrics; its two counters (`rollout_counters`, a device int64 tensor the trainer
+    hangs here) come to the host in the update's one read.  Auxiliary-loss modules and the adaptive entropy penalty are refused;
+    `clip_param`, `use_clipped_value_loss` and `use_normalized_advantage` are accepted and have no effect."""
+
+    def __init__(self, actor_critic, clip_param: float, ppo_epoch: int, num_mini_batch: int, value_loss_coef: float,
+                 entropy_coef: float, lr: Optional[float] = None, eps: Optional[float] = None,
+                 max_grad_norm: Optional[float] = None, use_clipped_value_loss: bool = False,
+                 use_normalized_advantage: bool = True, entropy_target_factor: float = 0.0,
+                 use_adaptive_entropy_pen: bool = False) -> None:
+        """PPO's signature.  clip_param, use_clipped_value_loss and use_normalized_advantage are accepted and have no effect here:
+        the BC loss has no ratio to clip, regresses the value head on the returns unclipped, and uses no advantages."""
+        if len(getattr(actor_critic, "aux_loss_modules", ())) > 0:
+            raise _lib.HabError("DAgger: auxiliary-loss modules are not supported by the imitation updater")
+        if use_adaptive_entropy_pen:
+            raise _lib.HabError("DAgger: the adaptive entropy penalty (use_adaptive_entropy_pen) is not supported by the imitation updater")
+        super().__init__(actor_critic, clip_param, ppo_epoch, num_mini_batch, value_loss_coef, entropy_coef, lr=lr, eps=eps,
+                         max_grad_norm=max_grad_norm, use_clipped_value_loss=use_clipped_value_loss,
+                         use_normalized_advantage=use_normalized_advantage, entropy_target_factor=entropy_target_factor,
+                         use_adaptive_entropy_pen=False)
+
+    @staticmethod
+    def _check_storage(rollouts) -> None:
+        buffers = getattr(rollouts, "buffers", {})
+        if "expert_actions" not in buffers or "expert_weights" not in buffers:
+            raise _lib.HabError("DAgger: the rollout storage has no `expert_actions` / `expert_weights` "
+                                "(habitat_baselines.rollout_storage_name must be ImitationRolloutStorage)")
+
+    def _update_from_batch(self, batch: MiniBatch, epoch: int, rollouts: RolloutStorage, slot: torch.Tensor):
+        eng = self.actor_critic.engine
+        Bf = batch.storage.buffers
+        rgb, depth, goal, extra = self.actor_critic._obs_ptrs(Bf["observations"])
+        Bn, n = batch.T * batch.n, batch.n
+        w = self._work(Bn)
+        eng.evaluate(rgb, depth, goal, batch.rows, Bf["recurrent_hidden_states"], Bf["masks"], Bf["expert_actions"], batch.pack, Bn, n,
+                     value=w["v"], log_prob=w["lp"], entropy=w["ent"], prev_actions=Bf["prev_actions"], extra=extra)
+        check(_lib.lib().hab_bc_loss(ptr(w["v"]), ptr(w["lp"]), ptr(w["ent"]), ptr(Bf["expert_weights"]), ptr(Bf["returns"]),
+                                     ptr(batch.rows), Bn, float(self.value_loss_coef), float(self.entropy_coef), ptr(w["dv"]),
+                                     ptr(w["dlp"]), ptr(w["dent"]), ptr(slot), stream_ptr()), "hab_bc_loss")
+        eng.backward(rgb, depth, goal, batch.rows, Bf["expert_actions"], batch.pack, w["dv"], w["dlp"], w["dent"],
+                     prev_actions=Bf["prev_actions"], extra=extra)
+        self.before_step()
+        self.optimizer.step(max_grad_norm=self.max_grad_norm, grad_scale=1.0 / self._world_size(), grad_norm_out=slot[12:13])
+        self.after_step()
+
+    def update(self, rollouts: RolloutStorage) -> Dict[str, float]:
+        self._check_storage(rollouts)
+        self._aux_metrics = {}
+        slots = torch.zeros(self.ppo_epoch * self.num_mini_batch + 1, SLOT_WIDTH, device=self.device)
+        k = 0
+        for epoch in range(self.ppo_epoch):
+            # (the generator's `advantages` slot is handed the returns: nothing here reads advantages)
+            for batch in rollouts.data_generator(rollouts.buffers["returns"], self.num_mini_batch):
+                if k >= slots.shape[0]:
+                    slots = torch.cat([slots, torch.zeros_like(slots)], 0)
+                self._update_from_batch(batch, epoch, rollouts, slots[k])
+                k += 1
+        # the single device->host read of the update: the metric rows and, behind them, the rollout's counters the trainer hung on
+        # `rollout_counters` (int64 on the device; float64 carries them and the float32 metrics exactly), which are then zeroed
+        flat, counters = slots[:k].reshape(-1).double(), getattr(self, "rollout_counters", None)
+        if counters is not None:
+            flat = torch.cat([flat, counters.reshape(-1).double()])
+        flat = flat.cpu()
+        host = flat[: k * SLOT_WIDTH].view(k, SLOT_WIDTH).float()
+        if counters is not None:
+            self.last_rollout_counts = tuple(int(x) for x in flat[k * SLOT_WIDTH:])
+            counters.zero_()
+        self.last_minibatch_metrics = host
+        out = {name: float(host[:, i].mean()) for i, name in enumerate(DAGGER_METRIC_KEYS) if not name.startswith("_")}
+        out["grad_norm"] = float(host[:, 12].mean())
+        return out

@@ -71,6 +71,67 @@ def batch_obs(observations, device):
     return out
 
 
+# ---- imitation (DAgger): habitat_baselines.rl.imitation --------------------------------------------------------------------------
+def imitation_settings(config):
+    """The `habitat_baselines.rl.imitation` block where it is enabled, else None (absent block included)."""
+    im = config.habitat_baselines.rl.get("imitation")
+    return im if im is not None and im.get("enabled", False) else None
+
+
+def imitation_beta(im, updates_done: int) -> float:
+    """The share of steps that execute the teacher's action: linear in the number of updates done, beta_start at 0, beta_end from
+    beta_decay_updates on.  num_updates_done is part of the resume state, so a resumed run continues the line."""
+    decay = float(im.beta_decay_updates)
+    frac = 1.0 if decay <= 0 else min(max(updates_done / decay, 0.0), 1.0)
+    return float(im.beta_start + (im.beta_end - im.beta_start) * frac)
+
+
+def refuse_imitation_config(config, ver: bool = False, distributed: bool = False):
+    """What of an imitation run can be refused from the configuration alone; returns the enabled block or None."""
+    hb = config.habitat_baselines
+    im = imitation_settings(config)
+    names = (hb.updater_name, hb.rollout_storage_name)
+    if im is None:
+        if hb.updater_name in ("DAgger", "DDDAgger") or hb.distrib_updater_name == "DDDAgger" or hb.rollout_storage_name == "ImitationRolloutStorage":
+            raise _lib.HabError("imitation: updater DAgger and ImitationRolloutStorage need habitat_baselines.rl.imitation.enabled=True "
+                                "(without it nothing labels the rollout)")
+        return None
+    if ver:
+        raise _lib.HabError("imitation: the VER trainer is not supported (its storage and loss carry importance weights the BC loss has "
+                            "no place for); use trainer_name ppo or ddppo")
+    if names != ("DAgger", "ImitationRolloutStorage"):
+        raise _lib.HabError(f"imitation: updater_name / rollout_storage_name must be the pair DAgger / ImitationRolloutStorage, the "
+                            f"configuration has {names[0]} / {names[1]}")
+    if distributed and hb.distrib_updater_name != "DDDAgger":
+        raise _lib.HabError(f"imitation: a distributed run needs distrib_updater_name DDDAgger, the configuration has "
+                            f"{hb.distrib_updater_name}")
+    if hb.rl.ppo.use_double_buffered_sampler:
+        raise _lib.HabError("imitation: use_double_buffered_sampler is not supported (the teacher labels all envs in one launch)")
+    for k in ("beta_start", "beta_end"):
+        if not 0.0 <= float(im[k]) <= 1.0:
+            raise _lib.HabError(f"imitation: {k} {im[k]!r} must lie in [0, 1]")
+    if not (np.isfinite(float(im.inflection_weight_coef)) and float(im.inflection_weight_coef) >= 0.0):
+        raise _lib.HabError(f"imitation: inflection_weight_coef {im.inflection_weight_coef!r} must be finite and >= 0")
+    return im
+
+
+def refuse_imitation_envs(envs, device_envs: bool, probe: bool = True) -> None:
+    """What of an imitation run can be refused once the envs exist.  The contract of an env source that can teach is one method,
+    `expert_actions(out=None, mask=None, next_d=None, status=None)`, which raises HabError with its reason where it cannot (a task
+    without a teacher, the Euclidean mode); `probe` makes that one call, after the envs' first reset."""
+    if not device_envs:
+        raise _lib.HabError("imitation: the host rollout path is not supported: the teacher labels the envs on the device, so the env "
+                            "source must offer step_into_obs and the trainer must run on a GPU")
+    if not hasattr(envs, "expert_actions"):
+        raise _lib.HabError(f"imitation: {type(envs).__name__}: the env source has no expert_actions (no teacher)")
+    if not probe:
+        return
+    try:  # one probing call (the teacher reads the env's records and writes none): an env that cannot teach says why itself
+        envs.expert_actions()
+    except _lib.HabError as err:
+        raise _lib.HabError(f"imitation: {err}") from err
+
+
 @baseline_registry.register_trainer(name="ddppo")
 @baseline_registry.register_trainer(name="ppo")
 class PPOTrainer(BaseRLTrainer):
@@ -127,6 +188,7 @@ class PPOTrainer(BaseRLTrainer):
                                   f"{hb.checkpoint_folder}")
         if hb.rl.ddppo.force_distributed:
             self._is_distributed = True
+        imitation = refuse_imitation_config(self.config, distributed=self._is_distributed)
         self._add_preemption_signal_handlers()
         if self._is_distributed:
             local_rank, tcp_store = init_distrib_slurm(hb.rl.ddppo.distrib_backend)
@@ -151,6 +213,8 @@ class PPOTrainer(BaseRLTrainer):
         else:
             self.device = torch.device("cpu")
         self._init_envs()
+        if imitation is not None:
+            refuse_imitation_envs(self.envs, hasattr(self.envs, "step_into_obs") and self.device.type == "cuda", probe=False)
         if rank0_only() and not os.path.isdir(hb.checkpoint_folder):
             os.makedirs(hb.checkpoint_folder, exist_ok=True)
         self._agent = self._create_agent(resume_state)
@@ -189,6 +253,19 @@ class PPOTrainer(BaseRLTrainer):
         self.running_episode_stats = dict(count=torch.zeros(N, 1, device=stat_dev), reward=torch.zeros(N, 1, device=stat_dev))
         self.window_episode_stats = defaultdict(lambda: deque(maxlen=self._ppo_cfg.reward_window_size))
         self._measure_base = None  # see _coalesce_post_step
+        self._imitation = None
+        if imitation is not None:
+            refuse_imitation_envs(self.envs, self._device_envs)  # the probing call, now that the envs hold their first episodes
+            # DAgger: what the rollout step needs beside the storage's two rows.  prev_expert is the mix kernel's carry (the label of
+            # each env's previous step, -1 before the first) and belongs to the resume state; agree = (agreements, weighted samples)
+            # since the last update
+            self._imitation = dict(cfg=imitation, beta=imitation_beta(imitation, self.num_updates_done), u=None, counts=(0, 0),
+                                   prev_expert=torch.full((N,), -1, dtype=torch.int64, device=self.device),
+                                   status=torch.zeros(N, dtype=torch.int32, device=self.device),
+                                   agree=torch.zeros(2, dtype=torch.int64, device=self.device))
+            if resume_state is not None and "imitation_prev_expert" in resume_state.get("requeue_stats", {}):
+                self._imitation["prev_expert"].copy_(resume_state["requeue_stats"]["imitation_prev_expert"])
+            self._agent.updater.rollout_counters = self._imitation["agree"]  # read with the updater's metrics, in its one transfer
         self.t_start = time.time()
 
     # ---- checkpoints ---------------------------------------------------------------------------------------
@@ -237,6 +314,17 @@ class PPOTrainer(BaseRLTrainer):
                    exp_noise=noise[t],
                    out=dict(values=B["value_preds"][t], actions=B["actions"][t], action_log_probs=B["action_log_probs"][t],
                             rnn_hidden_states=B["recurrent_hidden_states"][t + 1]))
+        im = getattr(self, "_imitation", None)
+        if im is not None:
+            # DAgger: the env's teacher labels the state the policy just acted in (it reads the env's records and writes none), then
+            # one launch weighs the label and replaces the sampled action by it where u < beta.  The env, the episode bookkeeping
+            # and prev_actions[t + 1] below see the EXECUTED action; action_log_probs[t] stays the policy sample's and is unused.
+            with g_timer.avg_time("trainer.imitation_label"):
+                self.envs.expert_actions(out=B["expert_actions"][t], status=im["status"])
+                _lib.check(_lib.lib().hab_dagger_mix(
+                    _lib.ptr(B["actions"][t]), _lib.ptr(B["expert_actions"][t]), _lib.ptr(im["status"]), _lib.ptr(B["masks"][t]),
+                    _lib.ptr(im["u"][t]), None, float(im["beta"]), float(im["cfg"].inflection_weight_coef), _lib.ptr(im["prev_expert"]),
+                    _lib.ptr(B["expert_weights"][t]), _lib.ptr(im["agree"]), self.envs.num_envs, _lib.stream_ptr()), "hab_dagger_mix")
         with g_timer.avg_time("trainer.step_env"):
             # an env whose observations depend on the actions (consumes_actions, e.g. Nav2DVectorEnv) is handed the row the policy
             # just wrote for THIS step
@@ -331,6 +419,10 @@ class PPOTrainer(BaseRLTrainer):
             losses = self._agent.updater.update(st)
             st.after_update()
             self._agent.after_update()
+            im = getattr(self, "_imitation", None)
+            if im is not None:  # the rollout's agreement counters came to the host in the updater's one read, which also zeroed them
+                agreed, counted = im["counts"] = self._agent.updater.last_rollout_counts
+                losses = dict(losses, imitation_agreement=agreed / max(counted, 1), imitation_beta=float(im["beta"]))
         return losses
 
     def _coalesce_post_step(self, losses: Dict[str, float], count_steps_delta: int) -> Dict[str, float]:
@@ -416,6 +508,8 @@ class PPOTrainer(BaseRLTrainer):
                                          prev_time=(time.time() - self.t_start) + prev_time,
                                          running_episode_stats={k: v.cpu() for k, v in self.running_episode_stats.items()},
                                          window_episode_stats=dict(self.window_episode_stats))
+                    if getattr(self, "_imitation", None) is not None:
+                        requeue_stats["imitation_prev_expert"] = self._imitation["prev_expert"].cpu()
                     save_resume_state(dict(**self._agent.get_resume_state(), config=self.config.to_dict(), requeue_stats=requeue_stats),
                                       self.config)
                 if EXIT.is_set():
@@ -458,6 +552,10 @@ class PPOTrainer(BaseRLTrainer):
         with g_timer.avg_time("trainer.rollout_collect"):
             if self._device_envs:
                 noise = self._draw_rollout_noise(T)
+                im = getattr(self, "_imitation", None)
+                if im is not None:  # the mix's uniforms, (T, N) in [0, 1) from the CPU generator after the sampling noise
+                    im["beta"] = imitation_beta(im["cfg"], self.num_updates_done)
+                    im["u"] = torch.rand(T, self.envs.num_envs).pin_memory().to(self.device, non_blocking=True)
                 # a rollout step is ~200 us of GPU work: the straggler counter is read through a cached poller, not one TCP round
                 # trip per step (at most 0.5 ms older than the reference's per-step query)
                 polling = contextlib.nullcontext()

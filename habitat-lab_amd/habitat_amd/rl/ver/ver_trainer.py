@@ -39,7 +39,7 @@ from habitat_amd.common.obs_transformers import apply_obs_transforms_obs_space, 
 from habitat_amd.config.default import read_write
 from habitat_amd.rl.ddppo.ddp_utils import (EXIT, get_distrib_size, init_distrib_slurm, load_resume_state, rank0_only, requeue_job,
                                             save_resume_state)
-from habitat_amd.rl.ppo.ppo_trainer import PPOTrainer
+from habitat_amd.rl.ppo.ppo_trainer import PPOTrainer, refuse_imitation_config
 from habitat_amd.rl.ppo.single_agent_access_mgr import EnvironmentSpec
 from habitat_amd.rl.ver.inference_worker import (InferenceWorker, InferenceWorkerPool, InferenceWorkerSync, PublishedWeights,
                                                  RequestQueue)
@@ -67,6 +67,7 @@ class VERTrainer(PPOTrainer):
 
     def _init_train(self, resume_state=None):
         hb = self.config.habitat_baselines
+        refuse_imitation_config(self.config, ver=True)
         if self._is_distributed:
             local_rank, world_rank, _ = get_distrib_size()
             with read_write(self.config):

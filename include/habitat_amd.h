@@ -473,6 +473,31 @@ int hab_ppo_loss_ver(const float* values, const float* logp, const float* entrop
                      float entropy_coef, int use_clipped_value_loss, const float* is_coeffs, const uint8_t* is_stale,
                      const int64_t* policy_version, int64_t current_policy_version, const float* log_alpha, float entropy_threshold,
                      float* d_value, float* d_logp, float* d_entropy, float* out24, hipStream_t stream);
+/* DAgger, one launch per rollout step, discrete actions, all arrays N rows (tests/dagger_reference.py states the rule; the kernel
+ * matches it bit for bit).  actions (in/out): the policy's sampled action of the step; expert / status: what the env's teacher
+ * answered (status is a HAB_NAV2D_ORACLE_* code; the follower's four codes are the first four); not_done: the step's mask, 0 where
+ * an episode starts; u: uniforms in [0, 1) drawn by the caller; prev_expert (in/out): the label of the env's previous step, -1
+ * before the first, carried from rollout to rollout.  Per env, skipped where mask (nullable, uint8) is 0:
+ *   gave_up = status is UNREACHABLE or STUCK;  inflection = not_done == 0 or prev_expert != expert
+ *   weights = 0 if gave_up, else inflection_coef if inflection, else 1
+ *   if weights > 0: agree[1] += 1, agree[0] += (actions == expert), compared before the mix
+ *   actions = expert iff u < beta (strict);  prev_expert = expert
+ * agree: 2 int64 counters, accumulated.  Refused (HAB_ERR_ARG): a NULL pointer other than mask, N <= 0, beta outside [0, 1] or not
+ * finite, inflection_coef negative or not finite. */
+int hab_dagger_mix(int64_t* actions, const int64_t* expert, const int32_t* status, const uint8_t* not_done, const float* u,
+                   const uint8_t* mask, float beta, float inflection_coef, int64_t* prev_expert, float* weights, int64_t* agree,
+                   int N, hipStream_t stream);
+
+/* Weighted behaviour-cloning loss + its gradient, the sibling of hab_ppo_loss for the DAgger updater.  values/logp/entropy: dense [B]
+ * outputs of hab_policy_evaluate called with the EXPERT actions.  weights/returns are (T+1,N) storage buffers gathered through rows[f]
+ * (NULL = dense).  With W = sum w, Wd = max(W, 1): bc_loss = sum w (-logp) / Wd, value_loss = mean 0.5 (v - ret)^2, ent = mean entropy,
+ * total = bc_loss + value_loss_coef value_loss - entropy_coef ent; d_logp = -w / Wd, d_value = value_loss_coef (v - ret) / B,
+ * d_entropy = -entropy_coef / B.  out12 = {value_loss, bc_loss, entropy, total, value_pred min/mean/max, expert_prob min/mean/max, W, B};
+ * expert_prob = exp(logp) over the frames with w > 0 (+inf, 0, -inf where there is none).  W == 0: bc_loss = 0, d_logp = 0. */
+int hab_bc_loss(const float* values, const float* logp, const float* entropy, const float* weights, const float* returns,
+                const int* rows, int B, float value_loss_coef, float entropy_coef, float* d_value, float* d_logp, float* d_entropy,
+                float* out12, hipStream_t stream);
+
 /* Adam step (torch.optim.Adam arithmetic, gradient first multiplied by grad_scale) + projection into [log_alpha_min, log_alpha_max] of
  * the adaptive entropy coefficient (rl/ppo/ppo.py:112-137,373-375). */
 int hab_lagrange_adam_step(float* log_alpha, float* exp_avg, float* exp_avg_sq, const float* grad, float grad_scale, float lr, float beta1,
