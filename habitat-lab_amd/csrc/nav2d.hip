@@ -13,6 +13,14 @@
 // nav2d_rearr_geo_step_kernel: two fields per env, one of which moves with the object) is specified by
 // tests/nav2d_rearr_geo_reference.py.  Nav2DSocial-v0 (a person who walks the graph's shortest paths, to be found and followed under
 // velocity control; nav2d_social_step_kernel, nav2d_social_build_kernel) is specified by tests/nav2d_social_reference.py.
+// The follower (nav2d_follow_kernel) and the pick-and-place oracle (nav2d_rearr_oracle_kernel) read the geodesic fields; their
+// specifications are tests/nav2d_follow_reference.py and tests/nav2d_rearr_oracle_reference.py.
+// What the tasks share is written once: the moves (discrete_move, vel_decode / vel_move, on a record or on a lane's MoveLane), the
+// end of a step (end_step_at for the point-goal and object tasks, rearr_end_step_at for the rearrangement tasks, close_episode under
+// the latter and under the social step), the sensors' frame (to_frame), the graph of the 32-node geodesic modes (GeoGraph and its
+// four helpers, which every build and every wave query goes through), the one-thread query (geo_query, on FreeBoxes) and the forward
+// search over headings (forward_search).  Two places keep statements of their own because the call changes the instructions of a
+// kernel that is held to them, and say so: end_step_at (close_episode's) and nav2d_rearr_step_kernel (discrete_move's).
 #include <cstddef>
 #include "hab_common.h"
 #include "../../include/habitat_amd.h"
@@ -121,17 +129,46 @@ __device__ inline float dist(float ax, float ay, float bx, float by) {
     const float dx = bx - ax, dy = by - ay;
     return sqrt_rn(dx * dx + dy * dy);
 }
+// The offset (dx, dy) in the frame of the heading whose direction is (c, sn): what every sensor that tells a position writes.
+__device__ inline void to_frame(float dx, float dy, float c, float sn, float& dot, float& cross) {
+    dot = dx * c + dy * sn;
+    cross = c * dy - sn * dx;
+}
+
+// The K inflated boxes -- is_free's expressions -- computed once into registers.  is_free reads the rectangles through the state
+// pointer, a memory latency per rectangle and test for the one wave that the 64 envs of a workgroup are; here the loops over k are
+// unrolled over MAX_K with the uniform k < K as a guard, so every index is static and a test is straight-line compares.  The
+// booleans are is_free's.
+struct FreeBoxes { float x0[MAX_K], y0[MAX_K], x1[MAX_K], y1[MAX_K]; };
+__device__ inline void load_free_boxes(FreeBoxes& b, const Nav2DState& s, int K) {
+#pragma unroll
+    for (int k = 0; k < MAX_K; ++k) {
+        if (k < K) {
+            b.x0[k] = s.rect[k][0] - RADIUS; b.y0[k] = s.rect[k][1] - RADIUS; b.x1[k] = s.rect[k][2] + RADIUS; b.y1[k] = s.rect[k][3] + RADIUS;
+        }
+    }
+}
+__device__ inline bool is_free_boxes(float x, float y, const FreeBoxes& b, int K) {
+    bool free = x >= LO && x <= HI && y >= LO && y <= HI;
+#pragma unroll
+    for (int k = 0; k < MAX_K; ++k)
+        if (k < K) free &= !((x > b.x0[k]) & (x < b.x1[k]) & (y > b.y0[k]) & (y < b.y1[k]));
+    return free;
+}
 
 // ---- geodesic distance (distance = "geodesic" of Nav2D-v0 and Nav2DVel-v0; specification: tests/nav2d_geo_reference.py) ------------
 // The field of one env's running episode (HAB_NAV2D_GEO_BYTES): D[4k + j] = the shortest-path length from corner j of obstacle k's
 // inflated box to the goal over the visibility graph of those corners, +inf for a corner that is no node; whether the start reached
-// the goal; the sweeps the build took; the steps of the episode at which the agent saw neither the goal nor a node.
+// the goal; the sweeps the build took; the steps of the episode at which the agent saw neither the goal nor a node.  Nav2DObj-v0's
+// field (HAB_NAV2D_OBJ_GEO_BYTES) is the same layout over its 64 nodes.
 constexpr int GEO_NODES = 4 * MAX_K;
 constexpr float GEO_E = 0.0009765625f;  // 2^-10: what a visibility box is shrunk by
-struct GeoField {
-    float D[GEO_NODES];
+template <int NODES>
+struct GeoFieldOf {
+    float D[NODES];
     int32_t reachable, sweeps, lost_steps, zero[5];
 };
+using GeoField = GeoFieldOf<GEO_NODES>;
 static_assert(sizeof(GeoField) == HAB_NAV2D_GEO_BYTES, "GeoField layout");
 static_assert(offsetof(GeoField, reachable) == 4 * HAB_NAV2D_GEO_W_REACHABLE && offsetof(GeoField, sweeps) == 4 * HAB_NAV2D_GEO_W_SWEEPS &&
               offsetof(GeoField, lost_steps) == 4 * HAB_NAV2D_GEO_W_LOST_STEPS, "GeoField layout");
@@ -141,12 +178,15 @@ __device__ inline void geo_corner(const Nav2DState& s, int k, int j, float& x, f
     x = (j & 1) ? s.rect[k][2] + RADIUS : s.rect[k][0] - RADIUS;
     y = (j & 2) ? s.rect[k][3] + RADIUS : s.rect[k][1] - RADIUS;
 }
-// Obstacle k's visibility box as centre and half extent per axis.
+// A visibility box as centre and half extent per axis: the inflated box (x0, y0) .. (x1, y1) shrunk by GEO_E; and obstacle k's.
 struct GeoBox { float cx, ex, cy, ey; };
-__device__ inline GeoBox geo_box(const Nav2DState& s, int k) {
-    const float lx = (s.rect[k][0] - RADIUS) + GEO_E, ly = (s.rect[k][1] - RADIUS) + GEO_E;
-    const float hx = (s.rect[k][2] + RADIUS) - GEO_E, hy = (s.rect[k][3] + RADIUS) - GEO_E;
+__device__ inline GeoBox geo_box(float x0, float y0, float x1, float y1) {
+    const float lx = x0 + GEO_E, ly = y0 + GEO_E;
+    const float hx = x1 - GEO_E, hy = y1 - GEO_E;
     return GeoBox{(lx + hx) * 0.5f, (hx - lx) * 0.5f, (ly + hy) * 0.5f, (hy - ly) * 0.5f};
+}
+__device__ inline GeoBox geo_box(const Nav2DState& s, int k) {
+    return geo_box(s.rect[k][0] - RADIUS, s.rect[k][1] - RADIUS, s.rect[k][2] + RADIUS, s.rect[k][3] + RADIUS);
 }
 // Whether the segment a-b meets the open box: the separating-axis test.
 __device__ inline bool geo_blocked(const GeoBox& b, float ax, float ay, float bx, float by) {
@@ -161,23 +201,19 @@ __device__ inline bool geo_visible(const GeoBox* boxes, int K, float ax, float a
         if (geo_blocked(boxes[k], ax, ay, bx, by)) return false;
     return true;
 }
-// geo(p) of one env by one thread: the goal if p sees it, and the nodes p sees, each with its field value.  The K inflated boxes and
-// visibility boxes are computed once into registers: the loops over k are unrolled over MAX_K with the uniform k < K as a guard, so
-// every index is static, and a visibility test is straight-line arithmetic over the boxes with no load and no branch in it: the
-// 64 envs of a workgroup are one wave, so a test that reads a box through the state pointer costs a memory latency each time.
+// geo(p) of one env by one thread: the goal if p sees it, and the nodes p sees, each with its field value.  The K inflated boxes
+// (FreeBoxes) and visibility boxes are computed once into registers, so a visibility test is straight-line arithmetic over the boxes
+// with no load and no branch in it.
 // p = (px, py) is the point the distance is taken from: the agent's position for the step kernels, a candidate's target for the
 // follower.  T = (tx, ty) is the target and D[GEO_NODES] the field towards it: the record's goal and GeoField::D for Nav2D-v0 and
-// Nav2DVel-v0 (the form below), the goal with DG or the object's place with DO for the rearrangement oracle.
+// Nav2DVel-v0, the goal with DG or the object's place with DO for the rearrangement oracle.
 __device__ inline float geo_query(const Nav2DState& s, const float* __restrict__ D, int K, float px, float py, float tx, float ty) {
-    float X0[MAX_K], Y0[MAX_K], X1[MAX_K], Y1[MAX_K];
+    FreeBoxes corner;
+    load_free_boxes(corner, s, K);
     GeoBox box[MAX_K];
 #pragma unroll
-    for (int k = 0; k < MAX_K; ++k) {
-        if (k < K) {
-            X0[k] = s.rect[k][0] - RADIUS; Y0[k] = s.rect[k][1] - RADIUS; X1[k] = s.rect[k][2] + RADIUS; Y1[k] = s.rect[k][3] + RADIUS;
-            box[k] = geo_box(s, k);
-        }
-    }
+    for (int k = 0; k < MAX_K; ++k)
+        if (k < K) box[k] = geo_box(corner.x0[k], corner.y0[k], corner.x1[k], corner.y1[k]);
     auto sees = [&](float x, float y) {
         bool blocked = false;
 #pragma unroll
@@ -189,19 +225,135 @@ __device__ inline float geo_query(const Nav2DState& s, const float* __restrict__
 #pragma unroll
     for (int k = 0; k < MAX_K; ++k) {
         if (k < K) {
+            const float x0 = corner.x0[k], y0 = corner.y0[k], x1 = corner.x1[k], y1 = corner.y1[k];
 #pragma unroll 1
             for (int j = 0; j < 4; ++j) {
                 const float Di = D[4 * k + j];
                 if (!(Di < INFINITY)) continue;
-                const float x = (j & 1) ? X1[k] : X0[k], y = (j & 2) ? Y1[k] : Y0[k];
+                const float x = (j & 1) ? x1 : x0, y = (j & 2) ? y1 : y0;
                 if (sees(x, y)) best = fminf(best, dist(px, py, x, y) + Di);
             }
         }
     }
     return best;
 }
-__device__ inline float geo_query(const Nav2DState& s, const GeoField& g, int K, float px, float py) {
-    return geo_query(s, g.D, K, px, py, s.gx, s.gy);
+
+// What one wavefront keeps in LDS of one env's graph: the 32 nodes, the K visibility boxes, the symmetric 32 x 32 weight matrix
+// (4 KiB) and two copies of D.  The nodes and boxes serve the queries; the weights and the two copies of D a build.
+struct GeoGraph {
+    float node_x[GEO_NODES], node_y[GEO_NODES];
+    int node_ok[GEO_NODES];
+    GeoBox boxes[MAX_K];
+    float W[GEO_NODES * GEO_NODES];
+    float D[2][GEO_NODES];
+};
+// The nodes (lane l < 32: node l), the diagonal of the weights and the K visibility boxes (lanes 32 ..); the caller puts the barrier
+// after it.
+__device__ inline void geo_graph_nodes(GeoGraph& G, const Nav2DState& s, int K, int lane) {
+    if (lane < GEO_NODES) {
+        float x = 0.0f, y = 0.0f;
+        bool ok = false;
+        if (lane < 4 * K) {
+            geo_corner(s, lane >> 2, lane & 3, x, y);
+            ok = is_free(x, y, s, K);
+        }
+        G.node_x[lane] = x; G.node_y[lane] = y; G.node_ok[lane] = ok ? 1 : 0;
+        G.W[lane * GEO_NODES + lane] = INFINITY;
+    } else if (lane - GEO_NODES < K) {
+        G.boxes[lane - GEO_NODES] = geo_box(s, lane - GEO_NODES);
+    }
+}
+// The symmetric weights; needs the nodes, and a barrier after it.  The 496 node pairs go round the lanes, 8 rounds: pair p lies in
+// rows a and 30 - a, which hold 32 pairs together (row 15 alone 16).
+__device__ inline void geo_graph_weights(GeoGraph& G, int K, int lane) {
+    for (int p = lane; p < GEO_NODES * (GEO_NODES - 1) / 2; p += 64) {
+        const int a = p >> 5, c = p & 31;
+        const int i = c < 31 - a ? a : 30 - a;
+        const int j = c < 31 - a ? a + 1 + c : i + 1 + (c - (31 - a));
+        float w = INFINITY;
+        if (G.node_ok[i] && G.node_ok[j] && geo_visible(G.boxes, K, G.node_x[i], G.node_y[i], G.node_x[j], G.node_y[j]))
+            w = dist(G.node_x[i], G.node_y[i], G.node_x[j], G.node_y[j]);
+        G.W[i * GEO_NODES + j] = w;
+        G.W[j * GEO_NODES + i] = w;
+    }
+}
+// One field by one wavefront, towards the target (tx, ty), over a graph whose nodes and weights are in LDS behind a barrier.  The 32
+// last hops take one lane each.  For the sweeps lane l owns half h = l & 1 of row i = l >> 1, its 16 weights in registers (read as
+// column i of rows 16 h + t: 32 banks, the two halves 2-way); a sweep reads D from one copy, joins the two halves of a row with one
+// lane exchange and writes the other copy, and the wave votes on whether any row changed.  Returns the sweeps; `Dl` is D[lane] on the
+// lanes below 32 and +inf on the others.  Uniform over the wave; ends behind a barrier, so that another field may follow.
+__device__ inline int geo_field_towards(GeoGraph& G, int K, float tx, float ty, int lane, float& Dl) {
+    if (lane < GEO_NODES) {
+        float d = INFINITY;
+        if (G.node_ok[lane] && geo_visible(G.boxes, K, G.node_x[lane], G.node_y[lane], tx, ty)) d = dist(G.node_x[lane], G.node_y[lane], tx, ty);
+        G.D[0][lane] = d;
+    }
+    __syncthreads();
+    const int row = lane >> 1, half = lane & 1;
+    float w[GEO_NODES / 2];
+#pragma unroll
+    for (int t = 0; t < GEO_NODES / 2; ++t) w[t] = G.W[(half * (GEO_NODES / 2) + t) * GEO_NODES + row];
+    int cur = 0, sweeps = 0;
+    while (sweeps < 4 * K) {  // the loop is uniform over the wave: K is an argument, the exit a vote
+        sweeps += 1;
+        float m = INFINITY;
+#pragma unroll
+        for (int t = 0; t < GEO_NODES / 2; ++t) m = fminf(m, w[t] + G.D[cur][half * (GEO_NODES / 2) + t]);
+        m = fminf(m, __shfl_xor(m, 1));
+        const float before = G.D[cur][row];
+        const float after = fminf(before, m);
+        if (half == 0) G.D[cur ^ 1][row] = after;
+        const bool changed = __ballot(after != before) != 0;
+        __syncthreads();
+        cur ^= 1;
+        if (!changed) break;
+    }
+    Dl = lane < GEO_NODES ? G.D[cur][lane] : INFINITY;
+    __syncthreads();
+    return sweeps;
+}
+// geo_T(x) by one wavefront: node l with its field value Dl on lane l < 32, the direct hop to the target T on lane 32, then the
+// minimum over the wave, which is exact and so the same as geo_query's serial one.  Needs the nodes and boxes in LDS.
+__device__ inline float geo_query_wave(const GeoGraph& G, int K, float x, float y, float tx, float ty, float Dl, int lane) {
+    float v = INFINITY;
+    if (lane < GEO_NODES) {
+        if (Dl < INFINITY && geo_visible(G.boxes, K, x, y, G.node_x[lane], G.node_y[lane])) v = dist(x, y, G.node_x[lane], G.node_y[lane]) + Dl;
+    } else if (lane == GEO_NODES) {
+        if (geo_visible(G.boxes, K, x, y, tx, ty)) v = dist(x, y, tx, ty);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+    return v;
+}
+
+// The field of one env per 64-thread workgroup (one wavefront).  Selected are the envs whose `mask` byte is set (NULL: all) and, with
+// `only_ended`, whose last step ended an episode; every other workgroup leaves before the first barrier.  The graph, the field towards
+// the goal, then g0 = geo(current position), which becomes the episode's first distance where it is finite.
+__global__ void __launch_bounds__(64)
+nav2d_geo_build_kernel(char* __restrict__ states, size_t state_stride, GeoField* __restrict__ geo, const uint8_t* __restrict__ mask,
+                       int only_ended, int K) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    if (mask && !mask[n]) return;
+    Nav2DState& s = *reinterpret_cast<Nav2DState*>(states + (size_t)n * state_stride);
+    if (only_ended && !s.ended) return;
+    __shared__ GeoGraph G;
+    geo_graph_nodes(G, s, K, lane);
+    __syncthreads();
+    geo_graph_weights(G, K, lane);
+    const float px = s.px, py = s.py, gx = s.gx, gy = s.gy;
+    __syncthreads();
+    float Dl;
+    const int sweeps = geo_field_towards(G, K, gx, gy, lane, Dl);
+    if (lane < GEO_NODES) geo[n].D[lane] = Dl;
+    const float v = geo_query_wave(G, K, px, py, gx, gy, Dl, lane);
+    if (lane == 0) {
+        const bool reachable = v < INFINITY;
+        geo[n].reachable = reachable ? 1 : 0;
+        geo[n].sweeps = sweeps;
+        geo[n].lost_steps = 0;
+        for (int z = 0; z < 5; ++z) geo[n].zero[z] = 0;
+        if (reachable) s.d_start = s.d_prev = v;
+    }
 }
 
 // A new episode's world.  GOAL (Nav2D-v0, Nav2DVel-v0): rectangles, their colours, the start, the goal, the heading, the distances and
@@ -248,23 +400,32 @@ __device__ inline void first_episode(Nav2DState& s, uint32_t seed, uint32_t env,
     begin_episode<GOAL>(s, seed, env, K, nh);
 }
 
-// What follows the move of one step, the same for every task: reward, step count, done, and on done the measures, their sums and
-// the next episode's world (`begin_episode<GOAL>`; the object task then adds its objects where `ended` is set).  `stop` is the
-// action's request to end the episode (STOP / both speeds below their minima), `success_dist` the task's success radius; the
-// distance is the one to (gx, gy).  A form that took the next world as a callable compiled to a velocity kernel whose distance was
-// that of the previous position; this form gives the Nav2D-v0 and Nav2DVel-v0 kernels the instructions they had before the object task.
-// GEO: `geo` is the env's field; in a reachable episode the distance is geo(p), and d_prev where p sees nothing (a lost step).
-template <bool GOAL = true, bool GEO = false>
-__device__ inline void end_step(Nav2DState& s, bool stop, float success_dist, float* __restrict__ reward, uint8_t* __restrict__ not_done,
-                                float* __restrict__ sums, uint32_t seed, uint32_t env, int n, int N, int K, int nh, int max_steps,
-                                GeoField* geo = nullptr) {
-    float d = dist(s.px, s.py, s.gx, s.gy);
-    if constexpr (GEO) {
-        if (geo->reachable) {
-            d = geo_query(s, *geo, K, s.px, s.py);
-            if (!(d < INFINITY)) { d = s.d_prev; geo->lost_steps += 1; }
-        }
-    }
+// What ends an episode in every task: the four measures of the episode, their sums, and the next episode's world
+// (`begin_episode<GOAL>`; a task with more than a world then adds its own where `ended` is set or right after this).
+template <bool GOAL>
+__device__ inline void close_episode(Nav2DState& s, float m0, float m1, float m2, float m3, float* __restrict__ sums, uint32_t seed,
+                                     uint32_t env, int n, int N, int K, int nh) {
+    s.last[0] = m0;
+    s.last[1] = m1;
+    s.last[2] = m2;
+    s.last[3] = m3;
+    if (sums)
+        for (int m = 0; m < 4; ++m) sums[(size_t)m * N + n] = sums[(size_t)m * N + n] + s.last[m];
+    s.episode += 1;
+    begin_episode<GOAL>(s, seed, env, K, nh);
+}
+
+// What follows the move of one step of the point-goal and object tasks, given the distance `d` of the new position: reward, step
+// count, done, and on done the measures, their sums and the next episode's world (the object task then adds its objects where
+// `ended` is set).  `stop` is the action's request to end the episode (STOP / both speeds below their minima), `success_dist` the
+// task's success radius.  The statements of close_episode are written out here and not called: with the call, the Nav2D-v0,
+// Nav2DVel-v0 and Nav2DObj-v0 step kernels are no longer the instructions they were, and two earlier forms of sharing in this
+// function (the distance computed by the kernel and the next world begun by it; the next world as a callable) compiled to a velocity
+// kernel whose distance was that of the previous position.  Whoever changes this function compares those kernels' code.
+template <bool GOAL>
+__device__ inline void end_step_at(Nav2DState& s, float d, bool stop, float success_dist, float* __restrict__ reward,
+                                   uint8_t* __restrict__ not_done, float* __restrict__ sums, uint32_t seed, uint32_t env, int n, int N,
+                                   int K, int nh, int max_steps) {
     const bool success = stop && (d < success_dist);
     reward[n] = (-0.01f + (s.d_prev - d)) + (success ? 2.5f : 0.0f);
     s.d_prev = d;
@@ -283,12 +444,42 @@ __device__ inline void end_step(Nav2DState& s, bool stop, float success_dist, fl
         begin_episode<GOAL>(s, seed, env, K, nh);
     }
 }
+// The distance to (gx, gy) of the new position, then end_step_at.  GEO: `geo` is the env's field; in a reachable episode the
+// distance is geo(p), and d_prev where p sees nothing (a lost step).
+template <bool GOAL = true, bool GEO = false>
+__device__ inline void end_step(Nav2DState& s, bool stop, float success_dist, float* __restrict__ reward, uint8_t* __restrict__ not_done,
+                                float* __restrict__ sums, uint32_t seed, uint32_t env, int n, int N, int K, int nh, int max_steps,
+                                GeoField* geo = nullptr) {
+    float d = dist(s.px, s.py, s.gx, s.gy);
+    if constexpr (GEO) {
+        if (geo->reachable) {
+            d = geo_query(s, geo->D, K, s.px, s.py, s.gx, s.gy);
+            if (!(d < INFINITY)) { d = s.d_prev; geo->lost_steps += 1; }
+        }
+    }
+    end_step_at<GOAL>(s, d, stop, success_dist, reward, not_done, sums, seed, env, n, N, K, nh, max_steps);
+}
+
+// The move of a discrete action: FORWARD under the task's free test `free(x, y)`, TURN_LEFT, TURN_RIGHT; every other action moves
+// nothing.  S: a record, or a lane's copy of the words a move changes.
+template <class S, class Free>
+__device__ inline void discrete_move(S& s, int64_t a, const float* __restrict__ dirs, int nh, Free free) {
+    if (a == 1) {
+        const float nx = s.px + FORWARD * dirs[2 * s.heading], ny = s.py + FORWARD * dirs[2 * s.heading + 1];
+        if (free(nx, ny)) { s.px = nx; s.py = ny; s.path = s.path + FORWARD; }
+        else s.collisions += 1;
+    } else if (a == 2) {
+        s.heading = (s.heading + 1) % nh;
+    } else if (a == 3) {
+        s.heading = (s.heading + nh - 1) % nh;
+    }
+}
 
 // pointgoal_with_gps_compass of the current state.
 __device__ inline void write_goal(const Nav2DState& s, const float* __restrict__ dirs, float* __restrict__ goal, int n) {
     const float c = dirs[2 * s.heading], sn = dirs[2 * s.heading + 1];
-    const float dx = s.gx - s.px, dy = s.gy - s.py;
-    const float dot = dx * c + dy * sn, cross = c * dy - sn * dx;
+    float dot, cross;
+    to_frame(s.gx - s.px, s.gy - s.py, c, sn, dot, cross);
     goal[2 * n + 0] = dist(s.px, s.py, s.gx, s.gy);
     goal[2 * n + 1] = atan2f(cross, dot);
 }
@@ -308,15 +499,7 @@ __global__ void __launch_bounds__(GEO ? 64 : 1024) nav2d_step_kernel(Nav2DState*
         first_episode(s, seed, env, K, nh);
     } else {
         const int64_t a = actions[n];  // anything outside 0..3 moves nothing (the host-side entry points refuse it)
-        if (a == 1) {
-            const float nx = s.px + FORWARD * dirs[2 * s.heading], ny = s.py + FORWARD * dirs[2 * s.heading + 1];
-            if (is_free(nx, ny, s, K)) { s.px = nx; s.py = ny; s.path = s.path + FORWARD; }
-            else s.collisions += 1;
-        } else if (a == 2) {
-            s.heading = (s.heading + 1) % nh;
-        } else if (a == 3) {
-            s.heading = (s.heading + nh - 1) % nh;
-        }
+        discrete_move(s, a, dirs, nh, [&](float x, float y) { return is_free(x, y, s, K); });
         end_step<true, GEO>(s, a == 0, 0.2f, reward, not_done, sums, seed, env, n, N, K, nh, max_steps, GEO ? geo + n : nullptr);
     }
     if (goal) write_goal(s, dirs, goal, n);
@@ -351,6 +534,17 @@ __device__ inline void vel_move(S& s, const float* __restrict__ dirs, float l, i
         }
     }
 }
+// What a move changes of a record, as a lane's own copy in registers: the members discrete_move and vel_move read and write.  In a
+// kernel of one wavefront per env every lane derives the move on its copy, from the same loads, and lane 0 writes it back.
+struct MoveLane {
+    float px, py, path;
+    int32_t heading, collisions;
+};
+__device__ inline MoveLane load_move(const Nav2DState& s) { return MoveLane{s.px, s.py, s.path, s.heading, s.collisions}; }
+template <class L>
+__device__ inline void store_move(Nav2DState& s, const L& m) {
+    s.px = m.px; s.py = m.py; s.path = m.path; s.heading = m.heading; s.collisions = m.collisions;
+}
 
 template <bool GEO>
 __global__ void __launch_bounds__(GEO ? 64 : 1024) nav2d_vel_step_kernel(Nav2DState* __restrict__ states, const float* __restrict__ dirs, const float2* __restrict__ actions,
@@ -373,97 +567,6 @@ __global__ void __launch_bounds__(GEO ? 64 : 1024) nav2d_vel_step_kernel(Nav2DSt
         end_step<true, GEO>(s, stop, 0.2f, reward, not_done, sums, seed, env, n, N, K, nh, max_steps, GEO ? geo + n : nullptr);
     }
     if (goal) write_goal(s, dirs, goal, n);
-}
-
-// The field of one env per 64-thread workgroup (one wavefront).  Selected are the envs whose `mask` byte is set (NULL: all) and, with
-// `only_ended`, whose last step ended an episode; every other workgroup leaves before the first barrier.  LDS: the 32 nodes, the K
-// visibility boxes, the symmetric 32 x 32 weight matrix (4 KiB) and two copies of D.  The 496 node pairs go round the lanes, 8 rounds;
-// the 32 last hops take one lane each.  For the sweeps lane l owns half h = l & 1 of row i = l >> 1, its 16 weights in registers
-// (read as column i of rows 16 h + t: 32 banks, the two halves 2-way); a sweep reads D from one copy, joins the two halves of a row
-// with one lane exchange and writes the other copy, and the wave votes on whether any row changed.  The query of the current
-// position takes one node per lane and a wave-wide minimum, which is exact and so the same as the step kernels' serial one.
-__global__ void __launch_bounds__(64)
-nav2d_geo_build_kernel(char* __restrict__ states, size_t state_stride, GeoField* __restrict__ geo, const uint8_t* __restrict__ mask,
-                       int only_ended, int K) {
-    const int n = blockIdx.x, lane = threadIdx.x;
-    if (mask && !mask[n]) return;
-    Nav2DState& s = *reinterpret_cast<Nav2DState*>(states + (size_t)n * state_stride);
-    if (only_ended && !s.ended) return;
-    __shared__ float node_x[GEO_NODES], node_y[GEO_NODES];
-    __shared__ int node_ok[GEO_NODES];
-    __shared__ GeoBox boxes[MAX_K];
-    __shared__ float W[GEO_NODES * GEO_NODES];
-    __shared__ float D[2][GEO_NODES];
-    if (lane < GEO_NODES) {
-        float x = 0.0f, y = 0.0f;
-        bool ok = false;
-        if (lane < 4 * K) {
-            geo_corner(s, lane >> 2, lane & 3, x, y);
-            ok = is_free(x, y, s, K);
-        }
-        node_x[lane] = x; node_y[lane] = y; node_ok[lane] = ok ? 1 : 0;
-        W[lane * GEO_NODES + lane] = INFINITY;
-    } else if (lane - GEO_NODES < K) {
-        boxes[lane - GEO_NODES] = geo_box(s, lane - GEO_NODES);
-    }
-    __syncthreads();
-    // pair p of the 496: rows a and 30 - a hold 32 pairs together (row 15 alone 16)
-    for (int p = lane; p < GEO_NODES * (GEO_NODES - 1) / 2; p += 64) {
-        const int a = p >> 5, c = p & 31;
-        const int i = c < 31 - a ? a : 30 - a;
-        const int j = c < 31 - a ? a + 1 + c : i + 1 + (c - (31 - a));
-        float w = INFINITY;
-        if (node_ok[i] && node_ok[j] && geo_visible(boxes, K, node_x[i], node_y[i], node_x[j], node_y[j]))
-            w = dist(node_x[i], node_y[i], node_x[j], node_y[j]);
-        W[i * GEO_NODES + j] = w;
-        W[j * GEO_NODES + i] = w;
-    }
-    const float gx = s.gx, gy = s.gy;
-    if (lane < GEO_NODES) {
-        float d = INFINITY;
-        if (node_ok[lane] && geo_visible(boxes, K, node_x[lane], node_y[lane], gx, gy)) d = dist(node_x[lane], node_y[lane], gx, gy);
-        D[0][lane] = d;
-    }
-    __syncthreads();
-    const int row = lane >> 1, half = lane & 1;
-    float w[GEO_NODES / 2];
-#pragma unroll
-    for (int t = 0; t < GEO_NODES / 2; ++t) w[t] = W[(half * (GEO_NODES / 2) + t) * GEO_NODES + row];
-    int cur = 0, sweeps = 0;
-    while (sweeps < 4 * K) {  // the loop is uniform over the wave: K is an argument, the exit a vote
-        sweeps += 1;
-        float m = INFINITY;
-#pragma unroll
-        for (int t = 0; t < GEO_NODES / 2; ++t) m = fminf(m, w[t] + D[cur][half * (GEO_NODES / 2) + t]);
-        m = fminf(m, __shfl_xor(m, 1));
-        const float before = D[cur][row];
-        const float after = fminf(before, m);
-        if (half == 0) D[cur ^ 1][row] = after;
-        const bool changed = __ballot(after != before) != 0;
-        __syncthreads();
-        cur ^= 1;
-        if (!changed) break;
-    }
-    // g0 = geo(current position): the goal on lane 32, node l on lane l
-    const float px = s.px, py = s.py;
-    float v = INFINITY;
-    if (lane < GEO_NODES) {
-        const float Di = D[cur][lane];
-        geo[n].D[lane] = Di;
-        if (Di < INFINITY && geo_visible(boxes, K, px, py, node_x[lane], node_y[lane])) v = dist(px, py, node_x[lane], node_y[lane]) + Di;
-    } else if (lane == GEO_NODES) {
-        if (geo_visible(boxes, K, px, py, gx, gy)) v = dist(px, py, gx, gy);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    if (lane == 0) {
-        const bool reachable = v < INFINITY;
-        geo[n].reachable = reachable ? 1 : 0;
-        geo[n].sweeps = sweeps;
-        geo[n].lost_steps = 0;
-        for (int z = 0; z < 5; ++z) geo[n].zero[z] = 0;
-        if (reachable) s.d_start = s.d_prev = v;
-    }
 }
 
 // ---- the shortest-path follower of Nav2D-v0 and Nav2DVel-v0 (specification: tests/nav2d_follow_reference.py) -----------------------
@@ -504,12 +607,34 @@ __device__ inline unsigned long long wave_min_key(unsigned long long key) {
     return key;
 }
 
-// One env per 64-thread workgroup (one wavefront), selected by `mask` (NULL: all); lane = candidate heading, the lanes stride over
-// the nh headings by 64.  State and field are read only, through pointers that are uniform over the wave.  A lane's candidate is the
-// target p' of a forward at its heading; where p' is free it runs the straight-line query of the step kernels at p'.  A valid
-// candidate (v finite and below D_PREV) has the 64-bit key v's bits << 32 | |delta| << 1 | (delta < 0): v is not negative, so the
-// bit patterns order like the floats, and the least key is the lowest value, then the fewest turns, then left.  One wave-wide
-// minimum; lane 0 writes the action, next_d and status.
+// The forward search of the follower and of the oracle, by one wavefront: lane = candidate heading, the lanes stride over the nh
+// headings by 64.  A lane's candidate is the target p' of a forward at its heading; where p' is free under the task's test
+// `free(x, y)` it runs the straight-line query of the step kernels at p', towards T = (tx, ty) over the field D.  A valid candidate
+// (v finite and below `bound`) has the 64-bit key v's bits << 32 | |delta| << 1 | (delta < 0): v is not negative, so the bit patterns
+// order like the floats, and the least key is the lowest value, then the fewest turns, then left.  Returns the least key of the
+// wave, NO_KEY where no candidate is valid.  Everything but `lane` is uniform over the wave.
+constexpr unsigned long long NO_KEY = ~0ull;
+template <class Free>
+__device__ inline unsigned long long forward_search(const Nav2DState& s, const float* __restrict__ D, const float* __restrict__ dirs, int K,
+                                                    int nh, float tx, float ty, float bound, int lane, Free free) {
+    const float px = s.px, py = s.py;
+    const int heading = s.heading;
+    unsigned long long key = NO_KEY;
+    for (int h0 = 0; h0 < nh; h0 += 64) {  // uniform over the wave
+        const int h = h0 + lane;
+        if (h >= nh) continue;
+        const float nx = px + FORWARD * dirs[2 * h], ny = py + FORWARD * dirs[2 * h + 1];
+        if (!free(nx, ny)) continue;
+        const float v = geo_query(s, D, K, nx, ny, tx, ty);
+        if (!(v < INFINITY && v < bound)) continue;
+        const unsigned long long k = ((unsigned long long)__float_as_uint(v) << 32) | turn_key(h, heading, nh);
+        key = k < key ? k : key;
+    }
+    return wave_min_key(key);
+}
+
+// One env per 64-thread workgroup (one wavefront), selected by `mask` (NULL: all).  State and field are read only, through pointers
+// that are uniform over the wave.  The forward search towards the goal below D_PREV; lane 0 writes the action, next_d and status.
 template <class Writer>
 __global__ void __launch_bounds__(64)
 nav2d_follow_kernel(const char* __restrict__ states, size_t state_stride, const GeoField* __restrict__ geo, const float* __restrict__ dirs,
@@ -528,22 +653,9 @@ nav2d_follow_kernel(const char* __restrict__ states, size_t state_stride, const 
         st = HAB_NAV2D_FOLLOW_ARRIVED;
         nd = d_prev;
     } else {
-        const float px = s.px, py = s.py;
-        const int heading = s.heading;
-        constexpr unsigned long long NONE = ~0ull;
-        unsigned long long key = NONE;
-        for (int h0 = 0; h0 < nh; h0 += 64) {  // uniform over the wave
-            const int h = h0 + lane;
-            if (h >= nh) continue;
-            const float nx = px + FORWARD * dirs[2 * h], ny = py + FORWARD * dirs[2 * h + 1];
-            if (!is_free(nx, ny, s, K)) continue;
-            const float v = geo_query(s, g, K, nx, ny);
-            if (!(v < INFINITY && v < d_prev)) continue;
-            const unsigned long long k = ((unsigned long long)__float_as_uint(v) << 32) | turn_key(h, heading, nh);
-            key = k < key ? k : key;
-        }
-        key = wave_min_key(key);
-        if (key == NONE) {
+        const unsigned long long key =
+            forward_search(s, g.D, dirs, K, nh, s.gx, s.gy, d_prev, lane, [&](float x, float y) { return is_free(x, y, s, K); });
+        if (key == NO_KEY) {
             st = HAB_NAV2D_FOLLOW_STUCK;
         } else {
             st = HAB_NAV2D_FOLLOW_GO;
@@ -635,8 +747,20 @@ __device__ void place_objects(Nav2DObjState& s, uint32_t seed, uint32_t env, int
     s.base.d_start = s.base.d_prev = nearest_target(s, M);
 }
 
-// One thread per env, as nav2d_step_kernel.  Then objectgoal, gps (the offset from the start in the start heading's frame, written
-// term by term like write_goal's dot and cross) and compass (a row of the host table).
+// The three 1-D sensors: objectgoal, gps (the offset from the start in the start heading's frame) and compass (a row of the host
+// table).
+__device__ inline void obj_write_sensors(const Nav2DObjState& o, const float* __restrict__ dirs, const float* __restrict__ ctab,
+                                         int64_t* __restrict__ objectgoal, float* __restrict__ gps, float* __restrict__ compass, int n, int nh) {
+    const Nav2DState& s = o.base;
+    if (objectgoal) objectgoal[n] = (int64_t)o.target;
+    if (gps) {
+        const float c = dirs[2 * o.h0], sn = dirs[2 * o.h0 + 1];
+        to_frame(s.px - o.sx, s.py - o.sy, c, sn, gps[2 * n + 0], gps[2 * n + 1]);
+    }
+    if (compass) compass[n] = ctab[(s.heading - o.h0 + nh) % nh];
+}
+
+// One thread per env, as nav2d_step_kernel.  Then the sensors.
 __global__ void nav2d_obj_step_kernel(Nav2DObjState* __restrict__ states, const float* __restrict__ dirs, const float* __restrict__ ctab,
                                       const int64_t* __restrict__ actions, const uint8_t* __restrict__ mask,
                                       int64_t* __restrict__ objectgoal, float* __restrict__ gps, float* __restrict__ compass,
@@ -652,27 +776,12 @@ __global__ void nav2d_obj_step_kernel(Nav2DObjState* __restrict__ states, const 
         place_objects(o, seed, env, K, M, C);
     } else {
         const int64_t a = actions[n];  // 4, 5 (LOOK_UP, LOOK_DOWN) and anything outside 0..5 move nothing
-        if (a == 1) {
-            const float nx = s.px + FORWARD * dirs[2 * s.heading], ny = s.py + FORWARD * dirs[2 * s.heading + 1];
-            if (is_free_obj(nx, ny, o, K, M)) { s.px = nx; s.py = ny; s.path = s.path + FORWARD; }
-            else s.collisions += 1;
-        } else if (a == 2) {
-            s.heading = (s.heading + 1) % nh;
-        } else if (a == 3) {
-            s.heading = (s.heading + nh - 1) % nh;
-        }
+        discrete_move(s, a, dirs, nh, [&](float x, float y) { return is_free_obj(x, y, o, K, M); });
         nearest_target(o, M);  // (gx, gy) of this step, which end_step measures the distance to
         end_step<false>(s, a == 0, OBJ_SUCCESS, reward, not_done, sums, seed, env, n, N, K, nh, max_steps);
         if (s.ended) place_objects(o, seed, env, K, M, C);
     }
-    if (objectgoal) objectgoal[n] = (int64_t)o.target;
-    if (gps) {
-        const float c = dirs[2 * o.h0], sn = dirs[2 * o.h0 + 1];
-        const float dx = s.px - o.sx, dy = s.py - o.sy;
-        gps[2 * n + 0] = dx * c + dy * sn;
-        gps[2 * n + 1] = c * dy - sn * dx;
-    }
-    if (compass) compass[n] = ctab[(s.heading - o.h0 + nh) % nh];
+    obj_write_sensors(o, dirs, ctab, objectgoal, gps, compass, n, nh);
 }
 
 // ---- Nav2DRearr-v0 (Nav2DRearrVectorEnv; specification: tests/nav2d_rearr_reference.py) ------------------------------------------------
@@ -732,16 +841,13 @@ __device__ inline void rearr_place(R& r, float c, float sn, int K) {
         r.invalid += 1;
     }
 }
-// The end of the step: a held object travels with the agent; then end_step's, with the potential in the distance's place, the pick
-// bonus and this task's measures.  `stop` is the action's request to end the episode.  Forced inline: left to itself the compiler
-// makes it a call from both kernels, and the discrete kernel would no longer be the code it was.
-__device__ __forceinline__ void rearr_end_step(Nav2DRearrState& r, bool stop, bool first_pick, float* __restrict__ reward, uint8_t* __restrict__ not_done,
-                                      float* __restrict__ sums, uint32_t seed, uint32_t env, int n, int N, int K, int nh, int max_steps,
-                                      int start_holding) {
+// What follows the move of one step of this task, given the potential `phi` and its second term `b`: end_step_at's, with the
+// potential in the distance's place, the pick bonus and this task's measures.  `stop` is the action's request to end the episode.
+// Forced inline, as is rearr_end_step: left to itself the compiler makes it a call from both Euclidean kernels.
+__device__ __forceinline__ void rearr_end_step_at(Nav2DRearrState& r, float phi, float b, bool stop, bool first_pick, float* __restrict__ reward,
+                                                  uint8_t* __restrict__ not_done, float* __restrict__ sums, uint32_t seed, uint32_t env, int n,
+                                                  int N, int K, int nh, int max_steps, int start_holding) {
     Nav2DState& s = r.base;
-    if (r.holding) { r.ox = s.px; r.oy = s.py; }
-    float b;
-    const float phi = rearr_potential(r, b);
     const bool success = stop && !r.holding && b < REARR_SUCCESS;
     reward[n] = ((-0.01f + (s.d_prev - phi)) + (first_pick ? 1.0f : 0.0f)) + (success ? 2.5f : 0.0f);
     s.d_prev = phi;
@@ -750,33 +856,26 @@ __device__ __forceinline__ void rearr_end_step(Nav2DRearrState& r, bool stop, bo
     not_done[n] = done ? 0 : 1;
     s.ended = done ? 1 : 0;
     if (done) {
-        s.last[0] = success ? 1.0f : 0.0f;
-        s.last[1] = (float)r.held;
-        s.last[2] = b;
-        s.last[3] = (float)s.collisions;
-        if (sums)
-            for (int m = 0; m < 4; ++m) sums[(size_t)m * N + n] = sums[(size_t)m * N + n] + s.last[m];
-        s.episode += 1;
-        begin_episode<false>(s, seed, env, K, nh);
+        close_episode<false>(s, success ? 1.0f : 0.0f, (float)r.held, b, (float)s.collisions, sums, seed, env, n, N, K, nh);
         rearr_begin(r, seed, env, K, start_holding);
     }
 }
-// The three vector sensors: the object's start and the goal as (dot, cross) in the heading's frame, written term by term like
-// write_goal's, and the holding flag.
+// The end of a Euclidean step: a held object travels with the agent; then the potential of the straight lines, and the rest.
+__device__ __forceinline__ void rearr_end_step(Nav2DRearrState& r, bool stop, bool first_pick, float* __restrict__ reward, uint8_t* __restrict__ not_done,
+                                               float* __restrict__ sums, uint32_t seed, uint32_t env, int n, int N, int K, int nh, int max_steps,
+                                               int start_holding) {
+    if (r.holding) { r.ox = r.base.px; r.oy = r.base.py; }
+    float b;
+    const float phi = rearr_potential(r, b);
+    rearr_end_step_at(r, phi, b, stop, first_pick, reward, not_done, sums, seed, env, n, N, K, nh, max_steps, start_holding);
+}
+// The three vector sensors: the object's start and the goal in the heading's frame, and the holding flag.
 __device__ inline void rearr_write_sensors(const Nav2DRearrState& r, const float* __restrict__ dirs, float* __restrict__ obj_start,
                                            float* __restrict__ obj_goal, float* __restrict__ is_holding, int n) {
     const Nav2DState& s = r.base;
     const float c = dirs[2 * s.heading], sn = dirs[2 * s.heading + 1];
-    if (obj_start) {
-        const float dx = r.obj[0][0] - s.px, dy = r.obj[0][1] - s.py;
-        obj_start[2 * n + 0] = dx * c + dy * sn;
-        obj_start[2 * n + 1] = c * dy - sn * dx;
-    }
-    if (obj_goal) {
-        const float dx = s.gx - s.px, dy = s.gy - s.py;
-        obj_goal[2 * n + 0] = dx * c + dy * sn;
-        obj_goal[2 * n + 1] = c * dy - sn * dx;
-    }
+    if (obj_start) to_frame(r.obj[0][0] - s.px, r.obj[0][1] - s.py, c, sn, obj_start[2 * n + 0], obj_start[2 * n + 1]);
+    if (obj_goal) to_frame(s.gx - s.px, s.gy - s.py, c, sn, obj_goal[2 * n + 0], obj_goal[2 * n + 1]);
     if (is_holding) is_holding[n] = (float)r.holding;
 }
 
@@ -798,6 +897,8 @@ __global__ void nav2d_rearr_step_kernel(Nav2DRearrState* __restrict__ states, co
         const int64_t a = actions[n];  // anything outside 0..5 moves nothing (the host-side entry points refuse it)
         const float c = dirs[2 * s.heading], sn = dirs[2 * s.heading + 1];
         bool first_pick = false;
+        // discrete_move's statements, written out: through the call, with this task's free test, the kernel is no longer the
+        // instructions it was (14 lines of mask arithmetic round the test), and this is one of the kernels held to that
         if (a == 1) {
             const float nx = s.px + FORWARD * c, ny = s.py + FORWARD * sn;
             if (rearr_is_free(nx, ny, r, K)) { s.px = nx; s.py = ny; s.path = s.path + FORWARD; }
@@ -821,28 +922,7 @@ __global__ void nav2d_rearr_step_kernel(Nav2DRearrState* __restrict__ states, co
 // 12-byte row of an (N, 3) float32 tensor, read as three scalars: a row is 4-byte aligned and no more.  The motion is vel_decode /
 // vel_move with this task's free test; then, on every step, the grip with the new position and heading: c_grip > 0 with empty hands
 // is a PICK attempt, c_grip < 0 while holding a PLACE attempt, every other combination nothing; then Nav2DRearr-v0's end of the step
-// with the velocity stop in STOP's place.
-// A step of this task tests up to three positions, and is_free reads the rectangles through the state pointer, a memory latency per
-// rectangle and test for the one wave that the 64 envs of a workgroup are.  So the K inflated boxes -- is_free's expressions -- are
-// computed once into registers, the loops over k unrolled over MAX_K with the uniform k < K as a guard as in geo_query, and a test is
-// straight-line compares.  The booleans are is_free's.
-struct FreeBoxes { float x0[MAX_K], y0[MAX_K], x1[MAX_K], y1[MAX_K]; };
-__device__ inline void load_free_boxes(FreeBoxes& b, const Nav2DState& s, int K) {
-#pragma unroll
-    for (int k = 0; k < MAX_K; ++k) {
-        if (k < K) {
-            b.x0[k] = s.rect[k][0] - RADIUS; b.y0[k] = s.rect[k][1] - RADIUS; b.x1[k] = s.rect[k][2] + RADIUS; b.y1[k] = s.rect[k][3] + RADIUS;
-        }
-    }
-}
-__device__ inline bool is_free_boxes(float x, float y, const FreeBoxes& b, int K) {
-    bool free = x >= LO && x <= HI && y >= LO && y <= HI;
-#pragma unroll
-    for (int k = 0; k < MAX_K; ++k)
-        if (k < K) free &= !((x > b.x0[k]) & (x < b.x1[k]) & (y > b.y0[k]) & (y < b.y1[k]));
-    return free;
-}
-
+// with the velocity stop in STOP's place.  A step of this task tests up to three positions, so it tests them on FreeBoxes.
 __global__ void __launch_bounds__(64)
 nav2d_rearr_vel_step_kernel(Nav2DRearrState* __restrict__ states, const float* __restrict__ dirs, const float* __restrict__ actions,
                             const uint8_t* __restrict__ mask, float* __restrict__ obj_start, float* __restrict__ obj_goal,
@@ -884,13 +964,10 @@ nav2d_rearr_vel_step_kernel(Nav2DRearrState* __restrict__ states, const float* _
 // The distance to the nearest instance of the target category along the shortest path.  Obstacles of the graph: the K rectangles
 // grown by the agent radius and, for each object, the bounding square of its keep-out disc, up to 16 boxes; 64 nodes, 4k + j corner j
 // of rectangle box k, 32 + 4m + j corner j of object m's square; targets, the centres of the objects of the target category, each
-// seen through its own square.  The field of one env's running episode (HAB_NAV2D_OBJ_GEO_BYTES) is laid out like GeoField.
+// seen through its own square.  The field of one env's running episode (HAB_NAV2D_OBJ_GEO_BYTES) is GeoField's layout over 64 nodes.
 constexpr int OBJ_GEO_NODES = GEO_NODES + 4 * MAX_M, OBJ_GEO_BOXES = MAX_K + MAX_M;
 static_assert(OBJ_GEO_NODES == 64, "one node per lane of a wavefront");
-struct ObjGeoField {
-    float D[OBJ_GEO_NODES];
-    int32_t reachable, sweeps, lost_steps, zero[5];
-};
+using ObjGeoField = GeoFieldOf<OBJ_GEO_NODES>;
 static_assert(sizeof(ObjGeoField) == HAB_NAV2D_OBJ_GEO_BYTES, "ObjGeoField layout");
 static_assert(offsetof(ObjGeoField, reachable) == 4 * HAB_NAV2D_OBJ_GEO_W_REACHABLE &&
               offsetof(ObjGeoField, sweeps) == 4 * HAB_NAV2D_OBJ_GEO_W_SWEEPS &&
@@ -910,11 +987,9 @@ __device__ inline bool obj_geo_node(const Nav2DObjState& o, int i, int K, int M,
     y = (j & 2) ? o.obj[m][1] + OBJ_BLOCK : o.obj[m][1] - OBJ_BLOCK;
     return true;
 }
-// Object m's visibility box: its square shrunk by GEO_E, with geo_box's expressions.
+// Object m's visibility box: its square shrunk by GEO_E.
 __device__ inline GeoBox obj_geo_box(const Nav2DObjState& o, int m) {
-    const float lx = (o.obj[m][0] - OBJ_BLOCK) + GEO_E, ly = (o.obj[m][1] - OBJ_BLOCK) + GEO_E;
-    const float hx = (o.obj[m][0] + OBJ_BLOCK) - GEO_E, hy = (o.obj[m][1] + OBJ_BLOCK) - GEO_E;
-    return GeoBox{(lx + hx) * 0.5f, (hx - lx) * 0.5f, (ly + hy) * 0.5f, (hy - ly) * 0.5f};
+    return geo_box(o.obj[m][0] - OBJ_BLOCK, o.obj[m][1] - OBJ_BLOCK, o.obj[m][0] + OBJ_BLOCK, o.obj[m][1] + OBJ_BLOCK);
 }
 // The K + M visibility boxes into the wave's LDS array, rectangles first; the caller puts the barrier after it.
 __device__ inline void obj_geo_fill_boxes(GeoBox* boxes, const Nav2DObjState& o, int K, int M, int lane) {
@@ -948,7 +1023,7 @@ __device__ inline float obj_geo_query(const Nav2DObjState& o, const GeoBox* boxe
 // bitwise symmetric in their two points -- and written to both places: a lane that computed its own row of 63 would run twice the
 // visibility tests, and they are what the kernel's time is.  The pairs go round the lanes in 32 rounds: rows a and 62 - a hold 64
 // pairs together, row 31 alone 32.  A sweep is 64 add / min per lane on its column of the matrix (row j of the array is one dword
-// per lane: no bank conflict) and D (a broadcast read), the two copies of D as in nav2d_geo_build_kernel, then a wave vote.
+// per lane: no bank conflict) and D (a broadcast read), the two copies of D as in geo_field_towards, then a wave vote.
 __global__ void __launch_bounds__(64)
 nav2d_obj_geo_build_kernel(char* __restrict__ states, size_t state_stride, ObjGeoField* __restrict__ geo, const uint8_t* __restrict__ mask,
                            int only_ended, int K, int M) {
@@ -1017,36 +1092,10 @@ nav2d_obj_geo_build_kernel(char* __restrict__ states, size_t state_stride, ObjGe
     }
 }
 
-// end_step for the geodesic object step, which has its distance already: a function of its own beside end_step's instantiations,
-// whose arguments stay as they are (see the comment above end_step).  Then the next world's objects, as nav2d_obj_step_kernel.
-__device__ inline void obj_geo_end_step(Nav2DObjState& o, float d, bool stop, float* __restrict__ reward, uint8_t* __restrict__ not_done,
-                                        float* __restrict__ sums, uint32_t seed, uint32_t env, int n, int N, int K, int nh, int max_steps,
-                                        int M, int C) {
-    Nav2DState& s = o.base;
-    const bool success = stop && (d < OBJ_SUCCESS);
-    reward[n] = (-0.01f + (s.d_prev - d)) + (success ? 2.5f : 0.0f);
-    s.d_prev = d;
-    s.steps += 1;
-    const bool done = stop || (s.steps >= max_steps);
-    not_done[n] = done ? 0 : 1;
-    s.ended = done ? 1 : 0;
-    if (done) {
-        s.last[0] = success ? 1.0f : 0.0f;
-        s.last[1] = success ? __fdiv_rn(s.d_start, fmaxf(s.d_start, s.path)) : 0.0f;
-        s.last[2] = d;
-        s.last[3] = (float)s.collisions;
-        if (sums)
-            for (int m = 0; m < 4; ++m) sums[(size_t)m * N + n] = sums[(size_t)m * N + n] + s.last[m];
-        s.episode += 1;
-        begin_episode<false>(s, seed, env, K, nh);
-        place_objects(o, seed, env, K, M, C);
-    }
-}
-
-// The geodesic form of the object step: one wavefront (a 64-thread workgroup) per env.  Every lane works out the move from the same
-// loads, so the new position is uniform and lane 0 alone writes it; the query of that position takes one node per lane plus the
-// targets and a wave minimum; lane 0 then does what nav2d_obj_step_kernel does after its move, with that distance.  The field of an
-// episode that begins here is built by the launch of nav2d_obj_geo_build_kernel that follows (only_ended).
+// The geodesic form of the object step: one wavefront (a 64-thread workgroup) per env.  Every lane derives the move on its own
+// MoveLane from the same loads, so the outcome is uniform and lane 0 alone writes it back; the query of the new position takes one
+// node per lane plus the targets and a wave minimum; lane 0 then does what nav2d_obj_step_kernel does after its move, with that
+// distance.  The field of an episode that begins here is built by the launch of nav2d_obj_geo_build_kernel that follows (only_ended).
 __global__ void __launch_bounds__(64)
 nav2d_obj_geo_step_kernel(Nav2DObjState* __restrict__ states, ObjGeoField* __restrict__ geo, const float* __restrict__ dirs,
                           const float* __restrict__ ctab, const int64_t* __restrict__ actions, const uint8_t* __restrict__ mask,
@@ -1067,12 +1116,8 @@ nav2d_obj_geo_step_kernel(Nav2DObjState* __restrict__ states, ObjGeoField* __res
     } else {
         __shared__ GeoBox boxes[OBJ_GEO_BOXES];
         const int64_t a = actions[n];
-        float px = s.px, py = s.py;
-        bool moved = false;
-        if (a == 1) {
-            const float nx = px + FORWARD * dirs[2 * s.heading], ny = py + FORWARD * dirs[2 * s.heading + 1];
-            if (is_free_obj(nx, ny, o, K, M)) { px = nx; py = ny; moved = true; }
-        }
+        MoveLane m = load_move(s);  // this lane's copy
+        discrete_move(m, a, dirs, nh, [&](float x, float y) { return is_free_obj(x, y, o, K, M); });
         const bool reachable = g.reachable != 0;  // of the env, so uniform over the workgroup
         float d = INFINITY;
         if (reachable) {
@@ -1080,34 +1125,19 @@ nav2d_obj_geo_step_kernel(Nav2DObjState* __restrict__ states, ObjGeoField* __res
             __syncthreads();
             float x, y;
             const float Di = obj_geo_node(o, lane, K, M, x, y) ? g.D[lane] : INFINITY;
-            d = obj_geo_query(o, boxes, K, M, px, py, x, y, Di, lane);
+            d = obj_geo_query(o, boxes, K, M, m.px, m.py, x, y, Di, lane);
         }
         __syncthreads();  // every lane has read the state and the field before lane 0 writes to them
         if (lane == 0) {
-            if (a == 1) {
-                if (moved) { s.px = px; s.py = py; s.path = s.path + FORWARD; }
-                else s.collisions += 1;
-            } else if (a == 2) {
-                s.heading = (s.heading + 1) % nh;
-            } else if (a == 3) {
-                s.heading = (s.heading + nh - 1) % nh;
-            }
+            store_move(s, m);
             const float straight = nearest_target(o, M);  // (gx, gy) stay the Euclidean-nearest centre
             if (!reachable) d = straight;
             else if (!(d < INFINITY)) { d = s.d_prev; g.lost_steps += 1; }
-            obj_geo_end_step(o, d, a == 0, reward, not_done, sums, seed, env, n, N, K, nh, max_steps, M, C);
+            end_step_at<false>(s, d, a == 0, OBJ_SUCCESS, reward, not_done, sums, seed, env, n, N, K, nh, max_steps);
+            if (s.ended) place_objects(o, seed, env, K, M, C);
         }
     }
-    if (lane == 0) {
-        if (objectgoal) objectgoal[n] = (int64_t)o.target;
-        if (gps) {
-            const float c = dirs[2 * o.h0], sn = dirs[2 * o.h0 + 1];
-            const float dx = s.px - o.sx, dy = s.py - o.sy;
-            gps[2 * n + 0] = dx * c + dy * sn;
-            gps[2 * n + 1] = c * dy - sn * dx;
-        }
-        if (compass) compass[n] = ctab[(s.heading - o.h0 + nh) % nh];
-    }
+    if (lane == 0) obj_write_sensors(o, dirs, ctab, objectgoal, gps, compass, n, nh);
 }
 
 // ---- geodesic distances of Nav2DRearr-v0 and Nav2DRearrVel-v0 (distance = "geodesic"; specification: --------------------------------
@@ -1131,92 +1161,6 @@ static_assert(offsetof(RearrGeoField, reachable) == 4 * HAB_NAV2D_REARR_GEO_W_RE
               offsetof(RearrGeoField, sweeps_obj) == 4 * HAB_NAV2D_REARR_GEO_W_SWEEPS_OBJ, "RearrGeoField layout");
 static_assert(offsetof(RearrGeoField, lost_steps) == 4 * HAB_NAV2D_REARR_GEO_W_LOST_STEPS &&
               offsetof(RearrGeoField, rebuilds) == 4 * HAB_NAV2D_REARR_GEO_W_REBUILDS, "RearrGeoField layout");
-
-// What one wavefront keeps in LDS of one env's graph: nav2d_geo_build_kernel's arrays.  The nodes and boxes serve the queries; the
-// weights and the two copies of D a build.
-struct GeoGraph {
-    float node_x[GEO_NODES], node_y[GEO_NODES];
-    int node_ok[GEO_NODES];
-    GeoBox boxes[MAX_K];
-    float W[GEO_NODES * GEO_NODES];
-    float D[2][GEO_NODES];
-};
-// The nodes (lane l < 32: node l), the diagonal of the weights and the K visibility boxes (lanes 32 ..); the caller puts the barrier
-// after it.
-__device__ inline void geo_graph_nodes(GeoGraph& G, const Nav2DState& s, int K, int lane) {
-    if (lane < GEO_NODES) {
-        float x = 0.0f, y = 0.0f;
-        bool ok = false;
-        if (lane < 4 * K) {
-            geo_corner(s, lane >> 2, lane & 3, x, y);
-            ok = is_free(x, y, s, K);
-        }
-        G.node_x[lane] = x; G.node_y[lane] = y; G.node_ok[lane] = ok ? 1 : 0;
-        G.W[lane * GEO_NODES + lane] = INFINITY;
-    } else if (lane - GEO_NODES < K) {
-        G.boxes[lane - GEO_NODES] = geo_box(s, lane - GEO_NODES);
-    }
-}
-// The symmetric weights, the 496 pairs round the lanes as in nav2d_geo_build_kernel; needs the nodes, and a barrier after it.
-__device__ inline void geo_graph_weights(GeoGraph& G, int K, int lane) {
-    for (int p = lane; p < GEO_NODES * (GEO_NODES - 1) / 2; p += 64) {
-        const int a = p >> 5, c = p & 31;
-        const int i = c < 31 - a ? a : 30 - a;
-        const int j = c < 31 - a ? a + 1 + c : i + 1 + (c - (31 - a));
-        float w = INFINITY;
-        if (G.node_ok[i] && G.node_ok[j] && geo_visible(G.boxes, K, G.node_x[i], G.node_y[i], G.node_x[j], G.node_y[j]))
-            w = dist(G.node_x[i], G.node_y[i], G.node_x[j], G.node_y[j]);
-        G.W[i * GEO_NODES + j] = w;
-        G.W[j * GEO_NODES + i] = w;
-    }
-}
-// One field by one wavefront, towards the target (tx, ty), over a graph whose nodes and weights are in LDS behind a barrier: the last
-// hops, then nav2d_geo_build_kernel's sweeps (lane l owns half l & 1 of row l >> 1, the wave votes on the end).  Returns the sweeps;
-// `Dl` is D[lane] on the lanes below 32 and +inf on the others.  Uniform over the wave; ends behind a barrier, so that another field
-// may follow.
-__device__ inline int geo_field_towards(GeoGraph& G, int K, float tx, float ty, int lane, float& Dl) {
-    if (lane < GEO_NODES) {
-        float d = INFINITY;
-        if (G.node_ok[lane] && geo_visible(G.boxes, K, G.node_x[lane], G.node_y[lane], tx, ty)) d = dist(G.node_x[lane], G.node_y[lane], tx, ty);
-        G.D[0][lane] = d;
-    }
-    __syncthreads();
-    const int row = lane >> 1, half = lane & 1;
-    float w[GEO_NODES / 2];
-#pragma unroll
-    for (int t = 0; t < GEO_NODES / 2; ++t) w[t] = G.W[(half * (GEO_NODES / 2) + t) * GEO_NODES + row];
-    int cur = 0, sweeps = 0;
-    while (sweeps < 4 * K) {
-        sweeps += 1;
-        float m = INFINITY;
-#pragma unroll
-        for (int t = 0; t < GEO_NODES / 2; ++t) m = fminf(m, w[t] + G.D[cur][half * (GEO_NODES / 2) + t]);
-        m = fminf(m, __shfl_xor(m, 1));
-        const float before = G.D[cur][row];
-        const float after = fminf(before, m);
-        if (half == 0) G.D[cur ^ 1][row] = after;
-        const bool changed = __ballot(after != before) != 0;
-        __syncthreads();
-        cur ^= 1;
-        if (!changed) break;
-    }
-    Dl = lane < GEO_NODES ? G.D[cur][lane] : INFINITY;
-    __syncthreads();
-    return sweeps;
-}
-// geo_T(x) by one wavefront: node l with its field value Dl on lane l < 32, the direct hop to the target T on lane 32, then the
-// minimum over the wave, which is exact and so the restatement's serial one.  Needs the nodes and boxes in LDS.
-__device__ inline float geo_query_wave(const GeoGraph& G, int K, float x, float y, float tx, float ty, float Dl, int lane) {
-    float v = INFINITY;
-    if (lane < GEO_NODES) {
-        if (Dl < INFINITY && geo_visible(G.boxes, K, x, y, G.node_x[lane], G.node_y[lane])) v = dist(x, y, G.node_x[lane], G.node_y[lane]) + Dl;
-    } else if (lane == GEO_NODES) {
-        if (geo_visible(G.boxes, K, x, y, tx, ty)) v = dist(x, y, tx, ty);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
 
 // What the beginning of an episode needs, one env per 64-thread workgroup (one wavefront), selected like nav2d_geo_build_kernel's.
 // `state` is a record that rearr_begin has just filled: the object is at its start, or at the agent's position under start_holding.
@@ -1261,39 +1205,19 @@ nav2d_rearr_geo_build_kernel(char* __restrict__ states, size_t state_stride, Rea
     }
 }
 
-// rearr_end_step for the geodesic step, which has its potential and its second term already: a function of its own, so that
-// rearr_end_step and the two Euclidean kernels stay the code they are (see the comment there).
+// rearr_end_step_at for the geodesic step, which has its potential and its second term already.  Not forced inline: the compiler makes
+// it one function that both forms of the step kernel call, and forced into them it grows each by half.
 __device__ inline void rearr_geo_end_step(Nav2DRearrState& r, float phi, float b, bool stop, bool first_pick, float* __restrict__ reward,
                                           uint8_t* __restrict__ not_done, float* __restrict__ sums, uint32_t seed, uint32_t env, int n, int N,
                                           int K, int nh, int max_steps, int start_holding) {
-    Nav2DState& s = r.base;
-    const bool success = stop && !r.holding && b < REARR_SUCCESS;
-    reward[n] = ((-0.01f + (s.d_prev - phi)) + (first_pick ? 1.0f : 0.0f)) + (success ? 2.5f : 0.0f);
-    s.d_prev = phi;
-    s.steps += 1;
-    const bool done = stop || (s.steps >= max_steps);
-    not_done[n] = done ? 0 : 1;
-    s.ended = done ? 1 : 0;
-    if (done) {
-        s.last[0] = success ? 1.0f : 0.0f;
-        s.last[1] = (float)r.held;
-        s.last[2] = b;
-        s.last[3] = (float)s.collisions;
-        if (sums)
-            for (int m = 0; m < 4; ++m) sums[(size_t)m * N + n] = sums[(size_t)m * N + n] + s.last[m];
-        s.episode += 1;
-        begin_episode<false>(s, seed, env, K, nh);
-        rearr_begin(r, seed, env, K, start_holding);
-    }
+    rearr_end_step_at(r, phi, b, stop, first_pick, reward, not_done, sums, seed, env, n, N, K, nh, max_steps, start_holding);
 }
 
 // What a step changes of a record before its end, as a lane's own copy in registers, with the rectangles, which it does not change,
 // behind a pointer to the record: the members the motion, PICK and PLACE helpers read and write.  A copy of the whole record would be
 // indexed by k and live in scratch memory.
 struct RearrLane {
-    struct Base {
-        float px, py, path;
-        int32_t heading, collisions;
+    struct Base : MoveLane {
         const float (*rect)[4];
     } base;
     float ox, oy;
@@ -1326,8 +1250,7 @@ nav2d_rearr_geo_step_kernel(Nav2DRearrState* __restrict__ states, RearrGeoField*
         }
     } else {
         __shared__ GeoGraph G;
-        RearrLane r{{rec.base.px, rec.base.py, rec.base.path, rec.base.heading, rec.base.collisions, rec.base.rect},
-                    rec.ox, rec.oy, rec.holding, rec.held, rec.picks, rec.invalid};  // this lane's copy
+        RearrLane r{{load_move(rec.base), rec.base.rect}, rec.ox, rec.oy, rec.holding, rec.held, rec.picks, rec.invalid};  // this lane's copy
         RearrLane::Base& s = r.base;
         const float gx = rec.base.gx, gy = rec.base.gy;
         const bool was_holding = r.holding != 0;
@@ -1345,19 +1268,9 @@ nav2d_rearr_geo_step_kernel(Nav2DRearrState* __restrict__ states, RearrGeoField*
         } else {
             const int64_t a = static_cast<const int64_t*>(actions)[n];
             const float c = dirs[2 * s.heading], sn = dirs[2 * s.heading + 1];
-            if (a == 1) {
-                const float nx = s.px + FORWARD * c, ny = s.py + FORWARD * sn;
-                if (rearr_is_free(nx, ny, r, K)) { s.px = nx; s.py = ny; s.path = s.path + FORWARD; }
-                else s.collisions += 1;
-            } else if (a == 2) {
-                s.heading = (s.heading + 1) % nh;
-            } else if (a == 3) {
-                s.heading = (s.heading + nh - 1) % nh;
-            } else if (a == 4) {
-                first_pick = rearr_pick(r, c, sn);
-            } else if (a == 5) {
-                rearr_place(r, c, sn, K);
-            }
+            discrete_move(s, a, dirs, nh, [&](float x, float y) { return rearr_is_free(x, y, r, K); });
+            if (a == 4) first_pick = rearr_pick(r, c, sn);
+            else if (a == 5) rearr_place(r, c, sn, K);
             stop = a == 0;
         }
         if (r.holding) { r.ox = s.px; r.oy = s.py; }
@@ -1386,8 +1299,7 @@ nav2d_rearr_geo_step_kernel(Nav2DRearrState* __restrict__ states, RearrGeoField*
         __syncthreads();  // every lane has read the record and the field before lane 0 writes to them
         if (reachable && placed && lane < GEO_NODES) g.DO[lane] = Do;
         if (lane == 0) {
-            Nav2DState& t = rec.base;
-            t.px = s.px; t.py = s.py; t.path = s.path; t.heading = s.heading; t.collisions = s.collisions;
+            store_move(rec.base, s);
             rec.ox = r.ox; rec.oy = r.oy;
             rec.holding = r.holding; rec.held = r.held; rec.picks = r.picks; rec.invalid = r.invalid;
             float phi, b;
@@ -1411,15 +1323,14 @@ nav2d_rearr_geo_step_kernel(Nav2DRearrState* __restrict__ states, RearrGeoField*
 
 // ---- the pick-and-place oracle of Nav2DRearr-v0 in geodesic mode (specification: tests/nav2d_rearr_oracle_reference.py) -------------
 // One env per 64-thread workgroup (one wavefront), selected by `mask` (NULL: all); lane = candidate heading, the lanes stride over
-// the nh headings by 64, as in nav2d_follow_kernel.  State and field are read only, through pointers that are uniform over the wave,
+// the nh headings by 64, as in forward_search.  State and field are read only, through pointers that are uniform over the wave,
 // and so are `holding` and "in reach": an env runs one of three paths.
 //   * Not holding, in reach: the dot test of rearr_pick per heading; the fewest turns win.
-//   * Not holding, out of reach: the follower's forward search towards o over DO below the term a, with the task's free test.
+//   * Not holding, out of reach: forward_search towards o over DO below the term a, with the task's free test.
 //   * Holding: the place search -- q of rearr_place per heading, eligible where the PLACE would be accepted and w = geo_g(q) < 0.5;
 //     the fewest turns win -- and, where no heading is eligible, the forward search towards g over DG below the term b.
-// Both forward searches are one piece of code with a uniform field pointer, target and bound, so a lane runs at most two
-// straight-line queries per pass of the lanes: one of the place search, one of the forward search.  The forward search has the
-// follower's 64-bit key; the two turn-only searches have the turn key in the high word and w's bits (0 for the dot test) in the low
+// Both forward searches are one call with a uniform field pointer, target and bound, so a lane runs at most two straight-line
+// queries per pass of the lanes: one of the place search, one of the forward search.  The two turn-only searches have the turn key in the high word and w's bits (0 for the dot test) in the low
 // word, which the minimum carries along for next_d.  One wave-wide minimum per search; lane 0 writes action, next_d and status.
 __global__ void __launch_bounds__(64)
 nav2d_rearr_oracle_kernel(const char* __restrict__ states, size_t state_stride, const RearrGeoField* __restrict__ geo,
@@ -1430,7 +1341,6 @@ nav2d_rearr_oracle_kernel(const char* __restrict__ states, size_t state_stride, 
     const Nav2DRearrState& r = *reinterpret_cast<const Nav2DRearrState*>(states + (size_t)n * state_stride);
     const Nav2DState& s = r.base;
     const RearrGeoField& g = geo[n];
-    constexpr unsigned long long NONE = ~0ull;
     const float px = s.px, py = s.py, ta = g.a, tb = g.b;
     const int heading = s.heading;
     const bool holding = r.holding != 0;
@@ -1445,7 +1355,7 @@ nav2d_rearr_oracle_kernel(const char* __restrict__ states, size_t state_stride, 
         nd = tb;
     } else if (!holding && dist(px, py, r.ox, r.oy) < REARR_REACH) {
         const float dx = r.ox - px, dy = r.oy - py;
-        unsigned long long key = NONE;
+        unsigned long long key = NO_KEY;
         for (int h0 = 0; h0 < nh; h0 += 64) {  // uniform over the wave
             const int h = h0 + lane;
             if (h >= nh) continue;
@@ -1454,7 +1364,7 @@ nav2d_rearr_oracle_kernel(const char* __restrict__ states, size_t state_stride, 
             key = k < key ? k : key;
         }
         key = wave_min_key(key);
-        if (key != NONE) {
+        if (key != NO_KEY) {
             delta = turn_key_delta((uint32_t)(key >> 32));
             st = delta == 0 ? HAB_NAV2D_ORACLE_PICK : HAB_NAV2D_ORACLE_GO;
             nd = delta == 0 ? 0.0f : ta;
@@ -1462,7 +1372,7 @@ nav2d_rearr_oracle_kernel(const char* __restrict__ states, size_t state_stride, 
     } else if (!holding) {
         D = g.DO; tx = r.ox; ty = r.oy; bound = ta;
     } else {
-        unsigned long long key = NONE;
+        unsigned long long key = NO_KEY;
         for (int h0 = 0; h0 < nh; h0 += 64) {
             const int h = h0 + lane;
             if (h >= nh) continue;
@@ -1474,7 +1384,7 @@ nav2d_rearr_oracle_kernel(const char* __restrict__ states, size_t state_stride, 
             key = k < key ? k : key;
         }
         key = wave_min_key(key);
-        if (key != NONE) {
+        if (key != NO_KEY) {
             delta = turn_key_delta((uint32_t)(key >> 32));
             st = delta == 0 ? HAB_NAV2D_ORACLE_PLACE : HAB_NAV2D_ORACLE_GO;
             nd = delta == 0 ? __uint_as_float((uint32_t)key) : tb;
@@ -1483,19 +1393,9 @@ nav2d_rearr_oracle_kernel(const char* __restrict__ states, size_t state_stride, 
         }
     }
     if (D) {
-        unsigned long long key = NONE;
-        for (int h0 = 0; h0 < nh; h0 += 64) {
-            const int h = h0 + lane;
-            if (h >= nh) continue;
-            const float nx = px + FORWARD * dirs[2 * h], ny = py + FORWARD * dirs[2 * h + 1];
-            if (!rearr_is_free(nx, ny, r, K)) continue;
-            const float v = geo_query(s, D, K, nx, ny, tx, ty);
-            if (!(v < INFINITY && v < bound)) continue;
-            const unsigned long long k = ((unsigned long long)__float_as_uint(v) << 32) | turn_key(h, heading, nh);
-            key = k < key ? k : key;
-        }
-        key = wave_min_key(key);
-        if (key != NONE) {
+        const unsigned long long key =
+            forward_search(s, D, dirs, K, nh, tx, ty, bound, lane, [&](float x, float y) { return rearr_is_free(x, y, r, K); });
+        if (key != NO_KEY) {
             st = HAB_NAV2D_ORACLE_GO;
             delta = turn_key_delta((uint32_t)key);
             nd = delta == 0 ? __uint_as_float((uint32_t)(key >> 32)) : bound;  // a turn leaves the leg's term as it is
@@ -1573,15 +1473,13 @@ __device__ inline void social_begin(Nav2DSocialState& r, uint32_t seed, uint32_t
     r.arrivals = r.person_waits = r.person_lost = r.sweeps = r.rebuilds = r.zero = 0;
     s.d_start = s.d_prev = dist(s.px, s.py, r.obj[0][0], r.obj[0][1]);
 }
-// (dot, cross) of h - p in the heading's frame, written term by term like write_goal's, and whether the agent sees the person: inside
-// the camera's 90 degree field of view and visible over the graph's boxes.  By one thread, the boxes through the record.
+// (dot, cross) of h - p in the heading's frame, and whether the agent sees the person: inside the camera's 90 degree field of view
+// and visible over the graph's boxes.  By one thread, the boxes through the record.
 __device__ inline bool social_sees(const Nav2DSocialState& r, const float* __restrict__ dirs, int K, float& dot, float& cross) {
     const Nav2DState& s = r.base;
     const float c = dirs[2 * s.heading], sn = dirs[2 * s.heading + 1];
     const float hx = r.obj[0][0], hy = r.obj[0][1];
-    const float dx = hx - s.px, dy = hy - s.py;
-    dot = dx * c + dy * sn;
-    cross = c * dy - sn * dx;
+    to_frame(hx - s.px, hy - s.py, c, sn, dot, cross);
     if (!(dot > 0.0f && fabsf(cross) <= dot)) return false;
     for (int k = 0; k < K; ++k)
         if (geo_blocked(geo_box(s, k), s.px, s.py, hx, hy)) return false;
@@ -1608,15 +1506,9 @@ nav2d_social_build_kernel(Nav2DSocialState* __restrict__ states, const uint8_t* 
     if (lane == 0) r.sweeps = sweeps;
 }
 
-// What the agent's move changes of a record, as a lane's own copy: the members vel_move reads and writes.
-struct SocialLane {
-    float px, py, path;
-    int32_t heading, collisions;
-};
-
-// One step of one env by one wavefront (a 64-thread workgroup), as nav2d_rearr_geo_step_kernel.  Every lane takes its own copy of the
-// record's changing words -- before lane 0 writes any -- and derives the agent's move on it, from the same loads, so the outcome is
-// uniform over the wave.  The person's hop is the arg-min form of geo_query_wave: node l with DW[l] on lane l < 32, the waypoint on
+// One step of one env by one wavefront (a 64-thread workgroup), as nav2d_rearr_geo_step_kernel.  Every lane takes its own MoveLane
+// -- before lane 0 writes any of the record -- and derives the agent's move on it, from the same loads, so the outcome is uniform
+// over the wave.  The person's hop is the arg-min form of geo_query_wave: node l with DW[l] on lane l < 32, the waypoint on
 // lane 32, and a reduction over (value, rank) with rank 0 for the waypoint and l + 1 for node l, so that among equal values the
 // waypoint wins, then the lowest node; the order is total, so every lane ends with the same pair.  A node at distance exactly 0 is
 // no candidate.  A waypoint reached or given up draws the next one and builds its field here, the weights included; a step that
@@ -1639,7 +1531,7 @@ nav2d_social_step_kernel(Nav2DSocialState* __restrict__ states, const float* __r
         }
     } else {
         __shared__ GeoGraph G;
-        SocialLane s{rec.base.px, rec.base.py, rec.base.path, rec.base.heading, rec.base.collisions};  // this lane's copy
+        MoveLane s = load_move(rec.base);  // this lane's copy
         float hx = rec.obj[0][0], hy = rec.obj[0][1], wx = rec.wx, wy = rec.wy;
         int wp = rec.wp_index;
         float Dl = lane < GEO_NODES ? rec.DW[lane] : INFINITY;
@@ -1702,7 +1594,7 @@ nav2d_social_step_kernel(Nav2DSocialState* __restrict__ states, const float* __r
         if (rebuild && lane < GEO_NODES) rec.DW[lane] = Dl;
         if (lane == 0) {
             Nav2DState& t = rec.base;
-            t.px = s.px; t.py = s.py; t.path = s.path; t.heading = s.heading; t.collisions = s.collisions;
+            store_move(t, s);
             rec.obj[0][0] = hx; rec.obj[0][1] = hy;
             rec.wx = wx; rec.wy = wy; rec.wp_index = wp;
             if (arrived) rec.arrivals += 1;
@@ -1724,14 +1616,8 @@ nav2d_social_step_kernel(Nav2DSocialState* __restrict__ states, const float* __r
             not_done[n] = done ? 0 : 1;
             t.ended = done ? 1 : 0;
             if (done) {
-                t.last[0] = (float)rec.found;
-                t.last[1] = __fdiv_rn((float)rec.following_steps, (float)t.steps);
-                t.last[2] = (float)(rec.found ? rec.first_encounter : t.steps);
-                t.last[3] = (float)t.collisions;
-                if (sums)
-                    for (int m = 0; m < 4; ++m) sums[(size_t)m * N + n] = sums[(size_t)m * N + n] + t.last[m];
-                t.episode += 1;
-                begin_episode<false>(t, seed, env, K, nh);
+                close_episode<false>(t, (float)rec.found, __fdiv_rn((float)rec.following_steps, (float)t.steps),
+                                     (float)(rec.found ? rec.first_encounter : t.steps), (float)t.collisions, sums, seed, env, n, N, K, nh);
                 social_begin(rec, seed, env, K);
             }
         }
@@ -2015,6 +1901,18 @@ static int check_step_args(const StepArgs& a, bool geo_entry, size_t state_strid
     return geo_entry ? check_geo_args(a.state, state_stride, a.geo, a.N, a.num_obstacles) : HAB_OK;
 }
 
+// The motion parameters of the velocity tasks.
+static bool vel_args_ok(int max_turn_steps, int stop_turn_steps, int num_headings) {
+    return max_turn_steps >= 1 && max_turn_steps <= num_headings / 2 && stop_turn_steps >= 1 && stop_turn_steps <= max_turn_steps;
+}
+static bool start_holding_ok(int start_holding) { return start_holding == 0 || start_holding == 1; }
+// What the follower and the oracle are given beside state and field; an action row is read and written as one word of its size.
+static bool guide_args_ok(const float* dirs, const void* actions, size_t action_bytes, const float* next_d, const int32_t* status,
+                          int num_headings) {
+    if (!dirs || ((uintptr_t)dirs & 3) || !actions || ((uintptr_t)actions & (action_bytes - 1))) return false;
+    return !((uintptr_t)next_d & 3) && !((uintptr_t)status & 3) && num_headings > 0;
+}
+
 // The render, where an image destination is given, in the task's form.  `semantic` and `num_objects` are used by the Nav2DObj-v0
 // instantiation alone.
 template <Render MODE>
@@ -2093,8 +1991,7 @@ static int vel_step(const StepArgs& a, int max_turn_steps, int stop_turn_steps, 
     const int rc = check_step_args(a, GEO);
     if (rc != HAB_OK) return rc;
     if ((uintptr_t)a.actions & 7) return HAB_ERR_ARG;  // a row is read as one float2
-    if (max_turn_steps < 1 || max_turn_steps > a.num_headings / 2 || stop_turn_steps < 1 || stop_turn_steps > max_turn_steps)
-        return HAB_ERR_ARG;
+    if (!vel_args_ok(max_turn_steps, stop_turn_steps, a.num_headings)) return HAB_ERR_ARG;
     nav2d_vel_step_kernel<GEO><<<cdiv(a.N, 64), 64, 0, a.stream>>>((Nav2DState*)a.state, a.dirs, (const float2*)a.actions, a.mask, a.goal,
                                                                     a.reward, a.not_done, a.measure_sums, a.seed, a.env_offset, a.N,
                                                                     a.num_obstacles, a.num_headings, a.max_episode_steps, max_turn_steps,
@@ -2125,16 +2022,14 @@ extern "C" int hab_nav2d_vel_step_geo(void* state, void* geo, const float* dirs,
                           max_turn_steps, stop_turn_steps, min_abs_lin_speed, allow_sliding);
 }
 
-// The shortest-path follower: the checks of the field entries, then those of its own arguments; an action row is read and written
-// as one word of its size.
+// The shortest-path follower: the checks of the field entries, then those of its own arguments.
 template <class Writer>
 static int follow(const void* state, size_t state_stride_bytes, const void* geo, const float* dirs, const uint8_t* mask,
                   typename Writer::Action* actions, float* next_d, int32_t* status, int N, int num_obstacles, int num_headings,
                   hipStream_t stream, Writer writer) {
     const int rc = check_geo_args(state, state_stride_bytes, geo, N, num_obstacles);
     if (rc != HAB_OK) return rc;
-    if (!dirs || ((uintptr_t)dirs & 3) || !actions || ((uintptr_t)actions & (sizeof(typename Writer::Action) - 1))) return HAB_ERR_ARG;
-    if (((uintptr_t)next_d & 3) || ((uintptr_t)status & 3) || num_headings <= 0) return HAB_ERR_ARG;
+    if (!guide_args_ok(dirs, actions, sizeof(typename Writer::Action), next_d, status, num_headings)) return HAB_ERR_ARG;
     nav2d_follow_kernel<Writer><<<N, 64, 0, stream>>>((const char*)state, state_stride_bytes, (const GeoField*)geo, dirs, mask, actions,
                                                       next_d, status, num_obstacles, num_headings, writer);
     HAB_LAUNCH_CHECK();
@@ -2156,80 +2051,66 @@ extern "C" int hab_nav2d_vel_follow(const void* state, size_t state_stride_bytes
                   FollowVelocity{max_turn_steps});
 }
 
+// Nav2DObj-v0, its two entries like Nav2D-v0's.  GEO: the step is one wavefront per env, and the fields of the episodes that began (at
+// a reset, of every env the mask selects) follow it.
+template <bool GEO>
+static int obj_step(const StepArgs& a, int64_t* objectgoal, float* gps, float* compass, const float* compass_table, int num_objects,
+                    int num_categories, int num_actions) {
+    const int rc = check_step_args(a, GEO, sizeof(Nav2DObjState));
+    if (rc != HAB_OK) return rc;
+    if (a.semantic && ((uintptr_t)a.semantic & 3)) return HAB_ERR_ARG;
+    if (compass && !compass_table) return HAB_ERR_ARG;
+    if (num_objects < 1 || num_objects > MAX_M || num_categories < 1 || num_categories > HAB_NAV2D_MAX_CATEGORIES) return HAB_ERR_ARG;
+    if (num_actions != 4 && num_actions != 6) return HAB_ERR_ARG;
+    Nav2DObjState* states = (Nav2DObjState*)a.state;
+    const int64_t* actions = (const int64_t*)a.actions;
+    if constexpr (GEO) {
+        nav2d_obj_geo_step_kernel<<<a.N, 64, 0, a.stream>>>(states, (ObjGeoField*)a.geo, a.dirs, compass_table, actions, a.mask, objectgoal, gps,
+                                                            compass, a.reward, a.not_done, a.measure_sums, a.seed, a.env_offset, a.N,
+                                                            a.num_obstacles, a.num_headings, a.max_episode_steps, num_objects,
+                                                            num_categories, a.advance);
+        HAB_LAUNCH_CHECK();
+        nav2d_obj_geo_build_kernel<<<a.N, 64, 0, a.stream>>>((char*)a.state, sizeof(Nav2DObjState), (ObjGeoField*)a.geo, a.mask,
+                                                             a.advance ? 1 : 0, a.num_obstacles, num_objects);
+    } else {
+        nav2d_obj_step_kernel<<<cdiv(a.N, 64), 64, 0, a.stream>>>(states, a.dirs, compass_table, actions, a.mask, objectgoal, gps, compass,
+                                                                  a.reward, a.not_done, a.measure_sums, a.seed, a.env_offset, a.N,
+                                                                  a.num_obstacles, a.num_headings, a.max_episode_steps, num_objects,
+                                                                  num_categories, a.advance);
+    }
+    HAB_LAUNCH_CHECK();
+    return launch_render<Render::OBJ>(a, num_objects);
+}
+
 extern "C" int hab_nav2d_obj_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
                                   const int64_t* actions, const uint8_t* mask, uint8_t* rgb, float* depth, int32_t* semantic,
                                   int64_t* objectgoal, float* gps, float* compass, const float* compass_table, float* reward,
                                   uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
                                   int num_obstacles, int num_headings, int max_episode_steps, int num_objects, int num_categories,
                                   int num_actions, int advance, hipStream_t stream) {
-    const StepArgs a{state, nullptr, dirs, ray, col_cos, tanv, actions, mask, rgb, depth, nullptr, semantic, reward, not_done,
-                     measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream};
-    const int rc = check_step_args(a, false);
-    if (rc != HAB_OK) return rc;
-    if (semantic && ((uintptr_t)semantic & 3)) return HAB_ERR_ARG;
-    if (compass && !compass_table) return HAB_ERR_ARG;
-    if (num_objects < 1 || num_objects > MAX_M || num_categories < 1 || num_categories > HAB_NAV2D_MAX_CATEGORIES) return HAB_ERR_ARG;
-    if (num_actions != 4 && num_actions != 6) return HAB_ERR_ARG;
-    nav2d_obj_step_kernel<<<cdiv(N, 64), 64, 0, stream>>>((Nav2DObjState*)state, dirs, compass_table, actions, mask, objectgoal, gps,
-                                                          compass, reward, not_done, measure_sums, seed, env_offset, N, num_obstacles,
-                                                          num_headings, max_episode_steps, num_objects, num_categories, advance);
-    HAB_LAUNCH_CHECK();
-    return launch_render<Render::OBJ>(a, num_objects);
+    return obj_step<false>({state, nullptr, dirs, ray, col_cos, tanv, actions, mask, rgb, depth, nullptr, semantic, reward, not_done,
+                            measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream},
+                           objectgoal, gps, compass, compass_table, num_objects, num_categories, num_actions);
 }
 
-extern "C" int hab_nav2d_rearr_state_bytes(void) { return (int)sizeof(Nav2DRearrState); }
-
-extern "C" int hab_nav2d_rearr_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
-                                    const int64_t* actions, const uint8_t* mask, uint8_t* head_rgb, float* head_depth, float* obj_start,
-                                    float* obj_goal, float* is_holding, float* reward, uint8_t* not_done, float* measure_sums,
-                                    uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings,
-                                    int max_episode_steps, int start_holding, int advance, hipStream_t stream) {
-    const StepArgs a{state, nullptr, dirs, ray, col_cos, tanv, actions, mask, head_rgb, head_depth, nullptr, nullptr, reward, not_done,
-                     measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream};
-    const int rc = check_step_args(a, false);
-    if (rc != HAB_OK) return rc;
-    if (start_holding != 0 && start_holding != 1) return HAB_ERR_ARG;
-    nav2d_rearr_step_kernel<<<cdiv(N, 64), 64, 0, stream>>>((Nav2DRearrState*)state, dirs, actions, mask, obj_start, obj_goal, is_holding,
-                                                            reward, not_done, measure_sums, seed, env_offset, N, num_obstacles,
-                                                            num_headings, max_episode_steps, start_holding, advance);
-    HAB_LAUNCH_CHECK();
-    return launch_render<Render::REARR>(a, 0);
-}
-
-extern "C" int hab_nav2d_rearr_vel_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
-                                        const float* actions, const uint8_t* mask, uint8_t* head_rgb, float* head_depth, float* obj_start,
-                                        float* obj_goal, float* is_holding, float* reward, uint8_t* not_done, float* measure_sums,
-                                        uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings,
-                                        int max_episode_steps, int start_holding, int max_turn_steps, int stop_turn_steps,
-                                        float min_abs_lin_speed, int allow_sliding, int advance, hipStream_t stream) {
-    const StepArgs a{state, nullptr, dirs, ray, col_cos, tanv, actions, mask, head_rgb, head_depth, nullptr, nullptr, reward, not_done,
-                     measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream};
-    const int rc = check_step_args(a, false);
-    if (rc != HAB_OK) return rc;
-    if (start_holding != 0 && start_holding != 1) return HAB_ERR_ARG;
-    if ((uintptr_t)actions & 3) return HAB_ERR_ARG;  // a row of three floats is read as three scalars
-    if (max_turn_steps < 1 || max_turn_steps > num_headings / 2 || stop_turn_steps < 1 || stop_turn_steps > max_turn_steps)
-        return HAB_ERR_ARG;
-    nav2d_rearr_vel_step_kernel<<<cdiv(N, 64), 64, 0, stream>>>((Nav2DRearrState*)state, dirs, actions, mask, obj_start, obj_goal,
-                                                                is_holding, reward, not_done, measure_sums, seed, env_offset, N,
-                                                                num_obstacles, num_headings, max_episode_steps, start_holding,
-                                                                max_turn_steps, stop_turn_steps, min_abs_lin_speed, allow_sliding, advance);
-    HAB_LAUNCH_CHECK();
-    return launch_render<Render::REARR>(a, 0);
+extern "C" int hab_nav2d_obj_step_geo(void* state, void* geo, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                                      const int64_t* actions, const uint8_t* mask, uint8_t* rgb, float* depth, int32_t* semantic,
+                                      int64_t* objectgoal, float* gps, float* compass, const float* compass_table, float* reward,
+                                      uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
+                                      int num_obstacles, int num_headings, int max_episode_steps, int num_objects, int num_categories,
+                                      int num_actions, int advance, hipStream_t stream) {
+    return obj_step<true>({state, geo, dirs, ray, col_cos, tanv, actions, mask, rgb, depth, nullptr, semantic, reward, not_done,
+                           measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream},
+                          objectgoal, gps, compass, compass_table, num_objects, num_categories, num_actions);
 }
 
 extern "C" int hab_nav2d_obj_geo_bytes(void) { return (int)sizeof(ObjGeoField); }
 
-static int check_obj_geo_args(const void* state, size_t state_stride_bytes, const void* geo, int N, int num_obstacles) {
-    const int rc = check_geo_args(state, state_stride_bytes, geo, N, num_obstacles);
-    if (rc != HAB_OK) return rc;
-    return state_stride_bytes < sizeof(Nav2DObjState) ? HAB_ERR_ARG : HAB_OK;
-}
-
 extern "C" int hab_nav2d_obj_geo_build(void* state, size_t state_stride_bytes, void* geo, const uint8_t* mask, int only_ended, int N,
                                        int num_obstacles, int num_objects, hipStream_t stream) {
-    const int rc = check_obj_geo_args(state, state_stride_bytes, geo, N, num_obstacles);
+    const int rc = check_geo_args(state, state_stride_bytes, geo, N, num_obstacles);
     if (rc != HAB_OK) return rc;
+    if (state_stride_bytes < sizeof(Nav2DObjState)) return HAB_ERR_ARG;
     if (num_objects < 1 || num_objects > MAX_M) return HAB_ERR_ARG;
     nav2d_obj_geo_build_kernel<<<N, 64, 0, stream>>>((char*)state, state_stride_bytes, (ObjGeoField*)geo, mask, only_ended, num_obstacles,
                                                      num_objects);
@@ -2237,33 +2118,7 @@ extern "C" int hab_nav2d_obj_geo_build(void* state, size_t state_stride_bytes, v
     return HAB_OK;
 }
 
-// hab_nav2d_obj_step with the field: the step (one wavefront per env), the fields of the episodes that began (at a reset, of every
-// env the mask selects), then the render.
-extern "C" int hab_nav2d_obj_step_geo(void* state, void* geo, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
-                                      const int64_t* actions, const uint8_t* mask, uint8_t* rgb, float* depth, int32_t* semantic,
-                                      int64_t* objectgoal, float* gps, float* compass, const float* compass_table, float* reward,
-                                      uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
-                                      int num_obstacles, int num_headings, int max_episode_steps, int num_objects, int num_categories,
-                                      int num_actions, int advance, hipStream_t stream) {
-    const StepArgs a{state, geo, dirs, ray, col_cos, tanv, actions, mask, rgb, depth, nullptr, semantic, reward, not_done,
-                     measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream};
-    int rc = check_step_args(a, false);
-    if (rc != HAB_OK) return rc;
-    rc = check_obj_geo_args(state, sizeof(Nav2DObjState), geo, N, num_obstacles);
-    if (rc != HAB_OK) return rc;
-    if (semantic && ((uintptr_t)semantic & 3)) return HAB_ERR_ARG;
-    if (compass && !compass_table) return HAB_ERR_ARG;
-    if (num_objects < 1 || num_objects > MAX_M || num_categories < 1 || num_categories > HAB_NAV2D_MAX_CATEGORIES) return HAB_ERR_ARG;
-    if (num_actions != 4 && num_actions != 6) return HAB_ERR_ARG;
-    nav2d_obj_geo_step_kernel<<<N, 64, 0, stream>>>((Nav2DObjState*)state, (ObjGeoField*)geo, dirs, compass_table, actions, mask, objectgoal,
-                                                    gps, compass, reward, not_done, measure_sums, seed, env_offset, N, num_obstacles,
-                                                    num_headings, max_episode_steps, num_objects, num_categories, advance);
-    HAB_LAUNCH_CHECK();
-    nav2d_obj_geo_build_kernel<<<N, 64, 0, stream>>>((char*)state, sizeof(Nav2DObjState), (ObjGeoField*)geo, mask, advance ? 1 : 0,
-                                                     num_obstacles, num_objects);
-    HAB_LAUNCH_CHECK();
-    return launch_render<Render::OBJ>(a, num_objects);
-}
+extern "C" int hab_nav2d_rearr_state_bytes(void) { return (int)sizeof(Nav2DRearrState); }
 
 extern "C" int hab_nav2d_rearr_geo_bytes(void) { return (int)sizeof(RearrGeoField); }
 
@@ -2272,36 +2127,74 @@ extern "C" int hab_nav2d_rearr_geo_build(void* state, size_t state_stride_bytes,
     const int rc = check_geo_args(state, state_stride_bytes, geo, N, num_obstacles);
     if (rc != HAB_OK) return rc;
     if (state_stride_bytes < sizeof(Nav2DRearrState)) return HAB_ERR_ARG;
-    if (start_holding != 0 && start_holding != 1) return HAB_ERR_ARG;
+    if (!start_holding_ok(start_holding)) return HAB_ERR_ARG;
     nav2d_rearr_geo_build_kernel<<<N, 64, 0, stream>>>((char*)state, state_stride_bytes, (RearrGeoField*)geo, mask, only_ended,
                                                        num_obstacles, start_holding);
     HAB_LAUNCH_CHECK();
     return HAB_OK;
 }
 
-// Both rearrangement steps with the fields: the step (one wavefront per env), the fields of the episodes that began (at a reset, of
-// every env the mask selects), then the render.  The four motion parameters are Nav2DRearrVel-v0's and unused without VEL.
-template <bool VEL>
-static int rearr_step_geo(const StepArgs& a, float* obj_start, float* obj_goal, float* is_holding, int start_holding, int max_turn_steps,
-                          int stop_turn_steps, float min_abs_lin_speed, int allow_sliding) {
-    const int rc = check_step_args(a, true, sizeof(Nav2DRearrState));
+// The four rearrangement steps.  VEL: `actions` are Nav2DRearrVel-v0's (N, 3) float rows and the four motion parameters are used; else
+// int64 actions, and the parameters are unused.  GEO: the step is one wavefront per env, and the fields of the episodes that began (at
+// a reset, of every env the mask selects) follow it.  Then the render.
+template <bool VEL, bool GEO>
+static int rearr_step(const StepArgs& a, float* obj_start, float* obj_goal, float* is_holding, int start_holding, int max_turn_steps,
+                      int stop_turn_steps, float min_abs_lin_speed, int allow_sliding) {
+    const int rc = check_step_args(a, GEO, sizeof(Nav2DRearrState));
     if (rc != HAB_OK) return rc;
-    if (start_holding != 0 && start_holding != 1) return HAB_ERR_ARG;
+    if (!start_holding_ok(start_holding)) return HAB_ERR_ARG;
     if (VEL) {
         if ((uintptr_t)a.actions & 3) return HAB_ERR_ARG;  // a row of three floats is read as three scalars
-        if (max_turn_steps < 1 || max_turn_steps > a.num_headings / 2 || stop_turn_steps < 1 || stop_turn_steps > max_turn_steps)
-            return HAB_ERR_ARG;
+        if (!vel_args_ok(max_turn_steps, stop_turn_steps, a.num_headings)) return HAB_ERR_ARG;
     }
-    nav2d_rearr_geo_step_kernel<VEL><<<a.N, 64, 0, a.stream>>>((Nav2DRearrState*)a.state, (RearrGeoField*)a.geo, a.dirs, a.actions, a.mask,
-                                                               obj_start, obj_goal, is_holding, a.reward, a.not_done, a.measure_sums,
-                                                               a.seed, a.env_offset, a.N, a.num_obstacles, a.num_headings,
-                                                               a.max_episode_steps, start_holding, max_turn_steps, stop_turn_steps,
-                                                               min_abs_lin_speed, allow_sliding, a.advance);
-    HAB_LAUNCH_CHECK();
-    nav2d_rearr_geo_build_kernel<<<a.N, 64, 0, a.stream>>>((char*)a.state, sizeof(Nav2DRearrState), (RearrGeoField*)a.geo, a.mask,
-                                                           a.advance ? 1 : 0, a.num_obstacles, start_holding);
+    Nav2DRearrState* states = (Nav2DRearrState*)a.state;
+    if constexpr (GEO) {
+        nav2d_rearr_geo_step_kernel<VEL><<<a.N, 64, 0, a.stream>>>(states, (RearrGeoField*)a.geo, a.dirs, a.actions, a.mask, obj_start, obj_goal,
+                                                                   is_holding, a.reward, a.not_done, a.measure_sums, a.seed, a.env_offset,
+                                                                   a.N, a.num_obstacles, a.num_headings, a.max_episode_steps, start_holding,
+                                                                   max_turn_steps, stop_turn_steps, min_abs_lin_speed, allow_sliding,
+                                                                   a.advance);
+        HAB_LAUNCH_CHECK();
+        nav2d_rearr_geo_build_kernel<<<a.N, 64, 0, a.stream>>>((char*)a.state, sizeof(Nav2DRearrState), (RearrGeoField*)a.geo, a.mask,
+                                                               a.advance ? 1 : 0, a.num_obstacles, start_holding);
+    } else if constexpr (VEL) {
+        nav2d_rearr_vel_step_kernel<<<cdiv(a.N, 64), 64, 0, a.stream>>>(states, a.dirs, (const float*)a.actions, a.mask, obj_start, obj_goal,
+                                                                        is_holding, a.reward, a.not_done, a.measure_sums, a.seed,
+                                                                        a.env_offset, a.N, a.num_obstacles, a.num_headings,
+                                                                        a.max_episode_steps, start_holding, max_turn_steps, stop_turn_steps,
+                                                                        min_abs_lin_speed, allow_sliding, a.advance);
+    } else {
+        nav2d_rearr_step_kernel<<<cdiv(a.N, 64), 64, 0, a.stream>>>(states, a.dirs, (const int64_t*)a.actions, a.mask, obj_start, obj_goal,
+                                                                    is_holding, a.reward, a.not_done, a.measure_sums, a.seed, a.env_offset,
+                                                                    a.N, a.num_obstacles, a.num_headings, a.max_episode_steps, start_holding,
+                                                                    a.advance);
+    }
     HAB_LAUNCH_CHECK();
     return launch_render<Render::REARR>(a, 0);
+}
+
+extern "C" int hab_nav2d_rearr_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                                    const int64_t* actions, const uint8_t* mask, uint8_t* head_rgb, float* head_depth, float* obj_start,
+                                    float* obj_goal, float* is_holding, float* reward, uint8_t* not_done, float* measure_sums,
+                                    uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings,
+                                    int max_episode_steps, int start_holding, int advance, hipStream_t stream) {
+    return rearr_step<false, false>({state, nullptr, dirs, ray, col_cos, tanv, actions, mask, head_rgb, head_depth, nullptr, nullptr, reward,
+                                     not_done, measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps,
+                                     advance, stream},
+                                    obj_start, obj_goal, is_holding, start_holding, 0, 0, 0.0f, 0);
+}
+
+extern "C" int hab_nav2d_rearr_vel_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                                        const float* actions, const uint8_t* mask, uint8_t* head_rgb, float* head_depth, float* obj_start,
+                                        float* obj_goal, float* is_holding, float* reward, uint8_t* not_done, float* measure_sums,
+                                        uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings,
+                                        int max_episode_steps, int start_holding, int max_turn_steps, int stop_turn_steps,
+                                        float min_abs_lin_speed, int allow_sliding, int advance, hipStream_t stream) {
+    return rearr_step<true, false>({state, nullptr, dirs, ray, col_cos, tanv, actions, mask, head_rgb, head_depth, nullptr, nullptr, reward,
+                                    not_done, measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps,
+                                    advance, stream},
+                                   obj_start, obj_goal, is_holding, start_holding, max_turn_steps, stop_turn_steps, min_abs_lin_speed,
+                                   allow_sliding);
 }
 
 extern "C" int hab_nav2d_rearr_step_geo(void* state, void* geo, const float* dirs, const float* ray, const float* col_cos,
@@ -2310,10 +2203,10 @@ extern "C" int hab_nav2d_rearr_step_geo(void* state, void* geo, const float* dir
                                         uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
                                         int num_obstacles, int num_headings, int max_episode_steps, int start_holding, int advance,
                                         hipStream_t stream) {
-    return rearr_step_geo<false>({state, geo, dirs, ray, col_cos, tanv, actions, mask, head_rgb, head_depth, nullptr, nullptr, reward,
-                                  not_done, measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps,
-                                  advance, stream},
-                                 obj_start, obj_goal, is_holding, start_holding, 0, 0, 0.0f, 0);
+    return rearr_step<false, true>({state, geo, dirs, ray, col_cos, tanv, actions, mask, head_rgb, head_depth, nullptr, nullptr, reward,
+                                    not_done, measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps,
+                                    advance, stream},
+                                   obj_start, obj_goal, is_holding, start_holding, 0, 0, 0.0f, 0);
 }
 
 extern "C" int hab_nav2d_rearr_vel_step_geo(void* state, void* geo, const float* dirs, const float* ray, const float* col_cos,
@@ -2323,11 +2216,11 @@ extern "C" int hab_nav2d_rearr_vel_step_geo(void* state, void* geo, const float*
                                             int W, int num_obstacles, int num_headings, int max_episode_steps, int start_holding,
                                             int max_turn_steps, int stop_turn_steps, float min_abs_lin_speed, int allow_sliding,
                                             int advance, hipStream_t stream) {
-    return rearr_step_geo<true>({state, geo, dirs, ray, col_cos, tanv, actions, mask, head_rgb, head_depth, nullptr, nullptr, reward,
-                                 not_done, measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps,
-                                 advance, stream},
-                                obj_start, obj_goal, is_holding, start_holding, max_turn_steps, stop_turn_steps, min_abs_lin_speed,
-                                allow_sliding);
+    return rearr_step<true, true>({state, geo, dirs, ray, col_cos, tanv, actions, mask, head_rgb, head_depth, nullptr, nullptr, reward,
+                                   not_done, measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps,
+                                   advance, stream},
+                                  obj_start, obj_goal, is_holding, start_holding, max_turn_steps, stop_turn_steps, min_abs_lin_speed,
+                                  allow_sliding);
 }
 
 // The pick-and-place oracle: the checks of hab_nav2d_rearr_geo_build for state, stride, field, N and K, then those of its own
@@ -2338,8 +2231,7 @@ extern "C" int hab_nav2d_rearr_oracle(const void* state, size_t state_stride_byt
     const int rc = check_geo_args(state, state_stride_bytes, geo, N, num_obstacles);
     if (rc != HAB_OK) return rc;
     if (state_stride_bytes < sizeof(Nav2DRearrState)) return HAB_ERR_ARG;
-    if (!dirs || ((uintptr_t)dirs & 3) || !actions || ((uintptr_t)actions & 7)) return HAB_ERR_ARG;
-    if (((uintptr_t)next_d & 3) || ((uintptr_t)status & 3) || num_headings <= 0) return HAB_ERR_ARG;
+    if (!guide_args_ok(dirs, actions, sizeof(int64_t), next_d, status, num_headings)) return HAB_ERR_ARG;
     nav2d_rearr_oracle_kernel<<<N, 64, 0, stream>>>((const char*)state, state_stride_bytes, (const RearrGeoField*)geo, dirs, mask, actions,
                                                     next_d, status, num_obstacles, num_headings);
     HAB_LAUNCH_CHECK();
@@ -2361,8 +2253,7 @@ extern "C" int hab_nav2d_social_step(void* state, const float* dirs, const float
     const int rc = check_step_args(a, false);
     if (rc != HAB_OK) return rc;
     if (((uintptr_t)state & 3) || ((uintptr_t)actions & 3)) return HAB_ERR_ARG;  // a row of two floats is read as two scalars
-    if (max_turn_steps < 1 || max_turn_steps > num_headings / 2 || stop_turn_steps < 1 || stop_turn_steps > max_turn_steps)
-        return HAB_ERR_ARG;
+    if (!vel_args_ok(max_turn_steps, stop_turn_steps, num_headings)) return HAB_ERR_ARG;
     if (!(person_speed > 0.0f && person_speed <= 0.25f)) return HAB_ERR_ARG;
     if (person_always_visible != 0 && person_always_visible != 1) return HAB_ERR_ARG;
     nav2d_social_step_kernel<<<N, 64, 0, stream>>>((Nav2DSocialState*)state, dirs, actions, mask, person_sensor, person_visible, reward,
