@@ -749,8 +749,8 @@ static int rn_conv_wgrad(hab_policy* e, const ConvDesc& c, const float* x, const
     return conv_wgrad(c, x, dy, dw, nullptr, ws, e->ws_floats, s);
 }
 // Backward of convolution c on B frames: the weight gradient from its input x and dy (a grouped convolution's dense into scratch, its block
-// diagonal gathered into the (Cout, C / groups, KH, KW) gradient), then the data gradient dx = dgrad(dy) * (relu_mask > 0) + add (either
-// may be null).
+// diagonal gathered into the (Cout, C / groups, KH, KW) gradient), then the data gradient dx = relu_mask > 0 ? dgrad(dy) + add : 0 (either
+// may be null; the add comes first, the mask zeroes the sum: problems.h epi_store).
 static int rn_conv_backward(hab_policy* e, const RnConv& c, int B, const float* x, const float* dy, const float* relu_mask, const float* add,
                             float* dx, hipStream_t s) {
     float* W = e->WK;

@@ -246,13 +246,16 @@ int conv_wgrad(const ConvDesc& d, const float* x, const float* dy, float* dw_oih
         ConvWgradProb q = p;
         q.colsum = nullptr;
         auto bias_grad = [&] { return dbias ? colsum(dy, p.N, p.K, p.N, dbias, 0, ws, ws_floats, stream) : HAB_OK; };
-        if (wgrad3x3_patch_ok(p)) {  // 3x3/1/1 with W in {16, 32}: patch-resident kernel
+        // A workspace too short for a form declines the form, it does not fail the call (the igemm tiles below need none and fuse the bias
+        // gradient).  Decided before anything is launched: the column sum needs one row of N floats, the patch kernel one slab.
+        const bool bias_fits = !dbias || ws_floats >= (size_t)p.N;
+        if (bias_fits && wgrad3x3_patch_ok(p) && wgrad3x3_patch_fits(p, ws_floats)) {  // 3x3/1/1 with W in {16, 32}: patch-resident kernel
             HAB_TRY(bias_grad());
             return wgrad3x3_patch(q, ws, ws_floats, stream);
         }
         // LDS-DMA staged variant (igemm_dma_wgrad.h): measured faster only for unpadded convolutions with Cout <= 32 (SimpleCNN conv3:
         // 51 -> 64 TFLOP/s); with padding the per-pixel scalar decode + border tests cost more than the VGPR staging they replace.
-        if (d.pad == 0 && p.N <= 32 && wgrad_dma_ok(q)) {
+        if (bias_fits && d.pad == 0 && p.N <= 32 && wgrad_dma_ok(q)) {
             HAB_TRY(bias_grad());
             if (rows_fit(q.M, 288, 256)) return igemm_dma_wgrad_launch<3, 3, 1>(q, ws, ws_floats, 1024, stream);
             return igemm_dma_wgrad_launch<2, 4, 1>(q, ws, ws_floats, 1024, stream);

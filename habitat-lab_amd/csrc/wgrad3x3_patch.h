@@ -149,6 +149,9 @@ inline bool wgrad3x3_patch_ok(const ConvWgradProb& p) {
            g.Cout % 32 == 0 && p.Creal == g.C && (size_t)g.H * g.W * std::max(g.C, g.Cout) * 4 < 0x7fffffffull;
 }
 
+// The kernel always writes slabs (one split included): the workspace must hold at least one.  conv_wgrad asks before it chooses the form.
+inline bool wgrad3x3_patch_fits(const ConvWgradProb& p, size_t ws_floats) { return ws_floats >= (size_t)9 * p.g.C * p.g.Cout; }
+
 // ws must hold splits * 9*C*Co floats; the final sum + OIHW scatter (+ nothing else: resnet convs have no bias) is the
 // implicit-GEMM path's split-K reduce.
 inline int wgrad3x3_patch(const ConvWgradProb& p, float* ws, size_t ws_floats, hipStream_t stream) {

@@ -573,6 +573,8 @@ int hab_sample_actions(const float* probs, const float* exp_noise, int64_t* acti
  * ------------------------------------------------------------------------------------------- */
 int hab_set_matrix_path(int mode);
 
+/* NHWC activations, w_fwd [Cout][KH][KW][C] (hab_repack_conv_weight).  Accepts C % 4 == 0 and any Cout (HAB_ERR_UNSUPPORTED otherwise);
+ * every element of y is written.  ws may be NULL or of any length: it only bounds the split-K plan. */
 int hab_conv2d_fwd(const float* x, const float* w_fwd, const float* bias, float* y, int B, int H, int W, int C, int Cout,
                    int KH, int KW, int stride, int pad, int relu, float* ws, size_t ws_floats, hipStream_t stream);
 int hab_obs_conv2d_fwd(const uint8_t* rgb, const float* depth, const int* rows, const float* w_fwd, const float* bias,
@@ -589,10 +591,14 @@ int hab_obs_conv2d_fwd(const uint8_t* rgb, const float* depth, const int* rows, 
 int hab_obs_conv2d_fwd_form(const uint8_t* rgb, const float* depth, const int* rows, const float* w_fwd, const float* bias,
                             float* y, int B, int H, int W, int Cout, int KH, int KW, int stride, int pad, int relu, const float* ws,
                             size_t ws_floats);
+/* The gradients accept C % 4 == 0 and Cout % 4 == 0 (HAB_ERR_UNSUPPORTED otherwise).  Every element of dx is overwritten, pixels that no
+ * tap reaches included: dx = relu_mask > 0 ? dgrad(dy) + add : +0.0 -- add (nullable) first, then relu_mask (nullable, shaped like dx); a
+ * mask entry that is zero, negative or NaN gives +0.0.  ws as for the forward: NULL or any length. */
 int hab_conv2d_dgrad(const float* dy, const float* w_dgrad, const float* relu_mask, const float* add, float* dx, int B,
                      int H, int W, int C, int Cout, int KH, int KW, int stride, int pad, float* ws, size_t ws_floats,
                      hipStream_t stream);
-/* dbias (nullable): bias gradient [Cout] = column sums of dy, produced by the same launch. */
+/* dw_oihw and dbias are overwritten, not accumulated.  dbias (nullable): bias gradient [Cout] = column sums of dy, produced by the same
+ * call.  A workspace too short for a kernel form selects another form; the call succeeds whenever it does with ws = NULL. */
 int hab_conv2d_wgrad(const float* x, const float* dy, float* dw_oihw, float* dbias, int B, int H, int W, int C, int Cout,
                      int KH, int KW, int stride, int pad, float* ws, size_t ws_floats, hipStream_t stream);
 int hab_obs_conv2d_wgrad(const uint8_t* rgb, const float* depth, const int* rows, const float* dy, float* dw_oihw,
