@@ -23,8 +23,6 @@
 
 namespace hab {
 
-typedef __bf16 c1g_bf16x8 __attribute__((ext_vector_type(8)));
-
 struct C1gArgs {
     const float* x;            // [B][H][W][C] NHWC, C in {32, 64, 128, 256}
     const unsigned short* wq;  // [3][Cout/32][C/16][64 lanes][8] bf16 (cgs_split_weights of the [Cout][C] filter)
@@ -84,7 +82,6 @@ __global__ void __launch_bounds__(512) conv1x1_gn_stream_kernel(const C1gArgs a)
 #pragma unroll
         for (int v = 0; v < 16; ++v) acc[m][v] = 0.f;
 
-    constexpr int PX[6] = {2, 0, 1, 1, 0, 0}, PW_[6] = {0, 2, 1, 0, 1, 0};  // smallest partial product first
     f32x4 nx[NU];
     // unit u = lane + 64 j of a tile chunk: pixel u / QPP, channel quad u % QPP
     auto issue = [&](int m, int kc) {
@@ -109,10 +106,10 @@ __global__ void __launch_bounds__(512) conv1x1_gn_stream_kernel(const C1gArgs a)
         for (int pl = 0; pl < 3; ++pl) wr[pl] = *reinterpret_cast<const u32x4*>(wbase + pl * wplane + (size_t)(kc * KSC) * 512);
 #pragma unroll
         for (int ks = 0; ks < KSC; ++ks) {
-            c1g_bf16x8 bw[3], af[3];
+            bf16x8 bw[3], af[3];
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
-                bw[pl] = __builtin_bit_cast(c1g_bf16x8, u32x4{wr[pl][0] ^ sgn2, wr[pl][1] ^ sgn2, wr[pl][2] ^ sgn2, wr[pl][3] ^ sgn2});
+                bw[pl] = __builtin_bit_cast(bf16x8, u32x4{wr[pl][0] ^ sgn2, wr[pl][1] ^ sgn2, wr[pl][2] ^ sgn2, wr[pl][3] ^ sgn2});
             if (ks + 1 < KSC) {
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
@@ -120,7 +117,7 @@ __global__ void __launch_bounds__(512) conv1x1_gn_stream_kernel(const C1gArgs a)
             }
             const f32x4 x0 = *reinterpret_cast<const f32x4*>(xs + li * CP + 16 * ks + 8 * hi);
             const f32x4 x1 = *reinterpret_cast<const f32x4*>(xs + li * CP + 16 * ks + 8 * hi + 4);
-            u32x4 p0, p1, p2;
+            u32x4 p0, p1, p2;  // bf3_split8's packing, written out: through the helper two of the seven instantiations are scheduled differently
             {
                 unsigned a1, a2, a3, b1, b2, b3;
                 bf3_split2(x0[0], x0[1], a1, a2, a3);
@@ -130,11 +127,11 @@ __global__ void __launch_bounds__(512) conv1x1_gn_stream_kernel(const C1gArgs a)
                 bf3_split2(x1[2], x1[3], b1, b2, b3);
                 p0[2] = a1; p0[3] = b1; p1[2] = a2; p1[3] = b2; p2[2] = a3; p2[3] = b3;
             }
-            af[0] = __builtin_bit_cast(c1g_bf16x8, p0);
-            af[1] = __builtin_bit_cast(c1g_bf16x8, p1);
-            af[2] = __builtin_bit_cast(c1g_bf16x8, p2);
+            af[0] = __builtin_bit_cast(bf16x8, p0);
+            af[1] = __builtin_bit_cast(bf16x8, p1);
+            af[2] = __builtin_bit_cast(bf16x8, p2);
 #pragma unroll
-            for (int q = 0; q < 6; ++q) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[PW_[q]], af[PX[q]], acc[m], 0, 0, 0);
+            for (int q = 0; q < 6; ++q) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[BF3_PB[q]], af[BF3_PA[q]], acc[m], 0, 0, 0);
         }
     }
     if (flip) {
@@ -297,9 +294,7 @@ inline int conv1x1_gn_stream(C1gArgs a, hipStream_t stream) {
     const size_t lds = (size_t)8 * 32 * (ch + 4) * sizeof(float) + (size_t)8 * mt * 32 * sizeof(int);  // <= 136 KB (+ 0.7 KB static)
 #define C1G_LAUNCH(MT_, CH_, NCH_)                                                                                                   \
     {                                                                                                                                \
-        static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_gn_stream_kernel<MT_, CH_, NCH_>), \
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);              \
-        if (attr_err != hipSuccess) return (int)attr_err;                                                                            \
+        HAB_TRY((lds_opt_in<conv1x1_gn_stream_kernel<MT_, CH_, NCH_>>(144 * 1024)));                                                 \
         conv1x1_gn_stream_kernel<MT_, CH_, NCH_><<<grid, 512, lds, stream>>>(a);                                                     \
     }
 #define C1G_C(MT_)                                                                        \

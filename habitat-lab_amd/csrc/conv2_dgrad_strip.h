@@ -60,10 +60,8 @@ __global__ void __launch_bounds__(512) conv2_dgrad_strip_kernel(const C2dArgs a)
     const int tap = wave >> 1, ph = wave & 1, ta = tap >> 1, tb = tap & 1;
     const int li = lane & 31, hi = lane >> 5;
 
-    const int xcd = blockIdx.x & 7, jw = blockIdx.x >> 3, wg_per_xcd = gridDim.x >> 3;
-    const int per_xcd = (a.items + 7) >> 3, per_wg = (per_xcd + wg_per_xcd - 1) / wg_per_xcd;
-    const int xcd_end = min(a.items, (xcd + 1) * per_xcd);
-    const int first = min(xcd_end, xcd * per_xcd + jw * per_wg), last = min(xcd_end, first + per_wg);
+    int first, last;  // this workgroup's strips
+    xcd_item_run(a.items, blockIdx.x, gridDim.x, first, last);
     if (first >= last) return;
 
     // border columns (and everything else until staged) read as zero
@@ -81,14 +79,9 @@ __global__ void __launch_bounds__(512) conv2_dgrad_strip_kernel(const C2dArgs a)
             const int kh = ph + 2 * ta, kw = pw + 2 * tb, co = j * 16 + hi * 8;
             const float* src = a.wd + ((size_t)(li * 4 + kh) * 4 + kw) * 64 + co;
             const f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 4);
-            unsigned p[3][4];
-            bf3_split2(v0[0], v0[1], p[0][0], p[1][0], p[2][0]);
-            bf3_split2(v0[2], v0[3], p[0][1], p[1][1], p[2][1]);
-            bf3_split2(v1[0], v1[1], p[0][2], p[1][2], p[2][2]);
-            bf3_split2(v1[2], v1[3], p[0][3], p[1][3], p[2][3]);
+            const Bf3Planes sp = bf3_split8(v0, v1, sgn2);
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
-                bw[j][pw][pl] = __builtin_bit_cast(bf16x8, u32x4{p[pl][0] ^ sgn2, p[pl][1] ^ sgn2, p[pl][2] ^ sgn2, p[pl][3] ^ sgn2});
+            for (int pl = 0; pl < 3; ++pl) bw[j][pw][pl] = sp.p[pl];
         }
 
     f32x4 yr[Cfg::YPT];
@@ -153,12 +146,12 @@ __global__ void __launch_bounds__(512) conv2_dgrad_strip_kernel(const C2dArgs a)
                 bf16x8 yf[3];
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) yf[pl] = *reinterpret_cast<const bf16x8*>(src + pl * Cfg::Y_PLANE);
-                constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};  // smallest weight first (A: dY, B: filter)
+                // A: dY, B: filter
 #pragma unroll
                 for (int q = 0; q < 6; ++q)
 #pragma unroll
                     for (int pw = 0; pw < 2; ++pw)  // operands swapped: D[m = input channel][n = cell]
-                        acc[pw] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[j][pw][PB[q]], yf[PA[q]], acc[pw], 0, 0, 0);
+                        acc[pw] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[j][pw][BF3_PB[q]], yf[BF3_PA[q]], acc[pw], 0, 0, 0);
             }
             if (tr > 0) __syncthreads();  // the previous tile's reduction has read `red`
             float* mine = red + (size_t)(wave * 32 + li) * Cfg::RED_LD;
@@ -220,19 +213,14 @@ inline int conv2_dgrad_strip(const ConvDesc& d, const float* dy, const float* wd
     a.strips = cdiv((d.H + 1) / 2, R2);  // cell rows = ceil(H / 2)
     a.items = d.B * a.strips;
     a.sign_schedule = bf3_sign_schedule();
-    // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
-    static const hipError_t attr_err = [] {
-        const hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_dgrad_strip_kernel<R2, false>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-        const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_dgrad_strip_kernel<R2, true>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-        return e0 != hipSuccess ? e0 : e1;
-    }();
-    if (attr_err != hipSuccess) return (int)attr_err;
-    int grid = 256;
-    while (grid > 8 && grid > a.items) grid -= 8;
-    if (d.H == 63 && d.W == 63) conv2_dgrad_strip_kernel<R2, false><<<grid, Cfg::NT, Cfg::LDS_BYTES, stream>>>(a);
-    else conv2_dgrad_strip_kernel<R2, true><<<grid, Cfg::NT, Cfg::LDS_BYTES, stream>>>(a);
+    const int grid = persistent_grid(a.items);
+    if (d.H == 63 && d.W == 63) {
+        HAB_TRY((lds_opt_in<conv2_dgrad_strip_kernel<R2, false>>((int)Cfg::LDS_BYTES)));
+        conv2_dgrad_strip_kernel<R2, false><<<grid, Cfg::NT, Cfg::LDS_BYTES, stream>>>(a);
+    } else {
+        HAB_TRY((lds_opt_in<conv2_dgrad_strip_kernel<R2, true>>((int)Cfg::LDS_BYTES)));
+        conv2_dgrad_strip_kernel<R2, true><<<grid, Cfg::NT, Cfg::LDS_BYTES, stream>>>(a);
+    }
     HAB_LAUNCH_CHECK();
     return HAB_OK;
 }

@@ -16,7 +16,8 @@
 //     4 consecutive output channels of one pixel);
 //   * the eight partial sums of a tile meet in LDS ([wave][pixel][64 + 4 pad] fp32, conflict-free 16-byte accesses) and are summed in
 //     wave order (fixed: deterministic), + bias, ReLU, one coalesced 16-byte store per thread;
-//   * the next strip's global loads are in flight under the MFMAs (registers), as in wgrad3x3_bf3.h.
+//   * the next strip's global loads are in flight under the MFMAs (registers), as in wgrad3x3_bf3.h; the strips are split over the
+//     workgroups by xcd_item_run (bf3_split.h).
 // Sign schedule as everywhere on the split path: every second workgroup accumulates the negated sum (weights negated when split).
 #pragma once
 #include "igemm_bf3.h"
@@ -66,10 +67,8 @@ __global__ void __launch_bounds__(512) conv2_fwd_strip_kernel(const C2fArgs a) {
     const int kh = wave >> 1, kwp = wave & 1;
     const int li = lane & 31, hi = lane >> 5;
 
-    const int xcd = blockIdx.x & 7, jw = blockIdx.x >> 3, wg_per_xcd = gridDim.x >> 3;
-    const int per_xcd = (a.items + 7) >> 3, per_wg = (per_xcd + wg_per_xcd - 1) / wg_per_xcd;
-    const int xcd_end = min(a.items, (xcd + 1) * per_xcd);
-    const int first = min(xcd_end, xcd * per_xcd + jw * per_wg), last = min(xcd_end, first + per_wg);
+    int first, last;  // this workgroup's strips
+    xcd_item_run(a.items, blockIdx.x, gridDim.x, first, last);
     if (first >= last) return;
 
     const bool flip = a.sign_schedule && (blockIdx.x & 1);
@@ -84,14 +83,9 @@ __global__ void __launch_bounds__(512) conv2_fwd_strip_kernel(const C2fArgs a) {
             const int co = ct * 32 + li, kw = 2 * kwp + (j >> 1), ci = (j & 1) * 16 + hi * 8;
             const float* src = a.wf + ((size_t)(co * 4 + kh) * 4 + kw) * 32 + ci;
             const f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 4);
-            unsigned p[3][4];
-            bf3_split2(v0[0], v0[1], p[0][0], p[1][0], p[2][0]);
-            bf3_split2(v0[2], v0[3], p[0][1], p[1][1], p[2][1]);
-            bf3_split2(v1[0], v1[1], p[0][2], p[1][2], p[2][2]);
-            bf3_split2(v1[2], v1[3], p[0][3], p[1][3], p[2][3]);
+            const Bf3Planes sp = bf3_split8(v0, v1, sgn2);
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
-                bw[j][ct][pl] = __builtin_bit_cast(bf16x8, u32x4{p[pl][0] ^ sgn2, p[pl][1] ^ sgn2, p[pl][2] ^ sgn2, p[pl][3] ^ sgn2});
+            for (int pl = 0; pl < 3; ++pl) bw[j][ct][pl] = sp.p[pl];
         }
 
     f32x4 xr[Cfg::XPT];
@@ -153,12 +147,12 @@ __global__ void __launch_bounds__(512) conv2_fwd_strip_kernel(const C2fArgs a) {
                 bf16x8 af[3];
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) af[pl] = *reinterpret_cast<const bf16x8*>(src + pl * X_PLANE);
-                constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};  // smallest weight first (A: input, B: filter)
+                // A: input, B: filter
 #pragma unroll
                 for (int q = 0; q < 6; ++q)
 #pragma unroll
                     for (int ct = 0; ct < 2; ++ct)  // operands swapped: D[m = output channel][n = pixel]
-                        acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[j][ct][PB[q]], af[PA[q]], acc[ct], 0, 0, 0);
+                        acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[j][ct][BF3_PB[q]], af[BF3_PA[q]], acc[ct], 0, 0, 0);
             }
             if (pt > 0) __syncthreads();  // the previous tile's reduction has read `red`
             // lane (pixel li): channels ct*32 + 8 g + 4 hi .. +3 in acc[ct][4 g .. 4 g + 3]
@@ -208,19 +202,14 @@ inline int conv2_fwd_strip(const ConvFwdProb& p, float* /*ws*/, size_t /*ws_floa
     a.relu = p.relu;
     a.sign_schedule = bf3_sign_schedule();
     const bool bench_geom = g.H == 63 && g.W == 63;
-    // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
-    static const hipError_t attr_err = [] {
-        const hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_fwd_strip_kernel<R, false>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-        const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv2_fwd_strip_kernel<R, true>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-        return e0 != hipSuccess ? e0 : e1;
-    }();
-    if (attr_err != hipSuccess) return (int)attr_err;
-    int grid = 256;
-    while (grid > 8 && grid > a.items) grid -= 8;
-    if (bench_geom) conv2_fwd_strip_kernel<R, false><<<grid, Cfg::NT, Cfg::LDS_BYTES, stream>>>(a);
-    else conv2_fwd_strip_kernel<R, true><<<grid, Cfg::NT, (size_t)3 * Cfg::XRS * g.W * 32 * 2 + Cfg::RED_BYTES, stream>>>(a);
+    const int grid = persistent_grid(a.items);
+    if (bench_geom) {
+        HAB_TRY((lds_opt_in<conv2_fwd_strip_kernel<R, false>>((int)Cfg::LDS_BYTES)));
+        conv2_fwd_strip_kernel<R, false><<<grid, Cfg::NT, Cfg::LDS_BYTES, stream>>>(a);
+    } else {
+        HAB_TRY((lds_opt_in<conv2_fwd_strip_kernel<R, true>>((int)Cfg::LDS_BYTES)));
+        conv2_fwd_strip_kernel<R, true><<<grid, Cfg::NT, (size_t)3 * Cfg::XRS * g.W * 32 * 2 + Cfg::RED_BYTES, stream>>>(a);
+    }
     HAB_LAUNCH_CHECK();
     return HAB_OK;
 }

@@ -98,13 +98,9 @@ __global__ void __launch_bounds__(512) conv3_dgrad_strip_kernel(const C3dArgs a)
         tapoff[j] = (2 - kh) * Cfg::YCOLS + 2 - kw;
         const float* src = a.wd + ((size_t)(chalf * 32 + li) * 9 + tap) * 32 + coh * 16 + hi * 8;
         const f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 4);
-        unsigned p[3][4];
-        bf3_split2(v0[0], v0[1], p[0][0], p[1][0], p[2][0]);
-        bf3_split2(v0[2], v0[3], p[0][1], p[1][1], p[2][1]);
-        bf3_split2(v1[0], v1[1], p[0][2], p[1][2], p[2][2]);
-        bf3_split2(v1[2], v1[3], p[0][3], p[1][3], p[2][3]);
+        const Bf3Planes sp = bf3_split8(v0, v1, 0u);
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) bw[j][pl] = __builtin_bit_cast(bf16x8, u32x4{p[pl][0], p[pl][1], p[pl][2], p[pl][3]});
+        for (int pl = 0; pl < 3; ++pl) bw[j][pl] = sp.p[pl];
     }
 
     f32x4 yr[Cfg::YPT];
@@ -199,10 +195,10 @@ __global__ void __launch_bounds__(512) conv3_dgrad_strip_kernel(const C3dArgs a)
                 for (int j = 0; j < 9; ++j) {
                     if (j + 1 < 9) read_frags(j + 1, yf[(j + 1) & 1]);
                     __builtin_amdgcn_sched_barrier(0);
-                    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};  // smallest weight first (A: dY, B: filter)
+                    // A: dY, B: filter
 #pragma unroll
                     for (int q = 0; q < 6; ++q)  // operands swapped: D[m = input channel][n = pixel]
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[j][PB[q]], yf[j & 1][PA[q]], acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[j][BF3_PB[q]], yf[j & 1][BF3_PA[q]], acc, 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 if (z == 0) {
@@ -266,19 +262,14 @@ inline int conv3_dgrad_strip(const ConvDesc& d, const float* dy, const float* wd
     static const hipError_t sym_err = hipGetSymbolAddress(reinterpret_cast<void**>(&pool), HIP_SYMBOL(c3d_draw_pool));
     if (sym_err != hipSuccess || !pool) return HAB_ERR_ARG;
     a.ctr = pool + (size_t)(next_slot.fetch_add(1, std::memory_order_relaxed) % C3D_DRAW_SLOTS) * 16;
-    // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
-    static const hipError_t attr_err = [] {
-        const hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_dgrad_strip_kernel<R, false>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-        const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_dgrad_strip_kernel<R, true>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-        return e0 != hipSuccess ? e0 : e1;
-    }();
-    if (attr_err != hipSuccess) return (int)attr_err;
-    int grid = 256;
-    while (grid > 8 && grid > a.items) grid -= 8;
-    if (d.H == Cfg::H && d.W == Cfg::H) conv3_dgrad_strip_kernel<R, false><<<grid, Cfg::NT, Cfg::LDS_BYTES, stream>>>(a);
-    else conv3_dgrad_strip_kernel<R, true><<<grid, Cfg::NT, Cfg::LDS_BYTES, stream>>>(a);
+    const int grid = persistent_grid(a.items);
+    if (d.H == Cfg::H && d.W == Cfg::H) {
+        HAB_TRY((lds_opt_in<conv3_dgrad_strip_kernel<R, false>>((int)Cfg::LDS_BYTES)));
+        conv3_dgrad_strip_kernel<R, false><<<grid, Cfg::NT, Cfg::LDS_BYTES, stream>>>(a);
+    } else {
+        HAB_TRY((lds_opt_in<conv3_dgrad_strip_kernel<R, true>>((int)Cfg::LDS_BYTES)));
+        conv3_dgrad_strip_kernel<R, true><<<grid, Cfg::NT, Cfg::LDS_BYTES, stream>>>(a);
+    }
     HAB_LAUNCH_CHECK();
     return HAB_OK;
 }

@@ -30,8 +30,6 @@
 
 namespace hab {
 
-typedef __bf16 cgs_bf16x8 __attribute__((ext_vector_type(8)));
-
 struct CgsArgs {
     const float* x;            // [B][H][W][C] NHWC, C % 16 == 0
     const unsigned short* wq;  // fragment-ordered weight planes [3][Cout/32][K/16][64 lanes][8] bf16 (cgs_split_weights)
@@ -193,7 +191,7 @@ __global__ void __launch_bounds__(512) conv_gn_slab_kernel(const CgsArgs a) {
         l_kh = tap / a.KW;
         l_kw = tap - l_kh * a.KW;
     }
-    struct AFrag { cgs_bf16x8 p[MT][3]; };
+    struct AFrag { bf16x8 p[MT][3]; };
     auto aread = [&](AFrag& f) {
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
@@ -207,7 +205,7 @@ __global__ void __launch_bounds__(512) conv_gn_slab_kernel(const CgsArgs a) {
             }
             const unsigned short* src = xs + r * PITCH + l_c + 8 * hi;
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl) f.p[i][pl] = *reinterpret_cast<const cgs_bf16x8*>(src + pl * plane);
+            for (int pl = 0; pl < 3; ++pl) f.p[i][pl] = *reinterpret_cast<const bf16x8*>(src + pl * plane);
         }
         l_c += 16;
         if (l_c >= a.C) {
@@ -226,22 +224,21 @@ __global__ void __launch_bounds__(512) conv_gn_slab_kernel(const CgsArgs a) {
 
     auto compute = [&](const AFrag& f, const WStage& g) {
         if (a.ablate & 2) return;
-        cgs_bf16x8 bw[NT][3];
+        bf16x8 bw[NT][3];
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) {
                 const u32x4 w = g.w[j][pl];
-                bw[j][pl] = __builtin_bit_cast(cgs_bf16x8, u32x4{w[0] ^ sgn2, w[1] ^ sgn2, w[2] ^ sgn2, w[3] ^ sgn2});
+                bw[j][pl] = __builtin_bit_cast(bf16x8, u32x4{w[0] ^ sgn2, w[1] ^ sgn2, w[2] ^ sgn2, w[3] ^ sgn2});
             }
-        constexpr int PX[6] = {2, 0, 1, 1, 0, 0}, PW[6] = {0, 2, 1, 0, 1, 0};  // smallest partial product first
 #pragma unroll
         for (int q = 0; q < 6; ++q)
 #pragma unroll
             for (int i = 0; i < MT; ++i)
 #pragma unroll
                 for (int j = 0; j < NT; ++j)  // operands swapped: D[m = output channel][n = pixel]
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[j][PW[q]], f.p[i][PX[q]], acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[j][BF3_PB[q]], f.p[i][BF3_PA[q]], acc[i][j], 0, 0, 0);
     };
 
     __syncthreads();  // the input image is complete
@@ -415,11 +412,8 @@ inline int cgs_launch(CgsArgs& a, hipStream_t stream) {
     a.sub = (a.KH == 1 && a.KW == 1) ? 1 : 0;
     const size_t lds = cgs_lds<MT, NT, WM, WK>(a, &a.region0_bytes, &a.prow);
     if (lds == 0) return HAB_NOT_APPLICABLE;
-    auto kern = conv_gn_slab_kernel<MT, NT, WM, WK, D>;
-    // set once per process and instantiation (thread-safe static initialisation: engines of several inference workers call this concurrently)
-    static const hipError_t attr_err =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, CGS_LDS_MAX);
-    if (attr_err != hipSuccess) return (int)attr_err;
+    constexpr auto kern = conv_gn_slab_kernel<MT, NT, WM, WK, D>;
+    HAB_TRY(lds_opt_in<kern>(CGS_LDS_MAX));
     const int nfg = (a.B + a.fpw - 1) / a.fpw;
     kern<<<nfg * a.nslab, 512, lds, stream>>>(a);
     HAB_LAUNCH_CHECK();

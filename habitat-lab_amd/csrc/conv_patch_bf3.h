@@ -281,13 +281,12 @@ __global__ void __launch_bounds__(WM* WN * 64) conv_patch_bf3_kernel(const P p, 
                 for (int g = 0; g < NG; g += 2) {
                     load_group(g, 0);
                     load_group(g + 1, 1);
-                    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
                     for (int q = 0; q < 6; ++q)
 #pragma unroll
                         for (int j = 0; j < TN; ++j) {
-                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[0][j][PB[q]], af[0][PA[q]], acc[j], 0, 0, 0);
-                            acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[1][j][PB[q]], af[1][PA[q]], acc2[j], 0, 0, 0);
+                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[0][j][BF3_PB[q]], af[0][BF3_PA[q]], acc[j], 0, 0, 0);
+                            acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[1][j][BF3_PB[q]], af[1][BF3_PA[q]], acc2[j], 0, 0, 0);
                         }
                 }
                 __syncthreads();
@@ -371,19 +370,15 @@ inline int conv_patch_bf3_launch(const P& p, PatchGeom gq, float* ws, size_t ws_
         ctr = pool + (size_t)(next_slot.fetch_add(1, std::memory_order_relaxed) % CPB_DRAW_SLOTS) * 16;
     }
     if (pre) {
-        auto kern = conv_patch_bf3_kernel<P, TW, WM, WN, TN, BT, true>;
-        // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
-        static const hipError_t attr_err = (Cfg::LDS_BYTES > 64 * 1024) ? hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES) : hipSuccess;
-        if (attr_err != hipSuccess) return (int)attr_err;
+        constexpr auto kern = conv_patch_bf3_kernel<P, TW, WM, WN, TN, BT, true>;
+        HAB_TRY(lds_opt_in<kern>((int)Cfg::LDS_BYTES, Cfg::LDS_BYTES > 64 * 1024));
         unsigned short* planes = reinterpret_cast<unsigned short*>(ws);
         cpb_split_weights<<<(unsigned)((wn_elems + 255) / 256), 256, 0, stream>>>(p.w, wn_elems, planes);
         HAB_LAUNCH_CHECK();
         kern<<<grid, Cfg::NT, Cfg::LDS_BYTES, stream>>>(p, gq, sign_schedule, planes, wn_elems, ctr);
     } else {
-        auto kern = conv_patch_bf3_kernel<P, TW, WM, WN, TN, BT, false>;
-        // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
-        static const hipError_t attr_err = (Cfg::LDS_BYTES > 64 * 1024) ? hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES) : hipSuccess;
-        if (attr_err != hipSuccess) return (int)attr_err;
+        constexpr auto kern = conv_patch_bf3_kernel<P, TW, WM, WN, TN, BT, false>;
+        HAB_TRY(lds_opt_in<kern>((int)Cfg::LDS_BYTES, Cfg::LDS_BYTES > 64 * 1024));
         kern<<<grid, Cfg::NT, Cfg::LDS_BYTES, stream>>>(p, gq, sign_schedule, nullptr, 0, ctr);
     }
     HAB_LAUNCH_CHECK();

@@ -59,11 +59,6 @@ constexpr bool DN_DEV = true;
 constexpr bool DN_DEV = false;
 #endif
 
-typedef short dn_v4s __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ dn_v4s dn_tr_read(const unsigned char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) dn_v4s*)p);
-}
-
 template <int A_IC, int B_IC>
 __global__ void __launch_bounds__(DN_NT) dense_bf3_kernel(const DenseArgs g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dn_smem[];
@@ -204,8 +199,7 @@ __global__ void __launch_bounds__(DN_NT) dense_bf3_kernel(const DenseArgs g) {
         }
     auto frag = [&](const unsigned char* p, bool ic) -> bf16x8 {
         if (ic) {
-            const dn_v4s lo = dn_tr_read(p), hi4 = dn_tr_read(p + 4 * 64);
-            return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi4, 0, 1, 2, 3, 4, 5, 6, 7));
+            return bf3_join(bf3_tr_read(reinterpret_cast<const unsigned short*>(p)), bf3_tr_read(reinterpret_cast<const unsigned short*>(p + 4 * 64)));
         }
         return *reinterpret_cast<const bf16x8*>(p);
     };
@@ -256,14 +250,13 @@ __global__ void __launch_bounds__(DN_NT) dense_bf3_kernel(const DenseArgs g) {
                 if (af[0][0][0] == (__bf16)123.f && bf[1][2][7] == (__bf16)77.f) acc[0][0][0] += 1.f;
                 continue;
             }
-            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};  // six partial products, smallest weight first
 #pragma unroll
             for (int q = 0; q < 6; ++q)
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[j][PB[q]], af[i][PA[q]], acc[i][j], 0, 0, 0);  // transposed accumulator
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[j][BF3_PB[q]], af[i][BF3_PA[q]], acc[i][j], 0, 0, 0);  // transposed accumulator
         }
         if (tr && lane == 0) dn_trace[wave][kt - 8][2] = __builtin_readcyclecounter();
         if (!early) {
@@ -379,9 +372,8 @@ inline int dense_bf3_splits(const DenseArgs& g, size_t ws_floats) {
 
 template <int A_IC, int B_IC>
 inline int dense_bf3_launch(DenseArgs g, hipStream_t stream) {
-    auto kern = dense_bf3_kernel<A_IC, B_IC>;
-    static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, DN_LDS_BYTES);
-    if (attr_err != hipSuccess) return (int)attr_err;
+    constexpr auto kern = dense_bf3_kernel<A_IC, B_IC>;
+    HAB_TRY(lds_opt_in<kern>(DN_LDS_BYTES));
     g.sign_schedule = bf3_sign_schedule();
     static const int skew = hab_env_int("HAB_DENSE_SKEW", 1);
     g.skew = skew;

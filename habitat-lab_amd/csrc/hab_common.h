@@ -45,6 +45,23 @@ inline int hab_env_int(const char* name, int dflt) { const char* v = getenv(name
 __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ inline long long cdivl(long long a, long long b) { return (a + b - 1) / b; }
 
+// Launch prologue of a kernel with dynamic LDS: raise Kern's MaxDynamicSharedMemorySize to `bytes` (the same value at every call of
+// an instantiation), once per process and instantiation; `needed` = false (launchers whose LDS may fit the default 64 KB) skips it.
+// Thread-safe static initialisation: engines of several inference-worker threads launch concurrently.
+template <auto Kern>
+inline hipError_t lds_opt_in(int bytes, bool needed = true) {
+    static const hipError_t err =
+        needed ? hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) : hipSuccess;
+    return err;
+}
+
+// Workgroups of a persistent kernel: max_grid, less 8 (one per XCD) while there are fewer items than workgroups, at least 8.
+inline int persistent_grid(int items, int max_grid = 256) {
+    int grid = max_grid;
+    while (grid > 8 && grid > items) grid -= 8;
+    return grid;
+}
+
 __device__ inline float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

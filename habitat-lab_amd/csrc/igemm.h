@@ -460,10 +460,8 @@ inline int igemm_launch(const P& p, float* ws, size_t ws_floats, int target_bloc
     using Cfg = IgemmCfg<P, TM, TN, WM, WN>;
     if (p.M <= 0 || p.N <= 0 || p.K <= 0) return HAB_ERR_ARG;
     const IgemmPlan pl = igemm_plan(Cfg::BM, Cfg::BN, p.M, p.N, p.K, target_blocks, 4096, ws ? ws_floats : 0);
-    auto kern = igemm_kernel<P, TM, TN, WM, WN>;
-    // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
-    static const hipError_t attr_err = (Cfg::LDS_BYTES > 64 * 1024) ? hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES) : hipSuccess;
-    if (attr_err != hipSuccess) return (int)attr_err;
+    constexpr auto kern = igemm_kernel<P, TM, TN, WM, WN>;
+    HAB_TRY(lds_opt_in<kern>((int)Cfg::LDS_BYTES, Cfg::LDS_BYTES > 64 * 1024));
     dim3 grid(cdiv(p.M, Cfg::BM) * cdiv(p.N, Cfg::BN), 1, pl.splits);
     kern<<<grid, Cfg::NT, Cfg::LDS_BYTES, stream>>>(p, pl.k_per_split, ws);
     HAB_LAUNCH_CHECK();

@@ -25,7 +25,6 @@
 
 namespace hab {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BF3_BKP = IGEMM_BK + 8;  // bf16 elements per LDS row
 
@@ -352,7 +351,6 @@ __global__ void __launch_bounds__(WM* WN * 64) igemm_bf3_kernel(const P p, const
                 for (int pl = 0; pl < 3; ++pl) bf[j][pl] = *reinterpret_cast<const bf16x8*>(src + pl * Cfg::B_PLANE);
             }
             // six partial products, smallest weight first
-            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
             for (int q = 0; q < 6; ++q)
 #pragma unroll
@@ -360,9 +358,9 @@ __global__ void __launch_bounds__(WM* WN * 64) igemm_bf3_kernel(const P p, const
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
                         if constexpr (EpiV4<P>::value)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[j][PB[q]], af[i][PA[q]], acc[i][j], 0, 0, 0);
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[j][BF3_PB[q]], af[i][BF3_PA[q]], acc[i][j], 0, 0, 0);
                         else
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][PA[q]], bf[j][PB[q]], acc[i][j], 0, 0, 0);
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][BF3_PA[q]], bf[j][BF3_PB[q]], acc[i][j], 0, 0, 0);
         }
         __syncthreads();
     }
@@ -437,10 +435,8 @@ inline int igemm_bf3_launch(const P& p, float* ws, size_t ws_floats, int target_
     using Cfg = IgemmBf3Cfg<P, TM, TN, WM, WN>;
     if (p.M <= 0 || p.N <= 0 || p.K <= 0) return HAB_ERR_ARG;
     const IgemmPlan pl = igemm_plan(Cfg::BM, Cfg::BN, p.M, p.N, p.K, target_blocks, 4096, ws ? ws_floats : 0);
-    auto kern = igemm_bf3_kernel<P, TM, TN, WM, WN>;
-    // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
-    static const hipError_t attr_err = (Cfg::LDS_BYTES > 64 * 1024) ? hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES) : hipSuccess;
-    if (attr_err != hipSuccess) return (int)attr_err;
+    constexpr auto kern = igemm_bf3_kernel<P, TM, TN, WM, WN>;
+    HAB_TRY(lds_opt_in<kern>((int)Cfg::LDS_BYTES, Cfg::LDS_BYTES > 64 * 1024));
     const int ntiles = cdiv(p.M, Cfg::BM) * cdiv(p.N, Cfg::BN);
     const int grid = pl.splits >= 16 ? ntiles * ((pl.splits + 7) / 8 * 8) : ntiles * pl.splits;
     const int sign_schedule = bf3_sign_schedule();

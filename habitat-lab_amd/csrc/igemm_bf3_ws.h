@@ -337,7 +337,6 @@ igemm_bf3_ws_kernel(const P p, const int k_per_split, float* __restrict__ partia
                 for (int pl = 0; pl < 3; ++pl) bf[c][j][pl] = *reinterpret_cast<const bf16x8*>(src + pl * Cfg::B_PLANE);
             }
         }
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};  // six partial products, smallest weight first
 #pragma unroll
         for (int c = 0; c < BK / 16; ++c)
 #pragma unroll
@@ -347,9 +346,9 @@ igemm_bf3_ws_kernel(const P p, const int k_per_split, float* __restrict__ partia
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
                         if constexpr (EpiV4<P>::value)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[c][j][PB[q]], af[c][i][PA[q]], acc[i][j], 0, 0, 0);
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[c][j][BF3_PB[q]], af[c][i][BF3_PA[q]], acc[i][j], 0, 0, 0);
                         else
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[c][i][PA[q]], bf[c][j][PB[q]], acc[i][j], 0, 0, 0);
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[c][i][BF3_PA[q]], bf[c][j][BF3_PB[q]], acc[i][j], 0, 0, 0);
     };
 
     if constexpr (Cfg::KSH) __syncthreads();  // barrier K
@@ -428,10 +427,8 @@ inline int igemm_bf3_ws_launch(const P& p, float* ws, size_t ws_floats, int targ
     using Cfg = IgemmBf3WsCfg<P, TM, TN, WM, WN, PW>;
     if (p.M <= 0 || p.N <= 0 || p.K <= 0) return HAB_ERR_ARG;
     const IgemmPlan pl = igemm_plan(Cfg::BM, Cfg::BN, p.M, p.N, p.K, target_blocks, 4096, ws ? ws_floats : 0);
-    auto kern = igemm_bf3_ws_kernel<P, TM, TN, WM, WN, PW>;
-    // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
-    static const hipError_t attr_err = (Cfg::LDS_BYTES > 64 * 1024) ? hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES) : hipSuccess;
-    if (attr_err != hipSuccess) return (int)attr_err;
+    constexpr auto kern = igemm_bf3_ws_kernel<P, TM, TN, WM, WN, PW>;
+    HAB_TRY(lds_opt_in<kern>((int)Cfg::LDS_BYTES, Cfg::LDS_BYTES > 64 * 1024));
     const int ntiles = cdiv(p.M, Cfg::BM) * cdiv(p.N, Cfg::BN);
     const int grid = pl.splits >= 16 ? ntiles * ((pl.splits + 7) / 8 * 8) : ntiles * pl.splits;
     const int sign_schedule = bf3_sign_schedule();

@@ -219,11 +219,10 @@ __global__ void __launch_bounds__(256) obs_conv_bf3_kernel(const ObsConvFwdProb 
                         a[i][pl] = *reinterpret_cast<const bf16x8*>(Adep + pl * Cfg::A_DEP + ((wm * TM + i) * 32 + li) * OBF_DEPP + hi * 8);
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) b[pl] = *reinterpret_cast<const bf16x8*>(Bdep + pl * Cfg::B_DEP + li * OBF_DEPP + hi * 8);
-                constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
                 for (int q = 0; q < 6; ++q)
 #pragma unroll
-                    for (int i = 0; i < TM; ++i) acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[PB[q]], a[i][PA[q]], acc[i][0], 0, 0, 0);
+                    for (int i = 0; i < TM; ++i) acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[BF3_PB[q]], a[i][BF3_PA[q]], acc[i][0], 0, 0, 0);
             }
             __syncthreads();
         }
@@ -249,10 +248,8 @@ inline int obs_conv_bf3_launch(const ObsConvFwdProb& p, float* ws, size_t ws_flo
     unsigned short* planes = reinterpret_cast<unsigned short*>(ws);
     obs_conv_bf3_split_weights<<<cdiv(2 * NP * p.K, 256), 256, 0, stream>>>(p.w, p.N, p.K, NP, planes);
     HAB_LAUNCH_CHECK();
-    auto kern = obs_conv_bf3_kernel<TM>;
-    // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
-    static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-    if (attr_err != hipSuccess) return (int)attr_err;
+    constexpr auto kern = obs_conv_bf3_kernel<TM>;
+    HAB_TRY(lds_opt_in<kern>((int)Cfg::LDS_BYTES));
     constexpr int wg_per_cu = 2;
     const int ntiles = cdiv(p.M, Cfg::BM) * cdiv(p.N, 32);
     const int grid = ntiles < 256 * wg_per_cu ? ntiles : 256 * wg_per_cu;

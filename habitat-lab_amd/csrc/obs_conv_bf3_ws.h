@@ -219,9 +219,8 @@ __global__ void __launch_bounds__(512) obs_conv_bf3_ws_kernel(const ObsConvFwdPr
 #pragma unroll
             for (int pl = 2; pl >= 0; --pl) acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(br[S][g][pl], ar[g], acc[0][0], 0, 0, 0);
         // depth: one k-group, both operands split
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
-        for (int q = 0; q < 6; ++q) acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bd[S][PB[q]], ad[PA[q]], acc[0][0], 0, 0, 0);
+        for (int q = 0; q < 6; ++q) acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bd[S][BF3_PB[q]], ad[BF3_PA[q]], acc[0][0], 0, 0, 0);
     };
     // every weight fragment has landed BEFORE the loop: with loads still pending at the loop entry, the s_waitcnt pass keeps a
     // vmcnt(0) in front of the loop's first MFMA (its operand happened to be the last load issued), which on every later pass waits
@@ -278,9 +277,7 @@ inline int obs_conv_bf3_ws_launch(const ObsConvFwdProb& p, float* ws, size_t ws_
     unsigned short* planes = reinterpret_cast<unsigned short*>(ws);
     obs_conv_bf3_split_weights<<<cdiv(2 * NPAD * p.K, 256), 256, 0, stream>>>(p.w, p.N, p.K, NPAD, planes);
     HAB_LAUNCH_CHECK();
-    // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
-    static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(obs_conv_bf3_ws_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-    if (attr_err != hipSuccess) return (int)attr_err;
+    HAB_TRY(lds_opt_in<obs_conv_bf3_ws_kernel>((int)Cfg::LDS_BYTES));
     const int ntiles = cdiv(p.M, Cfg::BM);
     const int grid = ntiles < 256 ? ntiles : 256;  // persistent: one workgroup per CU
     obs_conv_bf3_ws_kernel<<<(grid + 7) / 8 * 8, Cfg::NT, Cfg::LDS_BYTES, stream>>>(p, planes, NPAD);

@@ -468,10 +468,8 @@ inline bool obs_conv_patch_covers(const ObsConvFwdProb& p, const float* ws, size
 
 template <bool HOIST>
 inline int obs_conv_patch_launch_form(const ObsConvFwdProb& p, const ObsPatchGeom& gq, const unsigned short* wimg, hipStream_t stream) {
-    auto kern = obs_conv_patch_kernel<5, HOIST>;
-    // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
-    static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (attr_err != hipSuccess) return (int)attr_err;
+    constexpr auto kern = obs_conv_patch_kernel<5, HOIST>;
+    HAB_TRY(lds_opt_in<kern>(160 * 1024));
     const size_t lds = ((size_t)2 * 32 * OCP_KP + 32 * OCP_DP + 64 + (size_t)2 * gq.patch_elems) * 2;
     const int sign_schedule = bf3_sign_schedule();
     static const int ablate = hab_env_int("HAB_OCP_ABLATE", 0);

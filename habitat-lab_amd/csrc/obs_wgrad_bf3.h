@@ -159,9 +159,8 @@ __global__ void __launch_bounds__(256, 2) obs_wgrad_bf3_kernel(const ObsConvWgra
             bf16x8 a[3];
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) a[pl] = *reinterpret_cast<const bf16x8*>(Adep + pl * ADP + (dt * 32 + li) * OWG_P + koff);
-            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
-            for (int q = 0; q < 6; ++q) acc[6 + dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[q]], b[PB[q]], acc[6 + dt], 0, 0, 0);
+            for (int q = 0; q < 6; ++q) acc[6 + dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[BF3_PA[q]], b[BF3_PB[q]], acc[6 + dt], 0, 0, 0);
         }
         __syncthreads();
     }
@@ -228,9 +227,7 @@ inline int obs_wgrad_bf3_launch(const ObsConvWgradProb& p, float* ws, size_t ws_
     if (!obs_wgrad_bf3_covers(p, ws, ws_floats)) return HAB_NOT_APPLICABLE;
     ObsWgradGeom gg;
     const int wgs = obs_wgrad_partition(p, ws_floats, gg);
-    // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
-    static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(obs_wgrad_bf3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)OWG_LDS_BYTES);
-    if (attr_err != hipSuccess) return (int)attr_err;
+    HAB_TRY(lds_opt_in<obs_wgrad_bf3_kernel>((int)OWG_LDS_BYTES));
     obs_wgrad_bf3_kernel<<<wgs, 256, OWG_LDS_BYTES, stream>>>(p, gg, ws);
     HAB_LAUNCH_CHECK();
     igemm_splitk_reduce<ObsConvWgradProb>(p, ws, wgs, stream);

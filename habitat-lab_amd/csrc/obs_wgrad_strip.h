@@ -10,7 +10,7 @@
 //     rows of one frame: 4 of their 8 rows stay, so a tile loads 4 rows, all 8 when its run begins or the frame changes, none for the
 //     second 64-pixel block of a wide row;
 //   * dY is stored pixel-major as loaded, [pixel][32 channels] in three planes, one bf3_store4 per loaded f32x4;
-//   * fragments are built by the LDS transpose read (ds_read_b64_tr_b16): a 16-lane group passes the chunks (pixel p, 4 consecutive
+//   * fragments are built by the LDS transpose read (bf3_tr_read, bf3_split.h): a 16-lane group passes the chunks (pixel p, 4 consecutive
 //     reduction slots) of four pixels and receives the k-contiguous fragment.  For rgb the slot inside a filter row is m = kw * 3 + c:
 //     the 24 slots of output pixel wo are the 24 consecutive elements at column 4 wo of the row, so a chunk of 4 never leaves its filter
 //     row and is 8-byte aligned (pixel pitch 24 B).  For depth the slot is kw (pixel pitch 8 B).  No register transposes.
@@ -27,8 +27,6 @@
 
 namespace hab {
 
-typedef short ows_v4s __attribute__((ext_vector_type(4)));
-
 constexpr int OWS_MAXU = 4;              // staging units (4 pixels of one row) per thread when all 8 rows load, at most: W <= 512
 constexpr int OWS_YP = OWG_BK * 32;      // bf16 elements per dY plane
 constexpr size_t OWS_RED_BYTES = 256 * 32 * sizeof(float);  // the cross-wave fold's buffer
@@ -38,13 +36,6 @@ struct ObsWgradStripGeom {
     int UPR;     // staging units per input row: W / 4
     int RP, DP;  // LDS row pitch of the rgb / depth rows, bf16 elements
 };
-
-__device__ __forceinline__ ows_v4s ows_tr_read(const unsigned short* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ows_v4s*)p);
-}
-__device__ __forceinline__ u32x4 ows_join(const ows_v4s lo, const ows_v4s hi) {
-    return __builtin_bit_cast(u32x4, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 
 // MAXU: staging units per thread when all 8 rows load, 8 * (W / 4) <= 256 MAXU
 template <int MAXU>
@@ -186,14 +177,14 @@ __global__ void __launch_bounds__(256, 2) obs_wgrad_bf3_kernel_strip(const ObsCo
         bf16x8 b[3];
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) {
-            u32x4 raw = ows_join(ows_tr_read(Ys + pl * OWS_YP + ychunk), ows_tr_read(Ys + pl * OWS_YP + ychunk + 4 * 32));
+            u32x4 raw = __builtin_bit_cast(u32x4, bf3_join(bf3_tr_read(Ys + pl * OWS_YP + ychunk), bf3_tr_read(Ys + pl * OWS_YP + ychunk + 4 * 32)));
             raw ^= sign_flip;
             b[pl] = __builtin_bit_cast(bf16x8, raw);
         }
 #pragma unroll
         for (int mt = 0; mt < 6; ++mt) {
             const unsigned short* ar = Rs + (rgb_hi[mt] ? half[1] : half[0]) * RP + rgb_off[mt];
-            const bf16x8 a = __builtin_bit_cast(bf16x8, ows_join(ows_tr_read(ar + wo0 * 12), ows_tr_read(ar + wo1 * 12)));
+            const bf16x8 a = bf3_join(bf3_tr_read(ar + wo0 * 12), bf3_tr_read(ar + wo1 * 12));
 #pragma unroll
             for (int pl = 2; pl >= 0; --pl) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[pl], acc[mt], 0, 0, 0);
         }
@@ -203,10 +194,9 @@ __global__ void __launch_bounds__(256, 2) obs_wgrad_bf3_kernel_strip(const ObsCo
             bf16x8 a[3];
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
-                a[pl] = __builtin_bit_cast(bf16x8, ows_join(ows_tr_read(ad + pl * DPL + wo0 * 4), ows_tr_read(ad + pl * DPL + wo1 * 4)));
-            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
+                a[pl] = bf3_join(bf3_tr_read(ad + pl * DPL + wo0 * 4), bf3_tr_read(ad + pl * DPL + wo1 * 4));
 #pragma unroll
-            for (int q = 0; q < 6; ++q) acc[6 + dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[q]], b[PB[q]], acc[6 + dt], 0, 0, 0);
+            for (int q = 0; q < 6; ++q) acc[6 + dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[BF3_PA[q]], b[BF3_PB[q]], acc[6 + dt], 0, 0, 0);
         }
         __syncthreads();  // every wave is done with this tile's dY and with the 4 row slots the next tile replaces
     }
@@ -268,8 +258,7 @@ inline int obs_wgrad_strip_launch(const ObsConvWgradProb& p, float* ws, size_t w
     if (8 * sg.UPR <= 2 * 256) {  // W <= 256
         obs_wgrad_bf3_kernel_strip<2><<<wgs, 256, lds, stream>>>(p, gg, sg, ws);
     } else {
-        static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(obs_wgrad_bf3_kernel_strip<OWS_MAXU>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        if (attr_err != hipSuccess) return (int)attr_err;
+        HAB_TRY(lds_opt_in<obs_wgrad_bf3_kernel_strip<OWS_MAXU>>(80 * 1024));
         obs_wgrad_bf3_kernel_strip<OWS_MAXU><<<wgs, 256, lds, stream>>>(p, gg, sg, ws);
     }
     HAB_LAUNCH_CHECK();

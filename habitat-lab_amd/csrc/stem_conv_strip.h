@@ -26,7 +26,6 @@
 
 namespace hab {
 
-typedef __bf16 stem_bf16x8 __attribute__((ext_vector_type(8)));
 
 struct StemArgs {
     const float* x;            // [B][H][W][4]
@@ -129,22 +128,21 @@ __global__ void __launch_bounds__(512) stem_conv_strip_kernel(const StemArgs a) 
             const unsigned short* xrow = xs + (size_t)(2 * wave + kh) * a.PW * 4;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                stem_bf16x8 bw[3], af[2][3];
+                bf16x8 bw[3], af[2][3];
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
-                    bw[pl] = *reinterpret_cast<const stem_bf16x8*>(ws + ((size_t)(pl * STEM_KS + kh * 2 + j) * 64 + lane) * 8);
+                    bw[pl] = *reinterpret_cast<const bf16x8*>(ws + ((size_t)(pl * STEM_KS + kh * 2 + j) * 64 + lane) * 8);
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl)
-                        af[i][pl] = *reinterpret_cast<const stem_bf16x8*>(xrow + coff[i] + 16 * j + pl * plane);
-                constexpr int PX[6] = {2, 0, 1, 1, 0, 0}, PW_[6] = {0, 2, 1, 0, 1, 0};  // smallest partial product first
+                        af[i][pl] = *reinterpret_cast<const bf16x8*>(xrow + coff[i] + 16 * j + pl * plane);
 #pragma unroll
                 for (int q = 0; q < 6; ++q) {
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[PW_[q]], af[0][PX[q]], acc[0], 0, 0, 0);
+                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[BF3_PB[q]], af[0][BF3_PA[q]], acc[0], 0, 0, 0);
                     // (also when Wo <= 32: the second tile then recomputes the clamped last pixel and is dropped -- a branch here
                     //  makes the compiler shuffle the accumulator registers around every MFMA)
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[PW_[q]], af[1][PX[q]], acc[1], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[BF3_PB[q]], af[1][BF3_PA[q]], acc[1], 0, 0, 0);
                 }
             }
         }
@@ -258,6 +256,14 @@ inline bool stem_conv_strip_covers(int H, int W, int C, int Cout, int KH, int KW
     return STEM_W_BYTES + (size_t)3 * STEM_ROWS * PW * 8 + STEM_STAT_FLOATS * sizeof(float) <= 160 * 1024;
 }
 
+template <int CPG>
+inline int stem_conv_strip_launch(const StemArgs& a, size_t lds, hipStream_t stream) {
+    HAB_TRY(lds_opt_in<stem_conv_strip_kernel<CPG>>(160 * 1024));
+    stem_conv_strip_kernel<CPG><<<a.B * a.strips, 512, lds, stream>>>(a);
+    HAB_LAUNCH_CHECK();
+    return HAB_OK;
+}
+
 // HAB_NOT_APPLICABLE: geometry not covered.
 // part / groups: GroupNorm partial statistics of the output per (frame, strip of 8 rows, group), see the kernel; groups in {8, 16, 32}
 inline int stem_conv_strip(const float* x, const unsigned short* wq, float* y, int B, int H, int W, hipStream_t stream,
@@ -273,25 +279,12 @@ inline int stem_conv_strip(const float* x, const unsigned short* wq, float* y, i
     a.strips = (a.Ho + STEM_TH - 1) / STEM_TH;
     a.sign_schedule = bf3_sign_schedule();
     const size_t lds = STEM_W_BYTES + (size_t)3 * STEM_ROWS * a.PW * 8 + STEM_STAT_FLOATS * sizeof(float);
-    static const hipError_t attr_err = [] {
-        hipError_t e = hipSuccess;
-        const void* ks[4] = {reinterpret_cast<const void*>(stem_conv_strip_kernel<0>), reinterpret_cast<const void*>(stem_conv_strip_kernel<1>),
-                             reinterpret_cast<const void*>(stem_conv_strip_kernel<2>), reinterpret_cast<const void*>(stem_conv_strip_kernel<4>)};
-        for (const void* k : ks) {
-            const hipError_t r = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (r != hipSuccess) e = r;
-        }
-        return e;
-    }();
-    if (attr_err != hipSuccess) return (int)attr_err;
     if ((long long)B * a.strips > 0x7fffffffLL) return HAB_NOT_APPLICABLE;
     const int cpg = part ? 32 / groups : 0;
-    if (cpg == 0) stem_conv_strip_kernel<0><<<B * a.strips, 512, lds, stream>>>(a);
-    else if (cpg == 1) stem_conv_strip_kernel<1><<<B * a.strips, 512, lds, stream>>>(a);
-    else if (cpg == 2) stem_conv_strip_kernel<2><<<B * a.strips, 512, lds, stream>>>(a);
-    else stem_conv_strip_kernel<4><<<B * a.strips, 512, lds, stream>>>(a);
-    HAB_LAUNCH_CHECK();
-    return HAB_OK;
+    return cpg == 0   ? stem_conv_strip_launch<0>(a, lds, stream)
+           : cpg == 1 ? stem_conv_strip_launch<1>(a, lds, stream)
+           : cpg == 2 ? stem_conv_strip_launch<2>(a, lds, stream)
+                      : stem_conv_strip_launch<4>(a, lds, stream);
 }
 
 }  // namespace hab

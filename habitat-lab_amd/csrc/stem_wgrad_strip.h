@@ -6,9 +6,9 @@
 //
 // Why: as an implicit-GEMM weight gradient (igemm_bf3.h, both operands k-strided, register transposes, every x element re-gathered
 // 49 / 4 times) this was the slowest single kernel of the ResNet18 learner: 3.7 ms per 4096 frames (57 TFLOP/s-eq), 7 % of a minibatch.
-// Here, as in wgrad3x3_bf3.h:
+// Here, as in wgrad3x3_bf3.h (the transpose read, the product order and the item split are bf3_split.h's):
 //   * a (persistent) workgroup takes strips of 4 output rows of one frame: the 13 x rows under them (3 zero columns either side) and the
-//     4 dY rows are read from HBM once with 16-byte loads, split once (exact 3-term split, igemm_bf3.h) and kept pixel-major --
+//     4 dY rows are read from HBM once with 16-byte loads, split once (exact 3-term split, bf3_split.h) and kept pixel-major --
 //     x as [row][column][4 channels] (8 bytes per pixel), dY as [pixel][32 channels] (64 bytes per pixel);
 //   * the contraction index is the PIXEL, 16 consecutive wo of one output row per MFMA step; fragments are built by the LDS transpose
 //     read ds_read_b64_tr_b16: a 16-lane group passes 16 chunk addresses -- for dY (pixel p, channel quad q), for x (pixel p, TAP q):
@@ -25,9 +25,6 @@
 
 namespace hab {
 
-typedef short swg_v4s __attribute__((ext_vector_type(4)));
-typedef __bf16 swg_bf16x8 __attribute__((ext_vector_type(8)));
-
 struct StemWgArgs {
     const float* x;    // [B][H][W][4]
     const float* dy;   // [B][Ho][Wo][32]
@@ -41,13 +38,6 @@ struct StemWgArgs {
 constexpr int SWG_TH = 4, SWG_XROWS = 2 * SWG_TH + 5, SWG_NT = 448;
 constexpr int SWG_XPT = 4, SWG_YPT = 5;  // register-prefetched 16-byte units per thread at the largest covered width (Wo = 64)
 
-__device__ __forceinline__ swg_v4s swg_tr_read(const unsigned short* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) swg_v4s*)p);
-}
-__device__ __forceinline__ swg_bf16x8 swg_join(const swg_v4s lo, const swg_v4s hi) {
-    return __builtin_bit_cast(swg_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-
 __global__ void __launch_bounds__(SWG_NT) stem_wgrad_strip_kernel(const StemWgArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned short swg_sm[];
     const int xplane = SWG_XROWS * a.PW * 4;      // bf16 elements per plane of the x strip
@@ -58,11 +48,8 @@ __global__ void __launch_bounds__(SWG_NT) stem_wgrad_strip_kernel(const StemWgAr
     const int kh = __builtin_amdgcn_readfirstlane(t >> 6);  // this wave's filter row
     const int xunits = SWG_XROWS * a.PW, yunits = SWG_TH * a.Wo * 8;
 
-    // this workgroup's strips: XCD x takes the x-th eighth of the items, its workgroups contiguous pieces of it (conv2_fwd_strip.h)
-    const int xcd = blockIdx.x & 7, jw = blockIdx.x >> 3, wg_per_xcd = gridDim.x >> 3;
-    const int per_xcd = (a.items + 7) >> 3, per_wg = (per_xcd + wg_per_xcd - 1) / wg_per_xcd;
-    const int xcd_end = min(a.items, (xcd + 1) * per_xcd);
-    const int first = min(xcd_end, xcd * per_xcd + jw * per_wg), last = min(xcd_end, first + per_wg);
+    int first, last;  // this workgroup's strips
+    xcd_item_run(a.items, blockIdx.x, gridDim.x, first, last);
 
     const bool flip = a.sign_schedule && (blockIdx.x & 1);
     const unsigned sgn2 = flip ? 0x80008000u : 0u;
@@ -155,15 +142,14 @@ __global__ void __launch_bounds__(SWG_NT) stem_wgrad_strip_kernel(const StemWgAr
                 yoff[r] = pix * 32 + ychunk;
                 xoff[r] = ((2 * hol + kh) * a.PW + 2 * wo + xtap) * 4;
             }
-            swg_bf16x8 af[3], bf[3];
+            bf16x8 af[3], bf[3];
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) {
-                af[pl] = swg_join(swg_tr_read(ys + pl * yplane + yoff[0]), swg_tr_read(ys + pl * yplane + yoff[1]));
-                bf[pl] = swg_join(swg_tr_read(xs + pl * xplane + xoff[0]), swg_tr_read(xs + pl * xplane + xoff[1]));
+                af[pl] = bf3_join(bf3_tr_read(ys + pl * yplane + yoff[0]), bf3_tr_read(ys + pl * yplane + yoff[1]));
+                bf[pl] = bf3_join(bf3_tr_read(xs + pl * xplane + xoff[0]), bf3_tr_read(xs + pl * xplane + xoff[1]));
             }
-            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};  // smallest partial product first
 #pragma unroll
-            for (int q6 = 0; q6 < 6; ++q6) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PA[q6]], bf[PB[q6]], acc, 0, 0, 0);
+            for (int q = 0; q < 6; ++q) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[BF3_PA[q]], bf[BF3_PB[q]], acc, 0, 0, 0);
         }
     };
 
@@ -222,13 +208,10 @@ inline int stem_wgrad_strip(const float* x, const float* dy, float* dw_oihw, int
     if ((long long)B * a.strips > 0x7fffffffLL) return HAB_NOT_APPLICABLE;
     a.items = B * a.strips;
     a.sign_schedule = bf3_sign_schedule();
-    int grid = 256;
-    while (grid > 8 && grid > a.items) grid -= 8;
+    const int grid = persistent_grid(a.items);
     if ((size_t)grid * 7 * 1024 > ws_floats) return HAB_NOT_APPLICABLE;
     const size_t lds = (size_t)3 * SWG_XROWS * a.PW * 8 + (size_t)3 * SWG_TH * a.Wo * 64;
-    static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(stem_wgrad_strip_kernel),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (attr_err != hipSuccess) return (int)attr_err;
+    HAB_TRY(lds_opt_in<stem_wgrad_strip_kernel>(160 * 1024));
     stem_wgrad_strip_kernel<<<grid, SWG_NT, lds, stream>>>(a);
     HAB_LAUNCH_CHECK();
     const int total = 32 * creal * 49;

@@ -11,8 +11,8 @@
 //   * a workgroup owns a strip of R output rows of one image: the x rows it needs (R + 2, zero-padded columns included) and the dY
 //     rows are read from HBM ONCE, with whole-row coalesced 16-byte loads, split once, and stored as [pixel][32 channels] bf16
 //     planes (64 bytes per pixel);
-//   * MFMA fragments are built with the LDS TRANSPOSE read (ds_read_b64_tr_b16, semantics pinned on the hardware by
-//     tools/ubench/tr_read_probe.hip): every 16-lane group reads a [4 pixels][16 channels] block and lane i receives channel i of
+//   * MFMA fragments are built with the LDS TRANSPOSE read (ds_read_b64_tr_b16, bf3_tr_read of bf3_split.h): every 16-lane group
+//     reads a [4 pixels][16 channels] block (lane i passes 8-byte chunk i: row i / 4, chunk i % 4) and lane i receives channel i of
 //     the 4 pixels -- exactly the k-contiguous fragment, from the pixel-major image.  A filter tap is a ROW offset in that image
 //     (64-byte pitch), so all nine taps read the same resident strip with aligned reads; nothing is re-gathered;
 //   * k-slots are groups of 4 consecutive pixels of one output row (Wo % 4 == 0), two groups per lane and K = 16 step; 4 pixel rows of
@@ -58,18 +58,6 @@ struct W3bCfg {
     static_assert(LDS_BYTES % 16 == 0 && N32 % NS == 0 && NT % (N / 4) == 0 && LDS_BYTES >= (size_t)NT * 16, "");
 };
 
-typedef short w3b_v4s __attribute__((ext_vector_type(4)));
-typedef short w3b_v8s __attribute__((ext_vector_type(8)));
-
-// [4 pixels][16 channels] block at `p` (row pitch 64 bytes): lane i of a 16-lane group passes the address of 8-byte chunk i
-// (row i / 4, chunk i % 4) and receives channel i of the four pixels.
-__device__ __forceinline__ w3b_v4s w3b_tr_read(const unsigned short* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) w3b_v4s*)p);
-}
-__device__ __forceinline__ bf16x8 w3b_join(const w3b_v4s lo, const w3b_v4s hi) {
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-
 template <int C32, int N32, int W, int PAD, int KHW, int S, int R, int KS, int NS>
 __global__ void __launch_bounds__(64 * KHW * KS * NS) wgrad3x3_bf3_kernel(const W3bArgs a) {
     using Cfg = W3bCfg<C32, N32, W, PAD, KHW, S, R, KS, NS>;
@@ -84,11 +72,8 @@ __global__ void __launch_bounds__(64 * KHW * KS * NS) wgrad3x3_bf3_kernel(const 
     // zero padding columns / out-of-image rows of x and the tail rows of dY (k-slots beyond the strip): written once
     for (int i = t; i < (int)(Cfg::LDS_BYTES / 16); i += NT) reinterpret_cast<u32x4*>(smem16)[i] = u32x4{0u, 0u, 0u, 0u};
 
-    // this workgroup's strips: XCD x takes the x-th eighth of the strips, its workgroups contiguous pieces of it
-    const int xcd = blockIdx.x & 7, jw = blockIdx.x >> 3, wg_per_xcd = gridDim.x >> 3;
-    const int per_xcd = (a.items + 7) >> 3, per_wg = (per_xcd + wg_per_xcd - 1) / wg_per_xcd;
-    const int xcd_end = min(a.items, (xcd + 1) * per_xcd);
-    const int first = min(xcd_end, xcd * per_xcd + jw * per_wg), last = min(xcd_end, first + per_wg);
+    int first, last;  // this workgroup's strips
+    xcd_item_run(a.items, blockIdx.x, gridDim.x, first, last);
 
     const bool flip = a.sign_schedule && (blockIdx.x & 1);
     const unsigned sgn2 = flip ? 0x80008000u : 0u;
@@ -178,7 +163,7 @@ __global__ void __launch_bounds__(64 * KHW * KS * NS) wgrad3x3_bf3_kernel(const 
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) {
                     const unsigned short* src = ys + (pl * N32 + ns * NW + hn) * Cfg::Y_HALF;
-                    bfr[hn][pl] = w3b_join(w3b_tr_read(src + yoff[0]), w3b_tr_read(src + yoff[1]));
+                    bfr[hn][pl] = bf3_join(bf3_tr_read(src + yoff[0]), bf3_tr_read(src + yoff[1]));
                 }
 #pragma unroll
             for (int kw = 0; kw < KHW; ++kw)
@@ -188,14 +173,13 @@ __global__ void __launch_bounds__(64 * KHW * KS * NS) wgrad3x3_bf3_kernel(const 
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl) {
                         const unsigned short* src = xs + (pl * C32 + hc) * Cfg::X_HALF + Cfg::tap_col(kw) * 32;
-                        afr[pl] = w3b_join(w3b_tr_read(src + xoff[0]), w3b_tr_read(src + xoff[1]));
+                        afr[pl] = bf3_join(bf3_tr_read(src + xoff[0]), bf3_tr_read(src + xoff[1]));
                     }
-                    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};  // smallest weight first
 #pragma unroll
                     for (int q6 = 0; q6 < 6; ++q6)
 #pragma unroll
                         for (int hn = 0; hn < NW; ++hn)
-                            acc[kw][hc][hn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[PA[q6]], bfr[hn][PB[q6]], acc[kw][hc][hn], 0, 0, 0);
+                            acc[kw][hc][hn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[BF3_PA[q6]], bfr[hn][BF3_PB[q6]], acc[kw][hc][hn], 0, 0, 0);
                 }
         }
     };
@@ -251,14 +235,12 @@ inline int wgrad3x3_bf3_run(const ConvWgradProb& p, float* ws, size_t ws_floats,
     a.items = g.B * a.strips;
     a.sign_schedule = bf3_sign_schedule();
     a.colsum = p.colsum != nullptr;
-    auto kern = wgrad3x3_bf3_kernel<C32, N32, W, PAD, KHW, S, R, KS, NS>;
-    // once per process and instantiation; thread-safe static initialisation (engines of several inference-worker threads launch concurrently)
-    static const hipError_t attr_err = (Cfg::LDS_BYTES > 64 * 1024) ? hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES) : hipSuccess;
-    if (attr_err != hipSuccess) return (int)attr_err;
+    constexpr auto kern = wgrad3x3_bf3_kernel<C32, N32, W, PAD, KHW, S, R, KS, NS>;
+    HAB_TRY(lds_opt_in<kern>((int)Cfg::LDS_BYTES, Cfg::LDS_BYTES > 64 * 1024));
     const size_t MN = (size_t)(KHW * KHW * Cfg::C + (a.colsum ? 1 : 0)) * Cfg::N;
     const int per_cu = (int)std::min<size_t>(Cfg::NT <= 192 ? 4 : 2, (160 * 1024) / Cfg::LDS_BYTES);
-    int grid = 256 * std::max(per_cu, 1);
-    while (grid > 8 && (grid > a.items || (size_t)grid * KS * MN > ws_floats)) grid -= 8;
+    int grid = persistent_grid(a.items, 256 * std::max(per_cu, 1));
+    while (grid > 8 && (size_t)grid * KS * MN > ws_floats) grid -= 8;  // ... and no more slabs than the workspace holds
     if ((size_t)grid * KS * MN > ws_floats || (grid < 128 && a.items >= 1024)) return 1;  // workspace too small for a chip-filling launch
     kern<<<grid, Cfg::NT, Cfg::LDS_BYTES, stream>>>(a);
     HAB_LAUNCH_CHECK();
