@@ -18,6 +18,9 @@
 //     wave order (fixed: deterministic), + bias, ReLU, one coalesced 16-byte store per thread;
 //   * the next strip's global loads are in flight under the MFMAs (registers), as in wgrad3x3_bf3.h; the strips are split over the
 //     workgroups by xcd_item_run (bf3_split.h).
+//   * in the form that runs (FOLD, NOTEBOOK R21.1) a tile's sum, epilogue and store are done inside the NEXT tile's MFMA interval: two
+//     barriers per tile instead of five per strip, no interval without MFMAs but the one that stages the next strip; the phase-by-phase
+//     form is kept behind matrix-path bit 14 for the bitwise tests (the loop and its hazard rules: at the kernel).
 // Sign schedule as everywhere on the split path: every second workgroup accumulates the negated sum (weights negated when split).
 #pragma once
 #include "igemm_bf3.h"
@@ -52,7 +55,22 @@ struct C2fCfg {
 // RT = false: the benchmark geometry (63 x 63 -> 30 x 30), every index a compile-time constant.  RT = true: H, W, Ho, Wo from the
 // arguments (W <= 63: the register prefetch and the LDS image are sized for 63); the last strip may hold one output row, input rows
 // below the image are staged as zeros and never fetched.
-template <int R, bool RT>
+//
+// FOLD = false: the plain form, phases in strict sequence -- stage | MFMAs | partials to `red` | sum + epilogue + store -- five barriers per
+// strip.  FOLD = true (the form that runs): a tile's sum, epilogue and store are done by the same waves INSIDE the next tile's MFMA
+// interval, two barriers per tile.  `pending` is the tile whose eight partial tiles lie in `red`:
+//      stage(first); barrier
+//      per strip:  fetch(next strip)
+//        per tile t:  [A]  MFMAs of t  +  fold(pending)
+//                     barrier B1      every fold has read `red`; on a strip's last tile every MFMA has read the strip image
+//                     [W]  partials of t -> `red`; pending = t; on the strip's last tile: stage(next strip)
+//                     barrier B2      partials (and the new image) visible
+//      fold(pending)
+// `red` is read only in [A] and written only in [W]; the strip image is read only in [A] and written only in [W] behind the strip's last
+// [A].  `pending` carries its own output base, first pixel and extent (the tile behind it may belong to another strip, another frame or a
+// shorter last strip) as a buffer descriptor: with nothing pending the extent is 0 and the store is dropped, so [A] has no branch.
+// Same operands, same MFMA order, same sums in wave order, same epilogue: bit-identical to the plain form.
+template <int R, bool RT, bool FOLD>
 __global__ void __launch_bounds__(512) conv2_fwd_strip_kernel(const C2fArgs a) {
     using Cfg = C2fCfg<R>;
     constexpr int NT = Cfg::NT;
@@ -109,7 +127,11 @@ __global__ void __launch_bounds__(512) conv2_fwd_strip_kernel(const C2fArgs a) {
             const int c4 = u & 7, pix = u >> 3, w = pix % W, hh = pix / W;
             const int row = hh * W + xcol(w);
             unsigned short* dst = xs + row * 32 + (((c4 >> 1) ^ ((row >> 2) & 3)) << 3) + (c4 & 1) * 4;
-            bf3_store4((!RT || u < pf_units) ? xr[j] : f32x4{0.f, 0.f, 0.f, 0.f}, dst, dst + X_PLANE, dst + 2 * X_PLANE);
+            f32x4 v = xr[j];
+            // folded form: stage() runs under a condition inside the tile loop; without this the split is hoisted in front of the loop,
+            // where it waits for the loads that were only just issued (and keeps 36 more registers live across the MFMAs)
+            if constexpr (FOLD) asm volatile("" : "+v"(v));
+            bf3_store4((!RT || u < pf_units) ? v : f32x4{0.f, 0.f, 0.f, 0.f}, dst, dst + X_PLANE, dst + 2 * X_PLANE);
         }
     };
 
@@ -117,6 +139,83 @@ __global__ void __launch_bounds__(512) conv2_fwd_strip_kernel(const C2fArgs a) {
     const int rpix = t >> 4, rco = (t & 15) * 4;
     f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
     if (a.bias) bias4 = *reinterpret_cast<const f32x4*>(a.bias + rco);
+
+    if constexpr (FOLD) {
+        const unsigned sx = flip ? 0x80000000u : 0u;
+        const bool relu = a.relu != 0;
+        const int lane_off = (rpix * 64 + rco) * 4;       // bytes from the tile's first pixel
+        float* pend_y = a.y;                              // the pending tile's strip, its extent in bytes (0: nothing pending) and first pixel
+        int pend_bytes = 0, pend_p0 = 0;
+        auto fold = [&]() {
+            u32x4 s = __builtin_bit_cast(u32x4, [&] {
+                f32x4 v = *reinterpret_cast<const f32x4*>(red + (size_t)rpix * Cfg::RED_LD + rco);
+#pragma unroll
+                for (int w8 = 1; w8 < 8; ++w8) v += *reinterpret_cast<const f32x4*>(red + (size_t)(w8 * 32 + rpix) * Cfg::RED_LD + rco);
+                return v;
+            }());
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s[e] ^= sx;
+            f32x4 v = __builtin_bit_cast(f32x4, s);
+            v += bias4;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = (v[e] > 0.f || !relu) ? v[e] : 0.f;
+            const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(pend_y, 0, pend_bytes, 0x00020000);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry, pend_p0 * 256 + lane_off, 0, 0);
+        };
+        fetch(first);
+        stage();
+        __syncthreads();
+        for (int item = first; item < last; ++item) {
+            if (item + 1 < last) fetch(item + 1);
+            const int img = item / a.strips, ho0 = (item - img * a.strips) * R;
+            float* yb = a.y + ((size_t)img * Ho + ho0) * (size_t)(Wo * 64);
+            const int npix_here = RT ? min(R, Ho - ho0) * Wo : NPIX;
+            // At most two tiles (W <= 63), written out: around a loop whose body uses the prefetched registers (stage() under the last
+            // tile) the compiler waits for the loads in front of the loop, a full HBM round trip per strip.
+#pragma unroll
+            for (int pt = 0; pt < Cfg::NPT; ++pt) {
+                if (RT && pt >= NPT) break;
+                // ---- [A] this wave's share of tile pt, and the pending tile's sum, epilogue and store ----
+                const int p = pt * 32 + li;
+                const int pc = (!RT && Cfg::NPIX % 32 == 0) || p < NPIX ? p : 0;
+                const int hol = pc / Wo, wo = pc - hol * Wo;
+                const int row0 = (hol * 2 + kh) * W + wo;
+                f32x16 acc[2];
+                auto kstep = [&](int j) {
+                    const int kw = 2 * kwp + (j >> 1);
+                    const int row = row0 + (kw & 1) * WH + (kw >> 1);
+                    const int chunk = (j & 1) * 2 + hi;
+                    const unsigned short* src = xs + row * 32 + ((chunk ^ ((row >> 2) & 3)) << 3);
+                    bf16x8 af[3];
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl) af[pl] = *reinterpret_cast<const bf16x8*>(src + pl * X_PLANE);
+#pragma unroll
+                    for (int q = 0; q < 6; ++q)
+#pragma unroll
+                        for (int ct = 0; ct < 2; ++ct)  // the first product of a chain takes a literal 0 as C
+                            acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[j][ct][BF3_PB[q]], af[BF3_PA[q]],
+                                                                              (j == 0 && q == 0) ? f32x16{} : acc[ct], 0, 0, 0);
+                };
+#pragma unroll
+                for (int j = 0; j < 4; ++j) kstep(j);
+                fold();
+                __syncthreads();  // B1
+                // ---- [W] ----
+                float* mine = red + (size_t)(wave * 32 + li) * Cfg::RED_LD;
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+                        *reinterpret_cast<f32x4*>(mine + ct * 32 + 8 * g + 4 * hi) =
+                            f32x4{acc[ct][4 * g], acc[ct][4 * g + 1], acc[ct][4 * g + 2], acc[ct][4 * g + 3]};
+                pend_y = yb; pend_bytes = npix_here * 256; pend_p0 = pt * 32;
+                if (pt == NPT - 1 && item + 1 < last) stage();
+                __syncthreads();  // B2
+            }
+        }
+        fold();
+        return;
+    }
 
     fetch(first);
     for (int item = first; item < last; ++item) {
@@ -185,33 +284,42 @@ inline bool conv2_fwd_strip_covers(const ConvGeom& g) {
     return g.KH == 4 && g.KW == 4 && g.stride == 2 && g.pad == 0 && g.C == 32 && g.Cout == 64 && g.H >= 4 && g.W >= 4 && g.W <= 63;
 }
 
-// HAB_NOT_APPLICABLE: shape not covered.
-inline int conv2_fwd_strip(const ConvFwdProb& p, float* /*ws*/, size_t /*ws_floats*/, hipStream_t stream) {
+// the form serves this call (host only: the dispatch rule and the launcher both ask it)
+inline bool conv2_fwd_strip_serves(const ConvFwdProb& p) {
     const ConvGeom& g = p.g;
-    if (!conv2_fwd_strip_covers(g)) return HAB_NOT_APPLICABLE;
-    if ((p.ldy != 0 && p.ldy != 64) || g.B < 16) return HAB_NOT_APPLICABLE;
-    if ((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.w) | reinterpret_cast<uintptr_t>(p.y) | reinterpret_cast<uintptr_t>(p.bias)) & 15) return HAB_NOT_APPLICABLE;
+    if (!conv2_fwd_strip_covers(g)) return false;
+    if ((p.ldy != 0 && p.ldy != 64) || g.B < 16) return false;
+    if ((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.w) | reinterpret_cast<uintptr_t>(p.y) | reinterpret_cast<uintptr_t>(p.bias)) & 15) return false;
+    return (long long)g.B * (((g.H - 4) / 2 + 1 + 1) / 2) <= 0x7fffffffLL;
+}
+
+template <bool RT, bool FOLD>
+inline int conv2_fwd_strip_launch(const C2fArgs& a, int grid, size_t lds, hipStream_t stream) {
+    using Cfg = C2fCfg<2>;
+    HAB_TRY((lds_opt_in<conv2_fwd_strip_kernel<2, RT, FOLD>>((int)Cfg::LDS_BYTES)));
+    conv2_fwd_strip_kernel<2, RT, FOLD><<<grid, Cfg::NT, lds, stream>>>(a);
+    HAB_LAUNCH_CHECK();
+    return HAB_OK;
+}
+
+// HAB_NOT_APPLICABLE: call not served.  fold: the folded form of the kernel (the plain one is kept for the tests; equal bits).
+inline int conv2_fwd_strip(const ConvFwdProb& p, bool fold, hipStream_t stream) {
+    const ConvGeom& g = p.g;
+    if (!conv2_fwd_strip_serves(p)) return HAB_NOT_APPLICABLE;
     constexpr int R = 2;
     using Cfg = C2fCfg<R>;
     C2fArgs a;
     a.x = p.x; a.wf = p.w; a.bias = p.bias; a.y = p.y; a.B = g.B;
     a.H = g.H; a.W = g.W; a.Ho = (g.H - 4) / 2 + 1; a.Wo = (g.W - 4) / 2 + 1;
     a.strips = (a.Ho + R - 1) / R;
-    if ((long long)g.B * a.strips > 0x7fffffffLL) return HAB_NOT_APPLICABLE;
     a.items = g.B * a.strips;
     a.relu = p.relu;
     a.sign_schedule = bf3_sign_schedule();
-    const bool bench_geom = g.H == 63 && g.W == 63;
     const int grid = persistent_grid(a.items);
-    if (bench_geom) {
-        HAB_TRY((lds_opt_in<conv2_fwd_strip_kernel<R, false>>((int)Cfg::LDS_BYTES)));
-        conv2_fwd_strip_kernel<R, false><<<grid, Cfg::NT, Cfg::LDS_BYTES, stream>>>(a);
-    } else {
-        HAB_TRY((lds_opt_in<conv2_fwd_strip_kernel<R, true>>((int)Cfg::LDS_BYTES)));
-        conv2_fwd_strip_kernel<R, true><<<grid, Cfg::NT, (size_t)3 * Cfg::XRS * g.W * 32 * 2 + Cfg::RED_BYTES, stream>>>(a);
-    }
-    HAB_LAUNCH_CHECK();
-    return HAB_OK;
+    if (g.H == 63 && g.W == 63)
+        return fold ? conv2_fwd_strip_launch<false, true>(a, grid, Cfg::LDS_BYTES, stream) : conv2_fwd_strip_launch<false, false>(a, grid, Cfg::LDS_BYTES, stream);
+    const size_t lds = (size_t)3 * Cfg::XRS * g.W * 32 * 2 + Cfg::RED_BYTES;
+    return fold ? conv2_fwd_strip_launch<true, true>(a, grid, lds, stream) : conv2_fwd_strip_launch<true, false>(a, grid, lds, stream);
 }
 
 }  // namespace hab

@@ -141,12 +141,19 @@ static PatchGeom patch3x3_geom(const float* in, int Hi, int Wi, int Ci, int Ho, 
     return gq;
 }
 
+// The form of a convolution's forward (HAB_CONV_FWD_FORM_*): under MP_CONV2_FWD with MP_RC SimpleCNN's conv2 on its strip kernel (input
+// strip in LDS, filter slices in registers: conv2_fwd_strip.h) where that serves the call -- folded, or under MP_CONV2_STRIP_PLAIN plain;
+// the two give equal bits -- and the general kernels for everything else.  conv_fwd and hab_conv2d_fwd_form both ask it.
+static int choose_conv_fwd(const ConvFwdProb& p) {
+    if (!matrix_path_on(MP_CONV2_FWD | MP_RC) || !conv2_fwd_strip_serves(p)) return HAB_CONV_FWD_FORM_GENERAL;
+    return matrix_path_on(MP_CONV2_STRIP_PLAIN) ? HAB_CONV_FWD_FORM_CONV2_STRIP_PLAIN : HAB_CONV_FWD_FORM_CONV2_STRIP;
+}
 int conv_fwd(const ConvDesc& d, const float* x, const float* wf, const float* bias, float* y, int relu, float* ws,
              size_t ws_floats, hipStream_t stream) {
     ConvFwdProb p;
     HAB_TRY(build(p, d, x, wf, bias, y, relu));
-    if (matrix_path_on(MP_CONV2_FWD | MP_RC))  // SimpleCNN conv2: input strip in LDS, filter slices in registers (conv2_fwd_strip.h)
-        HAB_TRY_FORM(conv2_fwd_strip(p, ws, ws_floats, stream));
+    const int form = choose_conv_fwd(p);
+    if (form != HAB_CONV_FWD_FORM_GENERAL) HAB_TRY_FORM(conv2_fwd_strip(p, form == HAB_CONV_FWD_FORM_CONV2_STRIP, stream));
     if (patch3x3_wanted(d, p.M))
         HAB_TRY_FORM(conv_patch_bf3_dispatch(p, patch3x3_geom(x, d.H, d.W, d.C, p.g.Ho, p.g.Wo, -d.pad, 0), ws, ws_floats, stream));
     return run_igemm(p, ws, ws_floats, stream);
@@ -190,14 +197,16 @@ __global__ void dgrad_empty_class_kernel(ConvDgradProb p) {
 // both ask it.
 static int choose_conv_dgrad(const ConvDesc& d, const float* dy, const float* wd, const float* mask, const float* add, const float* dx) {
     if (!matrix_path_on(MP_CONV2_DGRAD | MP_RC)) return HAB_CONV_DGRAD_FORM_GENERAL;
-    if (conv2_dgrad_strip_serves(d, dy, wd, mask, add, dx)) return HAB_CONV_DGRAD_FORM_CONV2_STRIP;
+    if (conv2_dgrad_strip_serves(d, dy, wd, mask, add, dx))  // folded, or under MP_CONV2_STRIP_PLAIN plain: equal bits
+        return matrix_path_on(MP_CONV2_STRIP_PLAIN) ? HAB_CONV_DGRAD_FORM_CONV2_STRIP_PLAIN : HAB_CONV_DGRAD_FORM_CONV2_STRIP;
     if (conv3_dgrad_strip_serves(d, dy, wd, mask, add, dx)) return HAB_CONV_DGRAD_FORM_CONV3_STRIP;
     return HAB_CONV_DGRAD_FORM_GENERAL;
 }
 int conv_dgrad(const ConvDesc& d, const float* dy, const float* wd, const float* mask, const float* add, float* dx,
                float* ws, size_t ws_floats, hipStream_t stream) {
     const int form = choose_conv_dgrad(d, dy, wd, mask, add, dx);
-    if (form == HAB_CONV_DGRAD_FORM_CONV2_STRIP) HAB_TRY_FORM(conv2_dgrad_strip(d, dy, wd, mask, add, dx, stream));
+    if (form == HAB_CONV_DGRAD_FORM_CONV2_STRIP || form == HAB_CONV_DGRAD_FORM_CONV2_STRIP_PLAIN)
+        HAB_TRY_FORM(conv2_dgrad_strip(d, dy, wd, mask, add, dx, form == HAB_CONV_DGRAD_FORM_CONV2_STRIP, stream));
     if (form == HAB_CONV_DGRAD_FORM_CONV3_STRIP) HAB_TRY_FORM(conv3_dgrad_strip(d, dy, wd, mask, add, dx, stream));
     if (d.stride > 1) {
         // kernel size a multiple of the stride: the stride classes share their dY gather -> one contraction with N = s*s*Cin
@@ -540,6 +549,15 @@ extern "C" int hab_obs_conv2d_fwd_form(const uint8_t* rgb, const float* depth, c
     const int r = build(p, mk(B, H, W, o.C, Cout, KH, KW, stride, pad), o, w_fwd, bias, y, relu);
     if (r != HAB_OK) return r;
     return choose_obs_fwd(p, ws, ws_floats, nullptr);
+}
+extern "C" int hab_conv2d_fwd_form(const float* x, const float* w_fwd, const float* bias, float* y, int B, int H, int W, int C, int Cout,
+                                   int KH, int KW, int stride, int pad, int relu, const float* ws, size_t ws_floats) {
+    (void)ws; (void)ws_floats;  // no form depends on the workspace
+    if (!x || !w_fwd || !y) return HAB_ERR_ARG;
+    ConvFwdProb p;
+    const int r = build(p, mk(B, H, W, C, Cout, KH, KW, stride, pad), x, w_fwd, bias, y, relu);
+    if (r != HAB_OK) return r;
+    return choose_conv_fwd(p);
 }
 extern "C" int hab_conv2d_dgrad(const float* dy, const float* w_dgrad, const float* relu_mask, const float* add, float* dx,
                                 int B, int H, int W, int C, int Cout, int KH, int KW, int stride, int pad, float* ws,

@@ -108,6 +108,7 @@ enum MatrixPath : int {
     MP_DENSE_ALL = 1 << 11,    // (tests) MP_DENSE's kernel for every shape it applies to
     MP_RNN_STEPWISE = 1 << 12, // (tests) time-major recurrence as one launch per step instead of the persistent kernels (rnn_persist.h)
     MP_OBS_PATCH_PLAIN = 1 << 13, // (tests) with MP_OBS_PATCH: obs_conv_patch.h's forward kernel in its plain form (per-tile address arithmetic, sign applied at the fragments; bit-identical)
+    MP_CONV2_STRIP_PLAIN = 1 << 14, // (tests) with MP_CONV2_FWD / MP_CONV2_DGRAD: conv2's strip kernels in their plain form (phases in strict sequence; bit-identical)
     MP_DEFAULT = 2047,         // bits 0-10
 };
 int matrix_path_bits();  // the current mask (gemm_ops.hip)

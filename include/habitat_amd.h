@@ -568,6 +568,9 @@ int hab_sample_actions(const float* probs, const float* exp_noise, int64_t* acti
  *     bit 12 (tests) the time-major recurrence as one launch per step instead of the persistent kernels (rnn_persist.h; bit-identical)
  *     bit 13 (tests, with bit 6) obs_conv_patch.h's forward kernel in its plain form: load addresses and bounds worked out per tile and
  *            gather unit, the sign schedule applied to every fragment read (bit-identical; for the bitwise tests and A/B runs)
+ *     bit 14 (tests, with bit 8 or bit 9) SimpleCNN conv2's strip kernels (conv2_fwd_strip.h, conv2_dgrad_strip.h) in their plain form:
+ *            staging, MFMAs, partial tiles and their sums in strict sequence between workgroup barriers, instead of a tile's sums,
+ *            epilogue and stores inside the next tile's MFMA interval (bit-identical; for the bitwise tests and A/B runs)
  *   Default 2047 (bits 0-10), env HAB_BF3 overrides.  hab_set_matrix_path(mode >= 0) sets the mask and returns the previous one;
  *   mode < 0 only queries.  Results are fp32-equivalent on either path (tests/test_gpu_bf3.py: error vs float64 of both).
  * ------------------------------------------------------------------------------------------- */
@@ -591,6 +594,15 @@ int hab_obs_conv2d_fwd(const uint8_t* rgb, const float* depth, const int* rows, 
 int hab_obs_conv2d_fwd_form(const uint8_t* rgb, const float* depth, const int* rows, const float* w_fwd, const float* bias,
                             float* y, int B, int H, int W, int Cout, int KH, int KW, int stride, int pad, int relu, const float* ws,
                             size_t ws_floats);
+/* The form hab_conv2d_fwd runs for these arguments under the current matrix-path mask: 0 the general kernels (patch-resident 3x3, igemm
+ * tiles), 1 SimpleCNN conv2's strip kernel (conv2_fwd_strip.h) in the form that runs by default (a tile's sums folded under the next
+ * tile's MFMAs), 2 that kernel in its plain form (bit 14), or a negative HAB_ERR_* where the call itself would be refused.  Host only:
+ * nothing is launched and no pointer is read (null-ness and alignment count).  The launcher asks the same function.  For tests and tools. */
+#define HAB_CONV_FWD_FORM_GENERAL 0
+#define HAB_CONV_FWD_FORM_CONV2_STRIP 1
+#define HAB_CONV_FWD_FORM_CONV2_STRIP_PLAIN 2
+int hab_conv2d_fwd_form(const float* x, const float* w_fwd, const float* bias, float* y, int B, int H, int W, int C, int Cout, int KH,
+                        int KW, int stride, int pad, int relu, const float* ws, size_t ws_floats);
 /* The gradients accept C % 4 == 0 and Cout % 4 == 0 (HAB_ERR_UNSUPPORTED otherwise).  Every element of dx is overwritten, pixels that no
  * tap reaches included: dx = relu_mask > 0 ? dgrad(dy) + add : +0.0 -- add (nullable) first, then relu_mask (nullable, shaped like dx); a
  * mask entry that is zero, negative or NaN gives +0.0.  ws as for the forward: NULL or any length. */
@@ -615,12 +627,14 @@ int hab_obs_conv2d_wgrad_form(const uint8_t* rgb, const float* depth, const int*
                               float* dbias, int B, int H, int W, int Cout, int KH, int KW, int stride, int pad, const float* ws,
                               size_t ws_floats);
 /* The form hab_conv2d_dgrad runs for these arguments under the current matrix-path mask: 0 the general kernels (patch-resident 3x3,
- * merged stride classes, igemm tiles), 1 SimpleCNN conv2's strip kernel (conv2_dgrad_strip.h), 2 SimpleCNN conv3's strip kernel
- * (conv3_dgrad_strip.h), or a negative HAB_ERR_* where the call itself would be refused.  Host only: nothing is launched and no
+ * merged stride classes, igemm tiles), 1 SimpleCNN conv2's strip kernel (conv2_dgrad_strip.h) in the form that runs by default (a
+ * tile's sums folded under the next tile's MFMAs), 2 SimpleCNN conv3's strip kernel (conv3_dgrad_strip.h), 3 conv2's strip kernel in
+ * its plain form (bit 14), or a negative HAB_ERR_* where the call itself would be refused.  Host only: nothing is launched and no
  * pointer is read (null-ness and alignment count).  The launcher asks the same function.  For tests and tools. */
 #define HAB_CONV_DGRAD_FORM_GENERAL 0
 #define HAB_CONV_DGRAD_FORM_CONV2_STRIP 1
 #define HAB_CONV_DGRAD_FORM_CONV3_STRIP 2
+#define HAB_CONV_DGRAD_FORM_CONV2_STRIP_PLAIN 3
 int hab_conv2d_dgrad_form(const float* dy, const float* w_dgrad, const float* relu_mask, const float* add, float* dx, int B,
                           int H, int W, int C, int Cout, int KH, int KW, int stride, int pad, const float* ws, size_t ws_floats);
 int hab_linear_fwd(const float* x, int ldx, const float* w, int ldw, const float* bias, float* y, int ldy, int M, int N,
