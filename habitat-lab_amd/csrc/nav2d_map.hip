@@ -1,0 +1,360 @@
+// The top-down map of the Nav2D tasks, its fog of war and the video frame (hab_nav2d_map_update, hab_nav2d_map_frame).
+// Definition: habitat_amd/common/env_factory.py (Nav2DVectorEnv, "Top-down map"); specification: tests/nav2d_map_reference.py, which
+// these kernels reproduce bit for bit.  Every float operation below is one fp32 rounding in the written order (contraction is off for
+// the whole file, nothing divides and nothing takes a root); the rest is integer work.  The env records are read through the word
+// offsets of include/habitat_amd.h alone and never written: every Nav2D record begins with a Nav2D-v0 record.
+#include <cstddef>
+#include "hab_common.h"
+#include "../../include/habitat_amd.h"
+
+#pragma clang fp contract(off)
+
+using namespace hab;
+
+namespace nav2d_map {
+
+constexpr int MAX_K = HAB_NAV2D_MAX_OBSTACLES, MAX_M = HAB_NAV2D_MAX_OBJECTS;
+constexpr int THREADS = 256;          // the frame kernel's workgroup
+constexpr int UPDATE_THREADS = 1024;  // the update's: one workgroup per env has to fill a CU by itself
+constexpr float ARENA = 8.0f, HALF = 0.5f;
+// squared radii: each is one fp32 product of the rounded radius with itself
+constexpr float START_R2 = 0.15f * 0.15f, GOAL_R2 = 0.2f * 0.2f, OBJ_R2 = 0.3f * 0.3f, NEAR_R2 = 0.25f * 0.25f;
+constexpr float AGENT_R2 = 0.2f * 0.2f, TICK_R2 = 0.08f * 0.08f;
+constexpr float TRAJ_W = 0.75f, TICK_LEN = 0.45f;
+constexpr int REC_WORDS = HAB_NAV2D_MAP_REC_BYTES / 4;
+static_assert(REC_WORDS == 8 && HAB_NAV2D_MAP_W_ZERO + 3 == REC_WORDS, "map record layout");
+
+__constant__ uint32_t COLORS[32] = HAB_NAV2D_MAP_COLORS;
+
+__device__ inline float word_f(const int32_t* w, int i) { return __int_as_float(w[i]); }
+
+// A disc that the static layer marks with `code`.
+struct Marker { float x, y, r2; int code; };
+
+// What one workgroup knows of its env: the pose, the raw rectangles for the occupancy test and in the centre / half-extent form of
+// the separating-axis test, and the task's markers.
+struct World {
+    float px, py, c, s;
+    float x0[MAX_K], y0[MAX_K], x1[MAX_K], y1[MAX_K];
+    float cx[MAX_K], ex[MAX_K], cy[MAX_K], ey[MAX_K];
+    Marker marker[MAX_M];
+    int markers;
+};
+
+// The task's targets (code 6) and other objects (code 16), read from the words the header names for that task's record.
+template <int TASK>
+__device__ inline int read_markers(const int32_t* w, int M, Marker* out);
+template <>
+__device__ inline int read_markers<HAB_NAV2D_MAP_TASK_GOAL>(const int32_t* w, int, Marker* out) {
+    out[0] = {word_f(w, HAB_NAV2D_W_GX), word_f(w, HAB_NAV2D_W_GY), GOAL_R2, HAB_NAV2D_MAP_TARGET};
+    return 1;
+}
+template <>
+__device__ inline int read_markers<HAB_NAV2D_MAP_TASK_OBJ>(const int32_t* w, int M, Marker* out) {
+    const int target = w[HAB_NAV2D_OBJ_W_TARGET];
+    for (int j = 0; j < M; ++j)
+        out[j] = {word_f(w, HAB_NAV2D_OBJ_W_OBJECTS + 2 * j), word_f(w, HAB_NAV2D_OBJ_W_OBJECTS + 2 * j + 1), OBJ_R2,
+                  w[HAB_NAV2D_OBJ_W_CATEGORIES + j] == target ? HAB_NAV2D_MAP_TARGET : HAB_NAV2D_MAP_OBJECT};
+    return M;
+}
+template <>
+__device__ inline int read_markers<HAB_NAV2D_MAP_TASK_REARR>(const int32_t* w, int, Marker* out) {
+    out[0] = {word_f(w, HAB_NAV2D_REARR_W_GOAL), word_f(w, HAB_NAV2D_REARR_W_GOAL + 1), GOAL_R2, HAB_NAV2D_MAP_TARGET};
+    return 1;
+}
+template <>
+__device__ inline int read_markers<HAB_NAV2D_MAP_TASK_SOCIAL>(const int32_t*, int, Marker*) { return 0; }
+
+__device__ inline void load_pose_and_rects(World& e, const int32_t* w, const float* __restrict__ dirs, int K) {
+    e.px = word_f(w, HAB_NAV2D_W_PX);
+    e.py = word_f(w, HAB_NAV2D_W_PY);
+    const int h = w[HAB_NAV2D_W_HEADING];
+    e.c = dirs[2 * h];
+    e.s = dirs[2 * h + 1];
+    for (int k = 0; k < K; ++k) {
+        const float lx = word_f(w, HAB_NAV2D_W_RECTS + 4 * k), ly = word_f(w, HAB_NAV2D_W_RECTS + 4 * k + 1);
+        const float hx = word_f(w, HAB_NAV2D_W_RECTS + 4 * k + 2), hy = word_f(w, HAB_NAV2D_W_RECTS + 4 * k + 3);
+        e.x0[k] = lx; e.y0[k] = ly; e.x1[k] = hx; e.y1[k] = hy;
+        e.cx[k] = (lx + hx) * HALF; e.ex[k] = (hx - lx) * HALF;
+        e.cy[k] = (ly + hy) * HALF; e.ey[k] = (hy - ly) * HALF;
+    }
+}
+
+__device__ inline bool in_disc(float x, float y, float cx, float cy, float r2) {
+    const float dx = x - cx, dy = y - cy;
+    return dx * dx + dy * dy <= r2;
+}
+
+// A segment a -> b with what the distance test needs of it, the same for every cell.
+struct Segment { float ax, ay, bx, by, sx, sy, len2, w2, w2len; };
+__device__ inline Segment make_segment(float ax, float ay, float bx, float by, float w2) {
+    Segment g{ax, ay, bx, by, bx - ax, by - ay, 0.f, w2, 0.f};
+    g.len2 = g.sx * g.sx + g.sy * g.sy;
+    g.w2len = w2 * g.len2;
+    return g;
+}
+// Whether (x, y) is within sqrt(w2) of the segment, without a division: the end points, then the strip between them.
+__device__ inline bool near_segment(float x, float y, const Segment& g) {
+    const float ex = x - g.ax, ey = y - g.ay;
+    if (ex * ex + ey * ey <= g.w2) return true;
+    if (in_disc(x, y, g.bx, g.by, g.w2)) return true;
+    const float dot = ex * g.sx + ey * g.sy, cross = g.sx * ey - g.sy * ex;
+    return g.len2 > 0.f && dot >= 0.f && dot <= g.len2 && cross * cross <= g.w2len;
+}
+
+__device__ inline bool occupied(float x, float y, const World& e, int K) {
+    for (int k = 0; k < K; ++k)
+        if (x > e.x0[k] && x < e.x1[k] && y > e.y0[k] && y < e.y1[k]) return true;
+    return false;
+}
+
+// The geodesic mode's `visible` on the raw rectangles: the segment agent -> (x, y) meets no open rectangle.
+__device__ inline bool sees(float x, float y, const World& e, int K) {
+    const float hx = (e.px + x) * HALF, sx = (x - e.px) * HALF;
+    const float hy = (e.py + y) * HALF, sy = (y - e.py) * HALF;
+    const float asx = fabsf(sx), asy = fabsf(sy);
+    for (int k = 0; k < K; ++k) {
+        const float mx = hx - e.cx[k], my = hy - e.cy[k];
+        if (fabsf(mx) < e.ex[k] + asx && fabsf(my) < e.ey[k] + asy && fabsf(sx * my - sy * mx) < e.ex[k] * asy + e.ey[k] * asx) return false;
+    }
+    return true;
+}
+
+__device__ inline int static_code(float x, float y, const World& e, int K, float sx, float sy) {
+    int code = occupied(x, y, e, K) ? HAB_NAV2D_MAP_OCCUPIED : HAB_NAV2D_MAP_FREE;
+    for (int j = 0; j < e.markers; ++j)
+        if (in_disc(x, y, e.marker[j].x, e.marker[j].y, e.marker[j].r2) && code != HAB_NAV2D_MAP_TARGET) code = e.marker[j].code;
+    return in_disc(x, y, sx, sy, START_R2) ? HAB_NAV2D_MAP_START : code;
+}
+
+// One workgroup per env: the record is read by every thread before thread 0 advances it, so an env must not be split over
+// workgroups.  Each thread takes groups of four consecutive cells (one 32-bit word of each layer where `vec`).
+template <int TASK>
+__global__ void __launch_bounds__(UPDATE_THREADS)
+nav2d_map_update_kernel(const char* __restrict__ states, size_t stride, const float* __restrict__ dirs, const uint8_t* __restrict__ mask,
+                        uint8_t* __restrict__ map, uint8_t* __restrict__ fog, int32_t* __restrict__ rec, int S, int K, int M, float cell,
+                        float vis2, int advance, int vec) {
+    const int env = blockIdx.x, tid = threadIdx.x;
+    if (mask && !mask[env]) return;
+    const int32_t* w = (const int32_t*)(states + (size_t)env * stride);
+    int32_t* r = rec + (size_t)env * REC_WORDS;
+    __shared__ World e;
+    const bool begin = advance == 0 || w[HAB_NAV2D_W_ENDED] != 0;
+    const float prev_x = word_f(r, HAB_NAV2D_MAP_W_PREV_X), prev_y = word_f(r, HAB_NAV2D_MAP_W_PREV_Y);
+    if (tid == 0) {
+        load_pose_and_rects(e, w, dirs, K);
+        e.markers = read_markers<TASK>(w, M, e.marker);
+    }
+    __syncthreads();
+    const float px = e.px, py = e.py;
+    if (tid == 0) {
+        if (begin) {
+            r[HAB_NAV2D_MAP_W_EPISODE] = w[HAB_NAV2D_W_EPISODE];
+            r[HAB_NAV2D_MAP_W_START_X] = __float_as_int(px);
+            r[HAB_NAV2D_MAP_W_START_Y] = __float_as_int(py);
+            r[HAB_NAV2D_MAP_W_ZERO] = r[HAB_NAV2D_MAP_W_ZERO + 1] = r[HAB_NAV2D_MAP_W_ZERO + 2] = 0;
+        }
+        r[HAB_NAV2D_MAP_W_PREV_X] = __float_as_int(px);
+        r[HAB_NAV2D_MAP_W_PREV_Y] = __float_as_int(py);
+    }
+    const float tw = TRAJ_W * cell;
+    const Segment seg = make_segment(begin ? px : prev_x, begin ? py : prev_y, px, py, tw * tw);
+    const int total = S * S, groups = (total + 3) >> 2;
+    uint8_t* m = map + (size_t)env * total;
+    uint8_t* f = fog + (size_t)env * total;
+    for (int g = tid; g < groups; g += UPDATE_THREADS) {
+        const int i0 = g * 4, n = min(4, total - i0);
+        uint32_t mv = 0, fv = 0;
+        if (!begin) {
+            if (vec) {
+                mv = ((const uint32_t*)m)[g];
+                fv = ((const uint32_t*)f)[g];
+            } else {
+                for (int j = 0; j < n; ++j) { mv |= (uint32_t)m[i0 + j] << (8 * j); fv |= (uint32_t)f[i0 + j] << (8 * j); }
+            }
+        }
+        int rr = i0 / S, cc = i0 - rr * S;
+        uint32_t mo = 0, fo = 0;
+        for (int j = 0; j < n; ++j) {
+            const float x = ((float)cc + HALF) * cell, y = ((float)(S - 1 - rr) + HALF) * cell;
+            int code = begin ? static_code(x, y, e, K, px, py) : (int)((mv >> (8 * j)) & 255u);
+            uint32_t seen = begin ? 0u : ((fv >> (8 * j)) & 255u);
+            if (code != HAB_NAV2D_MAP_START && code != HAB_NAV2D_MAP_TARGET && near_segment(x, y, seg)) code = HAB_NAV2D_MAP_TRAJECTORY;
+            if (!seen) {
+                const float dx = x - px, dy = y - py;
+                const float d2 = dx * dx + dy * dy;
+                if (d2 <= vis2) {
+                    const float dot = dx * e.c + dy * e.s, cross = e.c * dy - e.s * dx;
+                    if ((d2 <= NEAR_R2 || (dot > 0.f && fabsf(cross) <= dot)) && !occupied(x, y, e, K) && sees(x, y, e, K)) seen = 1u;
+                }
+            }
+            mo |= (uint32_t)code << (8 * j);
+            fo |= seen << (8 * j);
+            if (++cc == S) { cc = 0; ++rr; }
+        }
+        if (vec) {
+            ((uint32_t*)m)[g] = mo;
+            ((uint32_t*)f)[g] = fo;
+        } else {
+            for (int j = 0; j < n; ++j) { m[i0 + j] = (uint8_t)(mo >> (8 * j)); f[i0 + j] = (uint8_t)(fo >> (8 * j)); }
+        }
+    }
+}
+
+// What the frame kernel knows of its env: the pose's overlays and the palette.
+struct Overlay {
+    float px, py, ox, oy;
+    Segment tick;
+    uint32_t color[32];
+};
+
+// The frame: grid (row tile, env), a thread takes groups of four pixels of a row (three 32-bit words where `vec`).  Reads only.
+template <int TASK>
+__global__ void __launch_bounds__(THREADS)
+nav2d_map_frame_kernel(const char* __restrict__ states, size_t stride, const float* __restrict__ dirs, const uint8_t* __restrict__ map,
+                       const uint8_t* __restrict__ fog, const uint8_t* __restrict__ rgb, const float* __restrict__ depth,
+                       uint8_t* __restrict__ frame, int S, int H, int W, int Hf, int Wf, int Wp, int rows, float cell, int draw_fog, int vec) {
+    const int env = blockIdx.y, tid = threadIdx.x, row0 = blockIdx.x * rows;
+    const int32_t* w = (const int32_t*)(states + (size_t)env * stride);
+    __shared__ Overlay o;
+    if (tid < 32) o.color[tid] = COLORS[tid];
+    if (tid == 0) {
+        const float px = word_f(w, HAB_NAV2D_W_PX), py = word_f(w, HAB_NAV2D_W_PY);
+        const int h = w[HAB_NAV2D_W_HEADING];
+        o.px = px; o.py = py;
+        o.tick = make_segment(px, py, px + TICK_LEN * dirs[2 * h], py + TICK_LEN * dirs[2 * h + 1], TICK_R2);
+        o.ox = o.oy = 0.f;
+        if (TASK == HAB_NAV2D_MAP_TASK_REARR) { o.ox = word_f(w, HAB_NAV2D_REARR_W_OBJ); o.oy = word_f(w, HAB_NAV2D_REARR_W_OBJ + 1); }
+        if (TASK == HAB_NAV2D_MAP_TASK_SOCIAL) { o.ox = word_f(w, HAB_NAV2D_SOCIAL_W_PERSON); o.oy = word_f(w, HAB_NAV2D_SOCIAL_W_PERSON + 1); }
+    }
+    __syncthreads();
+    const int groups = (Wf + 3) >> 2, x_rgb = rgb ? Wp : 0, x_map = x_rgb + (depth ? Wp : 0);
+    const uint8_t* m = map + (size_t)env * S * S;
+    const uint8_t* f = fog + (size_t)env * S * S;
+    uint8_t* out = frame + (size_t)env * Hf * Wf * 3;
+    const int tile = min(rows, Hf - row0);
+    for (int idx = tid; idx < tile * groups; idx += THREADS) {
+        const int lr = idx / groups, g = idx - lr * groups, r = row0 + lr;
+        const int c0 = g * 4, n = min(4, Wf - c0);
+        const int sr = H > 0 ? (r * H) / Hf : 0, cr = (r * S) / Hf;
+        uint32_t px3[4];
+        for (int j = 0; j < n; ++j) {
+            const int c = c0 + j;
+            uint32_t v;
+            if (c < x_rgb) {
+                const uint8_t* p = rgb + (((size_t)env * H + sr) * W + (c * W) / Wp) * 3;
+                v = p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16;
+            } else if (c < x_map) {
+                const float d = depth[((size_t)env * H + sr) * W + ((c - x_rgb) * W) / Wp];
+                const uint32_t grey = (uint32_t)min(max((int)(d * 255.0f), 0), 255);
+                v = grey * 0x010101u;
+            } else {
+                const int cc = ((c - x_map) * S) / Hf;
+                int code = m[cr * S + cc];
+                const bool dim = draw_fog && code == HAB_NAV2D_MAP_FREE && !f[cr * S + cc];
+                const float x = ((float)cc + HALF) * cell, y = ((float)(S - 1 - cr) + HALF) * cell;
+                if (TASK == HAB_NAV2D_MAP_TASK_REARR && in_disc(x, y, o.ox, o.oy, OBJ_R2)) code = HAB_NAV2D_MAP_CARRIED;
+                if (TASK == HAB_NAV2D_MAP_TASK_SOCIAL && in_disc(x, y, o.ox, o.oy, OBJ_R2)) code = HAB_NAV2D_MAP_PERSON;
+                if (in_disc(x, y, o.px, o.py, AGENT_R2)) code = HAB_NAV2D_MAP_AGENT;
+                if (near_segment(x, y, o.tick)) code = HAB_NAV2D_MAP_TICK;
+                v = o.color[code & 31];
+                if (dim && code == HAB_NAV2D_MAP_FREE) v = (v >> 1) & 0x7F7F7Fu;
+            }
+            px3[j] = v;
+        }
+        uint8_t* dst = out + ((size_t)r * Wf + c0) * 3;
+        if (vec && n == 4) {
+            uint32_t* d32 = (uint32_t*)dst;
+            d32[0] = px3[0] | px3[1] << 24;
+            d32[1] = px3[1] >> 8 | px3[2] << 16;
+            d32[2] = px3[2] >> 16 | px3[3] << 8;
+        } else {
+            for (int j = 0; j < n; ++j) { dst[3 * j] = (uint8_t)px3[j]; dst[3 * j + 1] = (uint8_t)(px3[j] >> 8); dst[3 * j + 2] = (uint8_t)(px3[j] >> 16); }
+        }
+    }
+}
+
+static bool task_ok(int task) { return task >= HAB_NAV2D_MAP_TASK_GOAL && task <= HAB_NAV2D_MAP_TASK_SOCIAL; }
+static bool resolution_ok(int S) { return S >= HAB_NAV2D_MAP_MIN_RESOLUTION && S <= HAB_NAV2D_MAP_MAX_RESOLUTION; }
+static bool records_ok(const void* state, size_t stride, int N) {
+    return state && !((uintptr_t)state & 3) && stride >= HAB_NAV2D_STATE_BYTES && !(stride & 3) && N > 0;
+}
+// the smallest record that holds the words the task's reader and overlays name
+static size_t task_bytes(int task) {
+    return task == HAB_NAV2D_MAP_TASK_OBJ ? HAB_NAV2D_OBJ_STATE_BYTES : task == HAB_NAV2D_MAP_TASK_REARR ? HAB_NAV2D_REARR_STATE_BYTES
+         : task == HAB_NAV2D_MAP_TASK_SOCIAL ? HAB_NAV2D_SOCIAL_STATE_BYTES : HAB_NAV2D_STATE_BYTES;
+}
+
+}  // namespace nav2d_map
+
+using namespace nav2d_map;
+
+extern "C" int hab_nav2d_map_rec_bytes(void) { return HAB_NAV2D_MAP_REC_BYTES; }
+
+extern "C" int hab_nav2d_map_update(const void* state, size_t state_stride_bytes, const float* dirs, const uint8_t* mask, uint8_t* map,
+                                    uint8_t* fog, void* rec, int N, int S, int num_obstacles, int num_headings, int task, int num_objects,
+                                    float vis_dist, int advance, hipStream_t stream) {
+    if (!resolution_ok(S) || !task_ok(task) || !map || !fog || !rec || ((uintptr_t)rec & 3) || !dirs) return HAB_ERR_ARG;
+    if (!records_ok(state, state_stride_bytes, N) || state_stride_bytes < task_bytes(task)) return HAB_ERR_ARG;
+    if (num_obstacles < 0 || num_obstacles > MAX_K || num_headings <= 0) return HAB_ERR_ARG;
+    if (task == HAB_NAV2D_MAP_TASK_OBJ && (num_objects < 1 || num_objects > MAX_M)) return HAB_ERR_ARG;
+    if (!(vis_dist > 0.f) || !(vis_dist <= 3.0e38f)) return HAB_ERR_ARG;
+    const float cell = ARENA / (float)S, vis2 = vis_dist * vis_dist;
+    const int vec = (S * S) % 4 == 0 && !((uintptr_t)map & 3) && !((uintptr_t)fog & 3);
+#define HAB_MAP_UPDATE(T)                                                                                                              \
+    case T:                                                                                                                            \
+        nav2d_map_update_kernel<T><<<N, UPDATE_THREADS, 0, stream>>>((const char*)state, state_stride_bytes, dirs, mask, map, fog, (int32_t*)rec, \
+                                                              S, num_obstacles, num_objects, cell, vis2, advance, vec);                 \
+        break;
+    switch (task) {
+        HAB_MAP_UPDATE(HAB_NAV2D_MAP_TASK_GOAL)
+        HAB_MAP_UPDATE(HAB_NAV2D_MAP_TASK_OBJ)
+        HAB_MAP_UPDATE(HAB_NAV2D_MAP_TASK_REARR)
+        HAB_MAP_UPDATE(HAB_NAV2D_MAP_TASK_SOCIAL)
+    }
+#undef HAB_MAP_UPDATE
+    HAB_LAUNCH_CHECK();
+    return HAB_OK;
+}
+
+extern "C" int hab_nav2d_map_frame_width(int frame_h, int H, int W, int has_rgb, int has_depth) {
+    if (frame_h <= 0 || frame_h > 4096) return HAB_ERR_ARG;
+    const int panels = (has_rgb ? 1 : 0) + (has_depth ? 1 : 0);
+    if (!panels) return frame_h;
+    if (H <= 0 || W <= 0 || W > HAB_NAV2D_MAX_WIDTH || H > 4096) return HAB_ERR_ARG;
+    const int Wp = (int)(((long long)frame_h * W) / H);
+    if (Wp < 1 || Wp > 65536) return HAB_ERR_ARG;
+    return frame_h + panels * Wp;
+}
+
+extern "C" int hab_nav2d_map_frame(const void* state, size_t state_stride_bytes, const float* dirs, const uint8_t* map, const uint8_t* fog,
+                                   const uint8_t* rgb, const float* depth, uint8_t* frame, int N, int S, int H, int W, int frame_h,
+                                   int frame_w, int num_headings, int task, int draw_fog, hipStream_t stream) {
+    if (!resolution_ok(S) || !task_ok(task) || !map || !fog || !frame || !dirs || num_headings <= 0) return HAB_ERR_ARG;
+    if (!records_ok(state, state_stride_bytes, N) || state_stride_bytes < task_bytes(task)) return HAB_ERR_ARG;
+    if (depth && ((uintptr_t)depth & 3)) return HAB_ERR_ARG;
+    const int want = hab_nav2d_map_frame_width(frame_h, H, W, rgb != nullptr, depth != nullptr);
+    if (want < 0 || want != frame_w) return HAB_ERR_ARG;
+    if (N > 65535) return HAB_ERR_UNSUPPORTED;  // grid.y is the env
+    const int Wp = (rgb || depth) ? (int)(((long long)frame_h * W) / H) : 0;
+    const float cell = ARENA / (float)S;
+    const int vec = frame_w % 4 == 0 && !((uintptr_t)frame & 3);
+    // about 16 KiB of stores per workgroup
+    int rows = cdiv(16384, frame_w * 3);
+    if (rows > frame_h) rows = frame_h;
+    dim3 grid(cdiv(frame_h, rows), N);
+#define HAB_MAP_FRAME(T)                                                                                                            \
+    case T:                                                                                                                         \
+        nav2d_map_frame_kernel<T><<<grid, THREADS, 0, stream>>>((const char*)state, state_stride_bytes, dirs, map, fog, rgb, depth, frame, S, \
+                                                                rgb || depth ? H : 0, W, frame_h, frame_w, Wp, rows, cell, draw_fog, vec); \
+        break;
+    switch (task) {
+        HAB_MAP_FRAME(HAB_NAV2D_MAP_TASK_GOAL)
+        HAB_MAP_FRAME(HAB_NAV2D_MAP_TASK_OBJ)
+        HAB_MAP_FRAME(HAB_NAV2D_MAP_TASK_REARR)
+        HAB_MAP_FRAME(HAB_NAV2D_MAP_TASK_SOCIAL)
+    }
+#undef HAB_MAP_FRAME
+    HAB_LAUNCH_CHECK();
+    return HAB_OK;
+}

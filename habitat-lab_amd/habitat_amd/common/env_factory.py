@@ -235,6 +235,40 @@ _W_EPISODE, _W_ENDED, _W_LAST = 10, 11, 12
 
 NAV2D_DISTANCES = ("euclidean", "geodesic")
 
+# the top-down map (include/habitat_amd.h: HAB_NAV2D_MAP_*): the resolution's range, which words of a task's record tell its targets,
+# the cell codes and the colour of every code, rows (r, g, b) of HAB_NAV2D_MAP_COLORS
+NAV2D_MAP_MIN_RESOLUTION, NAV2D_MAP_MAX_RESOLUTION = 16, 512
+NAV2D_MAP_TASK_GOAL, NAV2D_MAP_TASK_OBJ, NAV2D_MAP_TASK_REARR, NAV2D_MAP_TASK_SOCIAL = 0, 1, 2, 3
+NAV2D_MAP_CODES = dict(occupied=0, free=1, start=4, target=6, trajectory=10, object=16, carried=20, person=21, agent=22, tick=23)
+NAV2D_MAP_COLORS = np.full((32, 3), (255, 0, 255), dtype=np.uint8)
+for _code, _rgb in (("occupied", (64, 64, 64)), ("free", (200, 200, 200)), ("start", (50, 50, 200)), ("target", (255, 32, 32)),
+                    ("trajectory", (0, 160, 208)), ("object", (240, 160, 32)), ("carried", (255, 200, 0)), ("person", (200, 0, 200)),
+                    ("agent", (0, 160, 0)), ("tick", (0, 64, 0))):
+    NAV2D_MAP_COLORS[NAV2D_MAP_CODES[_code]] = _rgb
+NAV2D_MAP_DEFAULTS = dict(map_resolution=128, visibility_dist=5.0, draw_fog=True, fov=90)
+
+
+def nav2d_map_parameters(top_down_map, who: str = "Nav2D"):
+    """Checks the `top_down_map` keyword of a Nav2D env, a mapping with any of map_resolution, visibility_dist, draw_fog and fov (other
+    keys of habitat's measurement are accepted and not read), and returns (map_resolution, visibility_dist, draw_fog), or None where
+    the keyword is None."""
+    if top_down_map is None:
+        return None
+    if not isinstance(top_down_map, dict):
+        raise _lib.HabError(f"{who}: top_down_map {top_down_map!r} must be None or a mapping of the measurement's keys")
+    S, vis, draw, fov = (top_down_map.get(k, v) for k, v in NAV2D_MAP_DEFAULTS.items())
+    if not whole(S) or not NAV2D_MAP_MIN_RESOLUTION <= S <= NAV2D_MAP_MAX_RESOLUTION:
+        raise _lib.HabError(f"{who}: top_down_map.map_resolution {S!r} must be a whole number in {NAV2D_MAP_MIN_RESOLUTION}.."
+                            f"{NAV2D_MAP_MAX_RESOLUTION}")
+    if (isinstance(vis, bool) or not isinstance(vis, (int, float, np.integer, np.floating)) or not np.isfinite(np.float32(vis))
+            or not float(np.float32(vis)) > 0.0):
+        raise _lib.HabError(f"{who}: top_down_map.visibility_dist {vis!r} must be a positive finite length in metres")
+    if isinstance(fov, bool) or not isinstance(fov, (int, float, np.integer, np.floating)) or float(fov) != 90.0:
+        raise _lib.HabError(f"{who}: top_down_map.fov {fov!r} must be 90: the wedge of the fog of war is the camera's field of view")
+    if not isinstance(draw, (bool, np.bool_)):
+        raise _lib.HabError(f"{who}: top_down_map.draw_fog {draw!r} must be true or false")
+    return int(S), float(np.float32(vis)), bool(draw)
+
 
 def nav2d_distance(distance, who: str = "Nav2D") -> str:
     if not isinstance(distance, str) or distance not in NAV2D_DISTANCES:
@@ -332,6 +366,42 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
         lost-step counter goes up.  g0 infinite (the goal is walled off): the episode keeps the Euclidean d throughout.
       The field records (`_geo`, (N, 40) int32: D, reachable, sweeps, lost steps) exist in this mode only.
 
+    Top-down map (`top_down_map`, from `habitat.task.measurements.top_down_map`; every Nav2D task has it).  None, the default:
+      nothing is allocated and nothing is launched.  dict(map_resolution=128, visibility_dist=5.0, draw_fog=True): the env owns
+      `_map`, `_fog` (uint8 (N, S, S)) and `_map_rec` ((N, 8) int32) and `hab_nav2d_map_update` runs after every step entry on its
+      stream with its mask and advance (csrc/nav2d_map.hip; tests/nav2d_map_reference.py restates it, the kernels match it byte for
+      byte).  `top_down_map()` returns habitat's four fields, `render_frames()` the video frames; neither goes into the infos.
+      Every float operation is one float32 rounding in the written order; only the cell size divides.
+      * Grid.  S = map_resolution, a whole number in 16..512; cell = 8 / S; cell (r, c) has the centre x = (c + 0.5) * cell,
+        y = (S - 1 - r + 0.5) * cell: row 0 is the top, y is up.  "In a disc of radius R at q" is dx * dx + dy * dy <= R * R.
+      * Static layer, written when an episode begins: 0 where the centre is strictly inside a raw rectangle, else 1; then 16 in a
+        disc of 0.3 m at every object of Nav2DObj-v0 that is not of the target category; then 6 over that: a disc of 0.2 m at
+        (GX, GY) (Nav2D-v0, Nav2DVel-v0) or at the goal place (the rearrangement tasks), discs of 0.3 m at the objects of the
+        target category (Nav2DObj-v0), nothing for Nav2DSocial-v0; then 4 over all in a disc of 0.15 m at the start.  The
+        rearrangement object and the person move, so they are in the frame, not in the map.
+      * Trajectory, code 10, over every code but 4 and 6.  A cell is on the segment a -> b when its centre is within
+        w = 0.75 * cell of it: e = centre - a, s = b - a, len2 = s.s; hit iff e.e <= w * w, or the same at b, or len2 > 0 and
+        0 <= e.s <= len2 and cross * cross <= (w * w) * len2 with cross = sx * ey - sy * ex.  When an episode begins the start is
+        drawn as a segment of no length, so the agent's own cell is never shown occupied; on a step that did not end the episode
+        the segment from the record's previous position to the new one is drawn, then previous = new.
+      * Fog of war.  `_fog` is 1 where the cell has been seen in the episode.  A cell is seen at a step when its centre is not
+        strictly inside a rectangle, dx * dx + dy * dy <= vis * vis for (dx, dy) = centre - p, it lies in the camera's 90 degree
+        wedge (dot = dx * c + dy * s > 0 and |c * dy - s * dx| <= dot for the heading's (c, s)) or within 0.25 m, and the segment
+        p -> centre meets no open raw rectangle by the separating-axis expression of `visible` above on (x0, y0, x1, y1) itself,
+        neither grown nor shrunk.  Cylinders (objects, the person) do not block sight in the map, and occupied cells are never
+        marked: both are part of the definition.
+      * Episode boundaries.  At a reset, and for a stepped env whose step ended an episode, both layers are cleared, the new
+        episode's static layer is written with the record's current position as the start, and the first reveal is done from it.
+        So the finished episode's last move is never drawn: a STOP does not move, an end at the step limit loses one segment.
+        An env whose mask byte is clear keeps map, fog and record.
+      * Frame (`render_frames`, one launch of `nav2d_map_frame_kernel` for all envs), uint8 (N, Hf, Wf, 3), panels left to right:
+        the rgb image if the env has one, upscaled by nearest neighbour (source row (r * H) / Hf, panel width Wp = (Hf * W) / H,
+        source column (c * W) / Wp); depth likewise as grey (int)(d * 255); the map at Hf x Hf, pixel (r, c) showing cell
+        ((r * S) / Hf, (c * S) / Hf) in the colour NAV2D_MAP_COLORS gives its code.  Overlays at cell granularity, later ones on
+        top: the rearrangement object, resting or carried (0.3 m, code 20), the person (0.3 m, 21), the agent (0.2 m, 22), the
+        heading tick (cells within 0.08 m of p -> p + 0.45 * dir, 23).  With draw_fog a free cell (code 1) that has not been seen
+        is shown at half brightness, each channel >> 1; occupied cells, markers and overlays always at full brightness.
+
     Besides the VectorEnv API this env consumes actions (`consumes_actions`): `step_into_obs(obs, reward, not_done, actions=...)`
     on the device path; `async_step_at(i, a)` records a, and `advance_on_device` steps exactly the pending envs with their recorded
     actions through the kernels' per-env mask.  `measure_sums` holds the device-side running sums of the four measures."""
@@ -361,9 +431,10 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
 
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
                  use_depth: bool = True, num_actions: int = 4, device="cuda", num_obstacles: int = 3, turn_angle: int = 10,
-                 max_episode_steps: int = 500, distance: str = "euclidean"):
+                 max_episode_steps: int = 500, distance: str = "euclidean", top_down_map=None):
         self.num_headings = nav2d_num_headings(turn_angle)
         self.distance = nav2d_distance(distance)
+        self.map_parameters = nav2d_map_parameters(top_down_map, self._name)
         if not 0 <= int(num_obstacles) <= NAV2D_MAX_OBSTACLES:
             raise _lib.HabError(f"Nav2D: num_obstacles {num_obstacles} outside 0..{NAV2D_MAX_OBSTACLES}")
         if num_actions != 4:
@@ -393,6 +464,16 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
         self._head = (ptr(self._state), *field, *map(ptr, self._tables))
         self._tail = (ptr(self.measure_sums), self.seed, self.env_offset, self.num_envs, self.H, self.W, self.num_obstacles,
                       self.num_headings, self.max_episode_steps, *self._task_parameters())
+        # the top-down map: its layers and records exist, and its update is launched, only where the keyword asks for it
+        self._map = self._fog = self._map_rec = self._map_update = None
+        if self.map_parameters is not None:
+            S, vis, _ = self.map_parameters
+            self._map = torch.zeros(num_envs, S, S, dtype=torch.uint8, device=dev)
+            self._fog = torch.zeros(num_envs, S, S, dtype=torch.uint8, device=dev)
+            self._map_rec = torch.zeros(num_envs, _lib.lib().hab_nav2d_map_rec_bytes() // 4, dtype=torch.int32, device=dev)
+            self._map_update = (ptr(self._state), words * 4, ptr(self._tables[0])), (
+                ptr(self._map), ptr(self._fog), ptr(self._map_rec), num_envs, S, self.num_obstacles, self.num_headings, self._map_task,
+                getattr(self, "num_objects", 0), vis)
 
     # ---- device fast path ---------------------------------------------------------------------
     def _actions_shaped(self, actions) -> bool:
@@ -412,6 +493,63 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
             raise _lib.HabError(f"{self._name}: actions must be a contiguous {self._action_text}")
         check(self._step(*self._head, ptr(actions), ptr(mask), *self._sensor_rows(obs), ptr(reward), ptr(not_done), *self._tail, advance,
                          stream_ptr()), self._entry)
+        if self._map_update is not None:
+            records, layers = self._map_update
+            check(_lib.lib().hab_nav2d_map_update(*records, ptr(mask), *layers, advance, stream_ptr()), "hab_nav2d_map_update")
+            self._frame_obs = obs
+
+    # ---- the top-down map -----------------------------------------------------------------------
+    _map_task = NAV2D_MAP_TASK_GOAL  # which words of the record tell the targets (HAB_NAV2D_MAP_TASK_*)
+    _frame_keys = ("rgb", "depth")   # the observations of the frame's first two panels
+    _frame_obs = None                # the rows the last launch wrote its observations into
+
+    def _need_map(self, method: str):
+        if self._map is None:
+            raise _lib.HabError(f"{self._name}: {method} needs the top-down map: build the env with top_down_map=dict(...) "
+                                "(habitat.task.measurements.top_down_map in a config)")
+
+    def top_down_map(self):
+        """The measure's four fields as device tensors: `map` uint8 (N, S, S) of cell codes, `fog_of_war_mask` uint8 (N, S, S),
+        `agent_map_coord` int64 (N, 2) = (row, column) of the agent's cell, `agent_angle` float32 (N,) = the heading's angle in
+        radians from the host table.  The first two are the env's own tensors, not copies."""
+        self._need_map("top_down_map()")
+        S = self.map_parameters[0]
+        pos = self._state[:, 0:2].view(torch.float32)
+        cell = (pos / float(np.float32(8.0) / np.float32(S))).floor().to(torch.int64).clamp_(0, S - 1)  # a float32 division
+        angles = torch.arange(self.num_headings, device=self._state.device, dtype=torch.float64) * (2.0 * np.pi / self.num_headings)
+        return dict(map=self._map, fog_of_war_mask=self._fog, agent_map_coord=torch.stack([S - 1 - cell[:, 1], cell[:, 0]], 1),
+                    agent_angle=angles.to(torch.float32)[self._state[:, 7].long()])
+
+    def frame_size(self, height=None):
+        """(rows, columns) of a frame of `render_frames`; the default height is the larger of the image height and 128 rows."""
+        height = max(self.H, 128) if height is None else height
+        if not whole(height) or height <= 0:
+            raise _lib.HabError(f"{self._name}: render_frames: height {height!r} must be a positive whole number")
+        width = _lib.lib().hab_nav2d_map_frame_width(int(height), self.H, self.W, int(self.use_rgb), int(self.use_depth))
+        check(min(width, 0), "hab_nav2d_map_frame_width")
+        return int(height), width
+
+    def render_frames(self, out=None, height=None):
+        """The video frame of every env, uint8 (N, height, width, 3), composed on the device in one launch: the env's rgb and depth
+        (those of the rows its last step or reset wrote) upscaled by nearest neighbour, then the map with the fog of war and the
+        overlays (see the class docstring, Top-down map).  `out` receives the frames (allocated if None) and is returned."""
+        self._need_map("render_frames()")
+        Hf, Wf = self.frame_size(height)
+        N, dev = self.num_envs, self._state.device
+        if out is None:
+            out = torch.empty(N, Hf, Wf, 3, dtype=torch.uint8, device=dev)
+        if not (tuple(out.shape) == (N, Hf, Wf, 3) and out.dtype == torch.uint8 and out.is_contiguous() and out.device == dev):
+            raise _lib.HabError(f"{self._name}: render_frames: `out` must be a contiguous uint8 tensor of shape {(N, Hf, Wf, 3)} on {dev}")
+        obs = self._frame_obs or {}
+        rgb, depth = (obs.get(k) if use else None for k, use in zip(self._frame_keys, (self.use_rgb, self.use_depth)))
+        if (self.use_rgb and rgb is None) or (self.use_depth and depth is None):
+            raise _lib.HabError(f"{self._name}: render_frames: the last step or reset wrote no {' / '.join(self._frame_keys)} rows; "
+                                "reset the env first")
+        S, _, draw_fog = self.map_parameters
+        check(_lib.lib().hab_nav2d_map_frame(ptr(self._state), self._state.shape[1] * 4, ptr(self._tables[0]), ptr(self._map),
+                                             ptr(self._fog), ptr(rgb), ptr(depth), ptr(out), N, S, self.H, self.W, Hf, Wf,
+                                             self.num_headings, self._map_task, int(draw_fog), stream_ptr()), "hab_nav2d_map_frame")
+        return out
 
     def reset_into_obs(self, obs):
         self._launch(obs, None, None, None, None, 0)
@@ -599,7 +737,7 @@ class Nav2DVelVectorEnv(Nav2DVectorEnv):
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
                  use_depth: bool = True, num_actions: int = 1, device="cuda", num_obstacles: int = 3, turn_angle: int = 1,
                  max_episode_steps: int = 500, max_turn_angle: int = 10, min_abs_lin_speed: float = 0.025, min_abs_ang_speed: int = 5,
-                 allow_sliding: bool = True, distance: str = "euclidean"):
+                 allow_sliding: bool = True, distance: str = "euclidean", top_down_map=None):
         _, self.max_turn_steps, self.stop_turn_steps = nav2d_vel_parameters(turn_angle, max_turn_angle, min_abs_lin_speed,
                                                                             min_abs_ang_speed)
         if not isinstance(allow_sliding, (bool, np.bool_)):
@@ -610,7 +748,7 @@ class Nav2DVelVectorEnv(Nav2DVectorEnv):
         self.min_abs_lin_speed, self.allow_sliding = float(min_abs_lin_speed), bool(allow_sliding)
         super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
                          num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps,
-                         distance=nav2d_distance(distance, "Nav2DVel"))
+                         distance=nav2d_distance(distance, "Nav2DVel"), top_down_map=top_down_map)
         self.action_spaces = [spaces.Box(-1.0, 1.0, (2,), np.float32) for _ in range(num_envs)]
         self.orig_action_spaces = self.action_spaces
         self._actions_host = np.zeros((num_envs, 2), dtype=np.float32)
@@ -706,13 +844,14 @@ class Nav2DObjVectorEnv(Nav2DVectorEnv):
     _entries = ("hab_nav2d_obj_step", "hab_nav2d_obj_step_geo")
     _follow_entry = None  # no shortest-path follower: see Nav2DVectorEnv.follower_actions
     _sensor_set = "objectnav"
+    _map_task = NAV2D_MAP_TASK_OBJ
     _renders_without_rgb_depth = True
     _state_bytes = "hab_nav2d_obj_state_bytes"
     _geo_bytes = "hab_nav2d_obj_geo_bytes"
 
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
                  use_depth: bool = True, num_actions: int = 6, device="cuda", num_obstacles: int = 3, turn_angle: int = 10,
-                 max_episode_steps: int = 500, num_objects: int = 3, num_categories: int = 4, distance: str = "euclidean"):
+                 max_episode_steps: int = 500, num_objects: int = 3, num_categories: int = 4, distance: str = "euclidean", top_down_map=None):
         if nav2d_distance(distance, "Nav2DObj") == "geodesic" and torch.device(device).type != "cuda":
             raise _lib.HabError("Nav2DObj: distance 'geodesic' builds its field on the GPU; no GPU device given")
         if not whole(num_objects) or not 1 <= num_objects <= NAV2D_MAX_OBJECTS:
@@ -726,7 +865,8 @@ class Nav2DObjVectorEnv(Nav2DVectorEnv):
             raise _lib.HabError(f"Nav2DObj: the semantic image is always rendered, so the image size {height} x {width} must be positive")
         self.num_objects, self.num_categories, self.num_actions = int(num_objects), int(num_categories), int(num_actions)
         super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
-                         num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps, distance=distance)
+                         num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps, distance=distance,
+                         top_down_map=top_down_map)
         self.task = "nav2dobj"
         self.action_spaces = [spaces.Discrete(self.num_actions) for _ in range(num_envs)]
         self.orig_action_spaces = self.action_spaces
@@ -831,13 +971,14 @@ class Nav2DRearrVectorEnv(Nav2DVectorEnv):
     _geo_entry = "hab_nav2d_rearr_step_geo"
     _geo_bytes = "hab_nav2d_rearr_geo_bytes"
     _sensor_set = "rearrange"
+    _map_task, _frame_keys = NAV2D_MAP_TASK_REARR, ("head_rgb", "head_depth")
     _state_bytes = "hab_nav2d_rearr_state_bytes"
     measure_names = NAV2D_REARR_MEASURES
     num_actions = 6
 
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = False,
                  use_depth: bool = True, num_actions: int = 6, device="cuda", num_obstacles: int = 3, turn_angle: int = 10,
-                 max_episode_steps: int = 500, start_holding: bool = False, distance: str = "euclidean"):
+                 max_episode_steps: int = 500, start_holding: bool = False, distance: str = "euclidean", top_down_map=None):
         self._check_distance(distance, device)
         if not isinstance(start_holding, (bool, np.bool_)):
             raise _lib.HabError(f"Nav2DRearr: start_holding {start_holding!r} must be true or false")
@@ -848,7 +989,8 @@ class Nav2DRearrVectorEnv(Nav2DVectorEnv):
             raise _lib.HabError(f"Nav2DRearr: the image size {height} x {width} must be positive")
         self.start_holding = bool(start_holding)
         super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
-                         num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps, distance=distance)
+                         num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps, distance=distance,
+                         top_down_map=top_down_map)
         self.task = "nav2drearr"
         self.action_spaces = [spaces.Discrete(6) for _ in range(num_envs)]
         self.orig_action_spaces = self.action_spaces
@@ -963,7 +1105,7 @@ class Nav2DRearrVelVectorEnv(Nav2DRearrVectorEnv):
     def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = False,
                  use_depth: bool = True, num_actions: int = 1, device="cuda", num_obstacles: int = 3, turn_angle: int = 1,
                  max_episode_steps: int = 500, start_holding: bool = False, max_turn_angle: int = 10, min_abs_lin_speed: float = 0.025,
-                 min_abs_ang_speed: int = 5, allow_sliding: bool = True, distance: str = "euclidean"):
+                 min_abs_ang_speed: int = 5, allow_sliding: bool = True, distance: str = "euclidean", top_down_map=None):
         _, self.max_turn_steps, self.stop_turn_steps = nav2d_vel_parameters(turn_angle, max_turn_angle, min_abs_lin_speed,
                                                                             min_abs_ang_speed, "Nav2DRearrVel")
         if not isinstance(allow_sliding, (bool, np.bool_)):
@@ -978,7 +1120,7 @@ class Nav2DRearrVelVectorEnv(Nav2DRearrVectorEnv):
         self.min_abs_lin_speed, self.allow_sliding = float(min_abs_lin_speed), bool(allow_sliding)
         super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
                          num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps,
-                         start_holding=start_holding, distance=distance)
+                         start_holding=start_holding, distance=distance, top_down_map=top_down_map)
         self.task = "nav2drearrvel"
         self.action_spaces = [spaces.Box(-1.0, 1.0, (3,), np.float32) for _ in range(num_envs)]
         self.orig_action_spaces = self.action_spaces
@@ -1084,6 +1226,7 @@ class Nav2DSocialVectorEnv(Nav2DVectorEnv):
     _entries = ("hab_nav2d_social_step",)
     _follow_entry = None  # no shortest-path follower: see Nav2DVectorEnv.follower_actions
     _sensor_set = "social"
+    _map_task, _frame_keys = NAV2D_MAP_TASK_SOCIAL, ("head_rgb", "head_depth")
     _state_bytes = "hab_nav2d_social_state_bytes"
     _action_dtype, _action_text = torch.float32, "float32 device tensor of shape (N, 2)"
     measure_names = NAV2D_SOCIAL_MEASURES
@@ -1093,7 +1236,7 @@ class Nav2DSocialVectorEnv(Nav2DVectorEnv):
                  use_depth: bool = True, num_actions: int = 1, device="cuda", num_obstacles: int = 3, turn_angle: int = 1,
                  max_episode_steps: int = 500, max_turn_angle: int = 10, min_abs_lin_speed: float = 0.025, min_abs_ang_speed: int = 5,
                  allow_sliding: bool = True, person_speed: float = 0.125, person_always_visible: bool = False,
-                 distance: str = "euclidean"):
+                 distance: str = "euclidean", top_down_map=None):
         if nav2d_distance(distance, "Nav2DSocial") == "geodesic":
             raise _lib.HabError("Nav2DSocial: distance 'geodesic' is refused: the target moves every step, so it would need a field "
                                 "per step; the task has the Euclidean distance only")
@@ -1115,7 +1258,8 @@ class Nav2DSocialVectorEnv(Nav2DVectorEnv):
         self.person_speed, self.person_always_visible = float(person_speed), bool(person_always_visible)
         try:
             super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
-                             num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps)
+                             num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps,
+                             top_down_map=top_down_map)
         except _lib.HabError as err:
             # Nav2D-v0's own parameter refusals come first and stand; the one that is left where the spaces exist is the device's
             if torch.device(device).type != "cuda" and hasattr(self, "observation_spaces"):
@@ -1188,7 +1332,9 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
     Nav2DRearrVel-v0 (Nav2DRearrVelVectorEnv: that task under velocity and grip control), which reads Nav2DVel-v0's keys and
     start_holding and takes its image size like Nav2DRearr-v0.  A type starting with "nav2dsocial" -- tested before "nav2d" -- selects
     Nav2DSocial-v0 (Nav2DSocialVectorEnv: find and follow a walking person), which reads Nav2DVel-v0's keys, person_speed and
-    person_always_visible, takes its image size like Nav2DRearr-v0 and has the Euclidean distance mode only."""
+    person_always_visible, takes its image size like Nav2DRearr-v0 and has the Euclidean distance mode only.
+    `habitat.task.measurements.top_down_map`, where that key is present, becomes the `top_down_map` keyword of any Nav2D task with
+    whichever of map_resolution, visibility_dist, draw_fog and fov it holds (see Nav2DVectorEnv, Top-down map)."""
 
     def __init__(self, use_rgb: bool = True, use_depth: bool = True):
         self.use_rgb, self.use_depth = use_rgb, use_depth
@@ -1207,6 +1353,9 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
             kw = dict(seed=int(hab.seed), env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, num_actions=len(hab.task.actions),
                       device=device, num_obstacles=getattr(syn, "num_obstacles", 3), turn_angle=getattr(syn, "turn_angle", 10),
                       max_episode_steps=getattr(hab.environment, "max_episode_steps", 500), distance=distance)
+            tdm = getattr(getattr(hab.task, "measurements", {}), "top_down_map", None)
+            if tdm is not None:  # the measure: any of its keys may be missing (see nav2d_map_parameters)
+                kw.update(top_down_map={k: getattr(tdm, k) for k in NAV2D_MAP_DEFAULTS if getattr(tdm, k, None) is not None})
             make = Nav2DVectorEnv
             if task_type.startswith("nav2dsocial"):
                 use_rgb, use_depth = self.use_rgb and "head_rgb" in sens, self.use_depth and "head_depth" in sens

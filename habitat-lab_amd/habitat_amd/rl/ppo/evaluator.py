@@ -5,11 +5,14 @@ Same control flow as the reference: reset, then act -> step all (un-paused) envs
 `{"reward": episode return, **scalar infos}` under (scene_id, episode_id, eval count) -> pause an env once its NEXT episode has
 already been evaluated `evals_per_ep` times -> stop after `test_episode_count * evals_per_ep` episodes; finally average every
 statistic over the episodes and write `eval_reward/average_reward`, `eval_metrics/<k>` to the writer.  Sampling follows the
-reference (`deterministic=False`, :134-141).  Video / gfx-replay output is simulator-side and not reproduced: a non-empty
-`eval.video_option` is refused."""
+reference (`deterministic=False`, :134-141).  Video: `eval.video_option = ["disk"]` on envs that have `render_frames` (the Nav2D
+tasks with their top-down map, whose renderer is this project's and runs on the device) collects one frame per env per step and writes
+one file per finished episode (`write_episode_video`); "tensorboard", and any env without `render_frames`, is refused as before, since
+everything else is simulator-side.  gfx-replay output is not reproduced."""
 from __future__ import annotations
 
 import abc
+import os
 from collections import defaultdict
 from typing import Any, Dict, List
 
@@ -31,6 +34,47 @@ def extract_scalars_from_info(info: Dict[str, Any], prefix: str = "") -> Dict[st
         elif isinstance(v, (bool, int, float, np.integer, np.floating)) or (isinstance(v, np.ndarray) and v.size == 1):
             out[prefix + str(k)] = float(v)
     return out
+
+
+def write_episode_video(frames, video_dir: str, episode_id, checkpoint_index: int, measures: Dict[str, float], fps: int) -> str:
+    """Writes one episode's frames, a sequence of uint8 (H, W, 3) arrays, under the reference's name
+    `{video_dir}/episode={id}-ckpt={checkpoint_index}-{k}={v:.2f}-...` over the episode's measures (habitat's generate_video; ':' in
+    the id becomes '_'): an animated GIF at `fps` through PIL where PIL imports, else a .npy stack (T, H, W, 3).  No encoder for
+    mp4 is assumed.  Returns the path."""
+    os.makedirs(video_dir, exist_ok=True)
+    name = f"episode={str(episode_id).replace(':', '_')}-ckpt={checkpoint_index}" + "".join(f"-{k}={v:.2f}" for k, v in measures.items())
+    stack = np.stack(frames)
+    try:
+        from PIL import Image
+    except ImportError:
+        path = os.path.join(video_dir, name + ".npy")
+        np.save(path, stack)
+        return path
+    path = os.path.join(video_dir, name + ".gif")
+    images = [Image.fromarray(f) for f in stack]
+    # GIF times are hundredths of a second.  PIL stores a run of identical frames (a turn refused, a collision) as one image shown
+    # for the run's time, so the time of one frame goes into the file's comment and `read_episode_video` gives the run back.
+    frame_ms = max(10, int(round(100.0 / max(1, int(fps)))) * 10)
+    images[0].save(path, save_all=True, append_images=images[1:], duration=frame_ms, loop=0, optimize=False, disposal=1,
+                   comment=f"frame_ms={frame_ms}".encode())
+    return path
+
+
+def read_episode_video(path: str) -> np.ndarray:
+    """The frames `write_episode_video` wrote, uint8 (T, H, W, 3): one per step, an image that the GIF shows for k frame times k
+    times; a GIF's colours are those of its palette."""
+    if path.endswith(".npy"):
+        return np.load(path)
+    from PIL import Image, ImageSequence
+    with Image.open(path) as im:
+        comment = im.info.get("comment", b"")
+        comment = comment.decode() if isinstance(comment, bytes) else str(comment)
+        frame_ms = int(comment.split("frame_ms=")[1]) if "frame_ms=" in comment else 0
+        out = []
+        for f in ImageSequence.Iterator(im):
+            repeat = max(1, int(round(f.info.get("duration", frame_ms) / frame_ms))) if frame_ms else 1
+            out.extend([np.asarray(f.convert("RGB"))] * repeat)
+        return np.stack(out)
 
 
 def _episode_key(ep) -> tuple:
@@ -67,9 +111,14 @@ class HabitatEvaluator(Evaluator):
     def evaluate_agent(self, agent, envs, config, checkpoint_index, step_id, writer, device, obs_transforms, env_spec, rank0_keys):
         from habitat_amd.rl.ppo.ppo_trainer import batch_obs, host_env_action
         hb = config.habitat_baselines
-        if len(hb.eval.video_option) > 0:
+        video = len(hb.eval.video_option) > 0
+        if video and not (list(hb.eval.video_option) == ["disk"] and hasattr(envs, "render_frames")):
             raise _lib.HabError("eval.video_option: video generation needs the simulator's renderer and is not part of this path")
         observations = envs.post_step(envs.reset())
+        # per env the frames of its running episode; the frame after an ending step shows the next episode's first observation
+        rgb_frames = [[f] for f in envs.render_frames().cpu().numpy()] if video else None
+        episode_steps = [0] * envs.num_envs
+        self.last_video_files, self.last_episode_lengths = [], {}
         batch = apply_obs_transforms_batch(batch_obs(observations, device), obs_transforms)
         ac = agent.actor_critic
         action_shape, discrete_actions = get_action_space_info(ac.policy_action_space)
@@ -115,20 +164,33 @@ class HabitatEvaluator(Evaluator):
             not_done_masks = torch.tensor([[not done] for done in dones], dtype=torch.bool, device="cpu").repeat(1, *agent.masks_shape)
             current_episode_reward += torch.tensor(rewards_l, dtype=torch.float, device="cpu").unsqueeze(1)
             next_episodes_info = envs.current_episodes()
+            frames = envs.render_frames().cpu().numpy() if video else None
             envs_to_pause = []
             for i in range(envs.num_envs):
+                episode_steps[i] += 1
                 if ep_eval_count[_episode_key(next_episodes_info[i])] == evals_per_ep:
                     envs_to_pause.append(i)
                 if not not_done_masks[i].any().item():  # episode ended
                     episode_stats = {"reward": current_episode_reward[i].item()}
-                    episode_stats.update(extract_scalars_from_info({k: v for k, v in infos[i].items() if k not in rank0_keys}))
+                    measures = extract_scalars_from_info({k: v for k, v in infos[i].items() if k not in rank0_keys})
+                    episode_stats.update(measures)
                     current_episode_reward[i] = 0
                     k = _episode_key(current_episodes_info[i])
                     ep_eval_count[k] += 1
                     stats_episodes[(k, ep_eval_count[k])] = episode_stats
+                    self.last_episode_lengths[(k, ep_eval_count[k])] = episode_steps[i]
+                    episode_steps[i] = 0
+                    if video:
+                        self.last_video_files.append(write_episode_video(rgb_frames[i], hb.video_dir, k[1], checkpoint_index, measures,
+                                                                         hb.video_fps))
+                        rgb_frames[i] = []
+                if video:
+                    rgb_frames[i].append(frames[i])
             not_done_masks = not_done_masks.to(device=device)
-            (envs, test_recurrent_hidden_states, not_done_masks, current_episode_reward, prev_actions, batch, _) = pause_envs(
-                envs_to_pause, envs, test_recurrent_hidden_states, not_done_masks, current_episode_reward, prev_actions, batch)
+            if envs_to_pause:
+                episode_steps = [s for i, s in enumerate(episode_steps) if i not in envs_to_pause]
+            (envs, test_recurrent_hidden_states, not_done_masks, current_episode_reward, prev_actions, batch, rgb_frames) = pause_envs(
+                envs_to_pause, envs, test_recurrent_hidden_states, not_done_masks, current_episode_reward, prev_actions, batch, rgb_frames)
             if any(envs_to_pause):
                 ac.on_envs_pause(envs_to_pause)
         assert len(ep_eval_count) >= number_of_eval_episodes, f"Expected {number_of_eval_episodes} episodes, got {len(ep_eval_count)}."

@@ -29,7 +29,7 @@ from habitat_amd.common.env_factory import instantiate
 from habitat_amd.common.obs_transformers import (apply_obs_transforms_batch, apply_obs_transforms_obs_space,
                                                  get_active_obs_transforms)
 from habitat_amd.common.spaces import is_continuous_action_space
-from habitat_amd.config.default import read_write
+from habitat_amd.config.default import Config, read_write
 from habitat_amd.rl.ddppo.ddp_utils import (EXIT, StoreCounterPoller, get_distrib_size, init_distrib_slurm, load_resume_state, pin_rank_affinity, rank0_only,
                                             requeue_job, save_resume_state)
 from habitat_amd.rl.ppo.policy import VISUAL_FEATURES_KEY
@@ -597,6 +597,9 @@ class PPOTrainer(BaseRLTrainer):
         config = self._get_resume_state_config_or_new_config(ckpt_dict.get("config") if hb.eval.use_ckpt_config else None)
         with read_write(config):
             config.habitat.dataset.split = hb.eval.split
+            # as the reference's eval does: a video needs the map, so the measurement is added before the envs are built
+            if len(hb.eval.video_option) > 0 and getattr(config.habitat.task.measurements, "top_down_map", None) is None:
+                config.habitat.task.measurements["top_down_map"] = Config()
         self.device = torch.device("cuda", hb.torch_gpu_id) if torch.cuda.is_available() else torch.device("cpu")
         if self.device.type == "cuda":
             torch.cuda.set_device(self.device)

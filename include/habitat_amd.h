@@ -383,6 +383,61 @@ int hab_nav2d_social_step(void* state /*N,HAB_NAV2D_SOCIAL_STATE_BYTES*/, const 
                           int max_turn_steps, int stop_turn_steps, float min_abs_lin_speed, int allow_sliding, float person_speed,
                           int person_always_visible, int advance, hipStream_t stream);
 
+/* The top-down map of the Nav2D tasks with its fog of war, and the video frame (definition: habitat_amd/common/env_factory.py,
+ * Nav2DVectorEnv, "Top-down map"; bit-identical to tests/nav2d_map_reference.py; csrc/nav2d_map.hip).  `state` are records of any
+ * Nav2D task (stride >= HAB_NAV2D_STATE_BYTES, a multiple of 4), read through the words named above and never written.  Per env the
+ * caller owns `map` and `fog`, uint8 (S, S) (row 0 on top, S = the resolution in 16..512, cells of 8 / S metres), and a record `rec`
+ * of HAB_NAV2D_MAP_REC_BYTES, 4-byte aligned: the episode index, the episode's start, the position the trajectory was drawn up to
+ * and three zero words.  hab_nav2d_map_update is called after a step entry with the same mask and advance: for every env the mask
+ * selects (NULL = all) it begins a map -- clears both layers, writes the static codes, the start point and the first reveal -- at
+ * advance = 0 and where the ENDED word is set, and otherwise draws the segment from the record's position to the new one and reveals
+ * from there.  hab_nav2d_map_frame writes the frame (N, frame_h, frame_w, 3) uint8 of every env: left to right rgb (N,H,W,3) and
+ * depth (N,H,W,1), either may be NULL, upscaled by nearest neighbour to frame_h rows, then the map at frame_h x frame_h with the
+ * overlays; frame_w has to be hab_nav2d_map_frame_width's value.  It writes nothing else.  Refused with the invalid-argument code:
+ * S outside 16..512, an unknown task, NULL state, map, fog or rec (update) / frame (frame), a stride below a Nav2D-v0 record, N <= 0,
+ * num_obstacles outside 0..8, num_objects outside 1..8 for the object task, a vis_dist that is not positive and finite, an image
+ * pointer with H or W <= 0, frame_h <= 0 or a frame_w that is not the helper's. */
+#define HAB_NAV2D_MAP_REC_BYTES 32
+#define HAB_NAV2D_MAP_W_EPISODE 0
+#define HAB_NAV2D_MAP_W_START_X 1
+#define HAB_NAV2D_MAP_W_START_Y 2
+#define HAB_NAV2D_MAP_W_PREV_X 3
+#define HAB_NAV2D_MAP_W_PREV_Y 4
+#define HAB_NAV2D_MAP_W_ZERO 5       /* 5..7: zero */
+#define HAB_NAV2D_MAP_MIN_RESOLUTION 16
+#define HAB_NAV2D_MAP_MAX_RESOLUTION 512
+/* which words tell the targets: (GX, GY) / the objects of Nav2DObj-v0 / the goal place of the rearrangement tasks / none */
+#define HAB_NAV2D_MAP_TASK_GOAL 0
+#define HAB_NAV2D_MAP_TASK_OBJ 1
+#define HAB_NAV2D_MAP_TASK_REARR 2
+#define HAB_NAV2D_MAP_TASK_SOCIAL 3
+/* cell codes (habitat's where it has them) and the codes of the frame's overlays */
+#define HAB_NAV2D_MAP_OCCUPIED 0
+#define HAB_NAV2D_MAP_FREE 1
+#define HAB_NAV2D_MAP_START 4
+#define HAB_NAV2D_MAP_TARGET 6
+#define HAB_NAV2D_MAP_TRAJECTORY 10
+#define HAB_NAV2D_MAP_OBJECT 16
+#define HAB_NAV2D_MAP_CARRIED 20
+#define HAB_NAV2D_MAP_PERSON 21
+#define HAB_NAV2D_MAP_AGENT 22
+#define HAB_NAV2D_MAP_TICK 23
+/* code -> colour, r | g << 8 | b << 16, 32 entries; codes without a meaning are magenta */
+#define HAB_NAV2D_MAP_COLORS { \
+    0x00404040, 0x00C8C8C8, 0x00FF00FF, 0x00FF00FF, 0x00C83232, 0x00FF00FF, 0x002020FF, 0x00FF00FF, \
+    0x00FF00FF, 0x00FF00FF, 0x00D0A000, 0x00FF00FF, 0x00FF00FF, 0x00FF00FF, 0x00FF00FF, 0x00FF00FF, \
+    0x0020A0F0, 0x00FF00FF, 0x00FF00FF, 0x00FF00FF, 0x0000C8FF, 0x00C800C8, 0x0000A000, 0x00004000, \
+    0x00FF00FF, 0x00FF00FF, 0x00FF00FF, 0x00FF00FF, 0x00FF00FF, 0x00FF00FF, 0x00FF00FF, 0x00FF00FF }
+int hab_nav2d_map_rec_bytes(void);
+int hab_nav2d_map_update(const void* state, size_t state_stride_bytes, const float* dirs, const uint8_t* mask /*N*/, uint8_t* map /*N,S,S*/,
+                         uint8_t* fog /*N,S,S*/, void* rec /*N,HAB_NAV2D_MAP_REC_BYTES*/, int N, int S, int num_obstacles, int num_headings,
+                         int task, int num_objects, float vis_dist, int advance, hipStream_t stream);
+int hab_nav2d_map_frame_width(int frame_h, int H, int W, int has_rgb, int has_depth);
+int hab_nav2d_map_frame(const void* state, size_t state_stride_bytes, const float* dirs, const uint8_t* map /*N,S,S*/,
+                        const uint8_t* fog /*N,S,S*/, const uint8_t* rgb /*N,H,W,3*/, const float* depth /*N,H,W,1*/,
+                        uint8_t* frame /*N,frame_h,frame_w,3*/, int N, int S, int H, int W, int frame_h, int frame_w, int num_headings,
+                        int task, int draw_fog, hipStream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Observation transformers, fused: ResizeShortestEdge followed by CenterCropper
  * (habitat_baselines/common/obs_transformers.py:70-231; utils/common.py:481-557: F.interpolate(mode="area") -- "nearest" for
