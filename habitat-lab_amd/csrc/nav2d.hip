@@ -13,6 +13,8 @@
 // nav2d_rearr_geo_step_kernel: two fields per env, one of which moves with the object) is specified by
 // tests/nav2d_rearr_geo_reference.py.  Nav2DSocial-v0 (a person who walks the graph's shortest paths, to be found and followed under
 // velocity control; nav2d_social_step_kernel, nav2d_social_build_kernel) is specified by tests/nav2d_social_reference.py.
+// Nav2DExplore-v0 (area coverage: the reward is the cells seen for the first time; nav2d_explore_step_kernel, one workgroup per env
+// over the coverage layer, with the top-down map's rule from nav2d_seen.h) is specified by tests/nav2d_explore_reference.py.
 // The follower (nav2d_follow_kernel) and the pick-and-place oracle (nav2d_rearr_oracle_kernel) read the geodesic fields; their
 // specifications are tests/nav2d_follow_reference.py and tests/nav2d_rearr_oracle_reference.py.
 // What the tasks share is written once: the moves (discrete_move, vel_decode / vel_move, on a record or on a lane's MoveLane), the
@@ -24,6 +26,7 @@
 #include <cstddef>
 #include "hab_common.h"
 #include "../../include/habitat_amd.h"
+#include "nav2d_seen.h"
 
 #pragma clang fp contract(off)
 
@@ -1633,6 +1636,175 @@ nav2d_social_step_kernel(Nav2DSocialState* __restrict__ states, const float* __r
     }
 }
 
+// ---- Nav2DExplore-v0 (Nav2DExploreVectorEnv; specification: tests/nav2d_explore_reference.py) ----------------------------------------
+// One env of Nav2DExplore-v0: a Nav2D-v0 record (no goal: gx, gy, d_prev and d_start are zero), then the start pose the gps / compass
+// sensors refer to, the unoccupied cells of the episode's world, the cells seen so far and the cells the last step saw first.
+struct Nav2DExploreState {
+    Nav2DState base;
+    float sx, sy;
+    int32_t h0, free_cells, seen_cells, last_new;
+};
+static_assert(sizeof(Nav2DExploreState) == HAB_NAV2D_EXPLORE_STATE_BYTES && offsetof(Nav2DExploreState, base) == 0, "Nav2DExploreState layout");
+static_assert(offsetof(Nav2DExploreState, sx) == 4 * HAB_NAV2D_EXPLORE_W_START_X && offsetof(Nav2DExploreState, sy) == 4 * HAB_NAV2D_EXPLORE_W_START_Y,
+              "Nav2DExploreState layout");
+static_assert(offsetof(Nav2DExploreState, h0) == 4 * HAB_NAV2D_EXPLORE_W_START_HEADING &&
+              offsetof(Nav2DExploreState, free_cells) == 4 * HAB_NAV2D_EXPLORE_W_FREE_CELLS, "Nav2DExploreState layout");
+static_assert(offsetof(Nav2DExploreState, seen_cells) == 4 * HAB_NAV2D_EXPLORE_W_SEEN_CELLS &&
+              offsetof(Nav2DExploreState, last_new) == 4 * HAB_NAV2D_EXPLORE_W_LAST_NEW, "Nav2DExploreState layout");
+
+constexpr int EXPLORE_THREADS = 1024;  // one workgroup per env has to fill a CU by itself, as the map's update
+constexpr int EXPLORE_WAVES = EXPLORE_THREADS / 64;
+
+// The pose and the rectangles of the record as the sight rule reads them.
+__device__ inline void explore_load_sight(nav2d_seen::Sight& e, const Nav2DState& s, const float* __restrict__ dirs, int K) {
+    e.px = s.px;
+    e.py = s.py;
+    e.c = dirs[2 * s.heading];
+    e.s = dirs[2 * s.heading + 1];
+    for (int k = 0; k < K; ++k) nav2d_seen::set_rect(e, k, s.rect[k][0], s.rect[k][1], s.rect[k][2], s.rect[k][3]);
+}
+
+// The sum of `v` over the workgroup, on thread 0: the waves by lane exchange, then the waves' sums through `part`.  Integer, so exact
+// and independent of the order.  Ends behind a barrier, so that another sum may follow.
+__device__ inline int explore_block_sum(int v, int* part) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int total = 0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < EXPLORE_WAVES; ++w) total += part[w];
+    __syncthreads();
+    return total;
+}
+
+// The range of cell indices along one axis whose centres (i + 0.5) * cell can lie within `vis` of the coordinate p, widened by a
+// whole cell on either side.  The rule accepts a centre only if fl(dx * dx) <= fl(vis * vis), so |dx| exceeds vis by a few units
+// in the last place at the most, and this arithmetic (inv = G / 8 is 1 / cell to one rounding) is off by less than a thousandth of a
+// cell: the margin keeps every cell the rule can accept, so the restricted sweep writes what the full one would.
+__device__ inline void explore_axis_range(float p, float vis, float inv, int G, int& lo, int& hi) {
+    const float top = (float)(G - 1);
+    lo = (int)fminf(fmaxf(floorf((p - vis) * inv) - 1.0f, 0.0f), top);
+    hi = (int)fminf(fmaxf(floorf((p + vis) * inv) + 1.0f, 0.0f), top);
+}
+
+// One sweep of an env's layer by the workgroup; a thread takes groups of four consecutive cells (one 32-bit word where `vec`).
+// BEGIN: the layer is cleared, every cell is visited, `n_free` counts the unoccupied centres and `n_new` the cells of the first
+// reveal.  Otherwise only the words of the rows, and in them the columns, of the visibility disc's bounding box are visited, a word
+// is written where it changed, and `n_new` counts the cells that turned from 0 to 1.
+template <bool BEGIN>
+__device__ inline void explore_sweep(uint8_t* __restrict__ layer, const nav2d_seen::Sight& e, int G, int K, float cell, float vis,
+                                     float vis2, int vec, int& n_new, int& n_free) {
+    const int total = G * G;
+    int g_lo = 0, g_hi = (total + 3) >> 2, c_lo = 0, c_hi = G - 1;
+    if constexpr (!BEGIN) {
+        const float inv = (float)G * 0.125f;
+        int j_lo, j_hi;  // y indices: row r has the y index G - 1 - r
+        explore_axis_range(e.px, vis, inv, G, c_lo, c_hi);
+        explore_axis_range(e.py, vis, inv, G, j_lo, j_hi);
+        g_lo = ((G - 1 - j_hi) * G) >> 2;
+        g_hi = ((G - j_lo) * G + 3) >> 2;
+    }
+    for (int g = g_lo + (int)threadIdx.x; g < g_hi; g += EXPLORE_THREADS) {
+        const int i0 = g * 4, n = min(4, total - i0);
+        uint32_t fv = 0;
+        if constexpr (!BEGIN) {
+            if (vec) fv = ((const uint32_t*)layer)[g];
+            else
+                for (int j = 0; j < n; ++j) fv |= (uint32_t)layer[i0 + j] << (8 * j);
+        }
+        int rr = i0 / G, cc = i0 - rr * G;
+        uint32_t fo = fv;
+        for (int j = 0; j < n; ++j) {
+            if (BEGIN || (!((fv >> (8 * j)) & 255u) && cc >= c_lo && cc <= c_hi)) {
+                const float x = ((float)cc + nav2d_seen::HALF) * cell, y = ((float)(G - 1 - rr) + nav2d_seen::HALF) * cell;
+                if constexpr (BEGIN) n_free += nav2d_seen::occupied(x, y, e, K) ? 0 : 1;
+                if (nav2d_seen::seen_from(x, y, e, K, vis2)) { fo |= 1u << (8 * j); n_new += 1; }
+            }
+            if (++cc == G) { cc = 0; ++rr; }
+        }
+        if (BEGIN || fo != fv) {
+            if (vec) ((uint32_t*)layer)[g] = fo;
+            else
+                for (int j = 0; j < n; ++j) layer[i0 + j] = (uint8_t)(fo >> (8 * j));
+        }
+    }
+}
+
+// One workgroup per env, selected by `mask` (NULL: all): an env must not be split, because every thread reads the pose that thread 0
+// advances.  Thread 0 moves the agent in the record and puts pose and rectangles into LDS; behind the barrier all threads reveal from
+// the new pose and count the new cells; thread 0 ends the step and, where the episode ends, generates the next world; behind another
+// barrier the workgroup clears the layer, counts the free cells and does the first reveal.  advance = 0: episode 0, then that last part.
+__global__ void __launch_bounds__(EXPLORE_THREADS)
+nav2d_explore_step_kernel(Nav2DExploreState* __restrict__ states, const float* __restrict__ dirs, const float* __restrict__ ctab,
+                          const int64_t* __restrict__ actions, const uint8_t* __restrict__ mask, float* __restrict__ gps,
+                          float* __restrict__ compass, uint8_t* __restrict__ coverage, float* __restrict__ reward,
+                          uint8_t* __restrict__ not_done, float* __restrict__ sums, uint32_t seed, uint32_t env_offset, int N, int K, int nh,
+                          int max_steps, int G, float cell, float vis, float vis2, float rc, int advance, int vec) {
+    const int n = blockIdx.x, tid = threadIdx.x;
+    if (mask && !mask[n]) return;
+    Nav2DExploreState& o = states[n];
+    Nav2DState& s = o.base;
+    const uint32_t env = env_offset + (uint32_t)n;
+    uint8_t* layer = coverage + (size_t)n * G * G;
+    __shared__ nav2d_seen::Sight e;
+    __shared__ int part[EXPLORE_WAVES];
+    __shared__ int ended;
+    if (tid == 0) {
+        if (!advance) {
+            first_episode<false>(s, seed, env, K, nh);
+            s.gx = s.gy = 0.0f;
+            s.d_start = s.d_prev = 0.0f;
+            o.last_new = 0;
+        } else {
+            // anything outside 0..3 moves nothing (the host-side entry points refuse it)
+            discrete_move(s, actions[n], dirs, nh, [&](float x, float y) { return is_free(x, y, s, K); });
+        }
+        explore_load_sight(e, s, dirs, K);
+    }
+    __syncthreads();
+    bool begin = !advance;  // uniform over the workgroup, here and after the step
+    int n_new = 0, n_free = 0;
+    if (advance) {
+        explore_sweep<false>(layer, e, G, K, cell, vis, vis2, vec, n_new, n_free);
+        const int fresh = explore_block_sum(n_new, part);
+        if (tid == 0) {
+            reward[n] = -0.01f + rc * (float)fresh;
+            o.seen_cells += fresh;
+            o.last_new = fresh;
+            s.steps += 1;
+            const bool done = actions[n] == 0 || s.steps >= max_steps;
+            not_done[n] = done ? 0 : 1;
+            s.ended = done ? 1 : 0;
+            if (done) {
+                close_episode<false>(s, __fdiv_rn((float)o.seen_cells, (float)o.free_cells), (cell * cell) * (float)o.seen_cells,
+                                     (float)s.collisions, (float)s.steps, sums, seed, env, n, N, K, nh);
+                explore_load_sight(e, s, dirs, K);
+            }
+            ended = done ? 1 : 0;
+        }
+        __syncthreads();
+        begin = ended != 0;
+    }
+    if (begin) {
+        n_new = n_free = 0;
+        explore_sweep<true>(layer, e, G, K, cell, vis, vis2, vec, n_new, n_free);
+        const int first = explore_block_sum(n_new, part), free_cells = explore_block_sum(n_free, part);
+        if (tid == 0) {
+            o.sx = s.px; o.sy = s.py; o.h0 = s.heading;
+            o.free_cells = free_cells;
+            o.seen_cells = first;
+        }
+    }
+    if (tid == 0) {  // Nav2DObj-v0's gps and compass
+        if (gps) {
+            const float c = dirs[2 * o.h0], sn = dirs[2 * o.h0 + 1];
+            to_frame(s.px - o.sx, s.py - o.sy, c, sn, gps[2 * n + 0], gps[2 * n + 1]);
+        }
+        if (compass) compass[n] = ctab[(s.heading - o.h0 + nh) % nh];
+    }
+}
+
 // ---- rendering ---------------------------------------------------------------------------------------------------------------
 // Entry / exit of the ray p + t d through [lo, hi] on one axis.
 __device__ inline void slab(float lo, float hi, float p, float d, float inv, float& tmin, float& tmax) {
@@ -1722,7 +1894,8 @@ __device__ inline void sweep_dwords(T* __restrict__ img, int s_px, int e_px, int
 // the GOAL form, nearer than whatever the column hit, the cylinder included.  No semantic image: four column arrays.
 // Render::SOCIAL (Nav2DSocial-v0): `states` are Nav2DSocialState records; the person is one cylinder of category 0's colour, geometry
 // for depth and rgb alike, and there is no goal marker: nothing is drawn in rgb only.  No semantic image: four column arrays.
-enum class Render { GOAL, OBJ, REARR, SOCIAL };
+// Render::EXPLORE (Nav2DExplore-v0): `states` are Nav2DExploreState records; Nav2D-v0's geometry with no cylinder and no goal marker.
+enum class Render { GOAL, OBJ, REARR, SOCIAL, EXPLORE };
 template <Render MODE>
 __global__ void __launch_bounds__(RENDER_THREADS)
 nav2d_render_kernel(const void* __restrict__ states, const float* __restrict__ ray, const float* __restrict__ col_cos,
@@ -1737,12 +1910,13 @@ nav2d_render_kernel(const void* __restrict__ states, const float* __restrict__ r
     float* c_zr = c_dw + P;
     uint32_t* c_cw = reinterpret_cast<uint32_t*>(c_zr + P);
     int32_t* c_sem = reinterpret_cast<int32_t*>(c_cw + P);  // OBJ only
-    constexpr bool OBJ = MODE == Render::OBJ, REARR = MODE == Render::REARR, SOCIAL = MODE == Render::SOCIAL;
+    constexpr bool OBJ = MODE == Render::OBJ, REARR = MODE == Render::REARR, SOCIAL = MODE == Render::SOCIAL, EXPLORE = MODE == Render::EXPLORE;
     RowRec* row = reinterpret_cast<RowRec*>(lds + P) + (OBJ ? P / 4 : 0);
     const Nav2DObjState* os = OBJ ? static_cast<const Nav2DObjState*>(states) + n : nullptr;
     const Nav2DRearrState* rs = REARR ? static_cast<const Nav2DRearrState*>(states) + n : nullptr;
     const Nav2DSocialState* ss = SOCIAL ? static_cast<const Nav2DSocialState*>(states) + n : nullptr;
-    const Nav2DState& s = OBJ ? os->base : REARR ? rs->base : SOCIAL ? ss->base : static_cast<const Nav2DState*>(states)[n];
+    const Nav2DExploreState* es = EXPLORE ? static_cast<const Nav2DExploreState*>(states) + n : nullptr;
+    const Nav2DState& s = OBJ ? os->base : REARR ? rs->base : SOCIAL ? ss->base : EXPLORE ? es->base : static_cast<const Nav2DState*>(states)[n];
     // the cylinders of this env: Nav2DObj-v0's M objects, Nav2DRearr-v0's object unless it is held, Nav2DSocial-v0's person
     const float (*cyl)[2] = OBJ ? os->obj : REARR ? reinterpret_cast<const float (*)[2]>(&rs->ox) : SOCIAL ? ss->obj : nullptr;
     const int cyls = OBJ ? M : REARR ? (rs->holding ? 0 : 1) : SOCIAL ? 1 : 0;
@@ -1778,7 +1952,7 @@ nav2d_render_kernel(const void* __restrict__ states, const float* __restrict__ r
         const float z_wall = t * cf;
         float z_rgb = z_wall;
         bool marker = false;
-        if constexpr (!OBJ && !SOCIAL) {
+        if constexpr (!OBJ && !SOCIAL && !EXPLORE) {
             const float ox = px - s.gx, oy = py - s.gy;
             const float b = ox * dx + oy * dy;
             const float c = (ox * ox + oy * oy) - 0.2f * 0.2f;
@@ -2264,4 +2438,29 @@ extern "C" int hab_nav2d_social_step(void* state, const float* dirs, const float
     nav2d_social_build_kernel<<<N, 64, 0, stream>>>((Nav2DSocialState*)state, mask, advance ? 1 : 0, num_obstacles);
     HAB_LAUNCH_CHECK();
     return launch_render<Render::SOCIAL>(a, 0);
+}
+
+// Nav2DExplore-v0: the step of one workgroup per env over the coverage layer, then the render without a marker.
+extern "C" int hab_nav2d_explore_state_bytes(void) { return (int)sizeof(Nav2DExploreState); }
+
+extern "C" int hab_nav2d_explore_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                                      const int64_t* actions, const uint8_t* mask, uint8_t* rgb, float* depth, float* gps, float* compass,
+                                      const float* compass_table, uint8_t* coverage, float* reward, uint8_t* not_done, float* measure_sums,
+                                      uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings,
+                                      int max_episode_steps, int G, float visibility_dist, float rc, int advance, hipStream_t stream) {
+    const StepArgs a{state, nullptr, dirs, ray, col_cos, tanv, actions, mask, rgb, depth, nullptr, nullptr, reward, not_done, measure_sums,
+                     seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream};
+    const int code = check_step_args(a, false, sizeof(Nav2DExploreState));
+    if (code != HAB_OK) return code;
+    if (((uintptr_t)state & 3) || !coverage || (compass && !compass_table)) return HAB_ERR_ARG;
+    if (G < HAB_NAV2D_EXPLORE_MIN_RESOLUTION || G > HAB_NAV2D_EXPLORE_MAX_RESOLUTION) return HAB_ERR_ARG;
+    if (!(visibility_dist > 0.f) || !(visibility_dist <= 3.0e38f) || !(rc >= 0.f) || !(rc <= 3.0e38f)) return HAB_ERR_ARG;
+    const float cell = ARENA / (float)G;
+    const int vec = (G * G) % 4 == 0 && !((uintptr_t)coverage & 3);
+    nav2d_explore_step_kernel<<<N, EXPLORE_THREADS, 0, stream>>>((Nav2DExploreState*)state, dirs, compass_table, actions, mask, gps, compass,
+                                                                 coverage, reward, not_done, measure_sums, seed, env_offset, N, num_obstacles,
+                                                                 num_headings, max_episode_steps, G, cell, visibility_dist,
+                                                                 visibility_dist * visibility_dist, rc, advance, vec);
+    HAB_LAUNCH_CHECK();
+    return launch_render<Render::EXPLORE>(a, 0);
 }

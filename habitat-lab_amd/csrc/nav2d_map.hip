@@ -6,6 +6,7 @@
 #include <cstddef>
 #include "hab_common.h"
 #include "../../include/habitat_amd.h"
+#include "nav2d_seen.h"
 
 #pragma clang fp contract(off)
 
@@ -13,12 +14,21 @@ using namespace hab;
 
 namespace nav2d_map {
 
-constexpr int MAX_K = HAB_NAV2D_MAX_OBSTACLES, MAX_M = HAB_NAV2D_MAX_OBJECTS;
+// the pose and rectangles of an env, the occupancy test and the fog of war's rule, shared with Nav2DExplore-v0's coverage layer
+using nav2d_seen::HALF;
+using nav2d_seen::load_pose_and_rects;
+using nav2d_seen::MAX_K;
+using nav2d_seen::occupied;
+using nav2d_seen::seen_from;
+using nav2d_seen::Sight;
+using nav2d_seen::word_f;
+
+constexpr int MAX_M = HAB_NAV2D_MAX_OBJECTS;
 constexpr int THREADS = 256;          // the frame kernel's workgroup
 constexpr int UPDATE_THREADS = 1024;  // the update's: one workgroup per env has to fill a CU by itself
-constexpr float ARENA = 8.0f, HALF = 0.5f;
+constexpr float ARENA = 8.0f;
 // squared radii: each is one fp32 product of the rounded radius with itself
-constexpr float START_R2 = 0.15f * 0.15f, GOAL_R2 = 0.2f * 0.2f, OBJ_R2 = 0.3f * 0.3f, NEAR_R2 = 0.25f * 0.25f;
+constexpr float START_R2 = 0.15f * 0.15f, GOAL_R2 = 0.2f * 0.2f, OBJ_R2 = 0.3f * 0.3f;
 constexpr float AGENT_R2 = 0.2f * 0.2f, TICK_R2 = 0.08f * 0.08f;
 constexpr float TRAJ_W = 0.75f, TICK_LEN = 0.45f;
 constexpr int REC_WORDS = HAB_NAV2D_MAP_REC_BYTES / 4;
@@ -26,17 +36,11 @@ static_assert(REC_WORDS == 8 && HAB_NAV2D_MAP_W_ZERO + 3 == REC_WORDS, "map reco
 
 __constant__ uint32_t COLORS[32] = HAB_NAV2D_MAP_COLORS;
 
-__device__ inline float word_f(const int32_t* w, int i) { return __int_as_float(w[i]); }
-
 // A disc that the static layer marks with `code`.
 struct Marker { float x, y, r2; int code; };
 
-// What one workgroup knows of its env: the pose, the raw rectangles for the occupancy test and in the centre / half-extent form of
-// the separating-axis test, and the task's markers.
-struct World {
-    float px, py, c, s;
-    float x0[MAX_K], y0[MAX_K], x1[MAX_K], y1[MAX_K];
-    float cx[MAX_K], ex[MAX_K], cy[MAX_K], ey[MAX_K];
+// What one workgroup knows of its env: the pose and the raw rectangles (Sight), and the task's markers.
+struct World : Sight {
     Marker marker[MAX_M];
     int markers;
 };
@@ -64,21 +68,8 @@ __device__ inline int read_markers<HAB_NAV2D_MAP_TASK_REARR>(const int32_t* w, i
 }
 template <>
 __device__ inline int read_markers<HAB_NAV2D_MAP_TASK_SOCIAL>(const int32_t*, int, Marker*) { return 0; }
-
-__device__ inline void load_pose_and_rects(World& e, const int32_t* w, const float* __restrict__ dirs, int K) {
-    e.px = word_f(w, HAB_NAV2D_W_PX);
-    e.py = word_f(w, HAB_NAV2D_W_PY);
-    const int h = w[HAB_NAV2D_W_HEADING];
-    e.c = dirs[2 * h];
-    e.s = dirs[2 * h + 1];
-    for (int k = 0; k < K; ++k) {
-        const float lx = word_f(w, HAB_NAV2D_W_RECTS + 4 * k), ly = word_f(w, HAB_NAV2D_W_RECTS + 4 * k + 1);
-        const float hx = word_f(w, HAB_NAV2D_W_RECTS + 4 * k + 2), hy = word_f(w, HAB_NAV2D_W_RECTS + 4 * k + 3);
-        e.x0[k] = lx; e.y0[k] = ly; e.x1[k] = hx; e.y1[k] = hy;
-        e.cx[k] = (lx + hx) * HALF; e.ex[k] = (hx - lx) * HALF;
-        e.cy[k] = (ly + hy) * HALF; e.ey[k] = (hy - ly) * HALF;
-    }
-}
+template <>
+__device__ inline int read_markers<HAB_NAV2D_MAP_TASK_EXPLORE>(const int32_t*, int, Marker*) { return 0; }
 
 __device__ inline bool in_disc(float x, float y, float cx, float cy, float r2) {
     const float dx = x - cx, dy = y - cy;
@@ -100,24 +91,6 @@ __device__ inline bool near_segment(float x, float y, const Segment& g) {
     if (in_disc(x, y, g.bx, g.by, g.w2)) return true;
     const float dot = ex * g.sx + ey * g.sy, cross = g.sx * ey - g.sy * ex;
     return g.len2 > 0.f && dot >= 0.f && dot <= g.len2 && cross * cross <= g.w2len;
-}
-
-__device__ inline bool occupied(float x, float y, const World& e, int K) {
-    for (int k = 0; k < K; ++k)
-        if (x > e.x0[k] && x < e.x1[k] && y > e.y0[k] && y < e.y1[k]) return true;
-    return false;
-}
-
-// The geodesic mode's `visible` on the raw rectangles: the segment agent -> (x, y) meets no open rectangle.
-__device__ inline bool sees(float x, float y, const World& e, int K) {
-    const float hx = (e.px + x) * HALF, sx = (x - e.px) * HALF;
-    const float hy = (e.py + y) * HALF, sy = (y - e.py) * HALF;
-    const float asx = fabsf(sx), asy = fabsf(sy);
-    for (int k = 0; k < K; ++k) {
-        const float mx = hx - e.cx[k], my = hy - e.cy[k];
-        if (fabsf(mx) < e.ex[k] + asx && fabsf(my) < e.ey[k] + asy && fabsf(sx * my - sy * mx) < e.ex[k] * asy + e.ey[k] * asx) return false;
-    }
-    return true;
 }
 
 __device__ inline int static_code(float x, float y, const World& e, int K, float sx, float sy) {
@@ -180,14 +153,7 @@ nav2d_map_update_kernel(const char* __restrict__ states, size_t stride, const fl
             int code = begin ? static_code(x, y, e, K, px, py) : (int)((mv >> (8 * j)) & 255u);
             uint32_t seen = begin ? 0u : ((fv >> (8 * j)) & 255u);
             if (code != HAB_NAV2D_MAP_START && code != HAB_NAV2D_MAP_TARGET && near_segment(x, y, seg)) code = HAB_NAV2D_MAP_TRAJECTORY;
-            if (!seen) {
-                const float dx = x - px, dy = y - py;
-                const float d2 = dx * dx + dy * dy;
-                if (d2 <= vis2) {
-                    const float dot = dx * e.c + dy * e.s, cross = e.c * dy - e.s * dx;
-                    if ((d2 <= NEAR_R2 || (dot > 0.f && fabsf(cross) <= dot)) && !occupied(x, y, e, K) && sees(x, y, e, K)) seen = 1u;
-                }
-            }
+            if (!seen && seen_from(x, y, e, K, vis2)) seen = 1u;
             mo |= (uint32_t)code << (8 * j);
             fo |= seen << (8 * j);
             if (++cc == S) { cc = 0; ++rr; }
@@ -274,7 +240,7 @@ nav2d_map_frame_kernel(const char* __restrict__ states, size_t stride, const flo
     }
 }
 
-static bool task_ok(int task) { return task >= HAB_NAV2D_MAP_TASK_GOAL && task <= HAB_NAV2D_MAP_TASK_SOCIAL; }
+static bool task_ok(int task) { return task >= HAB_NAV2D_MAP_TASK_GOAL && task <= HAB_NAV2D_MAP_TASK_EXPLORE; }
 static bool resolution_ok(int S) { return S >= HAB_NAV2D_MAP_MIN_RESOLUTION && S <= HAB_NAV2D_MAP_MAX_RESOLUTION; }
 static bool records_ok(const void* state, size_t stride, int N) {
     return state && !((uintptr_t)state & 3) && stride >= HAB_NAV2D_STATE_BYTES && !(stride & 3) && N > 0;
@@ -282,7 +248,8 @@ static bool records_ok(const void* state, size_t stride, int N) {
 // the smallest record that holds the words the task's reader and overlays name
 static size_t task_bytes(int task) {
     return task == HAB_NAV2D_MAP_TASK_OBJ ? HAB_NAV2D_OBJ_STATE_BYTES : task == HAB_NAV2D_MAP_TASK_REARR ? HAB_NAV2D_REARR_STATE_BYTES
-         : task == HAB_NAV2D_MAP_TASK_SOCIAL ? HAB_NAV2D_SOCIAL_STATE_BYTES : HAB_NAV2D_STATE_BYTES;
+         : task == HAB_NAV2D_MAP_TASK_SOCIAL ? HAB_NAV2D_SOCIAL_STATE_BYTES
+         : task == HAB_NAV2D_MAP_TASK_EXPLORE ? HAB_NAV2D_EXPLORE_STATE_BYTES : HAB_NAV2D_STATE_BYTES;
 }
 
 }  // namespace nav2d_map
@@ -311,6 +278,7 @@ extern "C" int hab_nav2d_map_update(const void* state, size_t state_stride_bytes
         HAB_MAP_UPDATE(HAB_NAV2D_MAP_TASK_OBJ)
         HAB_MAP_UPDATE(HAB_NAV2D_MAP_TASK_REARR)
         HAB_MAP_UPDATE(HAB_NAV2D_MAP_TASK_SOCIAL)
+        HAB_MAP_UPDATE(HAB_NAV2D_MAP_TASK_EXPLORE)
     }
 #undef HAB_MAP_UPDATE
     HAB_LAUNCH_CHECK();
@@ -353,6 +321,7 @@ extern "C" int hab_nav2d_map_frame(const void* state, size_t state_stride_bytes,
         HAB_MAP_FRAME(HAB_NAV2D_MAP_TASK_OBJ)
         HAB_MAP_FRAME(HAB_NAV2D_MAP_TASK_REARR)
         HAB_MAP_FRAME(HAB_NAV2D_MAP_TASK_SOCIAL)
+        HAB_MAP_FRAME(HAB_NAV2D_MAP_TASK_EXPLORE)
     }
 #undef HAB_MAP_FRAME
     HAB_LAUNCH_CHECK();

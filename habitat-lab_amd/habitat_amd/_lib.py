@@ -89,6 +89,8 @@ SIGNATURES = {
     "hab_nav2d_rearr_oracle": (c_int, [vp, c_size_t] + [vp] * 6 + [c_int] * 3 + [vp]),
     "hab_nav2d_social_state_bytes": (c_int, []),
     "hab_nav2d_social_step": (c_int, [vp] * 14 + [c_uint32, c_uint32] + [c_int] * 8 + [c_float, c_int, c_float, c_int, c_int, vp]),
+    "hab_nav2d_explore_state_bytes": (c_int, []),
+    "hab_nav2d_explore_step": (c_int, [vp] * 16 + [c_uint32, c_uint32] + [c_int] * 7 + [c_float, c_float, c_int, vp]),
     "hab_nav2d_map_rec_bytes": (c_int, []),
     "hab_nav2d_map_update": (c_int, [vp, c_size_t] + [vp] * 5 + [c_int] * 6 + [c_float, c_int, vp]),
     "hab_nav2d_map_frame_width": (c_int, [c_int] * 5),

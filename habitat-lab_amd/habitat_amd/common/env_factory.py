@@ -64,6 +64,9 @@ class SyntheticVectorEnv:
         elif task == "social":  # sensor set of Nav2DSocial-v0: the head camera and two raw 1-D sensors, no goal sensor
             d["person_sensor"] = spaces.Box(fmin, fmax, (2,), np.float32)
             d["person_visible"] = spaces.Box(0.0, 1.0, (1,), np.float32)
+        elif task == "explore":  # sensor set of Nav2DExplore-v0: the camera, then gps and compass; no goal input at all
+            d["gps"] = spaces.Box(fmin, fmax, (2,), np.float32)
+            d["compass"] = spaces.Box(-np.pi, np.pi, (1,), np.float32)
         elif task == "objectnav":  # sensor set of the ObjectNav experiments (rgb, depth, semantic + objectgoal, compass, gps)
             d["semantic"] = spaces.Box(0, NUM_SEMANTIC_IDS - 1, (height, width, 1), np.int32)
             d["objectgoal"] = spaces.Box(0, NUM_OBJECT_CATEGORIES - 1, (1,), np.int64)
@@ -82,7 +85,7 @@ class SyntheticVectorEnv:
         self._since = torch.zeros(num_envs, dtype=torch.int64, device=dev)
         self._rgb = torch.zeros(num_envs, height, width, 3, dtype=torch.uint8, device=dev) if use_rgb else None
         self._depth = torch.zeros(num_envs, height, width, 1, device=dev) if use_depth else None
-        self._goal = torch.zeros(num_envs, 2, device=dev) if task not in ("objectnav", "rearrange", "social") else None
+        self._goal = torch.zeros(num_envs, 2, device=dev) if task not in ("objectnav", "rearrange", "social", "explore") else None
         self._obj = {}
         if task == "objectnav":
             self._obj = dict(semantic=torch.zeros(num_envs, height, width, 1, dtype=torch.int32, device=dev),
@@ -91,6 +94,8 @@ class SyntheticVectorEnv:
         elif task == "rearrange":
             self._obj = dict(obj_start_sensor=torch.zeros(num_envs, 2, device=dev), obj_goal_sensor=torch.zeros(num_envs, 2, device=dev),
                              is_holding=torch.zeros(num_envs, 1, device=dev))
+        elif task == "explore":
+            self._obj = dict(gps=torch.zeros(num_envs, 2, device=dev), compass=torch.zeros(num_envs, 1, device=dev))
         elif task == "social":
             self._obj = dict(person_sensor=torch.zeros(num_envs, 2, device=dev), person_visible=torch.zeros(num_envs, 1, device=dev))
         self._rew = torch.zeros(num_envs, device=dev)
@@ -238,7 +243,7 @@ NAV2D_DISTANCES = ("euclidean", "geodesic")
 # the top-down map (include/habitat_amd.h: HAB_NAV2D_MAP_*): the resolution's range, which words of a task's record tell its targets,
 # the cell codes and the colour of every code, rows (r, g, b) of HAB_NAV2D_MAP_COLORS
 NAV2D_MAP_MIN_RESOLUTION, NAV2D_MAP_MAX_RESOLUTION = 16, 512
-NAV2D_MAP_TASK_GOAL, NAV2D_MAP_TASK_OBJ, NAV2D_MAP_TASK_REARR, NAV2D_MAP_TASK_SOCIAL = 0, 1, 2, 3
+NAV2D_MAP_TASK_GOAL, NAV2D_MAP_TASK_OBJ, NAV2D_MAP_TASK_REARR, NAV2D_MAP_TASK_SOCIAL, NAV2D_MAP_TASK_EXPLORE = 0, 1, 2, 3, 4
 NAV2D_MAP_CODES = dict(occupied=0, free=1, start=4, target=6, trajectory=10, object=16, carried=20, person=21, agent=22, tick=23)
 NAV2D_MAP_COLORS = np.full((32, 3), (255, 0, 255), dtype=np.uint8)
 for _code, _rgb in (("occupied", (64, 64, 64)), ("free", (200, 200, 200)), ("start", (50, 50, 200)), ("target", (255, 32, 32)),
@@ -377,7 +382,7 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
       * Static layer, written when an episode begins: 0 where the centre is strictly inside a raw rectangle, else 1; then 16 in a
         disc of 0.3 m at every object of Nav2DObj-v0 that is not of the target category; then 6 over that: a disc of 0.2 m at
         (GX, GY) (Nav2D-v0, Nav2DVel-v0) or at the goal place (the rearrangement tasks), discs of 0.3 m at the objects of the
-        target category (Nav2DObj-v0), nothing for Nav2DSocial-v0; then 4 over all in a disc of 0.15 m at the start.  The
+        target category (Nav2DObj-v0), nothing for Nav2DSocial-v0 and Nav2DExplore-v0; then 4 over all in a disc of 0.15 m at the start.  The
         rearrangement object and the person move, so they are in the frame, not in the map.
       * Trajectory, code 10, over every code but 4 and 6.  A cell is on the segment a -> b when its centre is within
         w = 0.75 * cell of it: e = centre - a, s = b - a, len2 = s.s; hit iff e.e <= w * w, or the same at b, or len2 > 0 and
@@ -1316,6 +1321,128 @@ class Nav2DSocialVectorEnv(Nav2DVectorEnv):
         raise _lib.HabError("Nav2DSocial: the task has no pointgoal sensor; use step_into_obs with the task's sensor rows")
 
 
+NAV2D_EXPLORE_MEASURES = ("coverage", "area_seen", "collisions", "num_steps")
+NAV2D_EXPLORE_SENSORS = ("rgb", "depth", "gps", "compass")
+NAV2D_EXPLORE_MIN_RESOLUTION, NAV2D_EXPLORE_MAX_RESOLUTION = 16, 512  # HAB_NAV2D_EXPLORE_MIN_RESOLUTION, _MAX_RESOLUTION
+
+
+def nav2d_explore_parameters(coverage_resolution, visibility_dist, coverage_reward, who: str = "Nav2DExplore"):
+    """Checks the three `habitat.synthetic` keys of Nav2DExplore-v0 and returns (G, visibility_dist, rc): the layer's resolution, the
+    visibility as the float32 the kernel is given, and the reward of one cell, coverage_reward * cell ** 2 computed in float64 from
+    the float32 cell size 8 / G and rounded once to float32."""
+    number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+    G = coverage_resolution
+    if not whole(G) or not NAV2D_EXPLORE_MIN_RESOLUTION <= G <= NAV2D_EXPLORE_MAX_RESOLUTION:
+        raise _lib.HabError(f"{who}: coverage_resolution {G!r} must be a whole number in {NAV2D_EXPLORE_MIN_RESOLUTION}.."
+                            f"{NAV2D_EXPLORE_MAX_RESOLUTION}")
+    with np.errstate(over="ignore"):
+        if not number(visibility_dist) or not np.isfinite(np.float32(visibility_dist)) or not float(np.float32(visibility_dist)) > 0.0:
+            raise _lib.HabError(f"{who}: visibility_dist {visibility_dist!r} must be a positive finite length in metres")
+        if not number(coverage_reward) or not np.isfinite(np.float32(coverage_reward)) or not float(coverage_reward) >= 0.0:
+            raise _lib.HabError(f"{who}: coverage_reward {coverage_reward!r} must be a finite reward per square metre, >= 0")
+    cell = np.float32(8.0) / np.float32(G)
+    return int(G), float(np.float32(visibility_dist)), float(np.float32(float(coverage_reward) * float(cell) ** 2))
+
+
+class Nav2DExploreVectorEnv(Nav2DVectorEnv):
+    """Nav2DExplore-v0: area coverage in Nav2D-v0's world.  The agent is told no goal at all; the reward of a step is the area it saw
+    for the first time in the episode, a dense reward that is no potential and never telescopes; and a recurrent policy's memory is the
+    only record of where it has been.  The seen-area layer is kept on the device: it is the fog of war of the top-down map, made the
+    task.  Read through `depth` (and optionally `rgb`), `gps` and `compass` by PointNavResNetPolicy, without `objectgoal`.  A
+    measurement source, not a simulator.  tests/nav2d_explore_reference.py restates the task in numpy; `nav2d_explore_step_kernel` and
+    the markerless form of `nav2d_render_kernel` (csrc/nav2d.hip) match it bit for bit on every output -- no angle function runs on the
+    device, every float32 operation is one rounding in the written order, and the count of new cells is an integer sum.
+
+    World, physics and controls.  Everything is Nav2D-v0's (see Nav2DVectorEnv): the arena, K <= 8 rectangles, the start, the heading
+      table, the box free test, the 0.25 m forward step, turns of turn_angle, the collision count and streams 16-20.  There is no
+      goal: the record's (gx, gy) are 0.  The action space is Discrete(4) in habitat's order; any other action count is refused.  The
+      geodesic distance mode is refused by name, because there is no target.
+    Coverage layer.  One uint8 layer per env of shape (G, G), G = habitat.synthetic.coverage_resolution, a whole number in 16..512
+      (default 64), in the top-down map's cell geometry: cell = fl(8 / fl(G)), cell (r, c) has the centre x = (c + 0.5) * cell,
+      y = (G - 1 - r + 0.5) * cell, row 0 on top.  A cell becomes seen by exactly the fog of war's rule (see Nav2DVectorEnv,
+      Top-down map) with vis = habitat.synthetic.visibility_dist, a positive finite float32 (default 3.0): the centre is not strictly
+      inside a raw rectangle, d2 = dx * dx + dy * dy <= vis * vis, it lies in the 90 degree wedge (dot > 0 and |cross| <= dot) or
+      d2 <= 0.25 * 0.25, and the segment from the agent to the centre meets no open raw rectangle.
+    Beginning of an episode.  1. The layer is cleared.  2. free_cells = the number of unoccupied cell centres.  3. The first reveal is
+      done from the start pose; it earns nothing.  4. seen_cells = the count after that reveal.  5. The start pose (sx, sy, h0) is
+      recorded for gps and compass.
+    One step, in this order.  1. Nav2D-v0's discrete move; STOP moves nothing.  2. The reveal from the new pose; new = the number of
+      cells this step turned from 0 to 1.  3. reward = fl(-0.01f + fl(rc * (float)new)), where the host computes rc in float64 as
+      coverage_reward * cell ** 2 and rounds it once to float32; habitat.synthetic.coverage_reward is finite and >= 0, given per
+      square metre (default 0.1).  4. The step count goes up; the episode ends on STOP or at habitat.environment.max_episode_steps;
+      neither end carries a bonus.  5. On an end the measures are added into the sums, the next episode begins as above and
+      not_done = 0; the observations then describe the new episode.
+    Measures, in this order.  coverage = fl((float)seen_cells / (float)free_cells); area_seen = fl(fl(cell * cell) *
+      (float)seen_cells); collisions; num_steps.
+    Sensors.  rgb (H, W, 3) uint8, optional; depth (H, W, 1) float32; gps (2,) and compass (1,) float32, Nav2DObj-v0's expressions
+      and its host compass table.  The images are Nav2D-v0's geometry with nothing drawn beyond it: there is no goal cylinder.
+      Nothing is rendered when neither image is asked for.
+
+    `coverage()` returns the layers, uint8 (N, G, G), the env's own device tensor.  `step_into_obs` writes whichever of the four rows
+    `obs` holds; `actions` is int64 (N,) / (N, 1) as for Nav2D-v0.  The record's words beyond Nav2D-v0's are named in
+    include/habitat_amd.h (HAB_NAV2D_EXPLORE_W_*): start x, start y, start heading, free_cells, seen_cells, and last_new, the `new`
+    of the last step (0 after a reset).  The task has no follower, no teacher and no oracle.  With the `top_down_map` keyword the map
+    shows no marker, and its fog of war at the same resolution and visibility equals the coverage layer."""
+
+    _name = "Nav2DExplore"
+    _expert_method = None  # no teacher: see Nav2DVectorEnv.expert_actions
+    _entries = ("hab_nav2d_explore_step",)
+    _follow_entry = None  # no shortest-path follower: see Nav2DVectorEnv.follower_actions
+    _sensor_set = "explore"
+    _map_task = NAV2D_MAP_TASK_EXPLORE
+    _state_bytes = "hab_nav2d_explore_state_bytes"
+    measure_names = NAV2D_EXPLORE_MEASURES
+
+    def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = False,
+                 use_depth: bool = True, num_actions: int = 4, device="cuda", num_obstacles: int = 3, turn_angle: int = 10,
+                 max_episode_steps: int = 500, coverage_resolution: int = 64, visibility_dist: float = 3.0,
+                 coverage_reward: float = 0.1, distance: str = "euclidean", top_down_map=None):
+        if nav2d_distance(distance, "Nav2DExplore") == "geodesic":
+            raise _lib.HabError("Nav2DExplore: distance 'geodesic' is refused: the task has no target to take a distance to")
+        self.coverage_resolution, self.visibility_dist, self._cell_reward = nav2d_explore_parameters(coverage_resolution, visibility_dist,
+                                                                                                     coverage_reward)
+        self.coverage_reward = float(coverage_reward)
+        if num_actions != 4:
+            raise _lib.HabError("Nav2DExplore: the action space is Discrete(4) (STOP, MOVE_FORWARD, TURN_LEFT, TURN_RIGHT), got "
+                                f"{num_actions}")
+        if (use_rgb or use_depth) and (int(height) <= 0 or int(width) <= 0):
+            raise _lib.HabError(f"Nav2DExplore: the image size {height} x {width} must be positive")
+        try:
+            super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
+                             num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps,
+                             top_down_map=top_down_map)
+        except _lib.HabError as err:
+            # Nav2D-v0's own parameter refusals come first and stand; the one that is left where the spaces exist is the device's
+            if torch.device(device).type != "cuda" and hasattr(self, "observation_spaces"):
+                raise _lib.HabError("Nav2DExplore: the coverage layer is kept on the GPU; no GPU device given") from err
+            raise
+        self.task = "nav2dexplore"
+        G = self.coverage_resolution
+        self._coverage = torch.zeros(num_envs, G, G, dtype=torch.uint8, device=self.device)
+        self._compass_table = torch.from_numpy(nav2d_compass_table(self.turn_angle)).to(self.device)
+
+    def coverage(self):
+        """The coverage layers, uint8 (N, G, G): 1 where the cell has been seen in the env's running episode.  The env's own device
+        tensor, not a copy."""
+        return self._coverage
+
+    def _sensor_rows(self, obs):
+        return (*(ptr(obs.get(k)) for k in NAV2D_EXPLORE_SENSORS), ptr(self._compass_table), ptr(self._coverage))
+
+    def _task_parameters(self):
+        return self.coverage_resolution, self.visibility_dist, self._cell_reward
+
+    def step_infos_host(self, ids) -> List[dict]:
+        """The scalar infos of the last step of envs `ids`: this task's four measures where that step ended an episode, else {}."""
+        return [dict(zip(NAV2D_EXPLORE_MEASURES, info.values())) if info else {} for info in super().step_infos_host(ids)]
+
+    def reset_into(self, rgb, depth, goal):
+        raise _lib.HabError("Nav2DExplore: the task has no pointgoal sensor; use reset_into_obs with the task's sensor rows")
+
+    def step_into(self, rgb, depth, goal, reward, not_done, actions=None, mask=None):
+        raise _lib.HabError("Nav2DExplore: the task has no pointgoal sensor; use step_into_obs with the task's sensor rows")
+
+
 class SyntheticVectorEnvFactory(VectorEnvFactory):
     """Default `_target_`: N synthetic PointNav envs sized from habitat.simulator.sensors.*; per-rank env ids are
     offset by rank * num_environments exactly like the reference offsets the seed (ppo_trainer.py:208-211).  A
@@ -1332,7 +1459,9 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
     Nav2DRearrVel-v0 (Nav2DRearrVelVectorEnv: that task under velocity and grip control), which reads Nav2DVel-v0's keys and
     start_holding and takes its image size like Nav2DRearr-v0.  A type starting with "nav2dsocial" -- tested before "nav2d" -- selects
     Nav2DSocial-v0 (Nav2DSocialVectorEnv: find and follow a walking person), which reads Nav2DVel-v0's keys, person_speed and
-    person_always_visible, takes its image size like Nav2DRearr-v0 and has the Euclidean distance mode only.
+    person_always_visible, takes its image size like Nav2DRearr-v0 and has the Euclidean distance mode only.  A type starting with
+    "nav2dexplore" -- tested before "nav2d" too -- selects Nav2DExplore-v0 (Nav2DExploreVectorEnv: area coverage, no goal input), which
+    reads coverage_resolution, visibility_dist and coverage_reward, takes its image size like Nav2D-v0 and has the Euclidean mode only.
     `habitat.task.measurements.top_down_map`, where that key is present, becomes the `top_down_map` keyword of any Nav2D task with
     whichever of map_resolution, visibility_dist, draw_fog and fov it holds (see Nav2DVectorEnv, Top-down map)."""
 
@@ -1357,7 +1486,11 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
             if tdm is not None:  # the measure: any of its keys may be missing (see nav2d_map_parameters)
                 kw.update(top_down_map={k: getattr(tdm, k) for k in NAV2D_MAP_DEFAULTS if getattr(tdm, k, None) is not None})
             make = Nav2DVectorEnv
-            if task_type.startswith("nav2dsocial"):
+            if task_type.startswith("nav2dexplore"):
+                make = Nav2DExploreVectorEnv
+                kw.update(coverage_resolution=getattr(syn, "coverage_resolution", 64), visibility_dist=getattr(syn, "visibility_dist", 3.0),
+                          coverage_reward=getattr(syn, "coverage_reward", 0.1))
+            elif task_type.startswith("nav2dsocial"):
                 use_rgb, use_depth = self.use_rgb and "head_rgb" in sens, self.use_depth and "head_depth" in sens
                 ref = sens["head_rgb"] if use_rgb else (sens["head_depth"] if use_depth else dict(height=0, width=0))
                 make = Nav2DSocialVectorEnv

@@ -382,6 +382,39 @@ int hab_nav2d_social_step(void* state /*N,HAB_NAV2D_SOCIAL_STATE_BYTES*/, const 
                           uint32_t env_offset, int N, int H, int W, int num_obstacles, int num_headings, int max_episode_steps,
                           int max_turn_steps, int stop_turn_steps, float min_abs_lin_speed, int allow_sliding, float person_speed,
                           int person_always_visible, int advance, hipStream_t stream);
+/* Nav2DExplore-v0: area coverage in Nav2D-v0's world, with the seen-area layer on the device (definition:
+ * habitat_amd/common/env_factory.py, Nav2DExploreVectorEnv; bit-identical to tests/nav2d_explore_reference.py on every output, no
+ * angle function runs on the device).  There is no goal: the reward of a step is -0.01 + rc * (the cells the step saw for the first
+ * time in the episode).  `state` is N records of HAB_NAV2D_EXPLORE_STATE_BYTES whose first HAB_NAV2D_STATE_BYTES are a Nav2D-v0
+ * record: the words named above keep their meaning, with (GX, GY), D_PREV and D_START zero; LAST_MEASURES are coverage, area_seen,
+ * collisions, num_steps.  Every argument of hab_nav2d_step keeps its meaning and its checks; there is no goal sensor.  actions int64
+ * in 0..3.  rgb and depth: Nav2D-v0's images without the goal marker.  gps, compass and compass_table as hab_nav2d_obj_step's.
+ * coverage u8 (N,G,G), never NULL: 1 where the cell has been seen in the episode, in the top-down map's cell geometry (row 0 on top,
+ * cells of 8 / G metres, G in HAB_NAV2D_EXPLORE_MIN_RESOLUTION..HAB_NAV2D_EXPLORE_MAX_RESOLUTION, else HAB_ERR_ARG) and by its fog
+ * of war's rule with visibility_dist (positive and finite, else HAB_ERR_ARG); a layer that is 4-byte aligned with G * G a multiple of
+ * 4 is swept a word at a time, any other a byte at a time.  rc: the reward of one cell, finite and >= 0, else HAB_ERR_ARG.  Every
+ * other destination may be NULL.  One workgroup per env: the move, the reveal, the exact count of the new cells, the end of the step
+ * and, where an episode ends (advance = 0: for every selected env), the next world, the cleared layer, its free cells and the first
+ * reveal, in one launch; then the render. */
+#define HAB_NAV2D_EXPLORE_STATE_BYTES 248
+#define HAB_NAV2D_EXPLORE_MIN_RESOLUTION 16
+#define HAB_NAV2D_EXPLORE_MAX_RESOLUTION 512
+/* further words of a Nav2DExplore-v0 record: start position, start heading index, the unoccupied cells of the episode's world, the
+ * cells seen so far in the episode, the cells the last step saw for the first time (0 after a reset) */
+#define HAB_NAV2D_EXPLORE_W_START_X 56
+#define HAB_NAV2D_EXPLORE_W_START_Y 57
+#define HAB_NAV2D_EXPLORE_W_START_HEADING 58
+#define HAB_NAV2D_EXPLORE_W_FREE_CELLS 59
+#define HAB_NAV2D_EXPLORE_W_SEEN_CELLS 60
+#define HAB_NAV2D_EXPLORE_W_LAST_NEW 61
+int hab_nav2d_explore_state_bytes(void);
+int hab_nav2d_explore_step(void* state /*N,HAB_NAV2D_EXPLORE_STATE_BYTES*/, const float* dirs, const float* ray, const float* col_cos,
+                           const float* tanv, const int64_t* actions /*N*/, const uint8_t* mask /*N*/, uint8_t* rgb /*N,H,W,3*/,
+                           float* depth /*N,H,W,1*/, float* gps /*N,2*/, float* compass /*N,1*/,
+                           const float* compass_table /*num_headings*/, uint8_t* coverage /*N,G,G*/, float* reward /*N*/,
+                           uint8_t* not_done /*N*/, float* measure_sums /*4,N*/, uint32_t seed, uint32_t env_offset, int N, int H, int W,
+                           int num_obstacles, int num_headings, int max_episode_steps, int G, float visibility_dist, float rc,
+                           int advance, hipStream_t stream);
 
 /* The top-down map of the Nav2D tasks with its fog of war, and the video frame (definition: habitat_amd/common/env_factory.py,
  * Nav2DVectorEnv, "Top-down map"; bit-identical to tests/nav2d_map_reference.py; csrc/nav2d_map.hip).  `state` are records of any
@@ -406,11 +439,13 @@ int hab_nav2d_social_step(void* state /*N,HAB_NAV2D_SOCIAL_STATE_BYTES*/, const 
 #define HAB_NAV2D_MAP_W_ZERO 5       /* 5..7: zero */
 #define HAB_NAV2D_MAP_MIN_RESOLUTION 16
 #define HAB_NAV2D_MAP_MAX_RESOLUTION 512
-/* which words tell the targets: (GX, GY) / the objects of Nav2DObj-v0 / the goal place of the rearrangement tasks / none */
+/* which words tell the targets: (GX, GY) / the objects of Nav2DObj-v0 / the goal place of the rearrangement tasks / none / none, on
+ * a Nav2DExplore-v0 record (no marker and no overlay beyond the agent and its tick) */
 #define HAB_NAV2D_MAP_TASK_GOAL 0
 #define HAB_NAV2D_MAP_TASK_OBJ 1
 #define HAB_NAV2D_MAP_TASK_REARR 2
 #define HAB_NAV2D_MAP_TASK_SOCIAL 3
+#define HAB_NAV2D_MAP_TASK_EXPLORE 4
 /* cell codes (habitat's where it has them) and the codes of the frame's overlays */
 #define HAB_NAV2D_MAP_OCCUPIED 0
 #define HAB_NAV2D_MAP_FREE 1

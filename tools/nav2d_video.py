@@ -47,7 +47,10 @@ def main(argv=None):
         raise _lib.HabError(f"nav2d_video: {args.config} is no Nav2D task ({cfg.habitat.task.type}); only those have a world to draw")
     if getattr(cfg.habitat.task.measurements, "top_down_map", None) is None:
         cfg.habitat.task.measurements["top_down_map"] = Config()
-    env = SyntheticVectorEnvFactory().construct_envs(cfg, device="cuda")
+    # the config's own switches of the synthetic factory (use_rgb, use_depth), where it names that factory
+    factory = cfg.habitat_baselines.vector_env_factory
+    switches = {k: v for k, v in factory.items() if k != "_target_"} if str(factory["_target_"]).endswith(".SyntheticVectorEnvFactory") else {}
+    env = SyntheticVectorEnvFactory(**switches).construct_envs(cfg, device="cuda")
     generator = torch.Generator().manual_seed(args.seed)
     obs = env._own_obs()
     env.reset_into_obs(obs)
