@@ -15,6 +15,8 @@
 // velocity control; nav2d_social_step_kernel, nav2d_social_build_kernel) is specified by tests/nav2d_social_reference.py.
 // Nav2DExplore-v0 (area coverage: the reward is the cells seen for the first time; nav2d_explore_step_kernel, one workgroup per env
 // over the coverage layer, with the top-down map's rule from nav2d_seen.h) is specified by tests/nav2d_explore_reference.py.
+// Nav2DImageNav-v0 (Nav2D-v0 with the goal given only as an image: nav2d_imagenav_step_kernel and the IMAGENAV form of the render, which
+// draws the agent's view and the goal's in one launch) is specified by tests/nav2d_imagenav_reference.py.
 // The follower (nav2d_follow_kernel) and the pick-and-place oracle (nav2d_rearr_oracle_kernel) read the geodesic fields; their
 // specifications are tests/nav2d_follow_reference.py and tests/nav2d_rearr_oracle_reference.py.
 // What the tasks share is written once: the moves (discrete_move, vel_decode / vel_move, on a record or on a lane's MoveLane), the
@@ -1805,6 +1807,61 @@ nav2d_explore_step_kernel(Nav2DExploreState* __restrict__ states, const float* _
     }
 }
 
+// ---- Nav2DImageNav-v0 (Nav2DImageNavVectorEnv; specification: tests/nav2d_imagenav_reference.py) -------------------------------------
+// One env of Nav2DImageNav-v0: a Nav2D-v0 record, then the heading the goal image is taken with and the start pose the gps / compass
+// sensors refer to.
+struct Nav2DImageNavState {
+    Nav2DState base;
+    int32_t gh;
+    float sx, sy;
+    int32_t h0;
+};
+static_assert(sizeof(Nav2DImageNavState) == HAB_NAV2D_IMAGENAV_STATE_BYTES && offsetof(Nav2DImageNavState, base) == 0,
+              "Nav2DImageNavState layout");
+static_assert(offsetof(Nav2DImageNavState, gh) == 4 * HAB_NAV2D_IMAGENAV_W_GOAL_HEADING &&
+              offsetof(Nav2DImageNavState, sx) == 4 * HAB_NAV2D_IMAGENAV_W_START_X, "Nav2DImageNavState layout");
+static_assert(offsetof(Nav2DImageNavState, sy) == 4 * HAB_NAV2D_IMAGENAV_W_START_Y &&
+              offsetof(Nav2DImageNavState, h0) == 4 * HAB_NAV2D_IMAGENAV_W_START_HEADING, "Nav2DImageNavState layout");
+
+constexpr uint32_t S_GOAL_HEAD = 25u;
+
+// What an episode of Nav2DImageNav-v0 has beyond its Nav2D-v0 world: the goal heading (the start heading's expression on its own
+// stream) and the start pose.
+__device__ inline void imagenav_begin(Nav2DImageNavState& o, uint32_t seed, uint32_t env, int nh) {
+    const Nav2DState& s = o.base;
+    o.gh = (int32_t)(mix32(stream_key(seed, S_GOAL_HEAD, env, (uint32_t)s.episode) ^ 0u) % (uint32_t)nh);
+    o.sx = s.px; o.sy = s.py; o.h0 = s.heading;
+}
+
+// nav2d_step_kernel on such records, with the task's success distance; then Nav2DObj-v0's gps and compass in place of the goal sensor.
+template <bool GEO>
+__global__ void __launch_bounds__(GEO ? 64 : 1024)
+nav2d_imagenav_step_kernel(Nav2DImageNavState* __restrict__ states, const float* __restrict__ dirs, const float* __restrict__ ctab,
+                           const int64_t* __restrict__ actions, const uint8_t* __restrict__ mask, float* __restrict__ gps,
+                           float* __restrict__ compass, float* __restrict__ reward, uint8_t* __restrict__ not_done,
+                           float* __restrict__ sums, uint32_t seed, uint32_t env_offset, int N, int K, int nh, int max_steps,
+                           float success_dist, int advance, GeoField* __restrict__ geo) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N || (mask && !mask[n])) return;
+    Nav2DImageNavState& o = states[n];
+    Nav2DState& s = o.base;
+    const uint32_t env = env_offset + (uint32_t)n;
+    if (!advance) {
+        first_episode(s, seed, env, K, nh);
+        imagenav_begin(o, seed, env, nh);
+    } else {
+        const int64_t a = actions[n];  // anything outside 0..3 moves nothing (the host-side entry points refuse it)
+        discrete_move(s, a, dirs, nh, [&](float x, float y) { return is_free(x, y, s, K); });
+        end_step<true, GEO>(s, a == 0, success_dist, reward, not_done, sums, seed, env, n, N, K, nh, max_steps, GEO ? geo + n : nullptr);
+        if (s.ended) imagenav_begin(o, seed, env, nh);
+    }
+    if (gps) {
+        const float c = dirs[2 * o.h0], sn = dirs[2 * o.h0 + 1];
+        to_frame(s.px - o.sx, s.py - o.sy, c, sn, gps[2 * n + 0], gps[2 * n + 1]);
+    }
+    if (compass) compass[n] = ctab[(s.heading - o.h0 + nh) % nh];
+}
+
 // ---- rendering ---------------------------------------------------------------------------------------------------------------
 // Entry / exit of the ray p + t d through [lo, hi] on one axis.
 __device__ inline void slab(float lo, float hi, float p, float d, float inv, float& tmin, float& tmax) {
@@ -1895,15 +1952,27 @@ __device__ inline void sweep_dwords(T* __restrict__ img, int s_px, int e_px, int
 // Render::SOCIAL (Nav2DSocial-v0): `states` are Nav2DSocialState records; the person is one cylinder of category 0's colour, geometry
 // for depth and rgb alike, and there is no goal marker: nothing is drawn in rgb only.  No semantic image: four column arrays.
 // Render::EXPLORE (Nav2DExplore-v0): `states` are Nav2DExploreState records; Nav2D-v0's geometry with no cylinder and no goal marker.
-enum class Render { GOAL, OBJ, REARR, SOCIAL, EXPLORE };
+// Render::IMAGENAV (Nav2DImageNav-v0): `states` are Nav2DImageNavState records; the EXPLORE form's markerless geometry, drawn twice in
+// one launch: grid (row tiles, N, 2), and the third index selects the view, so the choice is uniform over a workgroup.  View 0 is the
+// agent's pose into `rgb` / `depth`; view 1 is the pose (gx, gy, gh) of the record into `goal_rgb`, colour only.  A view none of whose
+// destinations is given leaves before the first barrier.  `goal_rgb` is read by this form alone.
+enum class Render { GOAL, OBJ, REARR, SOCIAL, EXPLORE, IMAGENAV };
 template <Render MODE>
 __global__ void __launch_bounds__(RENDER_THREADS)
 nav2d_render_kernel(const void* __restrict__ states, const float* __restrict__ ray, const float* __restrict__ col_cos,
                     const float* __restrict__ tanv, const uint8_t* __restrict__ mask, uint8_t* __restrict__ rgb,
-                    float* __restrict__ depth, int32_t* __restrict__ semantic, int H, int W, int K, int M, int rows_per_tile) {
+                    float* __restrict__ depth, int32_t* __restrict__ semantic, int H, int W, int K, int M, int rows_per_tile,
+                    uint8_t* __restrict__ goal_rgb) {
     extern __shared__ uint4 lds[];
     const int n = blockIdx.y;
     if (mask && !mask[n]) return;
+    constexpr bool IMAGENAV = MODE == Render::IMAGENAV;
+    const bool goal_view = IMAGENAV && blockIdx.z == 1;
+    if constexpr (IMAGENAV) {
+        rgb = goal_view ? goal_rgb : rgb;
+        depth = goal_view ? nullptr : depth;
+        if (!rgb && !depth) return;
+    }
     const int P = col_pitch(W);
     float* c_zd = reinterpret_cast<float*>(lds);
     float* c_dw = c_zd + P;
@@ -1916,13 +1985,16 @@ nav2d_render_kernel(const void* __restrict__ states, const float* __restrict__ r
     const Nav2DRearrState* rs = REARR ? static_cast<const Nav2DRearrState*>(states) + n : nullptr;
     const Nav2DSocialState* ss = SOCIAL ? static_cast<const Nav2DSocialState*>(states) + n : nullptr;
     const Nav2DExploreState* es = EXPLORE ? static_cast<const Nav2DExploreState*>(states) + n : nullptr;
-    const Nav2DState& s = OBJ ? os->base : REARR ? rs->base : SOCIAL ? ss->base : EXPLORE ? es->base : static_cast<const Nav2DState*>(states)[n];
+    const Nav2DImageNavState* is = IMAGENAV ? static_cast<const Nav2DImageNavState*>(states) + n : nullptr;
+    const Nav2DState& s = OBJ ? os->base : REARR ? rs->base : SOCIAL ? ss->base : EXPLORE ? es->base : IMAGENAV ? is->base
+                                                                                              : static_cast<const Nav2DState*>(states)[n];
     // the cylinders of this env: Nav2DObj-v0's M objects, Nav2DRearr-v0's object unless it is held, Nav2DSocial-v0's person
     const float (*cyl)[2] = OBJ ? os->obj : REARR ? reinterpret_cast<const float (*)[2]>(&rs->ox) : SOCIAL ? ss->obj : nullptr;
     const int cyls = OBJ ? M : REARR ? (rs->holding ? 0 : 1) : SOCIAL ? 1 : 0;
     const int v0 = blockIdx.x * rows_per_tile, v1 = min(H, v0 + rows_per_tile);
-    const float px = s.px, py = s.py;
-    const float* rayh = ray + (size_t)s.heading * W * 2;
+    // the camera's pose: the agent's, or for the goal view of the IMAGENAV form the goal position with the goal heading
+    const float px = goal_view ? s.gx : s.px, py = goal_view ? s.gy : s.py;
+    const float* rayh = ray + (size_t)(goal_view ? is->gh : s.heading) * W * 2;
     for (int u = threadIdx.x; u < W; u += RENDER_THREADS) {
         const float dx = rayh[2 * u], dy = rayh[2 * u + 1];
         const float ix = __fdiv_rn(1.0f, dx), iy = __fdiv_rn(1.0f, dy);
@@ -1952,7 +2024,7 @@ nav2d_render_kernel(const void* __restrict__ states, const float* __restrict__ r
         const float z_wall = t * cf;
         float z_rgb = z_wall;
         bool marker = false;
-        if constexpr (!OBJ && !SOCIAL && !EXPLORE) {
+        if constexpr (!OBJ && !SOCIAL && !EXPLORE && !IMAGENAV) {
             const float ox = px - s.gx, oy = py - s.gy;
             const float b = ox * dx + oy * dy;
             const float c = (ox * ox + oy * oy) - 0.2f * 0.2f;
@@ -2052,7 +2124,8 @@ struct StepArgs {
     uint32_t seed, env_offset;
     int N, H, W, num_obstacles, num_headings, max_episode_steps, advance;
     hipStream_t stream;
-    bool image() const { return rgb || depth || semantic; }  // whether any image destination is given
+    uint8_t* goal_rgb = nullptr;  // Nav2DImageNav-v0's second view
+    bool image() const { return rgb || depth || semantic || goal_rgb; }  // whether any image destination is given
 };
 
 static int check_geo_args(const void* state, size_t state_stride_bytes, const void* geo, int N, int num_obstacles) {
@@ -2098,11 +2171,11 @@ static int launch_render(const StepArgs& a, int num_objects) {
     if (rows < 4) rows = 4;
     if (rows > RENDER_MAX_ROWS) rows = RENDER_MAX_ROWS;
     if (rows > a.H) rows = a.H;
-    dim3 grid(cdiv(a.H, rows), a.N);
+    dim3 grid(cdiv(a.H, rows), a.N, MODE == Render::IMAGENAV ? 2 : 1);
     const size_t lds = (size_t)(col_pitch(a.W) + rows) * sizeof(uint4) +
                        (MODE == Render::OBJ ? (size_t)col_pitch(a.W) * sizeof(int32_t) : 0);
     nav2d_render_kernel<MODE><<<grid, RENDER_THREADS, lds, a.stream>>>(a.state, a.ray, a.col_cos, a.tanv, a.mask, a.rgb, a.depth, a.semantic,
-                                                                       a.H, a.W, a.num_obstacles, num_objects, rows);
+                                                                       a.H, a.W, a.num_obstacles, num_objects, rows, a.goal_rgb);
     HAB_LAUNCH_CHECK();
     return HAB_OK;
 }
@@ -2463,4 +2536,51 @@ extern "C" int hab_nav2d_explore_step(void* state, const float* dirs, const floa
                                                                  visibility_dist * visibility_dist, rc, advance, vec);
     HAB_LAUNCH_CHECK();
     return launch_render<Render::EXPLORE>(a, 0);
+}
+
+// Nav2DImageNav-v0, its two entries like Nav2D-v0's: the step, for a `_geo` entry the fields of the episodes that began, then both
+// views in one launch of the render.
+extern "C" int hab_nav2d_imagenav_state_bytes(void) { return (int)sizeof(Nav2DImageNavState); }
+
+template <bool GEO>
+static int imagenav_step(const StepArgs& a, float* gps, float* compass, const float* compass_table, float success_distance) {
+    const int rc = check_step_args(a, GEO, sizeof(Nav2DImageNavState));
+    if (rc != HAB_OK) return rc;
+    if (((uintptr_t)a.state & 3) || (compass && !compass_table)) return HAB_ERR_ARG;
+    if (!(success_distance > 0.f) || !(success_distance <= 3.0e38f)) return HAB_ERR_ARG;
+    nav2d_imagenav_step_kernel<GEO><<<cdiv(a.N, 64), 64, 0, a.stream>>>((Nav2DImageNavState*)a.state, a.dirs, compass_table,
+                                                                         (const int64_t*)a.actions, a.mask, gps, compass, a.reward, a.not_done,
+                                                                         a.measure_sums, a.seed, a.env_offset, a.N, a.num_obstacles,
+                                                                         a.num_headings, a.max_episode_steps, success_distance, a.advance,
+                                                                         GEO ? (GeoField*)a.geo : nullptr);
+    HAB_LAUNCH_CHECK();
+    if (GEO) {
+        nav2d_geo_build_kernel<<<a.N, 64, 0, a.stream>>>((char*)a.state, sizeof(Nav2DImageNavState), (GeoField*)a.geo, a.mask,
+                                                         a.advance ? 1 : 0, a.num_obstacles);
+        HAB_LAUNCH_CHECK();
+    }
+    return launch_render<Render::IMAGENAV>(a, 0);
+}
+
+extern "C" int hab_nav2d_imagenav_step(void* state, const float* dirs, const float* ray, const float* col_cos, const float* tanv,
+                                       const int64_t* actions, const uint8_t* mask, uint8_t* rgb, float* depth, uint8_t* goal_rgb,
+                                       float* gps, float* compass, const float* compass_table, float* reward, uint8_t* not_done,
+                                       float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles,
+                                       int num_headings, int max_episode_steps, float success_distance, int advance, hipStream_t stream) {
+    return imagenav_step<false>({state, nullptr, dirs, ray, col_cos, tanv, actions, mask, rgb, depth, nullptr, nullptr, reward, not_done,
+                                 measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream,
+                                 goal_rgb},
+                                gps, compass, compass_table, success_distance);
+}
+
+extern "C" int hab_nav2d_imagenav_step_geo(void* state, void* geo, const float* dirs, const float* ray, const float* col_cos,
+                                           const float* tanv, const int64_t* actions, const uint8_t* mask, uint8_t* rgb, float* depth,
+                                           uint8_t* goal_rgb, float* gps, float* compass, const float* compass_table, float* reward,
+                                           uint8_t* not_done, float* measure_sums, uint32_t seed, uint32_t env_offset, int N, int H, int W,
+                                           int num_obstacles, int num_headings, int max_episode_steps, float success_distance, int advance,
+                                           hipStream_t stream) {
+    return imagenav_step<true>({state, geo, dirs, ray, col_cos, tanv, actions, mask, rgb, depth, nullptr, nullptr, reward, not_done,
+                                measure_sums, seed, env_offset, N, H, W, num_obstacles, num_headings, max_episode_steps, advance, stream,
+                                goal_rgb},
+                               gps, compass, compass_table, success_distance);
 }

@@ -91,6 +91,9 @@ SIGNATURES = {
     "hab_nav2d_social_step": (c_int, [vp] * 14 + [c_uint32, c_uint32] + [c_int] * 8 + [c_float, c_int, c_float, c_int, c_int, vp]),
     "hab_nav2d_explore_state_bytes": (c_int, []),
     "hab_nav2d_explore_step": (c_int, [vp] * 16 + [c_uint32, c_uint32] + [c_int] * 7 + [c_float, c_float, c_int, vp]),
+    "hab_nav2d_imagenav_state_bytes": (c_int, []),
+    "hab_nav2d_imagenav_step": (c_int, [vp] * 16 + [c_uint32, c_uint32] + [c_int] * 6 + [c_float, c_int, vp]),
+    "hab_nav2d_imagenav_step_geo": (c_int, [vp] * 17 + [c_uint32, c_uint32] + [c_int] * 6 + [c_float, c_int, vp]),
     "hab_nav2d_map_rec_bytes": (c_int, []),
     "hab_nav2d_map_update": (c_int, [vp, c_size_t] + [vp] * 5 + [c_int] * 6 + [c_float, c_int, vp]),
     "hab_nav2d_map_frame_width": (c_int, [c_int] * 5),

@@ -67,6 +67,10 @@ class SyntheticVectorEnv:
         elif task == "explore":  # sensor set of Nav2DExplore-v0: the camera, then gps and compass; no goal input at all
             d["gps"] = spaces.Box(fmin, fmax, (2,), np.float32)
             d["compass"] = spaces.Box(-np.pi, np.pi, (1,), np.float32)
+        elif task == "imagenav":  # sensor set of Nav2DImageNav-v0: the camera, the goal as a second image, then gps and compass
+            d["goal_rgb"] = spaces.Box(0, 255, (height, width, 3), np.uint8)
+            d["gps"] = spaces.Box(fmin, fmax, (2,), np.float32)
+            d["compass"] = spaces.Box(-np.pi, np.pi, (1,), np.float32)
         elif task == "objectnav":  # sensor set of the ObjectNav experiments (rgb, depth, semantic + objectgoal, compass, gps)
             d["semantic"] = spaces.Box(0, NUM_SEMANTIC_IDS - 1, (height, width, 1), np.int32)
             d["objectgoal"] = spaces.Box(0, NUM_OBJECT_CATEGORIES - 1, (1,), np.int64)
@@ -85,7 +89,7 @@ class SyntheticVectorEnv:
         self._since = torch.zeros(num_envs, dtype=torch.int64, device=dev)
         self._rgb = torch.zeros(num_envs, height, width, 3, dtype=torch.uint8, device=dev) if use_rgb else None
         self._depth = torch.zeros(num_envs, height, width, 1, device=dev) if use_depth else None
-        self._goal = torch.zeros(num_envs, 2, device=dev) if task not in ("objectnav", "rearrange", "social", "explore") else None
+        self._goal = torch.zeros(num_envs, 2, device=dev) if task not in ("objectnav", "rearrange", "social", "explore", "imagenav") else None
         self._obj = {}
         if task == "objectnav":
             self._obj = dict(semantic=torch.zeros(num_envs, height, width, 1, dtype=torch.int32, device=dev),
@@ -96,6 +100,9 @@ class SyntheticVectorEnv:
                              is_holding=torch.zeros(num_envs, 1, device=dev))
         elif task == "explore":
             self._obj = dict(gps=torch.zeros(num_envs, 2, device=dev), compass=torch.zeros(num_envs, 1, device=dev))
+        elif task == "imagenav":
+            self._obj = dict(goal_rgb=torch.zeros(num_envs, height, width, 3, dtype=torch.uint8, device=dev),
+                             gps=torch.zeros(num_envs, 2, device=dev), compass=torch.zeros(num_envs, 1, device=dev))
         elif task == "social":
             self._obj = dict(person_sensor=torch.zeros(num_envs, 2, device=dev), person_visible=torch.zeros(num_envs, 1, device=dev))
         self._rew = torch.zeros(num_envs, device=dev)
@@ -580,8 +587,8 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
         forward if the agent faces it, else a turn towards it.
         `out` receives the actions (allocated if None) and is returned; `mask` (uint8 (N,)) selects envs, the outputs of the others
         stay untouched; `next_d` (float32 (N,)) receives the distance the env will report after the step of a GO (D_PREV where
-        ARRIVED, +inf otherwise), `status` (int32 (N,)) the code 0 GO, 1 ARRIVED, 2 UNREACHABLE, 3 STUCK.  Only Nav2D-v0 and
-        Nav2DVel-v0 in the geodesic distance mode have a follower."""
+        ARRIVED, +inf otherwise), `status` (int32 (N,)) the code 0 GO, 1 ARRIVED, 2 UNREACHABLE, 3 STUCK.  Only Nav2D-v0,
+        Nav2DVel-v0 and Nav2DImageNav-v0 (Nav2D-v0's follower on its longer record) in the geodesic distance mode have a follower."""
         if self._follow_entry is None:
             raise _lib.HabError(f"{self._name}: the task has no shortest-path follower (Nav2D-v0 and Nav2DVel-v0 have one)")
         if self.distance != "geodesic":
@@ -594,7 +601,7 @@ class Nav2DVectorEnv(SyntheticVectorEnv):
     _expert_method = "follower_actions"  # which of the task's advisers labels the learner's states; None where the task has none
 
     def expert_actions(self, out=None, mask=None, next_d=None, status=None):
-        """One discrete teacher action per env for imitation (the DAgger updater): `follower_actions` on Nav2D-v0, `oracle_actions` on
+        """One discrete teacher action per env for imitation (the DAgger updater): `follower_actions` on Nav2D-v0 and Nav2DImageNav-v0, `oracle_actions` on
         Nav2DRearr-v0, with their arguments; `status` holds HAB_NAV2D_ORACLE_* codes, of which the follower's four are the first
         four.  Every other Nav2D task refuses: the velocity tasks' advice is a float row, Nav2DObj-v0 and Nav2DSocial-v0 have no
         adviser.  The Euclidean distance mode refuses as the two advisers do."""
@@ -1443,6 +1450,99 @@ class Nav2DExploreVectorEnv(Nav2DVectorEnv):
         raise _lib.HabError("Nav2DExplore: the task has no pointgoal sensor; use step_into_obs with the task's sensor rows")
 
 
+NAV2D_IMAGENAV_SENSORS = ("rgb", "depth", "goal_rgb", "gps", "compass")
+NAV2D_FOLLOWER_STOP_DISTANCE = 0.2  # below this D_PREV the shortest-path follower stops (see Nav2DVectorEnv.follower_actions)
+
+
+def nav2d_imagenav_success_distance(success_distance, distance: str, who: str = "Nav2DImageNav") -> float:
+    """Checks `habitat.synthetic.success_distance` of Nav2DImageNav-v0 and returns it as the float32 the kernel is given.  In the
+    geodesic mode a value below the follower's stop distance is refused: the follower would stop outside the success radius."""
+    number = isinstance(success_distance, (int, float, np.integer, np.floating)) and not isinstance(success_distance, bool)
+    with np.errstate(over="ignore"):
+        if not number or not np.isfinite(np.float32(success_distance)) or not float(np.float32(success_distance)) > 0.0:
+            raise _lib.HabError(f"{who}: success_distance {success_distance!r} must be a positive finite length in metres")
+    if distance == "geodesic" and np.float32(success_distance) < np.float32(NAV2D_FOLLOWER_STOP_DISTANCE):
+        raise _lib.HabError(f"{who}: success_distance {success_distance!r} is below {NAV2D_FOLLOWER_STOP_DISTANCE}, the distance at "
+                            "which the shortest-path follower of the geodesic mode stops: its episodes would end outside the radius")
+    return float(np.float32(success_distance))
+
+
+class Nav2DImageNavVectorEnv(Nav2DVectorEnv):
+    """Nav2DImageNav-v0: Nav2D-v0 with the goal given only as an image.  The place to reach is told by `goal_rgb`, the picture the
+    task's camera takes from there, and in no other way: there is no pointgoal sensor.  It is the early-fusion form of ImageNav:
+    PointNavResNetPolicy stacks `rgb` (3), `depth` (1) and `goal_rgb` (3) along the channels, 7 of its encoder's 8, and one encoder
+    reads both views.  The sensor is deliberately not called `imagegoal`: that name (and `instance_imagegoal`) is refused by both
+    policies, because the reference builds a second encoder for it.  A measurement source, not a simulator.
+    tests/nav2d_imagenav_reference.py restates the task in numpy; `nav2d_imagenav_step_kernel` and the IMAGENAV form of
+    `nav2d_render_kernel` (csrc/nav2d.hip) match it bit for bit on every output.
+
+    World, physics and controls.  Everything is Nav2D-v0's, bit for bit (see Nav2DVectorEnv): the arena, K <= 8 rectangles, the start,
+      the goal position (gx, gy), the heading table, the box free test, the moves, the collision count, the step limit, Discrete(4)
+      and streams 16-20.  Any other action count is refused.
+    Goal view.  When an episode begins, gh = mix32(stream_key(seed, 25, env, episode) ^ 0) % num_headings, the expression the start
+      heading uses on stream 19.  `goal_rgb` is what the camera sees from (gx, gy) with heading gh: the same pinhole, tables, shading
+      and truncation as the agent's view, without any marker.  It is a pure function of the record, constant within an episode, and
+      drawn again at every step by the same launch that draws the agent's view (view 1 of the IMAGENAV form); the env keeps no image.
+    Reward, success, measures.  Nav2D-v0's: reward = (-0.01 + (d_prev - d)) + 2.5 * success; success = STOP with
+      d < success_distance; measures success, spl, distance_to_goal, collisions.  habitat.synthetic.success_distance is a positive
+      finite float32, default 1.0 (the distance the object task uses); with 0.2 every reward, not-done byte and measure is bitwise
+      Nav2D-v0's under the same seed and actions.  Both distance modes exist (`distance`, habitat.synthetic.distance_to_goal); the
+      geodesic one uses Nav2D-v0's field records, hab_nav2d_geo_build with this record's stride.
+    Sensors, in this order.  rgb (H, W, 3) uint8, required: use_rgb=False is refused; depth (H, W, 1) float32, optional; goal_rgb
+      (H, W, 3) uint8; gps (2,) and compass (1,) float32, Nav2DObj-v0's expressions and host compass table, relative to the start
+      pose.  The agent's rgb carries NO goal cylinder: its pixels are the markerless geometry of Nav2DExplore-v0, not Nav2D-v0's.
+    Follower, teacher, map.  In the geodesic mode `follower_actions` is Nav2D-v0's follower on this record and `expert_actions` is
+      that follower; in the Euclidean mode both refuse as Nav2D-v0's do.  The follower stops where D_PREV < 0.2, which is inside
+      every success distance >= 0.2; a success_distance below 0.2 is refused in the geodesic mode.  The top-down map and the frames
+      use Nav2D-v0's map task code (the goal disc at (gx, gy)); the goal image is not part of a frame.
+
+    The record's words beyond Nav2D-v0's are named in include/habitat_amd.h (HAB_NAV2D_IMAGENAV_W_*): gh, then the start pose
+    (sx, sy, h0).  `step_into_obs` writes whichever of the five rows `obs` holds.  A non-GPU device is refused by name, as for every
+    Nav2D task; on a GPU device the VectorEnv API (the host path: `reset`, `step`, `async_step_at` / `wait_step_at`) works as
+    Nav2D-v0's does, with `goal_rgb` among the host observations."""
+
+    _name = "Nav2DImageNav"
+    _entries = ("hab_nav2d_imagenav_step", "hab_nav2d_imagenav_step_geo")
+    _sensor_set = "imagenav"
+    _state_bytes = "hab_nav2d_imagenav_state_bytes"
+
+    def __init__(self, num_envs: int, height: int, width: int, seed: int = 100, env_offset: int = 0, use_rgb: bool = True,
+                 use_depth: bool = True, num_actions: int = 4, device="cuda", num_obstacles: int = 3, turn_angle: int = 10,
+                 max_episode_steps: int = 500, success_distance: float = 1.0, distance: str = "euclidean", top_down_map=None):
+        if not use_rgb:
+            raise _lib.HabError("Nav2DImageNav: the rgb sensor is required: the goal image is given in its size and the policy "
+                                "compares the two views")
+        if num_actions != 4:
+            raise _lib.HabError("Nav2DImageNav: the action space is Discrete(4) (STOP, MOVE_FORWARD, TURN_LEFT, TURN_RIGHT), got "
+                                f"{num_actions}")
+        if int(height) <= 0 or int(width) <= 0:
+            raise _lib.HabError(f"Nav2DImageNav: the image size {height} x {width} must be positive")
+        self.success_distance = nav2d_imagenav_success_distance(success_distance, nav2d_distance(distance, "Nav2DImageNav"))
+        try:
+            super().__init__(num_envs, height, width, seed=seed, env_offset=env_offset, use_rgb=use_rgb, use_depth=use_depth, device=device,
+                             num_obstacles=num_obstacles, turn_angle=turn_angle, max_episode_steps=max_episode_steps, distance=distance,
+                             top_down_map=top_down_map)
+        except _lib.HabError as err:
+            # Nav2D-v0's own parameter refusals come first and stand; the one that is left where the spaces exist is the device's
+            if torch.device(device).type != "cuda" and hasattr(self, "observation_spaces"):
+                raise _lib.HabError("Nav2DImageNav: both views are rendered on the GPU; no GPU device given") from err
+            raise
+        self.task = "nav2dimagenav"
+        self._compass_table = torch.from_numpy(nav2d_compass_table(self.turn_angle)).to(self.device)
+
+    def _sensor_rows(self, obs):
+        return (*(ptr(obs.get(k)) for k in NAV2D_IMAGENAV_SENSORS), ptr(self._compass_table))
+
+    def _task_parameters(self):
+        return (self.success_distance,)
+
+    def reset_into(self, rgb, depth, goal):
+        raise _lib.HabError("Nav2DImageNav: the task has no pointgoal sensor; use reset_into_obs with the task's sensor rows")
+
+    def step_into(self, rgb, depth, goal, reward, not_done, actions=None, mask=None):
+        raise _lib.HabError("Nav2DImageNav: the task has no pointgoal sensor; use step_into_obs with the task's sensor rows")
+
+
 class SyntheticVectorEnvFactory(VectorEnvFactory):
     """Default `_target_`: N synthetic PointNav envs sized from habitat.simulator.sensors.*; per-rank env ids are
     offset by rank * num_environments exactly like the reference offsets the seed (ppo_trainer.py:208-211).  A
@@ -1462,6 +1562,9 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
     person_always_visible, takes its image size like Nav2DRearr-v0 and has the Euclidean distance mode only.  A type starting with
     "nav2dexplore" -- tested before "nav2d" too -- selects Nav2DExplore-v0 (Nav2DExploreVectorEnv: area coverage, no goal input), which
     reads coverage_resolution, visibility_dist and coverage_reward, takes its image size like Nav2D-v0 and has the Euclidean mode only.
+    A type starting with "nav2dimagenav" -- tested before "nav2d" as well -- selects Nav2DImageNav-v0 (Nav2DImageNavVectorEnv: the goal
+    given only as the image `goal_rgb`), which reads success_distance, takes its image size from the rgb sensor, which it requires, and
+    has both distance modes.
     `habitat.task.measurements.top_down_map`, where that key is present, becomes the `top_down_map` keyword of any Nav2D task with
     whichever of map_resolution, visibility_dist, draw_fog and fov it holds (see Nav2DVectorEnv, Top-down map)."""
 
@@ -1486,7 +1589,11 @@ class SyntheticVectorEnvFactory(VectorEnvFactory):
             if tdm is not None:  # the measure: any of its keys may be missing (see nav2d_map_parameters)
                 kw.update(top_down_map={k: getattr(tdm, k) for k in NAV2D_MAP_DEFAULTS if getattr(tdm, k, None) is not None})
             make = Nav2DVectorEnv
-            if task_type.startswith("nav2dexplore"):
+            if task_type.startswith("nav2dimagenav"):
+                make = Nav2DImageNavVectorEnv
+                ref = sens["rgb"] if use_rgb else dict(height=0, width=0)  # the goal image has the rgb sensor's size
+                kw.update(success_distance=getattr(syn, "success_distance", 1.0))
+            elif task_type.startswith("nav2dexplore"):
                 make = Nav2DExploreVectorEnv
                 kw.update(coverage_resolution=getattr(syn, "coverage_resolution", 64), visibility_dist=getattr(syn, "visibility_dist", 3.0),
                           coverage_reward=getattr(syn, "coverage_reward", 0.1))

@@ -136,7 +136,7 @@ def refuse_imitation_envs(envs, device_envs: bool, probe: bool = True) -> None:
 @baseline_registry.register_trainer(name="ppo")
 class PPOTrainer(BaseRLTrainer):
     supported_tasks = ["Nav-v0", "ObjectNav-v1", "Nav2D-v0", "Nav2DObj-v0", "Nav2DRearr-v0", "Nav2DRearrVel-v0", "Nav2DSocial-v0",
-                       "Nav2DExplore-v0"]
+                       "Nav2DExplore-v0", "Nav2DImageNav-v0"]
     SHORT_ROLLOUT_THRESHOLD: float = 0.25
 
     def __init__(self, config=None):

@@ -415,6 +415,37 @@ int hab_nav2d_explore_step(void* state /*N,HAB_NAV2D_EXPLORE_STATE_BYTES*/, cons
                            uint8_t* not_done /*N*/, float* measure_sums /*4,N*/, uint32_t seed, uint32_t env_offset, int N, int H, int W,
                            int num_obstacles, int num_headings, int max_episode_steps, int G, float visibility_dist, float rc,
                            int advance, hipStream_t stream);
+/* Nav2DImageNav-v0: Nav2D-v0 with the goal given only as an image (definition: habitat_amd/common/env_factory.py,
+ * Nav2DImageNavVectorEnv; bit-identical to tests/nav2d_imagenav_reference.py on every output, no angle function runs on the device).
+ * `state` is N records of HAB_NAV2D_IMAGENAV_STATE_BYTES whose first HAB_NAV2D_STATE_BYTES are a Nav2D-v0 record with every word's
+ * meaning kept; LAST_MEASURES are success, spl, distance_to_goal, collisions.  Every argument of hab_nav2d_step keeps its meaning and
+ * its checks; there is no goal sensor.  actions int64 in 0..3.  rgb and depth: the agent's view in Nav2D-v0's geometry without the goal
+ * marker.  goal_rgb u8 (N,H,W,3): the same camera at (GX, GY) with the record's goal heading, colour only; any byte alignment.  The
+ * three image destinations are written by one launch and each may be NULL, which skips it.  gps, compass and compass_table as
+ * hab_nav2d_obj_step's.  success_distance: STOP succeeds where the distance is below it; positive and finite, else HAB_ERR_ARG;
+ * with 0.2 every reward, not_done and measure is Nav2D-v0's.  hab_nav2d_imagenav_step_geo is hab_nav2d_step_geo's counterpart: `geo`
+ * are N records of HAB_NAV2D_GEO_BYTES, built for the episodes that began; hab_nav2d_geo_build and hab_nav2d_follow serve these
+ * records with state_stride_bytes = HAB_NAV2D_IMAGENAV_STATE_BYTES, and the map entries with HAB_NAV2D_MAP_TASK_GOAL. */
+#define HAB_NAV2D_IMAGENAV_STATE_BYTES 240
+/* further words of a Nav2DImageNav-v0 record: the heading index the goal image is taken with, start position, start heading index */
+#define HAB_NAV2D_IMAGENAV_W_GOAL_HEADING 56
+#define HAB_NAV2D_IMAGENAV_W_START_X 57
+#define HAB_NAV2D_IMAGENAV_W_START_Y 58
+#define HAB_NAV2D_IMAGENAV_W_START_HEADING 59
+int hab_nav2d_imagenav_state_bytes(void);
+int hab_nav2d_imagenav_step(void* state /*N,HAB_NAV2D_IMAGENAV_STATE_BYTES*/, const float* dirs, const float* ray, const float* col_cos,
+                            const float* tanv, const int64_t* actions /*N*/, const uint8_t* mask /*N*/, uint8_t* rgb /*N,H,W,3*/,
+                            float* depth /*N,H,W,1*/, uint8_t* goal_rgb /*N,H,W,3*/, float* gps /*N,2*/, float* compass /*N,1*/,
+                            const float* compass_table /*num_headings*/, float* reward /*N*/, uint8_t* not_done /*N*/,
+                            float* measure_sums /*4,N*/, uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles,
+                            int num_headings, int max_episode_steps, float success_distance, int advance, hipStream_t stream);
+int hab_nav2d_imagenav_step_geo(void* state /*N,HAB_NAV2D_IMAGENAV_STATE_BYTES*/, void* geo /*N,HAB_NAV2D_GEO_BYTES*/, const float* dirs,
+                                const float* ray, const float* col_cos, const float* tanv, const int64_t* actions /*N*/,
+                                const uint8_t* mask /*N*/, uint8_t* rgb /*N,H,W,3*/, float* depth /*N,H,W,1*/,
+                                uint8_t* goal_rgb /*N,H,W,3*/, float* gps /*N,2*/, float* compass /*N,1*/,
+                                const float* compass_table /*num_headings*/, float* reward /*N*/, uint8_t* not_done /*N*/,
+                                float* measure_sums /*4,N*/, uint32_t seed, uint32_t env_offset, int N, int H, int W, int num_obstacles,
+                                int num_headings, int max_episode_steps, float success_distance, int advance, hipStream_t stream);
 
 /* The top-down map of the Nav2D tasks with its fog of war, and the video frame (definition: habitat_amd/common/env_factory.py,
  * Nav2DVectorEnv, "Top-down map"; bit-identical to tests/nav2d_map_reference.py; csrc/nav2d_map.hip).  `state` are records of any
